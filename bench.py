@@ -7,10 +7,17 @@ i.e. Trainer.train()'s timed stages Time-SampleProc + Time-InnerStep + Time-Oute
 on BASELINE config 3: 40-task HalfCheetahRandVel shapes (obs 20, act 6, 2x64 tanh MLP, H=200, P=20, K=1).
 
   python bench.py --gpus N --steps K --warmup W      (N>1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py ... --full                         (also every secondary measurement: see below)
+  python bench.py ... --dump-outputs DIR             (what the last timed step computed, as DIR/<name>.npy)
+
+A plain run sets up, warms up, times exactly K steps in one loop, and prints the line.  Everything else the line can carry
+is measured only with --full: the median of repeated timed loops, `h2d` (uploads, staged uploads), `exact_hvp` / `host_cg_loop`
+(config 5), `roofline` with `stage_a`, `plugin_path`, `cpu_baseline`, and for N > 1 `rccl`, `strong_scaling` and the other
+scaling mode ("weak_batch" / "fixed_batch").
 
 Multi-GPU: tasks are sharded i -> GPU (i mod N); the only exchange is one RCCL all-reduce of [Theta+K+2] floats per Adam
 epoch (+1 for the stats pass).  Default is STRONG scaling: the named 40-task batch split over the N ranks (5 tasks per GPU
-at N = 8); the same line also carries "weak_batch": 40 tasks per GPU (meta_batch_size = 40 N), timed right after.
+at N = 8); with --full the same line also carries "weak_batch": 40 tasks per GPU (meta_batch_size = 40 N), timed right after.
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -55,8 +62,15 @@ def main():
                     help='developer option: with --gpus 1, run only the shard rank 0 of an N-GPU job would hold '
                          '(M/N tasks, no collective) to study the per-rank step time of strong scaling')
     ap.add_argument('--repeats', type=int, default=0,
-                    help='timed loops of exactly --steps steps each; `value` is the MEDIAN loop (default: 5 when one loop is '
-                         'shorter than half a second, else 1)')
+                    help='timed loops of exactly --steps steps each; `value` is the MEDIAN loop (default: 1; with --full 5 when one '
+                         'loop is shorter than half a second, else 1)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every secondary measurement (repeated loops, h2d, roofline, stage_a, plugin_path, cpu_baseline, '
+                         'config 5\'s exact_hvp / host_cg_loop, and for N > 1 rccl and the other scaling mode); off by default')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='after the timed steps, write what the last timed step computed (meta-parameters, adapted task '
+                         'parameters, processed samples of both sampling steps, the outer step\'s statistics) as DIR/<name>.npy '
+                         '(float32 / float64; rank 0\'s tasks when N > 1)')
     ap.add_argument('--no-plugin-path', action='store_true')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
@@ -266,8 +280,14 @@ def main():
     # A loop of K steps is tens of milliseconds at config 3: one loop is one sample of the box's clocks.  Every repeat is the
     # contract's measurement again -- exactly K steps between barrier + device sync, max over ranks -- and `value` is the median
     # loop (all of them are listed).  The number of repeats is agreed on by the ranks (rank-local clocks differ).
+    # A plain run times one loop (--steps is the number of timed steps); --full repeats it as below.
     loops = [elapsed]
-    n_rep = args.repeats if args.repeats > 0 else (5 if ctx.allreduce_f64([elapsed], op='max')[0] < 0.5 else 1)
+    if args.repeats > 0:
+        n_rep = args.repeats
+    elif args.full:
+        n_rep = 5 if ctx.allreduce_f64([elapsed], op='max')[0] < 0.5 else 1
+    else:
+        n_rep = 1
     if not args.staged_only:
         for _ in range(n_rep - 1):
             el, r = run_timed(ctx, iteration, 0, args.steps)
@@ -276,6 +296,8 @@ def main():
         elapsed = float(np.median(loops))
     if not np.isfinite(res['loss_after']):
         raise SystemExit('bench: non-finite loss')
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, res)
     split_events = dict(ctx.split_events(), steps=args.warmup + args.steps * len(loops))      # over the warm-up and every timed loop
     trpo_last = None
     if trpo and res is not None:       # what the last timed step's trust-region step did (the same resident batch every step: see the note)
@@ -322,7 +344,7 @@ def main():
     if args.test_shape:
         out['test_shape'] = 'NOT A BENCHMARK RESULT: --test-shape %s (a code-path test of this file)' % args.test_shape
     # ---- N ranks: who took part (what the communicator itself reports), every rank's own loop time, the exchange's latency ----
-    if world > 1:
+    if world > 1 and args.full:
         ci = ctx.comm_info()
         bus = ci['pci_bus_id'].encode()[:32]
         row = np.zeros((world, 35))
@@ -375,7 +397,7 @@ def main():
 
     # ---- config 5 with the exact constraint Hessian-vector product (promp_constraint_hvp) instead of the reference's finite
     # difference: reported beside the timed default, never as `value` ----
-    if trpo and rank == 0 and world == 1 and iteration.mode is not None:
+    if args.full and trpo and rank == 0 and world == 1 and iteration.mode is not None:
         iteration.reset()
         iteration.mode['hvp'] = 'exact'
         n_ex = max(2, min(args.steps, 5))
@@ -399,7 +421,7 @@ def main():
                                        'host, 22 constraint gradients fetched one at a time'}
 
     # ---- host -> device cost of the two slabs (never part of `value`: the timed region starts with the batch in HBM) ----
-    if rank == 0 and world == 1 and not args.staged_only:
+    if args.full and rank == 0 and world == 1 and not args.staged_only:
         iteration.upload()
         t0 = time.perf_counter()
         for _ in range(3):
@@ -427,7 +449,7 @@ def main():
             iteration()
 
     # ---- roofline of the dominant kernel: HIP events around every launch, on the stream it runs on ----
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         ctx.prof_enable(True)
         n_prof = max(3, min(args.steps, 10))
         for _ in range(n_prof):
@@ -486,7 +508,7 @@ def main():
                                                                                            + 2 * fl['fwd'] + fl['bwd']) / 2.0) / 1e12 / world}
 
     # ---- Stage A alone (the scan / fit / normalise chain against HBM): process_samples on the stream, nothing else ----
-    if not args.no_roofline and rank == 0 and world == 1:
+    if args.full and not args.no_roofline and rank == 0 and world == 1:
         n_a = 50
         ctx.switch_to_pre_update()
         for _ in range(5):
@@ -505,20 +527,20 @@ def main():
                                               'traffic (SURVEY 8d); latency-bound -- five dependent launches over %d rows' % (4 * (O + 1) + 8, M * N)}
 
     # ---- the same step through the plugin classes (what a user who swaps the imports runs: meta_trainer.py:96-142) ----
-    if rank == 0 and world == 1 and not trpo and not args.no_plugin_path and not args.staged_only:
+    if args.full and rank == 0 and world == 1 and not trpo and not args.no_plugin_path and not args.staged_only:
         try:
             out['plugin_path'] = plugin_path(cfg, theta0, E, eta, opts, value, out.get('h2d', {}).get('upload_ms_per_step'))
         except Exception as e:          # the secondary measurement must never cost the primary line
             print('bench.py: plugin-path measurement skipped: %r' % (e,), file=sys.stderr)
 
     # ---- CPU baseline: the C + OpenMP restatement ("port") on the host cores, rank 0, bounded sample ----
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline(cfg, theta0, alpha, eta, opts, E, trpo=trpo, steps=3 if args.config != 4 else 1,
                                            oracle_tasks=8 if args.config != 4 else 2)
 
     ctx.close()
     # ---- N > 1: also time the other scaling mode on the same ranks (weak: a 40-task batch per GPU) ----
-    if world > 1:
+    if world > 1 and args.full:
         other = 'weak' if args.scaling == 'strong' else 'strong'
         try:
             M_other = cfg['M'] * (world if other == 'weak' else 1)
@@ -532,6 +554,32 @@ def main():
             print('bench.py: %s-scaling measurement skipped: %r' % (other, e), file=sys.stderr)
     if rank == 0:
         print(json.dumps(out))
+
+
+DUMP_LIMIT_BYTES = 60 << 20       # --dump-outputs: the whole set, .npy headers aside, stays under 64 MB
+
+
+def dump_outputs(out_dir, ctx, res):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as <out_dir>/<name>.npy (float32 / float64):
+    the meta-parameters the outer step left (theta), the task parameters _adapt returned (adapted_task_params), the processed
+    samples of both sampling steps (returns, advantages, baseline coefficients) and the outer step's statistics (`res`).
+    Read back from the device after the timed region.  An array larger than its share of DUMP_LIMIT_BYTES is replaced by a
+    fixed, seeded sample of its elements (in index order), so the same arguments always write the same elements."""
+    arrays = [('theta', ctx.get_theta()), ('adapted_task_params', ctx.get_task_thetas())]
+    for k in (0, 1):
+        pr = ctx.download_processed(k)
+        arrays += [('returns_step%d' % k, pr['returns']), ('advantages_step%d' % k, pr['advantages']),
+                   ('baseline_coeffs_step%d' % k, pr['coeffs'])]
+    arrays += [(key, np.asarray(res[key], np.float64).reshape(-1)) for key in sorted(res)]
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES
+    for i, (name, a) in enumerate(arrays):
+        a = np.array(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)   # a copy: the download buffers are pooled
+        share = budget // (len(arrays) - i)
+        if a.nbytes > share:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, share // a.itemsize, replace=False))]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        budget -= a.nbytes
 
 
 def plugin_path(cfg, theta0, E, eta, opts, device_value, upload_ms):

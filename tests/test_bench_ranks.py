@@ -15,7 +15,7 @@ def test_bench_gpus_2_launches_its_ranks_and_describes_them():
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, 'tests', 'bench_emu_driver.py'), '--gpus', '2', '--steps', '1', '--warmup', '0',
-           '--repeats', '1', '--test-shape', '4,2,12,5,3,32', '--no-roofline', '--no-cpu-baseline', '--no-plugin-path']
+           '--repeats', '1', '--test-shape', '4,2,12,5,3,32', '--full', '--no-roofline', '--no-cpu-baseline', '--no-plugin-path']
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500, cwd=ROOT)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith('{')]
@@ -48,7 +48,7 @@ def test_bench_under_torch_distributed_run_with_two_ranks():
         port = s.getsockname()[1]
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.join(ROOT, 'tests', 'bench_emu_driver.py'), '--gpus', '2', '--steps', '1',
-           '--warmup', '0', '--repeats', '1', '--test-shape', '4,2,12,5,3,32', '--no-roofline', '--no-cpu-baseline', '--no-plugin-path']
+           '--warmup', '0', '--repeats', '1', '--test-shape', '4,2,12,5,3,32', '--full', '--no-roofline', '--no-cpu-baseline', '--no-plugin-path']
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500, cwd=ROOT)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith('{')]

@@ -15,7 +15,7 @@ for rep in $(seq $REPS); do
 for f in tools/ablate/lib_*.so; do
   cp $f promp_amd/libpromp_hip.so
   echo "== $f"
-  timeout 300 python bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-plugin-path 2>/dev/null | python -c "
+  timeout 300 python bench.py --steps 30 --warmup 3 --full --no-cpu-baseline --no-plugin-path 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 k=d['roofline']['kernels']

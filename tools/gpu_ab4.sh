@@ -6,7 +6,7 @@ for rep in $(seq ${1:-1}); do
 for f in tools/ablate/lib_*.so; do
   cp $f promp_amd/libpromp_hip.so
   echo "== $f"
-  timeout 300 python bench.py --config 4 --steps 10 --warmup 2 --no-cpu-baseline --no-plugin-path 2>/dev/null | python -c "
+  timeout 300 python bench.py --config 4 --steps 10 --warmup 2 --full --no-cpu-baseline --no-plugin-path 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 k=d['roofline']['kernels']

@@ -9,7 +9,7 @@ for f in tools/ablate/lib_*.so; do
   timeout 600 python -m pytest tests -m gpu -q -s -k "full_config_meta_gradient or split_gemm_accuracy_guard" 2>&1 | grep -E "full-size parity|passed|failed"
   python tools/split_accuracy_gpu.py 2>&1 | grep "^(128\|^(64, 64) 20"
   for cfg in 3 4; do
-  timeout 300 python bench.py --config $cfg --steps 10 --warmup 2 --no-cpu-baseline --no-plugin-path 2>/dev/null | python -c "
+  timeout 300 python bench.py --config $cfg --steps 10 --warmup 2 --full --no-cpu-baseline --no-plugin-path 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 k=d['roofline']['kernels']
