@@ -2286,10 +2286,9 @@ int promp_cg_solve(promp_ctx* c, int inner_kind, const float* b, int cg_iters, f
         return fail(-3, "this context holds %d of %d tasks and has no communicator: the products would be this rank's share only "
                         "(promp_comm_init first)", c->d.n_tasks, c->d.n_tasks_global);
     const int NP = c->NP;
-    if (!c->cg_buf) {
-        if (dev_alloc(&c->cg_buf, (size_t)7 * NP)) return -2;
-        if (dev_alloc(&c->cg_scal, 4)) return -2;
-    }
+    // (one guard each: a call whose second allocation failed must not leave the next one running k_cg_step without its scalars)
+    if (!c->cg_buf && dev_alloc(&c->cg_buf, (size_t)7 * NP)) return -2;
+    if (!c->cg_scal && dev_alloc(&c->cg_scal, 4)) return -2;
     float *x = c->cg_buf, *r = x + NP, *d = r + NP, *hd = d + NP, *ga = hd + NP, *th0 = ga + NP;
     if (params_in(c, r, b, 1)) return -2;                       // (blocking: b is the caller's)
     float eta[PROMP_ETA_MAX] = {};

@@ -596,6 +596,181 @@ def check_cg_solve_on_device(lib, seed, M, P, T, O, A, hidden, K=1, inner='logli
     ctx.close()
 
 
+def _param_layout(ctx):
+    """(to the device's layout, back to the caller's, padded parameter count) of a context: promp_hip.hip pad_dims / remap_params"""
+    d = ctx.dims
+    hidden = (d.hidden1, d.hidden2, d.hidden3, d.hidden4)[:d.n_hidden]
+    padded = helpers.padded_hidden(d.obs_dim, d.act_dim, hidden, plain_tanh=d.hidden_act == 0)
+    if padded == hidden:
+        return (lambda v: np.asarray(v, np.float32).copy()), (lambda v: np.asarray(v, np.float32).copy()), ctx.n_params
+    to_dev = lambda v: helpers.remap_params(d.obs_dim, d.act_dim, hidden, padded, np.asarray(v, np.float32), True)
+    to_host = lambda v: helpers.remap_params(d.obs_dim, d.act_dim, hidden, padded, np.asarray(v, np.float32), False)
+    return to_dev, to_host, op.PolicySpec(d.obs_dim, d.act_dim, padded).n_params
+
+
+def cg_solve_mirror(ctx, b, cg_iters=10, reg_coeff=0.0, eps=1e-5, hvp_mode=0, residual_tol=1e-10, inner_kind=_lib.INNER_LOGLIK):
+    """promp_cg_solve / k_cg_step / k_cg_displace transcribed step by step in NumPy over the context's own gradients and products:
+    -> (x, x . (H + reg I) x, [r.r after each iteration that updated], number of iterations that updated).
+
+    Everything downstream of the displaced parameters is deterministic, so this reproduces the device's x and quadratic form bit
+    for bit:
+      * the displaced parameters are theta0 + s v in ONE rounding (fma32), set with set_theta; the constraint gradient there is
+        ctx.meta_grad(0, eta = 0, inner_kind, OUTER_KL) -- the same pass and the same grad_mean the solve reads;
+      * one-sided (hvp_mode 1): the gradient at theta0 is taken once, before the first product; exact (hvp_mode 2): ctx.constraint_hvp
+        (its red * (1 / tasks) is the product's mul_s), the adapted chain refreshed on the first product only;
+      * (H + reg I) v = fma(reg, v, ((g_ahead - g_behind) / div_h) * mul_s) in float32, div_h = 2 eps (symmetric) or eps;
+      * dot products in float64 in the workgroup's order (helpers.cg_block_sum), over the device's (zero-padded) layout: the
+        vectors are scattered into it first, since the padding moves every entry's thread;
+      * step = float32(r.r / d.Hd), x and r by fma, beta = float32(r.r_new / r.r); the solve freezes once r.r_new <
+        float64(float32(residual_tol)): later products still run, nothing is updated;
+      * the closing product on x; the parameters are set back to theta0."""
+    f32 = np.float32
+    to_dev, to_host, n = _param_layout(ctx)
+    reg, eps, tol = f32(reg_coeff), f32(eps), float(f32(residual_tol))
+    exact = hvp_mode == 2
+    eta = np.zeros(ctx.K, np.float32)
+    theta0 = ctx.get_theta()
+    th0 = to_dev(theta0)
+    r = to_dev(b)
+    assert r.shape == (n,)
+    x, d = np.zeros(n, np.float32), r.copy()
+    dsum = lambda u, w: helpers.cg_block_sum(u.astype(np.float64) * w.astype(np.float64))
+    res = dsum(r, r)
+
+    def gradient_at(s, v):
+        ctx.set_theta(to_host(helpers.fma32(s, v, th0)))
+        return to_dev(ctx.meta_grad(0.0, eta, inner_kind=inner_kind, outer_kind=_lib.OUTER_KL)[0])
+    g0 = None
+    if hvp_mode == 1:
+        g0 = to_dev(ctx.meta_grad(0.0, eta, inner_kind=inner_kind, outer_kind=_lib.OUTER_KL)[0])
+    fresh = [False]
+
+    def product(v):
+        if exact:
+            q = to_dev(ctx.constraint_hvp(to_host(v), inner_kind=inner_kind, refresh_chain=not fresh[0]))
+            fresh[0] = True
+        else:
+            ga = gradient_at(eps, v)
+            gb, div = (gradient_at(-eps, v), f32(2) * eps) if hvp_mode == 0 else (g0, eps)
+            q = ((ga - gb) / div) * f32(1)
+        return helpers.fma32(reg, v, q)
+    history, updates, frozen = [], 0, False
+    with np.errstate(all='ignore'):       # (a zero right-hand side: 0 / 0, NaN from there on, as the device computes it)
+        for _ in range(cg_iters):
+            hd = product(d)
+            dot = dsum(d, hd)
+            if frozen:
+                continue
+            step = f32(res / dot)
+            x = helpers.fma32(step, d, x)
+            r = helpers.fma32(-step, hd, r)
+            nres = dsum(r, r)
+            beta = f32(nres / res)
+            d = helpers.fma32(beta, d, r)
+            res = nres
+            history.append(nres)
+            updates += 1
+            frozen = nres < tol
+        xhx = dsum(x, product(x))
+    if not exact:
+        ctx.set_theta(theta0)
+    return to_host(x), xhx, history, updates
+
+
+def _bitwise(a, b):
+    """the same float32 values bit for bit (NaN: at the same places, whatever their payload)"""
+    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
+    if a.shape != b.shape or not np.array_equal(np.isnan(a), np.isnan(b)):
+        return False
+    m = ~np.isnan(a)
+    return np.array_equal(a[m].view(np.uint32), b[m].view(np.uint32))
+
+
+def check_cg_solve_mirror(lib, seed, M, P, T, O, A, hidden, K=1, inner='loglik', modes=(0, 1, 2), iters=(1, 3, 10),
+                          regs=(0.0, 0.5), freeze=True, zero_rhs=True, on_policy=True, eps=1e-5, freeze_iters=10):
+    """promp_cg_solve against cg_solve_mirror: x and x . (H + reg I) x BITWISE equal, for every product mode (0 symmetric finite
+    differences, 1 one-sided, 2 exact), number of iterations and Tikhonov coefficient asked for; the residual_tol freeze
+    (after exactly the iteration whose r.r drops below it: the same x as a solve of that many iterations, another x than the
+    full one); a zero right-hand side (0 / 0 on the first iteration: NaN where the mirror has NaN, as the reference's
+    conjugate_gradients); the parameters and the next evaluation unchanged by every solve.  -> {(mode, iters, reg): updates}"""
+    spec = op.PolicySpec(O, A, hidden)
+    alpha = np.full(spec.n_params, 0.05, np.float32)
+    kind = dict(loglik=_lib.INNER_LOGLIK, ratio=_lib.INNER_RATIO)[inner]
+    okind = dict(loglik=pm.INNER_LOGLIK, ratio=pm.INNER_RATIO)[inner]
+    if on_policy:
+        theta, all_slabs, all_paths = on_policy_case(seed, M, P, T, O, A, hidden, K, alpha, okind)
+    else:
+        theta, all_slabs, all_paths = helpers.make_promp_case(seed, M, P, T, O, A, hidden, K)
+    ctx = make_ctx(lib, M, O, A, hidden, K, all_paths)
+    try:
+        helpers.upload_slabs(ctx, all_paths, all_slabs)
+        ctx.set_theta(theta)
+        ctx.set_step_sizes(alpha)
+        eta = np.zeros(K, np.float32)
+        b, st0 = ctx.meta_grad(0.0, eta, inner_kind=kind, outer_kind=_lib.OUTER_RATIO)      # the loss gradient: the right-hand side
+        gc0 = ctx.meta_grad(0.0, eta, inner_kind=kind, outer_kind=_lib.OUTER_KL)[0]
+
+        def solve(mode, it, reg, tol=1e-10, rhs=b):
+            x, q = ctx.cg_solve(rhs, cg_iters=it, reg_coeff=reg, eps=eps, hvp_mode=mode, residual_tol=tol, inner_kind=kind)
+            assert _bitwise(ctx.get_theta(), theta), (mode, it, reg)
+            return x, q
+
+        def mirror(mode, it, reg, tol=1e-10, rhs=b):
+            out = cg_solve_mirror(ctx, rhs, cg_iters=it, reg_coeff=reg, eps=eps, hvp_mode=mode, residual_tol=tol, inner_kind=kind)
+            assert _bitwise(ctx.get_theta(), theta)
+            return out
+        seen = {}
+        for mode in modes:
+            for it in iters:
+                for reg in regs:
+                    x, q = solve(mode, it, reg)
+                    xm, qm, hist, upd = mirror(mode, it, reg)
+                    assert _bitwise(x, xm), (mode, it, reg, rel_max(x, xm), int(np.count_nonzero(x != xm)))
+                    assert q == qm, (mode, it, reg, q, qm)
+                    assert np.isfinite(x).all() and upd == it
+                    seen[(mode, it, reg)] = upd
+        if freeze:
+            for mode in modes:
+                nf = freeze_iters
+                x10, _ = solve(mode, nf, 0.0, tol=0.0)
+                *_, hist, upd = mirror(mode, nf, 0.0, tol=0.0)
+                assert upd == nf and len(hist) == nf
+                # a tol below r.r of every iteration before the k-th and above the k-th's (the finite-difference products make the
+                # residuals non-monotone: the first iteration from the third on whose r.r is a new minimum): the solve stops after it
+                k = next((j for j in range(2, nf - 1) if hist[j] < min(hist[:j])), 1)
+                assert hist[k] < min(hist[:k]), hist
+                tol = np.float32(np.sqrt(hist[k] * min(hist[:k])))
+                if not float(tol) > hist[k]:
+                    tol = np.nextafter(tol, np.float32(np.inf))
+                assert hist[k] < float(tol) <= min(hist[:k]), (hist, k, tol)
+                xf, qf = solve(mode, nf, 0.0, tol=float(tol))
+                xfm, qfm, hf, updf = mirror(mode, nf, 0.0, tol=float(tol))
+                x3, q3 = solve(mode, k + 1, 0.0)
+                assert updf == k + 1 and _bitwise(xf, xfm) and qf == qfm, (mode, k, updf)
+                assert _bitwise(xf, x3) and qf == q3, mode
+                assert not np.array_equal(xf, x10), mode
+                # tol = 1e30: frozen after the first iteration
+                xb, qb = solve(mode, nf, 0.0, tol=1e30)
+                xbm, qbm, _, updb = mirror(mode, nf, 0.0, tol=1e30)
+                x1, q1 = solve(mode, 1, 0.0)
+                assert updb == 1 and _bitwise(xb, xbm) and qb == qbm and _bitwise(xb, x1) and qb == q1, mode
+                seen[(mode, 'freeze')] = updf
+        if zero_rhs:
+            z = np.zeros_like(b)
+            for mode in modes:
+                x, q = solve(mode, 3, 0.0, rhs=z)
+                xm, qm, _, _ = mirror(mode, 3, 0.0, rhs=z)
+                assert np.isnan(x).all() and np.isnan(q), mode          # r.r / d.Hd = 0 / 0 on the first iteration
+                assert np.array_equal(x, xm, equal_nan=True) and np.isnan(qm), mode
+        # the solves leave nothing behind: the same evaluations as before them
+        b2, st2 = ctx.meta_grad(0.0, eta, inner_kind=kind, outer_kind=_lib.OUTER_RATIO)
+        assert _bitwise(b, b2) and st2['loss'] == st0['loss']
+        assert _bitwise(gc0, ctx.meta_grad(0.0, eta, inner_kind=kind, outer_kind=_lib.OUTER_KL)[0])
+        return seen
+    finally:
+        ctx.close()
+
+
 def check_exact_constraint_hvp(lib, seed, M, P, T, O, A, hidden, K=1, inner='loglik', tol=1e-4):
     """promp_constraint_hvp (2K+1 R-operator passes, Gauss-Newton form through the adaptation) against the float64 central
     difference of the oracle's constraint gradient, at the operating point of TRPO (old distribution = adapted policy)"""
@@ -907,6 +1082,16 @@ def check_trpo(lib, seed, M, P, T, O, A, hidden, inner_type='log_likelihood', cg
         # (2) the step
         algo.optimize_policy(samples, log=False)
         st, last = algo.last_stats, algo.optimizer.last
+        if hvp_approach == 'finite_difference':
+            # the plugin's wiring into promp_cg_solve (eps, symmetric, reg_coeff, cg_iters, the gradient): its direction is bitwise
+            # the mirror's solve from the same parameters with the optimizer's own settings
+            opt, hv = algo.optimizer, algo.optimizer._hvp_approach
+            th_after = ctx.get_theta()
+            ctx.set_theta(theta)
+            xm = cg_solve_mirror(ctx, last['gradient'], cg_iters=opt._cg_iters, reg_coeff=float(opt._reg_coeff), eps=float(hv.base_eps),
+                                 hvp_mode=0 if hv.symmetric else 1, inner_kind=algo.inner_kind)[0]
+            assert _bitwise(last['descent_direction'], xm), rel_max(last['descent_direction'], xm)
+            ctx.set_theta(th_after)
         ref = None
         if oracle_step:      # (skipped at full BASELINE size: ~70 float64 meta-gradient evaluations of the NumPy oracle)
             ref = otrpo.trpo_maml_step(spec, theta, all_slabs, alpha, inner_kind=kind, max_kl=0.01, cg_iters=cg_iters,
@@ -928,6 +1113,40 @@ def check_trpo(lib, seed, M, P, T, O, A, hidden, inner_type='log_likelihood', cg
         else:
             np.testing.assert_allclose(st['loss_after'], st['loss_before'], rtol=1e-6)     # parameters restored
         return st, ref
+    finally:
+        _lib.set_library_for_testing(None)
+        session._current = None
+
+
+def check_trpo_zero_gradient(lib, seed, M, P, T, O, A, hidden, inner_type='log_likelihood', cg_iters=3, max_backtracks=2):
+    """TRPOMAML.optimize_policy on a batch whose advantages are all zero: the loss gradient is exactly zero, the device solve
+    divides 0 by 0 on its first iteration (NaN, as the reference's conjugate_gradients), and the step is rejected -- no exception,
+    no NumPy warning, the parameters left as they were"""
+    import warnings
+    from promp_amd import session
+    from promp_amd.meta_algos.trpo_maml import TRPOMAML
+    from promp_amd.policies.meta_gaussian_mlp_policy import MetaGaussianMLPPolicy
+    from promp_amd.utils import logger
+    logger.configure(quiet=True)
+    _lib.set_library_for_testing(lib)
+    try:
+        spec = op.PolicySpec(O, A, hidden)
+        theta, all_slabs, _ = helpers.make_promp_case(seed, M, P, T, O, A, hidden, 1)
+        policy = MetaGaussianMLPPolicy(name='p', obs_dim=O, action_dim=A, meta_batch_size=M, hidden_sizes=hidden)
+        policy.set_params(spec.to_ordered_dict(theta))
+        algo = TRPOMAML(policy=policy, step_size=0.01, inner_type=inner_type, inner_lr=0.1, meta_batch_size=M, num_inner_grad_steps=1)
+        algo.optimizer._cg_iters = cg_iters
+        algo.optimizer._max_backtracks = max_backtracks
+        samples = [[dict(observations=s['observations'], actions=s['actions'], advantages=np.zeros_like(s['advantages']),
+                         agent_infos=s['agent_infos']) for s in step] for step in all_slabs]
+        with warnings.catch_warnings():
+            warnings.simplefilter('error')
+            algo.optimize_policy(samples, log=False)
+        last = algo.optimizer.last
+        assert not np.any(last['gradient'])
+        assert np.isnan(last['descent_direction']).all() and np.isnan(last['initial_step_size'])
+        assert last['rejected'] and last['n_backtracks'] == 0
+        assert _bitwise(algo.session.ctx.get_theta(), theta)
     finally:
         _lib.set_library_for_testing(None)
         session._current = None

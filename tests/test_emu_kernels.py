@@ -311,3 +311,13 @@ def test_sample_processing_fit_with_one_launch_per_phase(lib, two_cus, monkeypat
     pc.check_sample_processing_oracle(lib, 5, M=2, P=3, T=40, O=200, ragged=True, kwargs=kw)
     monkeypatch.setenv('PROMP_FIT_ONE_LAUNCH', '1')
     pc.check_sample_processing_oracle(lib, 5, M=2, P=3, T=40, O=200, ragged=True, kwargs=kw)
+
+
+def test_cg_solve_matches_a_bit_exact_mirror(lib, two_cus):
+    """promp_cg_solve bitwise against its NumPy transcription (parity_checks.cg_solve_mirror): the three product modes, the
+    residual_tol freeze, a zero right-hand side"""
+    pc.check_cg_solve_mirror(lib, 19, M=2, P=1, T=16, O=4, A=2, hidden=(32, 32), iters=(3,), freeze_iters=5)
+
+
+def test_trpo_maml_step_rejects_a_zero_gradient(lib, two_cus):
+    pc.check_trpo_zero_gradient(lib, 20, M=2, P=1, T=16, O=4, A=2, hidden=(32, 32), cg_iters=2, max_backtracks=1)

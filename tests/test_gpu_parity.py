@@ -491,6 +491,32 @@ def test_cg_solve_on_device_equals_the_host_loop(lib):
     pc.check_cg_solve_on_device(lib, 74, M=3, P=4, T=60, O=20, A=6, hidden=(100, 100), inner='loglik', cg_iters=3, fd=False)  # zero-padded layout
 
 
+@pytest.mark.parametrize('case', ['fused_h64', 'fused_h32_ratio', 'cooperative_h128', 'zero_padded_h100', 'layer_by_layer',
+                                  'two_inner_steps', 'full_config5'])
+def test_cg_solve_matches_a_bit_exact_mirror(lib, case):
+    """promp_cg_solve BITWISE against its NumPy transcription over the library's own gradients (parity_checks.cg_solve_mirror):
+    symmetric / one-sided finite differences and the exact product, 1, 3 and 10 iterations, reg_coeff 0 and 0.5, the residual_tol
+    freeze, a zero right-hand side -- on every kernel family's layout, the zero-padded one included; and the solve bench.py times
+    (config 5 at full size: 10 iterations of symmetric finite differences)"""
+    args = dict(fused_h64=dict(seed=81, M=4, P=5, T=100, O=20, A=6, hidden=(64, 64)),
+                fused_h32_ratio=dict(seed=82, M=3, P=4, T=60, O=5, A=3, hidden=(32, 32), inner='ratio'),
+                cooperative_h128=dict(seed=83, M=3, P=4, T=80, O=111, A=8, hidden=(128, 128)),
+                zero_padded_h100=dict(seed=84, M=3, P=4, T=60, O=20, A=6, hidden=(100, 100)),
+                layer_by_layer=dict(seed=85, M=3, P=2, T=50, O=20, A=6, hidden=(48, 48, 48)),
+                two_inner_steps=dict(seed=86, M=3, P=3, T=50, O=11, A=3, hidden=(64, 32), K=2, inner='ratio'),
+                full_config5=dict(seed=87, M=40, P=20, T=200, O=20, A=6, hidden=(64, 64), modes=(0,), iters=(10,), regs=(0.0,),
+                                  freeze=False, zero_rhs=False, on_policy=False))[case]
+    seen = pc.check_cg_solve_mirror(lib, **args)
+    print('cg mirror %s: bitwise equal in %d solves; freeze after iteration %s' % (
+        case, sum('freeze' not in m for m in seen), {m[0]: v for m, v in seen.items() if 'freeze' in m}))
+
+
+def test_trpo_maml_step_rejects_a_zero_gradient(lib):
+    """all advantages zero: 0 / 0 in the first conjugate-gradient iteration, the step rejected without an exception or a warning"""
+    pc.check_trpo_zero_gradient(lib, 88, M=3, P=4, T=60, O=20, A=6, hidden=(64, 64))
+    pc.check_trpo_zero_gradient(lib, 89, M=3, P=4, T=60, O=5, A=3, hidden=(32, 32), inner_type='likelihood_ratio')
+
+
 def test_trpo_maml_step_with_exact_constraint_hvp(lib):
     """the plugin with hvp_approach='exact': with the finite-difference noise gone, the float32 step tracks the float64 oracle"""
     pc.check_trpo(lib, 66, M=4, P=5, T=100, O=20, A=6, hidden=(64, 64), inner_type='log_likelihood', hvp_approach='exact', on_policy=True)
