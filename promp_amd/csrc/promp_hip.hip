@@ -96,6 +96,39 @@ int chain_ksteps(int obs_dim) { return obs_dim <= 8 ? 2 : obs_dim <= 20 ? 5 : 8;
 #define PROMP_PASS_ALL(X) X(2, 2) X(2, 4) X(4, 2) X(4, 4)
 #define PROMP_WB_ALL(X) X(1, 4, 2) X(2, 7, 4) X(3, 8, 4)
 #define PROMP_CHAIN_ALL(X) X(2, 2, 2) X(2, 2, 5) X(2, 2, 8) X(2, 4, 2) X(2, 4, 5) X(2, 4, 8) X(4, 2, 2) X(4, 2, 5) X(4, 2, 8) X(4, 4, 2) X(4, 4, 5) X(4, 4, 8)
+// k_wide_* instances: (hidden width, observation blocks of 16)
+#define PROMP_WIDE_ALL(X) X(128, 2) X(128, 4) X(128, 8) X(64, 2) X(64, 4) X(64, 8)
+int wide_nob(int obs_dim) { return obs_dim <= 32 ? 2 : obs_dim <= 64 ? 4 : 8; }
+
+// which kernels run the policy passes of a context (promp_ctx_create chooses once, from the padded dims)
+enum class PassFamily {
+    Chain,       // register-chained k_pass / k_chain_hvp (promp_kernels_chain.h, promp_kernels_pass.h): widths from {32, 64}, obs_dim <= 32
+    CoopFp32,    // cooperative exact-FP32 k_wide_* (promp_kernels_policy_wide.h): (64,64) with obs_dim > 32, (128,128) outside CoopSplit
+    CoopSplit,   // cooperative k_wb_* on the BF16 matrix pipe (promp_kernels_wide_bf16.h): (128,128) with obs_dim <= 127
+    Layered,     // layer-by-layer k_gen_* / k_gb_* (promp_kernels_generic*.h): every shape policy_shape_generic() names
+};
+
+// One policy pass (launch_pass): the defaults are a first-order pass with the plain per-task reduction
+struct PassReq {
+    bool hvp = false;                  // R-operator pass along the direction in c->vbuf
+    const float* theta = nullptr;      // parameters: one row per task at theta_stride (0: one row shared by every task)
+    long long theta_stride = 0;
+    int loss_kind = LOSS_RATIO;
+    float clip_eps = 0.f;
+    int clip_ls = 0;                   // clip log_std at log(min_std)
+    float klw = 0.f;                   // weight of the KL term
+    bool fwd_only = false;             // loss and KL only, no gradient
+    int red_mode = RED_PLAIN;          // k_reduce_task (promp_kernels_chain.h): RED_STEP / RED_OUTER / RED_HVP / RED_PLAIN / RED_SCAL
+    const float* cur = nullptr;        // RED_STEP: next = cur - step sizes * gradient
+    long long cur_stride = 0;
+    float* next = nullptr;
+    float* scal = nullptr;             // per-task loss and KL (nullptr: c->scal_tmp)
+    int cache = 0;                     // primal cache: 0 none, 1 the gradient pass fills it, 2 the R-operator pass reads it
+    const float* adv = nullptr;        // per-row weights instead of the step's advantages (DiCE coupling pass)
+    float* row_tan = nullptr;          // R-operator pass: where the rows' log-likelihood tangents go (DiCE)
+    float* next2 = nullptr;            // RED_STEP: second destinations of next and scal (see adapt0)
+    float* scal2 = nullptr;
+};
 
 struct ProfSlot {
     std::vector<hipEvent_t> ev;  // start/stop pairs
@@ -136,9 +169,8 @@ struct promp_ctx {
     size_t rollout_capacity = 0;
     double* fit_scratch = nullptr;       // k_fit_wide: [tasks][2][(D+1)^2] when the matrices do not fit in LDS
     size_t smem_fwd = 0, smem_hvp = 0;
-    bool wide = false;                   // cooperative kernels for hidden 128 / obs_dim > 32
-    int wbf = 0;                         // hidden 128, obs_dim <= 127: the BF16-pipe cooperative kernels (promp_kernels_wide_bf16.h);
-                                         // 1..3 = the observation class (NKO, NXB) = (4,2) (7,4) (8,4): obs_dim <= 63 / 111 / 127
+    PassFamily family = PassFamily::Chain;
+    int wb_cls = 0;                      // CoopSplit: the observation class 1..3 = (NKO, NXB) = (4,2) (7,4) (8,4): obs_dim <= 63 / 111 / 127
     size_t smem_wb_fwd = 0, smem_wb_bwd = 0, smem_wb_hvp = 0;
     unsigned *wb_planes = nullptr, *wb_vplanes = nullptr;   // [tasks][wb_planes_words]: k_wb_planes' output for theta / the direction
     // The planes of the META-parameters (theta itself, stride 0) have their own block: an epoch passes over step 0 at theta twice --
@@ -156,8 +188,7 @@ struct promp_ctx {
     int gramt_map_nblk = -1;             // the block count c->gramt_map was balanced for
     GramtMap gramt_map;                  // one-slice k_gram_tiled launches: wave -> rectangle
     bool fit_one_launch = false;         // PROMP_FIT_ONE_LAUNCH=1: k_fit_wide alone at every width (A/B runs against the per-phase launches)
-    bool generic = false;
-    bool gen_bf16 = true;                // their GEMMs on the BF16 matrix pipe (promp_kernels_generic_bf16.h); PROMP_GEN_FP32=1: the exact-FP32 kernels (A/B runs)
+    bool gen_bf16 = true;                // Layered: the GEMMs on the BF16 matrix pipe (promp_kernels_generic_bf16.h); PROMP_GEN_FP32=1: the exact-FP32 kernels (A/B runs)
     unsigned short *gb_wplanes = nullptr, *gb_vplanes = nullptr;   // [tasks][gb_plane_stride]: k_gb_planes' output for theta / minus the direction
     long long gb_plane_stride = 0;
     int gb_pf_off[GEN_MAX_LIN] = {}, gb_pb_off[GEN_MAX_LIN] = {};
@@ -174,10 +205,7 @@ struct promp_ctx {
     bool learn_std = true;               // false: log_std is neither adapted (step size 0) nor trained (no Adam update)
     int fuse_min_tasks = 1 << 30;        // k_chain_hvp sums a task's partial rows in-launch from this many local tasks on (default: never)
     int stats_slot = 0;                  // promp_optimize parks the first epoch's statistics in slot 1 (loss_before)
-    const float* pass_adv = nullptr;     // launch_pass: per-row weights instead of the step's advantages (DiCE coupling pass)
-    float* pass_row_tan = nullptr;       // launch_pass (R-operator pass): where the rows' log-likelihood tangents go
-    int pass_cache = 0;                  // launch_pass: 1 = the gradient pass fills the step's primal cache, 2 = the R-operator pass reads it
-    int primal_cache = -1;               // promp_set_primal_cache: 1 on, 0 off, -1 default (on: primal_cache_worth)
+    int primal_cache = -1;               // promp_set_primal_cache: 1 on, 0 off, -1 default (on: primal_cache_on)
     // promp_inner_adapt(step 0) from the meta-parameters evaluates exactly what the first epoch of the following optimisation
     // evaluates first (the inner pass at theta on step 0's slab): it leaves theta', the inner scalars and the primal cache
     // where that epoch expects them, and the epoch skips its pass while nothing it depends on has changed (reuse_adapt).
@@ -194,8 +222,6 @@ struct promp_ctx {
     struct { bool valid = false; unsigned long long theta_version = 0, sizes_version = 0, data_version[PROMP_ETA_MAX + 1] = {},
              tag[PROMP_ETA_MAX + 1] = {}; int inner_kind = 0; float min_log_std = 0.f; } chvp;
     long long chvp_cached_passes = 0;          // R-operator passes of promp_constraint_hvp that read a primal cache (tests, tools)
-    float* pass_next2 = nullptr;         // launch_pass: second destinations of the RED_STEP reduction (see adapt0)
-    float* pass_scal2 = nullptr;
     long long adapt_passes_skipped = 0;
     bool force_split = false;            // take the multi-rank launch sequence (reduce / all-reduce / Adam) on one rank too
     bool fixed_order = false;            // exchange = ncclAllGather + sum in rank order (bitwise-identical replicas) instead of ncclAllReduce
@@ -221,6 +247,12 @@ template <class T>
 int dev_alloc(T** p, size_t n) {
     HIPCHECK(hipMalloc((void**)p, (n ? n : 1) * sizeof(T)));
     HIPCHECK(hipMemset(*p, 0, (n ? n : 1) * sizeof(T)));
+    return 0;
+}
+// lets each kernel take up to `bytes` of dynamic LDS
+template <class... Kernels>
+int allow_lds(int bytes, Kernels... kernels) {
+    for (const void* k : {(const void*)kernels...}) HIPCHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
     return 0;
 }
 
@@ -294,13 +326,7 @@ bool policy_shape_generic(const promp_dims* d) {   // layer-by-layer kernels (pr
     const HiddenList L = hidden_list(d);
     return L.n != 2 || d->obs_dim > 128 || d->act_dim > 8 || d->hidden1 > 128 || d->hidden2 > 128 || d->hidden_act != PROMP_ACT_TANH;      // (an output nonlinearity sits in the upper bits: != too)
 }
-bool policy_shape_chain(const promp_dims* d) {     // register-chained kernels: hidden widths from {32, 64}, obs_dim <= 32
-    return !policy_shape_generic(d) && d->obs_dim <= 32 && (d->hidden1 == 32 || d->hidden1 == 64) && (d->hidden2 == 32 || d->hidden2 == 64);
-}
 int wb_nko(int cls) { return cls == 1 ? 4 : cls == 2 ? 7 : 8; }      // K = 16 steps of the observation per class
-bool policy_shape_coop(const promp_dims* d) {      // cooperative kernels: (128,128), or (64,64) with wide observations
-    return !policy_shape_generic(d) && d->hidden1 == d->hidden2 && (d->hidden1 == 128 || (d->hidden1 == 64 && d->obs_dim > 32));
-}
 
 int check_dims(const promp_dims* d) {
     if (!d) return fail(-1, "dims is NULL");
@@ -377,6 +403,24 @@ int prof_collect(promp_ctx* c) {
 }
 
 // ---- launches ----------------------------------------------------------------------------------
+// One layer's GEMM (k_gen_linear's MODE: GEN_FWD / GEN_BWD, the R-operator pass's GEN_FWD_T / GEN_BWD_T) or weight gradient
+// (NT = 1, 2 with the tangents): on the BF16 matrix pipe, or the exact-FP32 kernels when PROMP_GEN_FP32=1 cleared gen_bf16.
+template <int MODE, int NBW>
+void gen_linear(promp_ctx* c, dim3 grid, const GenArgs& g, int li, int pp) {
+    const int nt = (MODE == GEN_FWD_T || MODE == GEN_BWD_T) ? 2 : 1;
+    if (c->gen_bf16) { auto k = k_gb_linear<MODE, NBW>; PROMP_LAUNCH(k, grid, 256, gb_smem(nt, NBW), c->stream, g, li, pp); }
+    else { auto k = k_gen_linear<MODE, NBW>; PROMP_LAUNCH(k, grid, 256, gen_linear_smem(MODE, NBW), c->stream, g, li, pp); }
+}
+template <int NT, int NBW>
+void gen_wgrad(promp_ctx* c, const StepData& S, const GenArgs& g, int li, int pp) {
+    if (c->gen_bf16) {
+        auto k = k_gb_wgrad<NT, NBW>;
+        PROMP_LAUNCH(k, dim3(S.n_work[0] * Ly_K_slabs(c->lin[li].K)), 256, gb_smem(NT, NBW), c->stream, g, li, pp);
+    } else {      // one slab of 64 input units per workgroup
+        auto k = k_gen_wgrad<NT, NBW>;
+        PROMP_LAUNCH(k, dim3(S.n_work[0], (c->lin[li].K + GEN_KC - 1) / GEN_KC), 256, gen_wgrad_smem(NT, c->lin[li].N), c->stream, g, li, pp);
+    }
+}
 // A pass on the layer-by-layer kernels (promp_kernels_generic.h): forward chain, loss level, then per layer (output first) the
 // weight gradient and the cotangent of the layer below.  One workgroup per entry of work table 0 in every launch; the partial
 // rows are the cooperative kernels' (one per work item, summed by k_reduce_task).
@@ -403,8 +447,7 @@ int launch_pass_generic(promp_ctx* c, StepData& S, const PassArgs& a, bool hvp, 
     // k_gen_linear / k_gb_linear: the 64-row rounds of a work item (about one CU's share of the rows) dealt to GEN_SPLIT workgroups
     const dim3 lgrid(S.n_work[0], GEN_SPLIT);
     hipStream_t st = c->stream;
-    const bool bf = c->gen_bf16;
-    if (bf) {
+    if (c->gen_bf16) {
         // the parameters' (and minus the direction's) kernels as BF16 planes, both orientations, in the GEMMs' chunk order
         GbPlaneArgs pa;
         memset(&pa, 0, sizeof pa);
@@ -429,12 +472,7 @@ int launch_pass_generic(promp_ctx* c, StepData& S, const PassArgs& a, bool hvp, 
     }
     for (int li = 0; li < c->n_lin; ++li) {
         const int nbw = (c->lin[li].N + 63) / 64;
-        PROMP_GEN_NBW(nbw,
-            if (bf) {
-                if (hvp) { auto k = k_gb_linear<GEN_FWD_T, NBW>; PROMP_LAUNCH(k, lgrid, 256, gb_smem(2, NBW), st, g, li, 0); }
-                else { auto k = k_gb_linear<GEN_FWD, NBW>; PROMP_LAUNCH(k, lgrid, 256, gb_smem(1, NBW), st, g, li, 0); }
-            } else if (hvp) { auto k = k_gen_linear<GEN_FWD_T, NBW>; PROMP_LAUNCH(k, lgrid, 256, gen_linear_smem(GEN_FWD_T, NBW), st, g, li, 0); }
-            else { auto k = k_gen_linear<GEN_FWD, NBW>; PROMP_LAUNCH(k, lgrid, 256, gen_linear_smem(GEN_FWD, NBW), st, g, li, 0); })
+        PROMP_GEN_NBW(nbw, if (hvp) gen_linear<GEN_FWD_T, NBW>(c, lgrid, g, li, 0); else gen_linear<GEN_FWD, NBW>(c, lgrid, g, li, 0);)
     }
     if (hvp) { auto k = k_gen_loss<true, true>; PROMP_LAUNCH(k, grid, 256, gen_loss_smem(g.A), st, g, 0); }
     else if (fwd_only) { auto k = k_gen_loss<false, false>; PROMP_LAUNCH(k, grid, 256, gen_loss_smem(g.A), st, g, 0); }
@@ -442,22 +480,10 @@ int launch_pass_generic(promp_ctx* c, StepData& S, const PassArgs& a, bool hvp, 
     int pp = 0;
     for (int li = c->n_lin - 1; li >= 0 && !fwd_only; --li) {
         const int nbw = (c->lin[li].N + 63) / 64;
-        const dim3 wgrid(S.n_work[0], (c->lin[li].K + GEN_KC - 1) / GEN_KC);     // one slab of 64 input units per workgroup
-        PROMP_GEN_NBW(nbw,
-            if (bf) {
-                const dim3 bgrid(S.n_work[0] * Ly_K_slabs(c->lin[li].K));
-                if (hvp) { auto k = k_gb_wgrad<2, NBW>; PROMP_LAUNCH(k, bgrid, 256, gb_smem(2, NBW), st, g, li, pp); }
-                else { auto k = k_gb_wgrad<1, NBW>; PROMP_LAUNCH(k, bgrid, 256, gb_smem(1, NBW), st, g, li, pp); }
-            } else if (hvp) { auto k = k_gen_wgrad<2, NBW>; PROMP_LAUNCH(k, wgrid, 256, gen_wgrad_smem(2, c->lin[li].N), st, g, li, pp); }
-            else { auto k = k_gen_wgrad<1, NBW>; PROMP_LAUNCH(k, wgrid, 256, gen_wgrad_smem(1, c->lin[li].N), st, g, li, pp); })
+        PROMP_GEN_NBW(nbw, if (hvp) gen_wgrad<2, NBW>(c, S, g, li, pp); else gen_wgrad<1, NBW>(c, S, g, li, pp);)
         if (li == 0) break;
         const int nbk = (c->lin[li].K + 63) / 64;
-        PROMP_GEN_NBW(nbk,
-            if (bf) {
-                if (hvp) { auto k = k_gb_linear<GEN_BWD_T, NBW>; PROMP_LAUNCH(k, lgrid, 256, gb_smem(2, NBW), st, g, li, pp); }
-                else { auto k = k_gb_linear<GEN_BWD, NBW>; PROMP_LAUNCH(k, lgrid, 256, gb_smem(1, NBW), st, g, li, pp); }
-            } else if (hvp) { auto k = k_gen_linear<GEN_BWD_T, NBW>; PROMP_LAUNCH(k, lgrid, 256, gen_linear_smem(GEN_BWD_T, NBW), st, g, li, pp); }
-            else { auto k = k_gen_linear<GEN_BWD, NBW>; PROMP_LAUNCH(k, lgrid, 256, gen_linear_smem(GEN_BWD, NBW), st, g, li, pp); })
+        PROMP_GEN_NBW(nbk, if (hvp) gen_linear<GEN_BWD_T, NBW>(c, lgrid, g, li, pp); else gen_linear<GEN_BWD, NBW>(c, lgrid, g, li, pp);)
         pp ^= 1;
     }
     HIPCHECK(hipGetLastError());
@@ -480,149 +506,156 @@ int enqueue_obs_range(promp_ctx* c, StepData& S, hipStream_t st) {
     return 0;
 }
 
-// Does the gradient pass fill the primal cache for the R-operator pass behind it?  promp_set_primal_cache: 1 / 0; -1 (default) = yes at
-// every size.  Through round 5 the default was "from two rounds of tiles per compute unit" (a small shard's passes are all fixed cost
-// and the stores cost what the R-operator pass got back: 0.750 vs 0.737 ms per step at 5 tasks).  Since the cache-reading instance
-// runs every product on the FP16 pipe (round 6: 12.2 k cycles per tile against 26.3 k for the recomputing one) the cache pays on
-// small shards too: 0.516 vs 0.545 ms at 5 tasks, 0.475 vs 0.485 at 3 (two A/B pairs, one box).
-static bool primal_cache_worth(const promp_ctx* c, long long n_rows) {
-    (void)n_rows;
-    return c->primal_cache != 0;
+// Does the gradient pass fill the primal cache for the R-operator pass behind it?  Only the Chain family keeps one (the cooperative
+// kernels keep theta' and the scalars only).  promp_set_primal_cache: 1 / 0; -1 (default) = yes at every size.  Through round 5 the
+// default was "from two rounds of tiles per compute unit" (a small shard's passes are all fixed cost and the stores cost what the
+// R-operator pass got back: 0.750 vs 0.737 ms per step at 5 tasks).  Since the cache-reading instance runs every product on the
+// FP16 pipe (round 6: 12.2 k cycles per tile against 26.3 k for the recomputing one) the cache pays on small shards too: 0.516 vs
+// 0.545 ms at 5 tasks, 0.475 vs 0.485 at 3 (two A/B pairs, one box).
+static bool primal_cache_on(const promp_ctx* c) { return c->family == PassFamily::Chain && c->primal_cache != 0; }
+// the step's primal cache (promp_kernels_chain.h: chain_cache_row), allocated on first use
+static int ensure_primal_cache(promp_ctx* c, StepData& S) {
+    if (S.hcache) return 0;
+    return dev_alloc(&S.hcache, ((size_t)c->d.max_rows + 16 * (size_t)c->d.n_tasks) * chain_cache_row(c->d.hidden1, c->d.hidden2));
 }
 
-// One policy pass over a step's slabs plus the per-task reduction that consumes it:
-//   red_mode RED_STEP / RED_OUTER / RED_HVP / RED_PLAIN / RED_SCAL (promp_kernels_chain.h).
-// k_chain_hvp can do both in one launch; k_pass and the cooperative kernels (hidden 128 / wide observations) are
-// followed by k_reduce_task.
-int launch_pass(promp_ctx* c, StepData& S, bool hvp, const float* theta, long long theta_stride, int loss_kind,
-                float clip_eps, int clip_ls, float klw, bool fwd_only, int red_mode, const float* cur, long long cur_stride,
-                float* next, float* scal) {
+// Chain: k_chain_hvp reduces in-launch when a.fuse_reduce says so; k_pass is followed by k_reduce_task
+static void launch_chain(promp_ctx* c, StepData& S, const PassArgs& a, const PassReq& q, int cache) {
+    const int n1 = c->d.hidden1 / 16, n2 = c->d.hidden2 / 16, ks = chain_ksteps(c->d.obs_dim);
+    const dim3 grid(S.n_chain_wg);
+    if (q.hvp) {
+#define PROMP_CHAIN_CASE(N1, N2, KS)                                                                                             \
+    if (n1 == N1 && n2 == N2 && ks == KS) {                                                                                      \
+        if (cache == 2) { auto k = k_chain_hvp<N1, N2, KS, CHAIN_NW_HVP, true>; PROMP_LAUNCH(k, grid, 64 * CHAIN_NW_HVP, c->smem_hvp, c->stream, a); } \
+        else { auto k = k_chain_hvp<N1, N2, KS, CHAIN_NW_HVP, false>; PROMP_LAUNCH(k, grid, 64 * CHAIN_NW_HVP, c->smem_hvp, c->stream, a); }           \
+    }
+        PROMP_CHAIN_ALL(PROMP_CHAIN_CASE)
+#undef PROMP_CHAIN_CASE
+        return;
+    }
+#define PROMP_PASS_CASE(N1, N2)                                                                                                          \
+    if (n1 == N1 && n2 == N2) {                                                                                                          \
+        if (q.fwd_only) { auto k = k_pass<N1, N2, CHAIN_NW_HVP, false, false>; PROMP_LAUNCH(k, grid, 64 * CHAIN_NW_HVP, c->smem_fwd, c->stream, a); }   \
+        else if (cache == 1) { auto k = k_pass<N1, N2, CHAIN_NW_HVP, true, true>; PROMP_LAUNCH(k, grid, 64 * CHAIN_NW_HVP, c->smem_fwd, c->stream, a); } \
+        else { auto k = k_pass<N1, N2, CHAIN_NW_HVP, true, false>; PROMP_LAUNCH(k, grid, 64 * CHAIN_NW_HVP, c->smem_fwd, c->stream, a); }            \
+    }
+    PROMP_PASS_ALL(PROMP_PASS_CASE)
+#undef PROMP_PASS_CASE
+}
+
+// CoopFp32: hidden 128, or hidden 64 with obs_dim > 32 (promp_kernels_policy_wide.h)
+static void launch_coop_fp32(promp_ctx* c, StepData& S, const PassArgs& a, const PassReq& q) {
+    const int nob = wide_nob(c->d.obs_dim);
+    const size_t sm = q.hvp ? c->smem_hvp : c->smem_fwd;
+#define PROMP_WIDE_CASE(HH, NOB)                                                                                                \
+    if (c->d.hidden1 == HH && nob == NOB) {                                                                                      \
+        if (q.hvp) { auto k = k_wide_hvp<HH, NOB>; PROMP_LAUNCH(k, dim3(S.n_work[0]), 4 * HH, sm, c->stream, a); }               \
+        else if (q.fwd_only) { auto k = k_wide_fwd_bwd<HH, NOB, false>; PROMP_LAUNCH(k, dim3(S.n_work[0]), 4 * HH, sm, c->stream, a); } \
+        else { auto k = k_wide_fwd_bwd<HH, NOB, true>; PROMP_LAUNCH(k, dim3(S.n_work[0]), 4 * HH, sm, c->stream, a); }            \
+    }
+    PROMP_WIDE_ALL(PROMP_WIDE_CASE)
+#undef PROMP_WIDE_CASE
+}
+
+// CoopSplit: two layers of 128 units on the BF16 matrix pipe (promp_kernels_wide_bf16.h), behind the small launches that lay the
+// parameters' (and the direction's) hidden kernels out as BF16 planes in fragment order (276 KB per task)
+static void launch_coop_split(promp_ctx* c, StepData& S, PassArgs& a, const PassReq& q) {
+    const int nko = wb_nko(c->wb_cls);
+    WbPlaneArgs pa;
+    const bool at_meta = q.theta == c->theta && q.theta_stride == 0 && c->wb_planes_meta;
+    const bool standing = at_meta && c->wbp.valid && c->wbp.theta_version == c->theta_version && c->wbp.data_version == S.data_version &&
+                          c->wbp.sizes_version == c->sizes_version && c->wbp.step == (const void*)&S;
+    pa.src = q.theta; pa.src_stride = q.theta_stride; pa.dst = at_meta ? c->wb_planes_meta : c->wb_planes; pa.O = c->d.obs_dim; pa.A = c->d.act_dim; pa.NKO = nko; pa.row_sign = 1.f;
+    pa.obs_absmax = a.obs_absmax; pa.vec_absmax = nullptr;       // FP16 split: the hidden_0 kernel takes the inverse of the observations' scale
+    // (one copy per task even when the tasks share their parameters: the hidden_0 kernel's planes carry the task's observation scale)
+    const bool per_task = q.theta_stride != 0 || PROMP_NT == 2;
+    if (!standing) PROMP_LAUNCH(k_wb_planes, dim3((4 * (nko + 16) * 64 + 256 + 255) / 256, per_task ? c->d.n_tasks : 1), 256, 0, c->stream, pa);
+    if (at_meta) {
+        c->wbp.valid = true; c->wbp.theta_version = c->theta_version; c->wbp.data_version = S.data_version;
+        c->wbp.sizes_version = c->sizes_version; c->wbp.step = (const void*)&S;
+    }
+    a.wb_theta_planes = pa.dst;
+    a.wb_plane_stride = per_task ? wb_planes_words(nko) : 0;
+    if (q.hvp) {
+        // the direction's planes carry its scale: its largest entry per task first (one small launch)
+        VecAbsmaxArgs va;
+        va.src = c->vbuf; va.stride = c->NP; va.n = c->NP; va.out = c->vdir_absmax;
+        va.n_w1 = c->d.obs_dim * c->d.hidden1; va.obs_absmax = a.obs_absmax;
+        PROMP_LAUNCH(k_vec_absmax, dim3(c->d.n_tasks), 1024, 64, c->stream, va);
+        a.vdir_absmax = (const float*)c->vdir_absmax;
+        pa.src = c->vbuf; pa.src_stride = c->NP; pa.dst = c->wb_vplanes; pa.vec_absmax = a.vdir_absmax;
+        PROMP_LAUNCH(k_wb_planes, dim3((4 * (nko + 16) * 64 + 256 + 255) / 256, c->d.n_tasks), 256, 0, c->stream, pa);
+        a.wb_v_planes = c->wb_vplanes;
+    }
+#define PROMP_WB_CASE(CLS, NKO, NXB)                                                                                              \
+    if (c->wb_cls == CLS) {                                                                                                       \
+        if (q.hvp) { auto k = k_wb_hvp<NKO, NXB>; PROMP_LAUNCH(k, dim3(S.n_work[0]), 256, c->smem_wb_hvp, c->stream, a); }          \
+        else if (q.fwd_only) { auto k = k_wb_fwd_bwd<NKO, NXB, false>; PROMP_LAUNCH(k, dim3(S.n_work[0]), 256, c->smem_wb_fwd, c->stream, a); } \
+        else { auto k = k_wb_fwd_bwd<NKO, NXB, true>; PROMP_LAUNCH(k, dim3(S.n_work[0]), 256, c->smem_wb_bwd, c->stream, a); }       \
+    }
+    PROMP_WB_ALL(PROMP_WB_CASE)
+#undef PROMP_WB_CASE
+}
+
+// One policy pass over a step's slabs plus the per-task reduction that consumes it (q.red_mode, promp_kernels_chain.h).
+// k_chain_hvp can do both in one launch; every other pass kernel is followed by k_reduce_task.
+int launch_pass(promp_ctx* c, StepData& S, const PassReq& q) {
     if (!S.has_policy) return fail(-3, "step has no actions / agent_infos uploaded");
     if (!S.has_adv) return fail(-3, "step has no advantages: call promp_process_samples or promp_set_advantages first");
-    if (!policy_shape_chain(&c->d) && !c->wide && !c->generic)
-        return fail(-1, "internal: no pass kernel for this policy shape");
     if (!S.obs_range_valid && enqueue_obs_range(c, S, c->stream)) return -2;
+    const bool chain = c->family == PassFamily::Chain;
     PassArgs a;
     memset(&a, 0, sizeof a);
     a.obs_absmax = (const float*)S.obs_absmax;
-    a.obs = S.obs; a.act = S.act; a.adv = c->pass_adv ? c->pass_adv : S.adv32; a.old_mean = S.old_mean; a.old_log_std = S.old_ls;
-    a.row_tan = hvp ? c->pass_row_tan : nullptr;
-    const int cache = (c->wide || c->generic || fwd_only || !S.hcache) ? 0 : c->pass_cache;
+    a.obs = S.obs; a.act = S.act; a.adv = q.adv ? q.adv : S.adv32; a.old_mean = S.old_mean; a.old_log_std = S.old_ls;
+    a.row_tan = q.hvp ? q.row_tan : nullptr;
+    const int cache = (!chain || q.fwd_only || !S.hcache) ? 0 : q.cache;
     a.hcache = cache ? S.hcache : nullptr;
     if (cache == 1) S.cache_tag = ++c->cache_counter;
     a.ls_per_row = S.ls_per_row;
     a.task_row_offsets = S.task_row_offsets;
     a.work = S.work[0];
     a.segs = S.chain_segs; a.wg_seg_offsets = S.chain_wg_offsets;
-    a.theta = theta; a.theta_task_stride = theta_stride;
+    a.theta = q.theta; a.theta_task_stride = q.theta_stride;
     a.vdir = c->vbuf;
     a.partials = c->partials; a.partial_stride = c->partial_stride;
     a.O = c->d.obs_dim; a.A = c->d.act_dim;
-    a.loss_kind = loss_kind; a.clip_eps = clip_eps; a.clip_log_std = clip_ls;
+    a.loss_kind = q.loss_kind; a.clip_eps = q.clip_eps; a.clip_log_std = q.clip_ls;
     a.min_log_std = c->min_log_std;   // GaussianMLPPolicy min_std (policies/gaussian_mlp_policy.py:31,35)
-    a.kl_weight = klw;
+    a.kl_weight = q.klw;
     a.task_counters = c->task_counters; a.task_slot_offsets = S.chain_slot_offsets;
     // In-launch reduction (the last-arriving workgroup of a task sums its partial rows) against the grid-wide k_reduce_task
     // behind the launch: with few tasks every task finishes at once and one workgroup per task streaming ~50 partial rows
     // is exposed (66 us vs 46 + 5 us at 5 tasks); with 40 tasks the sums partly hide under other tasks' tiles, but since
     // k_reduce_task keeps eight rows per thread in flight the separate launch wins there too (123 + 5 us vs 137 us with the
     // primal cache, 147 + 5 vs 162 us without).  The in-launch form stays available (promp_set_schedule).
-    a.fuse_reduce = (hvp && !c->wide && !c->generic && c->d.n_tasks >= c->fuse_min_tasks) ? 1 : 0;
-    a.red_mode = red_mode; a.step_sizes = c->step_sizes; a.cur = cur; a.cur_task_stride = cur_stride; a.next = next;
+    a.fuse_reduce = (q.hvp && chain && c->d.n_tasks >= c->fuse_min_tasks) ? 1 : 0;
+    float* scal = q.scal ? q.scal : c->scal_tmp;
+    a.red_mode = q.red_mode; a.step_sizes = c->step_sizes; a.cur = q.cur; a.cur_task_stride = q.cur_stride; a.next = q.next;
     a.lam = c->lam; a.v = c->vbuf; a.scal = scal;
     a.dbg = c->dbg_enabled ? c->dbg : nullptr;
     a.split_events = c->split_events;
-    const int id = hvp ? PROMP_KERNEL_HVP : fwd_only ? PROMP_KERNEL_FWD : PROMP_KERNEL_FWD_BWD;
+    const int id = q.hvp ? PROMP_KERNEL_HVP : q.fwd_only ? PROMP_KERNEL_FWD : PROMP_KERNEL_FWD_BWD;
     // (the timed slot covers the pass with the small launches that prepare its operands: k_wb_planes, k_vec_absmax)
     if (prof_begin(c, id, S.n_rows)) return -2;
-    if (c->wbf) {
-        // the parameters' (and the direction's) hidden kernels as BF16 planes in fragment order (one small launch each: 276 KB per task)
-        const int nko = wb_nko(c->wbf);
-        WbPlaneArgs pa;
-        const bool at_meta = theta == c->theta && theta_stride == 0 && c->wb_planes_meta;
-        const bool standing = at_meta && c->wbp.valid && c->wbp.theta_version == c->theta_version && c->wbp.data_version == S.data_version &&
-                              c->wbp.sizes_version == c->sizes_version && c->wbp.step == (const void*)&S;
-        pa.src = theta; pa.src_stride = theta_stride; pa.dst = at_meta ? c->wb_planes_meta : c->wb_planes; pa.O = c->d.obs_dim; pa.A = c->d.act_dim; pa.NKO = nko; pa.row_sign = 1.f;
-        pa.obs_absmax = a.obs_absmax; pa.vec_absmax = nullptr;       // FP16 split: the hidden_0 kernel takes the inverse of the observations' scale
-        // (one copy per task even when the tasks share their parameters: the hidden_0 kernel's planes carry the task's observation scale)
-        const bool per_task = theta_stride != 0 || PROMP_NT == 2;
-        if (!standing) PROMP_LAUNCH(k_wb_planes, dim3((4 * (nko + 16) * 64 + 256 + 255) / 256, per_task ? c->d.n_tasks : 1), 256, 0, c->stream, pa);
-        if (at_meta) {
-            c->wbp.valid = true; c->wbp.theta_version = c->theta_version; c->wbp.data_version = S.data_version;
-            c->wbp.sizes_version = c->sizes_version; c->wbp.step = (const void*)&S;
-        }
-        a.wb_theta_planes = pa.dst;
-        a.wb_plane_stride = per_task ? wb_planes_words(nko) : 0;
-        if (hvp) {
-            // the direction's planes carry its scale: its largest entry per task first (one small launch)
-            VecAbsmaxArgs va;
-            va.src = c->vbuf; va.stride = c->NP; va.n = c->NP; va.out = c->vdir_absmax;
-            va.n_w1 = c->d.obs_dim * c->d.hidden1; va.obs_absmax = a.obs_absmax;
-            PROMP_LAUNCH(k_vec_absmax, dim3(c->d.n_tasks), 1024, 64, c->stream, va);
-            a.vdir_absmax = (const float*)c->vdir_absmax;
-            pa.src = c->vbuf; pa.src_stride = c->NP; pa.dst = c->wb_vplanes; pa.vec_absmax = a.vdir_absmax;
-            PROMP_LAUNCH(k_wb_planes, dim3((4 * (nko + 16) * 64 + 256 + 255) / 256, c->d.n_tasks), 256, 0, c->stream, pa);
-            a.wb_v_planes = c->wb_vplanes;
-        }
-    }
-    if (c->generic) {
-        if (launch_pass_generic(c, S, a, hvp, fwd_only)) return -2;
-    } else if (c->wbf) {
-        // two layers of 128 units on the BF16 matrix pipe (promp_kernels_wide_bf16.h)
-#define PROMP_WB_CASE(CLS, NKO, NXB)                                                                                              \
-    if (c->wbf == CLS) {                                                                                                          \
-        if (hvp) { auto k = k_wb_hvp<NKO, NXB>; PROMP_LAUNCH(k, dim3(S.n_work[0]), 256, c->smem_wb_hvp, c->stream, a); }            \
-        else if (fwd_only) { auto k = k_wb_fwd_bwd<NKO, NXB, false>; PROMP_LAUNCH(k, dim3(S.n_work[0]), 256, c->smem_wb_fwd, c->stream, a); } \
-        else { auto k = k_wb_fwd_bwd<NKO, NXB, true>; PROMP_LAUNCH(k, dim3(S.n_work[0]), 256, c->smem_wb_bwd, c->stream, a); }         \
-    }
-        PROMP_WB_ALL(PROMP_WB_CASE)
-#undef PROMP_WB_CASE
-    } else if (c->wide) {
-        // cooperative kernels (promp_kernels_policy_wide.h): hidden 128, or hidden 64 with obs_dim > 32
-        const int nob = c->d.obs_dim <= 32 ? 2 : c->d.obs_dim <= 64 ? 4 : 8;
-        const size_t sm = hvp ? c->smem_hvp : c->smem_fwd;
-#define PROMP_WIDE_CASE(HH, NOB)                                                                                                \
-    if (c->d.hidden1 == HH && nob == NOB) {                                                                                      \
-        if (hvp) { auto k = k_wide_hvp<HH, NOB>; PROMP_LAUNCH(k, dim3(S.n_work[0]), 4 * HH, sm, c->stream, a); }                 \
-        else if (fwd_only) { auto k = k_wide_fwd_bwd<HH, NOB, false>; PROMP_LAUNCH(k, dim3(S.n_work[0]), 4 * HH, sm, c->stream, a); } \
-        else { auto k = k_wide_fwd_bwd<HH, NOB, true>; PROMP_LAUNCH(k, dim3(S.n_work[0]), 4 * HH, sm, c->stream, a); }            \
-    }
-        PROMP_WIDE_CASE(128, 2) PROMP_WIDE_CASE(128, 4) PROMP_WIDE_CASE(128, 8) PROMP_WIDE_CASE(64, 2) PROMP_WIDE_CASE(64, 4) PROMP_WIDE_CASE(64, 8)
-#undef PROMP_WIDE_CASE
-    } else if (hvp) {
-        // register-chained R-operator pass: the per-task reduction happens inside the launch (last-arriving workgroup)
-        const int n1 = c->d.hidden1 / 16, n2 = c->d.hidden2 / 16, ks = chain_ksteps(c->d.obs_dim);
-#define PROMP_CHAIN_CASE(N1, N2, KS)                                                                                             \
-    if (n1 == N1 && n2 == N2 && ks == KS) {                                                                                      \
-        if (cache == 2) { auto k = k_chain_hvp<N1, N2, KS, CHAIN_NW_HVP, true>; PROMP_LAUNCH(k, dim3(S.n_chain_wg), 64 * CHAIN_NW_HVP, c->smem_hvp, c->stream, a); } \
-        else { auto k = k_chain_hvp<N1, N2, KS, CHAIN_NW_HVP, false>; PROMP_LAUNCH(k, dim3(S.n_chain_wg), 64 * CHAIN_NW_HVP, c->smem_hvp, c->stream, a); }           \
-    }
-        PROMP_CHAIN_ALL(PROMP_CHAIN_CASE)
-#undef PROMP_CHAIN_CASE
-        HIPCHECK(hipGetLastError());
-        if (a.fuse_reduce) return prof_end(c, id);
-    } else {
-        const int n1 = c->d.hidden1 / 16, n2 = c->d.hidden2 / 16;
-#define PROMP_PASS_CASE(N1, N2)                                                                                                          \
-    if (n1 == N1 && n2 == N2) {                                                                                                          \
-        if (fwd_only) { auto k = k_pass<N1, N2, CHAIN_NW_HVP, false, false>; PROMP_LAUNCH(k, dim3(S.n_chain_wg), 64 * CHAIN_NW_HVP, c->smem_fwd, c->stream, a); }   \
-        else if (cache == 1) { auto k = k_pass<N1, N2, CHAIN_NW_HVP, true, true>; PROMP_LAUNCH(k, dim3(S.n_chain_wg), 64 * CHAIN_NW_HVP, c->smem_fwd, c->stream, a); } \
-        else { auto k = k_pass<N1, N2, CHAIN_NW_HVP, true, false>; PROMP_LAUNCH(k, dim3(S.n_chain_wg), 64 * CHAIN_NW_HVP, c->smem_fwd, c->stream, a); }            \
-    }
-        PROMP_PASS_ALL(PROMP_PASS_CASE)
-#undef PROMP_PASS_CASE
+    switch (c->family) {
+    case PassFamily::Chain: launch_chain(c, S, a, q, cache); break;
+    case PassFamily::CoopFp32: launch_coop_fp32(c, S, a, q); break;
+    case PassFamily::CoopSplit: launch_coop_split(c, S, a, q); break;
+    case PassFamily::Layered: if (launch_pass_generic(c, S, a, q.hvp, q.fwd_only)) return -2; break;
     }
     HIPCHECK(hipGetLastError());
     if (prof_end(c, id)) return -2;
+    if (a.fuse_reduce) return 0;
     ReduceArgs r;
     r.partials = c->partials; r.partial_stride = c->partial_stride;
     // the register-chained kernels write one row per segment
-    r.task_wg_offsets = (c->wide || c->generic) ? S.task_wg_offsets[0] : S.chain_slot_offsets;
+    r.task_wg_offsets = chain ? S.chain_slot_offsets : S.task_wg_offsets[0];
     r.NP = c->NP;
-    r.step_sizes = c->step_sizes; r.mode = red_mode;
-    r.cur = cur; r.cur_task_stride = cur_stride; r.next = next;
+    r.step_sizes = c->step_sizes; r.mode = q.red_mode;
+    r.cur = q.cur; r.cur_task_stride = q.cur_stride; r.next = q.next;
     r.lam = c->lam; r.v = c->vbuf; r.scal = scal;
-    r.next2 = red_mode == RED_STEP ? c->pass_next2 : nullptr; r.scal2 = red_mode == RED_STEP ? c->pass_scal2 : nullptr;
+    r.next2 = q.red_mode == RED_STEP ? q.next2 : nullptr; r.scal2 = q.red_mode == RED_STEP ? q.scal2 : nullptr;
     PROMP_LAUNCH(k_reduce_task, dim3((c->NP + 2 + 255) / 256, c->d.n_tasks), 256, 0, c->stream, r);
     HIPCHECK(hipGetLastError());
     return 0;
@@ -641,7 +674,7 @@ static bool adapt0_stands(const promp_ctx* c, int inner_kind, bool cached) {
     return c->reuse_adapt && c->adapt0.valid && c->adapt0.theta_version == c->theta_version &&
            c->adapt0.data_version == c->steps[0].data_version && c->adapt0.sizes_version == c->sizes_version &&
            c->adapt0.inner_kind == inner_kind && c->adapt0.cached == cached && c->adapt0.min_log_std == c->min_log_std &&
-           c->adapt0.learn_std == c->learn_std && c->ls_known && c->ls_min >= c->min_log_std && !c->pass_adv;
+           c->adapt0.learn_std == c->learn_std && c->ls_known && c->ls_min >= c->min_log_std;
 }
 
 // The one exchange of the path (meta_algos/pro_mp.py:122,151,155: the mean over tasks): the ranks' sums of n floats, in place.
@@ -700,10 +733,8 @@ int enqueue_meta(promp_ctx* c, float clip_eps, const float* eta_host, int inner_
         if (join_side(c, c->steps[k])) return -2;
         // the R-operator pass of this step (below) runs at these parameters on this slab: it reads the activations and means
         // back instead of recomputing them (primal cache, promp_kernels_chain.h)
-        const bool worth = primal_cache_worth(c, c->steps[k].n_rows);
-        const bool cached = want_grad && worth && !c->wide && policy_shape_chain(&c->d);
-        if (cached && !c->steps[k].hcache &&
-            dev_alloc(&c->steps[k].hcache, ((size_t)c->d.max_rows + 16 * (size_t)M) * chain_cache_row(c->d.hidden1, c->d.hidden2))) return -2;
+        const bool cached = want_grad && primal_cache_on(c);
+        if (cached && ensure_primal_cache(c, c->steps[k])) return -2;
         // promp_inner_adapt has left exactly this pass's results behind (see there) if nothing it read has changed since and
         // the clip of log_std at log(min_std) -- the one difference between the two -- is not active
         const bool reuse = k == 0 && adapt0_stands(c, inner_kind, cached);
@@ -712,16 +743,20 @@ int enqueue_meta(promp_ctx* c, float clip_eps, const float* eta_host, int inner_
             filled[k] = cached;
             continue;
         }
-        c->pass_cache = cached ? 1 : 0;
-        const int rc0 = launch_pass(c, c->steps[k], false, th, st, loss_kind_inner(inner_kind), clip_eps, k == 0, 0.f, false, RED_STEP, th, st,
-                                    c->chain + (size_t)(k + 1) * MNP, c->scal_inner + (size_t)k * M * 2);
-        c->pass_cache = 0;
-        if (rc0) return -2;
+        PassReq q;
+        q.theta = th; q.theta_stride = st; q.loss_kind = loss_kind_inner(inner_kind); q.clip_eps = clip_eps; q.clip_ls = k == 0;
+        q.red_mode = RED_STEP; q.cur = th; q.cur_stride = st; q.next = c->chain + (size_t)(k + 1) * MNP; q.scal = c->scal_inner + (size_t)k * M * 2;
+        q.cache = cached ? 1 : 0;
+        if (launch_pass(c, c->steps[k], q)) return -2;
         filled[k] = cached;
     }
     if (join_side(c, c->steps[K])) return -2;
-    if (launch_pass(c, c->steps[K], false, c->chain + (size_t)K * MNP, NP, loss_kind_outer(outer_kind), clip_eps, 0, 0.f, !want_grad,
-                    want_grad ? RED_OUTER : RED_SCAL, nullptr, 0, nullptr, c->scal_outer)) return -2;
+    {
+        PassReq q;
+        q.theta = c->chain + (size_t)K * MNP; q.theta_stride = NP; q.loss_kind = loss_kind_outer(outer_kind); q.clip_eps = clip_eps;
+        q.fwd_only = !want_grad; q.red_mode = want_grad ? RED_OUTER : RED_SCAL; q.scal = c->scal_outer;
+        if (launch_pass(c, c->steps[K], q)) return -2;
+    }
     if (want_grad) {
         for (int k = K - 1; k >= 0; --k) {
             const float* th = (k == 0) ? c->theta : c->chain + (size_t)k * MNP;
@@ -729,13 +764,11 @@ int enqueue_meta(promp_ctx* c, float clip_eps, const float* eta_host, int inner_
             StepData& Sk = c->steps[k];
             const bool dice = inner_kind == PROMP_INNER_DICE;
             if (dice && !Sk.has_dice) return fail(-3, "step %d has no DiCE rewards: call promp_set_dice_rewards first", k);
-            c->pass_row_tan = dice ? Sk.dice_c : nullptr;
-            c->pass_cache = filled[k] ? 2 : 0;
-            const int rc1 = launch_pass(c, Sk, true, th, st, loss_kind_inner(inner_kind), clip_eps, k == 0, dice ? 0.f : eta_host[k] / (float)K, false,
-                                        RED_HVP, nullptr, 0, nullptr, c->scal_tmp);
-            c->pass_row_tan = nullptr;
-            c->pass_cache = 0;
-            if (rc1) return -2;
+            PassReq q;
+            q.hvp = true; q.theta = th; q.theta_stride = st; q.loss_kind = loss_kind_inner(inner_kind); q.clip_eps = clip_eps; q.clip_ls = k == 0;
+            q.klw = dice ? 0.f : eta_host[k] / (float)K; q.red_mode = RED_HVP;
+            q.cache = filled[k] ? 2 : 0; q.row_tan = dice ? Sk.dice_c : nullptr;
+            if (launch_pass(c, Sk, q)) return -2;
             if (dice) {
                 // The magic box couples the time steps of a path: H v = H_loglik(w) v + grad_loglik(u(v)), u from the row tangents
                 // c_t = dlogpi_t . v of the pass above (meta_algos/dice_maml.py:245-258).  The pass ran on the direction -v, so its
@@ -745,10 +778,9 @@ int enqueue_meta(promp_ctx* c, float clip_eps, const float* eta_host, int inner_
                 ds.mode = 1;
                 PROMP_LAUNCH(k_dice_scan, dim3(Sk.n_paths), 64, 0, c->stream, ds);
                 HIPCHECK(hipGetLastError());
-                c->pass_adv = Sk.dice_u;
-                const int rc2 = launch_pass(c, Sk, false, th, st, LOSS_LOGLIK, 0.f, k == 0, 0.f, false, RED_HVP, nullptr, 0, nullptr, c->scal_tmp);
-                c->pass_adv = nullptr;
-                if (rc2) return -2;
+                PassReq qc;
+                qc.theta = th; qc.theta_stride = st; qc.loss_kind = LOSS_LOGLIK; qc.clip_ls = k == 0; qc.red_mode = RED_HVP; qc.adv = Sk.dice_u;
+                if (launch_pass(c, Sk, qc)) return -2;
             }
         }
     }
@@ -929,9 +961,15 @@ int promp_ctx_create(promp_ctx** out, int device_id, const promp_dims* user_dims
     c->partial_stride = (c->NP + PROMP_PARTIAL_EXTRA + 3) & ~3;
     const int nblk_max = (c->Dmax + 1 + 15) / 16;
     c->gram_stride = nblk_max * (nblk_max + 1) / 2 * 256;
-    c->wide = policy_shape_coop(dims);
-    c->generic = policy_shape_generic(dims);
-    if (c->generic) {
+    // The pass family, chosen once.  Every shape check_dims accepts falls into exactly one, so launch_pass has a kernel for every
+    // context:
+    //   - policy_shape_generic() (not two layers, obs_dim > 128, act_dim > 8, a width > 128, not tanh): Layered, dims as given;
+    //   - otherwise pad_dims has made the widths (32|64, 32|64) with obs_dim <= 32: Chain; or equal widths of 64 / 128 when
+    //     obs_dim > 32 or a width exceeded 64: the cooperative kernels, CoopSplit for (128,128) with obs_dim <= 127 unless
+    //     PROMP_WIDE_FP32=1 keeps the exact-FP32 CoopFp32 (the A/B switch of the measurements), CoopFp32 for the rest:
+    //     (128,128) with obs_dim 128 and (64,64) with obs_dim > 32.
+    if (policy_shape_generic(dims)) {
+        c->family = PassFamily::Layered;
         const HiddenList L = hidden_list(dims);
         int in = dims->obs_dim, off = 0;
         c->n_lin = L.n + 1;
@@ -948,132 +986,57 @@ int promp_ctx_create(promp_ctx** out, int device_id, const promp_dims* user_dims
             c->gb_pf_off[l] = (int)c->gb_plane_stride; c->gb_plane_stride += gb_f_elems(c->lin[l].K, c->lin[l].N);
             c->gb_pb_off[l] = (int)c->gb_plane_stride; c->gb_plane_stride += gb_b_elems(c->lin[l].K, c->lin[l].N);
         }
-    } else if (c->wide) {
-        const int nob = dims->obs_dim <= 32 ? 2 : dims->obs_dim <= 64 ? 4 : 8;
+    } else if (dims->obs_dim > 32 || dims->hidden1 == 128) {
+        const int nob = wide_nob(dims->obs_dim);
         c->smem_fwd = sizeof(float) * (size_t)make_layout_wide(dims->hidden1, 4, nob, false).total;
         c->smem_hvp = sizeof(float) * (size_t)make_layout_wide(dims->hidden1, 2, nob, true).total;
-        // two layers of 128 units: the first-order pass on the BF16 matrix pipe (float32-equivalent 3-way split).  PROMP_WIDE_FP32=1
-        // (environment, at context creation) keeps the exact-FP32 cooperative kernels -- the A/B switch of the measurements.
+        // two layers of 128 units: the first-order pass on the BF16 matrix pipe (float32-equivalent 3-way split)
         const char* fp32_env = getenv("PROMP_WIDE_FP32");
+        c->family = PassFamily::CoopFp32;
         if (dims->hidden1 == 128 && dims->obs_dim <= 127 && !(fp32_env && atoi(fp32_env) != 0)) {
-            c->wbf = dims->obs_dim <= 63 ? 1 : dims->obs_dim <= 111 ? 2 : 3;
+            c->family = PassFamily::CoopSplit;
+            c->wb_cls = dims->obs_dim <= 63 ? 1 : dims->obs_dim <= 111 ? 2 : 3;
             c->smem_wb_bwd = sizeof(float) * (size_t)wb_layout(false).total;
             c->smem_wb_fwd = c->smem_wb_bwd;
             c->smem_wb_hvp = sizeof(float) * (size_t)wb_layout(true).total;
         }
     } else {
-        // (sized for obs_dim 32: constant offsets in the kernels; contexts with wider observations and these hidden sizes run
-        //  sample processing only -- the policy passes reject them at launch -- and must not fail here on LDS they never use)
-        promp_dims pd = *dims;
-        if (pd.obs_dim > 32) pd.obs_dim = 32;
-        c->smem_fwd = sizeof(float) * (size_t)pass_layout(dims->hidden1 / 16, dims->hidden2 / 16, CHAIN_NW_HVP, param_count(&pd)).total;
+        c->family = PassFamily::Chain;
+        c->smem_fwd = sizeof(float) * (size_t)pass_layout(dims->hidden1 / 16, dims->hidden2 / 16, CHAIN_NW_HVP, c->NP).total;
         // (one size for both instances: the cache-reading one lays LDS out with the backward planes)
-        c->smem_hvp = sizeof(float) * (size_t)std::max(chain_layout(dims->hidden1 / 16, dims->hidden2 / 16, CHAIN_NW_HVP, true, param_count(&pd)).total,
-                                                       chain_layout(dims->hidden1 / 16, dims->hidden2 / 16, CHAIN_NW_HVP, true, param_count(&pd), true).total);
+        c->smem_hvp = sizeof(float) * (size_t)std::max(chain_layout(dims->hidden1 / 16, dims->hidden2 / 16, CHAIN_NW_HVP, true, c->NP).total,
+                                                       chain_layout(dims->hidden1 / 16, dims->hidden2 / 16, CHAIN_NW_HVP, true, c->NP, true).total);
     }
     if (c->smem_hvp > 160 * 1024 || c->smem_fwd > 160 * 1024) {
         const size_t need = c->smem_hvp > c->smem_fwd ? c->smem_hvp : c->smem_fwd;
         promp_ctx_destroy(c);
         return fail(-1, "LDS budget exceeded (%zu bytes)", need);
     }
-    {
-#define PROMP_CHAIN_ATTR(N1, N2, KS)                                                                                        \
-    {                                                                                                                     \
-        auto c2 = k_chain_hvp<N1, N2, KS, CHAIN_NW_HVP, false>; auto c3 = k_chain_hvp<N1, N2, KS, CHAIN_NW_HVP, true>;     \
-        HIPCHECK(hipFuncSetAttribute((const void*)c2, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));           \
-        HIPCHECK(hipFuncSetAttribute((const void*)c3, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));           \
-    }
-        PROMP_CHAIN_ALL(PROMP_CHAIN_ATTR)
-#undef PROMP_CHAIN_ATTR
-#define PROMP_PASS_ATTR(N1, N2)                                                                                             \
-    {                                                                                                                     \
-        auto c0 = k_pass<N1, N2, CHAIN_NW_HVP, true, false>; auto c1 = k_pass<N1, N2, CHAIN_NW_HVP, false, false>;         \
-        auto cs = k_pass<N1, N2, CHAIN_NW_HVP, true, true>;                                                                \
-        HIPCHECK(hipFuncSetAttribute((const void*)cs, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));           \
-        HIPCHECK(hipFuncSetAttribute((const void*)c0, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));           \
-        HIPCHECK(hipFuncSetAttribute((const void*)c1, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));           \
-    }
-        PROMP_PASS_ALL(PROMP_PASS_ATTR)
-#undef PROMP_PASS_ATTR
-#define PROMP_WB_ATTR(CLS, NKO, NXB)                                                                                       \
-    {                                                                                                                     \
-        auto b0 = k_wb_fwd_bwd<NKO, NXB, true>; auto b1 = k_wb_fwd_bwd<NKO, NXB, false>; auto b2 = k_wb_hvp<NKO, NXB>;         \
-        HIPCHECK(hipFuncSetAttribute((const void*)b2, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));           \
-        HIPCHECK(hipFuncSetAttribute((const void*)b0, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));           \
-        HIPCHECK(hipFuncSetAttribute((const void*)b1, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));           \
-    }
-        PROMP_WB_ALL(PROMP_WB_ATTR)
-#undef PROMP_WB_ATTR
-#define PROMP_WIDE_ATTR(HH, NOB)                                                                                          \
-    {                                                                                                                     \
-        auto w0 = k_wide_fwd_bwd<HH, NOB, true>; auto w1 = k_wide_fwd_bwd<HH, NOB, false>; auto w2 = k_wide_hvp<HH, NOB>;   \
-        HIPCHECK(hipFuncSetAttribute((const void*)w0, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));           \
-        HIPCHECK(hipFuncSetAttribute((const void*)w1, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));           \
-        HIPCHECK(hipFuncSetAttribute((const void*)w2, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));           \
-    }
-        PROMP_WIDE_ATTR(128, 2) PROMP_WIDE_ATTR(128, 4) PROMP_WIDE_ATTR(128, 8) PROMP_WIDE_ATTR(64, 2) PROMP_WIDE_ATTR(64, 4) PROMP_WIDE_ATTR(64, 8)
-#undef PROMP_WIDE_ATTR
-        auto g1 = k_gram<1>; auto g2 = k_gram<2>; auto g3 = k_gram<3>; auto g4 = k_gram<4>; auto g5 = k_gram<5>;
-        HIPCHECK(hipFuncSetAttribute((const void*)g1, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHECK(hipFuncSetAttribute((const void*)g2, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHECK(hipFuncSetAttribute((const void*)g3, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHECK(hipFuncSetAttribute((const void*)g4, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHECK(hipFuncSetAttribute((const void*)g5, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHECK(hipFuncSetAttribute((const void*)k_fit, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        {
-            auto f1 = k_fit_wave<12>; auto f2 = k_fit_wave<48>; auto f3 = k_fit_wave<64>; auto f4 = k_fit_wave<45>;
-            HIPCHECK(hipFuncSetAttribute((const void*)f4, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            HIPCHECK(hipFuncSetAttribute((const void*)f1, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            HIPCHECK(hipFuncSetAttribute((const void*)f2, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            HIPCHECK(hipFuncSetAttribute((const void*)f3, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        }
-        HIPCHECK(hipFuncSetAttribute((const void*)k_gram_wide, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        {
-            auto t1 = k_gram_tiled<GRAMT_TB, GRAMT_NWV, GRAMT_NLD>;
-            HIPCHECK(hipFuncSetAttribute((const void*)t1, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        }
-#define PROMP_GEN_ATTR(NBW)                                                                                            \
-    {                                                                                                                \
-        auto w1 = k_gen_wgrad<1, NBW>; auto w2 = k_gen_wgrad<2, NBW>;                                                 \
-        auto l0 = k_gen_linear<GEN_FWD, NBW>; auto l1 = k_gen_linear<GEN_FWD_T, NBW>;                                 \
-        auto l2 = k_gen_linear<GEN_BWD, NBW>; auto l3 = k_gen_linear<GEN_BWD_T, NBW>;                                 \
-        HIPCHECK(hipFuncSetAttribute((const void*)l0, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));      \
-        HIPCHECK(hipFuncSetAttribute((const void*)l1, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));      \
-        HIPCHECK(hipFuncSetAttribute((const void*)l2, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));      \
-        HIPCHECK(hipFuncSetAttribute((const void*)l3, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));      \
-        HIPCHECK(hipFuncSetAttribute((const void*)w1, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));      \
-        HIPCHECK(hipFuncSetAttribute((const void*)w2, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));      \
-        auto bw1 = k_gb_wgrad<1, NBW>; auto bw2 = k_gb_wgrad<2, NBW>;                                                 \
-        auto b0 = k_gb_linear<GEN_FWD, NBW>; auto b1 = k_gb_linear<GEN_FWD_T, NBW>;                                   \
-        auto b2 = k_gb_linear<GEN_BWD, NBW>; auto b3 = k_gb_linear<GEN_BWD_T, NBW>;                                   \
-        HIPCHECK(hipFuncSetAttribute((const void*)b0, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));      \
-        HIPCHECK(hipFuncSetAttribute((const void*)b1, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));      \
-        HIPCHECK(hipFuncSetAttribute((const void*)b2, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));      \
-        HIPCHECK(hipFuncSetAttribute((const void*)b3, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));      \
-        HIPCHECK(hipFuncSetAttribute((const void*)bw1, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));     \
-        HIPCHECK(hipFuncSetAttribute((const void*)bw2, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));     \
-    }
-        PROMP_GEN_ATTR(1) PROMP_GEN_ATTR(2) PROMP_GEN_ATTR(3) PROMP_GEN_ATTR(4)
-#undef PROMP_GEN_ATTR
-        {
-            auto s0 = k_gen_loss<true, true>; auto s1 = k_gen_loss<false, true>; auto s2 = k_gen_loss<false, false>;
-            HIPCHECK(hipFuncSetAttribute((const void*)s0, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_loss_smem(GEN_MAX_A)));
-            HIPCHECK(hipFuncSetAttribute((const void*)s1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_loss_smem(GEN_MAX_A)));
-            HIPCHECK(hipFuncSetAttribute((const void*)s2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_loss_smem(GEN_MAX_A)));
-        }
-        {
-            auto fw32 = k_fit_wide<32>; auto fw16 = k_fit_wide<16>;
-            auto p32 = k_fitw_panel<32>; auto p16 = k_fitw_panel<16>; auto u32 = k_fitw_update<32>; auto u16 = k_fitw_update<16>;
-            auto b32 = k_fitw_back<32>; auto b16 = k_fitw_back<16>;
-            HIPCHECK(hipFuncSetAttribute((const void*)p32, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            HIPCHECK(hipFuncSetAttribute((const void*)p16, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            HIPCHECK(hipFuncSetAttribute((const void*)u32, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            HIPCHECK(hipFuncSetAttribute((const void*)u16, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            HIPCHECK(hipFuncSetAttribute((const void*)b32, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            HIPCHECK(hipFuncSetAttribute((const void*)b16, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            HIPCHECK(hipFuncSetAttribute((const void*)fw32, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            HIPCHECK(hipFuncSetAttribute((const void*)fw16, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        }
+    {   // dynamic LDS past the default limit, for every instance of every family
+        const int lds = 160 * 1024;
+#define PROMP_CHAIN_LDS(N1, N2, KS) if (allow_lds(lds, k_chain_hvp<N1, N2, KS, CHAIN_NW_HVP, false>, k_chain_hvp<N1, N2, KS, CHAIN_NW_HVP, true>)) return -2;
+        PROMP_CHAIN_ALL(PROMP_CHAIN_LDS)
+#undef PROMP_CHAIN_LDS
+#define PROMP_PASS_LDS(N1, N2) \
+    if (allow_lds(lds, k_pass<N1, N2, CHAIN_NW_HVP, true, true>, k_pass<N1, N2, CHAIN_NW_HVP, true, false>, k_pass<N1, N2, CHAIN_NW_HVP, false, false>)) return -2;
+        PROMP_PASS_ALL(PROMP_PASS_LDS)
+#undef PROMP_PASS_LDS
+#define PROMP_WB_LDS(CLS, NKO, NXB) if (allow_lds(lds, k_wb_hvp<NKO, NXB>, k_wb_fwd_bwd<NKO, NXB, true>, k_wb_fwd_bwd<NKO, NXB, false>)) return -2;
+        PROMP_WB_ALL(PROMP_WB_LDS)
+#undef PROMP_WB_LDS
+#define PROMP_WIDE_LDS(HH, NOB) if (allow_lds(lds, k_wide_fwd_bwd<HH, NOB, true>, k_wide_fwd_bwd<HH, NOB, false>, k_wide_hvp<HH, NOB>)) return -2;
+        PROMP_WIDE_ALL(PROMP_WIDE_LDS)
+#undef PROMP_WIDE_LDS
+#define PROMP_GEN_LDS(NBW)                                                                                                   \
+    if (allow_lds(lds, k_gen_linear<GEN_FWD, NBW>, k_gen_linear<GEN_FWD_T, NBW>, k_gen_linear<GEN_BWD, NBW>, k_gen_linear<GEN_BWD_T, NBW>, \
+                  k_gen_wgrad<1, NBW>, k_gen_wgrad<2, NBW>, k_gb_linear<GEN_FWD, NBW>, k_gb_linear<GEN_FWD_T, NBW>,            \
+                  k_gb_linear<GEN_BWD, NBW>, k_gb_linear<GEN_BWD_T, NBW>, k_gb_wgrad<1, NBW>, k_gb_wgrad<2, NBW>)) return -2;
+        PROMP_GEN_LDS(1) PROMP_GEN_LDS(2) PROMP_GEN_LDS(3) PROMP_GEN_LDS(4)
+#undef PROMP_GEN_LDS
+        if (allow_lds((int)gen_loss_smem(GEN_MAX_A), k_gen_loss<true, true>, k_gen_loss<false, true>, k_gen_loss<false, false>)) return -2;
+        if (allow_lds(lds, k_gram<1>, k_gram<2>, k_gram<3>, k_gram<4>, k_gram<5>, k_fit, k_fit_wave<12>, k_fit_wave<48>, k_fit_wave<64>,
+                      k_fit_wave<45>, k_gram_wide, k_gram_tiled<GRAMT_TB, GRAMT_NWV, GRAMT_NLD>, k_fitw_panel<32>, k_fitw_panel<16>,
+                      k_fitw_update<32>, k_fitw_update<16>, k_fitw_back<32>, k_fitw_back<16>, k_fit_wide<32>, k_fit_wide<16>)) return -2;
     }
     const size_t NP = c->NP, MNP = (size_t)M * NP;
     int rc = 0;
@@ -1081,8 +1044,8 @@ int promp_ctx_create(promp_ctx** out, int device_id, const promp_dims* user_dims
     rc |= dev_alloc(&c->adam_m, NP); rc |= dev_alloc(&c->adam_v, NP);
     rc |= dev_alloc(&c->theta_tasks, MNP); rc |= dev_alloc(&c->chain, (size_t)(K + 1) * MNP);
     rc |= dev_alloc(&c->lam, MNP); rc |= dev_alloc(&c->vbuf, MNP);
-    if (c->wbf) {
-        const size_t pw = (size_t)M * wb_planes_words(wb_nko(c->wbf));
+    if (c->family == PassFamily::CoopSplit) {
+        const size_t pw = (size_t)M * wb_planes_words(wb_nko(c->wb_cls));
         rc |= dev_alloc(&c->wb_planes, pw); rc |= dev_alloc(&c->wb_vplanes, pw); rc |= dev_alloc(&c->wb_planes_meta, pw);
         rc |= dev_alloc(&c->vdir_absmax, (size_t)M);
     }
@@ -1094,7 +1057,7 @@ int promp_ctx_create(promp_ctx** out, int device_id, const promp_dims* user_dims
     // (the baseline fit's partial Gram blocks and scratch matrices -- 2.7 GB per set at Humanoid's 757 columns -- are allocated by the
     //  first promp_process_samples that fits a baseline on that stream: fit_buffers())
     rc |= dev_alloc(&c->red64, 64);
-    if (c->generic) {
+    if (c->family == PassFamily::Layered) {
         const size_t R = (size_t)dims->max_rows;
         for (int l = 1; l < c->n_lin; ++l) {
             rc |= dev_alloc(&c->g_act[l], R * c->lin[l].K);
@@ -1698,7 +1661,7 @@ int promp_set_advantages(promp_ctx* c, int step, const float* adv) {
 int promp_set_dice_rewards(promp_ctx* c, int step, const float* rw) {
     if (!c || !rw) return fail(-1, "NULL argument");
     if (step < 0 || step > c->d.num_inner_steps) return fail(-1, "step %d out of range", step);
-    if (c->wide || c->generic) return fail(-1, "the DiCE objective is built on the register-chained kernels (hidden sizes from {32,64}, obs_dim <= 32)");
+    if (c->family != PassFamily::Chain) return fail(-1, "the DiCE objective is built on the register-chained kernels (hidden sizes from {32,64}, obs_dim <= 32)");
     StepData& S = c->steps[step];
     StepScope scope_(c, S);
     if (scope_.rc) return -2;
@@ -1867,20 +1830,18 @@ int promp_inner_adapt(promp_ctx* c, int step, int inner_kind) {
     const bool leave = c->reuse_adapt && c->tasks_shared && step == 0 &&
                        (inner_kind == PROMP_INNER_RATIO || inner_kind == PROMP_INNER_LOGLIK);
     if (step == 0) c->adapt0.valid = false;       // (inner steps on later sampling steps touch nothing the record stands for)
-    bool cached = false;
+    PassReq q;
+    q.theta = cur; q.theta_stride = st; q.loss_kind = loss_kind_inner(inner_kind);
+    q.red_mode = RED_STEP; q.cur = cur; q.cur_stride = st; q.next = c->theta_tasks;
+    const bool cached = leave && primal_cache_on(c);
+    if (cached && ensure_primal_cache(c, S)) return -2;
+    q.cache = cached ? 1 : 0;
     if (leave) {
-        const size_t MNP = (size_t)c->d.n_tasks * c->NP;
-        const bool worth = primal_cache_worth(c, S.n_rows);
-        cached = worth && !c->wide && policy_shape_chain(&c->d);      // (the cooperative kernels keep no primal cache: theta' and the scalars only)
-        if (cached && !S.hcache &&
-            dev_alloc(&S.hcache, ((size_t)c->d.max_rows + 16 * (size_t)c->d.n_tasks) * chain_cache_row(c->d.hidden1, c->d.hidden2))) return -2;
-        c->pass_next2 = c->chain + MNP;
-        c->pass_scal2 = c->scal_inner;
-        c->pass_cache = cached ? 1 : 0;
+        q.next2 = c->chain + (size_t)c->d.n_tasks * c->NP;
+        q.scal2 = c->scal_inner;
     }
     c->tasks_shared = false;
-    const int rc = launch_pass(c, S, false, cur, st, loss_kind_inner(inner_kind), 0.f, 0, 0.f, false, RED_STEP, cur, st, c->theta_tasks, c->scal_tmp);
-    c->pass_next2 = nullptr; c->pass_scal2 = nullptr; c->pass_cache = 0;
+    const int rc = launch_pass(c, S, q);
     if (rc) return rc;
     if (leave) {
         c->adapt0.valid = true; c->adapt0.theta_version = c->theta_version; c->adapt0.data_version = S.data_version;
@@ -1895,7 +1856,7 @@ int promp_policy_forward(promp_ctx* c, const float* obs, int batch, float* mean_
     if (batch < 1) return fail(-1, "batch must be positive");
     const int M = c->d.n_tasks, O = c->d.obs_dim, A = c->d.act_dim;
     const size_t n_obs = (size_t)M * batch * O, n_out = (size_t)M * batch * A;
-    const size_t n_scr = c->generic ? (size_t)M * batch * 2 * c->g_maxw : 0;
+    const size_t n_scr = c->family == PassFamily::Layered ? (size_t)M * batch * 2 * c->g_maxw : 0;
     if (n_obs + n_out + n_scr > c->fwd_capacity) {
         if (c->fwd_buf) (void)hipFree(c->fwd_buf);
         c->fwd_buf = nullptr;
@@ -1909,7 +1870,7 @@ int promp_policy_forward(promp_ctx* c, const float* obs, int batch, float* mean_
     if (tasks_materialize(c)) return -2;
     f.obs = d_obs; f.theta_tasks = c->theta_tasks; f.mean = d_out;
     f.B = batch; f.O = O; f.A = A; f.H1 = c->d.hidden1; f.H2 = c->d.hidden2;
-    if (c->generic) {
+    if (c->family == PassFamily::Layered) {
         GenForwardArgs gf;
         gf.obs = d_obs; gf.theta_tasks = c->theta_tasks; gf.mean = d_out; gf.scratch = d_out + n_out;
         gf.B = batch; gf.NP = c->NP; gf.n_lin = c->n_lin; gf.maxw = c->g_maxw; gf.act_kind = gen_act_kinds(&c->d);
@@ -1983,7 +1944,7 @@ int promp_rollout_point_env(promp_ctx* c, int step, int envs_per_task, int path_
     a.obs = S.obs; a.act = S.act; a.rew = S.rew; a.mean = S.old_mean; a.old_ls = S.old_ls;
     a.clip_infos = o->clip_infos; a.min_log_std = c->min_log_std;
     a.normalization_scale = o->normalization_scale; a.max_step = o->max_step; a.reward_type = o->reward_type; a.sparse_radius = o->sparse_radius;
-    if (c->generic) {          // any layer table: one workgroup per environment (promp_kernels_generic.h)
+    if (c->family == PassFamily::Layered) {          // any layer table: one workgroup per environment (promp_kernels_generic.h)
         GenPointRolloutArgs g;
         g.p = a; g.n_lin = c->n_lin; g.act_kind = gen_act_kinds(&c->d);
         for (int l = 0; l < c->n_lin; ++l) g.lin[l] = c->lin[l];
@@ -2089,7 +2050,7 @@ int promp_policy_step(promp_ctx* c, int step, int t, const float* obs, uint64_t 
     a.B = B; a.T = T; a.t = t; a.O = O; a.A = A; a.H1 = c->d.hidden1; a.H2 = c->d.hidden2; a.NP = c->NP;
     a.clip_infos = clip_infos; a.min_log_std = c->min_log_std;
     a.seed = seed; a.stream = (unsigned)step;
-    if (c->generic) {          // any layer table: one workgroup per environment (promp_kernels_generic.h)
+    if (c->family == PassFamily::Layered) {          // any layer table: one workgroup per environment (promp_kernels_generic.h)
         GenPolicyStepArgs g;
         g.p = a; g.n_lin = c->n_lin; g.act_kind = gen_act_kinds(&c->d);
         for (int l = 0; l < c->n_lin; ++l) g.lin[l] = c->lin[l];
@@ -2192,32 +2153,27 @@ static int enqueue_constraint_hvp(promp_ctx* c, int inner_kind, int refresh_chai
     // passes that refresh the chain store their activations (and one extra storing pass with the KL objective covers step K);
     // every R-operator pass below then reads them back instead of recomputing layers 1 and 2.  Same worth-it rule as the
     // meta-objective's cache (enqueue_meta).
-    bool use_cache = !c->wide && policy_shape_chain(&c->d);      // (the cooperative kernels keep no primal cache)
-    for (int k = 0; k <= K && use_cache; ++k)
-        use_cache = primal_cache_worth(c, c->steps[k].n_rows);
+    const bool use_cache = primal_cache_on(c);
     if (refresh_chain) {
         c->chvp.valid = false;
         for (int k = 0; k <= K && use_cache; ++k)
-            if (!c->steps[k].hcache &&
-                dev_alloc(&c->steps[k].hcache, ((size_t)c->d.max_rows + 16 * (size_t)M) * chain_cache_row(c->d.hidden1, c->d.hidden2))) return -2;
+            if (ensure_primal_cache(c, c->steps[k])) return -2;
         for (int k = 0; k < K; ++k) {
             const float* th = theta_of(k, &st);
             if (k == 0 && adapt0_stands(c, inner_kind, use_cache)) {       // promp_inner_adapt has just run exactly this pass
                 c->adapt_passes_skipped += 1;
                 continue;
             }
-            c->pass_cache = use_cache ? 1 : 0;
-            const int rc = launch_pass(c, c->steps[k], false, th, st, lk, 0.f, k == 0, 0.f, false, RED_STEP, th, st,
-                                       c->chain + (size_t)(k + 1) * MNP, c->scal_inner + (size_t)k * M * 2);
-            c->pass_cache = 0;
-            if (rc) return -2;
+            PassReq q;
+            q.theta = th; q.theta_stride = st; q.loss_kind = lk; q.clip_ls = k == 0;
+            q.red_mode = RED_STEP; q.cur = th; q.cur_stride = st; q.next = c->chain + (size_t)(k + 1) * MNP; q.scal = c->scal_inner + (size_t)k * M * 2;
+            q.cache = use_cache ? 1 : 0;
+            if (launch_pass(c, c->steps[k], q)) return -2;
         }
         if (use_cache) {
-            const float* th = theta_of(K, &st);
-            c->pass_cache = 1;
-            const int rc = launch_pass(c, c->steps[K], false, th, st, LOSS_KL, 0.f, K == 0, 0.f, false, RED_PLAIN, nullptr, 0, nullptr, c->scal_tmp);
-            c->pass_cache = 0;
-            if (rc) return -2;
+            PassReq q;
+            q.theta = theta_of(K, &q.theta_stride); q.loss_kind = LOSS_KL; q.clip_ls = K == 0; q.cache = 1;
+            if (launch_pass(c, c->steps[K], q)) return -2;
             c->chvp.valid = true; c->chvp.theta_version = c->theta_version; c->chvp.sizes_version = c->sizes_version;
             c->chvp.inner_kind = inner_kind; c->chvp.min_log_std = c->min_log_std;
             for (int k = 0; k <= K; ++k) {
@@ -2234,13 +2190,11 @@ static int enqueue_constraint_hvp(promp_ctx* c, int inner_kind, int refresh_chai
     PROMP_LAUNCH(k_replicate, dim3((NP + 255) / 256), 256, 0, c->stream, c->vbuf, c->grad_mean, NP, M);
     const dim3 eg((NP + 255) / 256, M);
     auto pass = [&](int k, int kind) -> int {
-        const float* th = theta_of(k, &st);
-        const bool cached = cache_ok(k);
-        c->pass_cache = cached ? 2 : 0;
-        c->chvp_cached_passes += cached ? 1 : 0;
-        const int rc = launch_pass(c, c->steps[k], true, th, st, kind, 0.f, k == 0, 0.f, false, RED_PLAIN, nullptr, 0, nullptr, c->scal_tmp);
-        c->pass_cache = 0;
-        return rc;
+        PassReq q;
+        q.hvp = true; q.theta = theta_of(k, &q.theta_stride); q.loss_kind = kind; q.clip_ls = k == 0;
+        q.cache = cache_ok(k) ? 2 : 0;
+        c->chvp_cached_passes += q.cache ? 1 : 0;
+        return launch_pass(c, c->steps[k], q);
     };
     for (int k = 0; k < K; ++k) {                      // u = J_{K-1} ... J_0 v
         if (pass(k, lk)) return -2;
@@ -2453,7 +2407,9 @@ int promp_eval_loss_grad(promp_ctx* c, int step, int kind, float clip_eps, int c
     if (scope_.rc) return -2;
     const int M = c->d.n_tasks;
     if (tasks_materialize(c)) return -2;
-    if (launch_pass(c, S, false, c->theta_tasks, c->NP, kind, clip_eps, clip_ls, 0.f, false, RED_PLAIN, nullptr, 0, nullptr, c->scal_tmp)) return -2;
+    PassReq q;
+    q.theta = c->theta_tasks; q.theta_stride = c->NP; q.loss_kind = kind; q.clip_eps = clip_eps; q.clip_ls = clip_ls;
+    if (launch_pass(c, S, q)) return -2;
     if (grads_out && params_out(c, grads_out, c->lam, (size_t)M)) return -2;
     std::vector<float> sc((size_t)M * 2);
     if (copy_out(c, sc.data(), c->scal_tmp, sc.size())) return -2;
@@ -2474,7 +2430,9 @@ int promp_eval_hvp(promp_ctx* c, int step, int inner_kind, int clip_ls, float kl
     if (params_in(c, c->vbuf, v, (size_t)M)) return -2;
     HIPCHECK(hipMemsetAsync(c->lam, 0, sizeof(float) * (size_t)M * NP, c->stream));
     if (tasks_materialize(c)) return -2;
-    if (launch_pass(c, S, true, c->theta_tasks, NP, loss_kind_inner(inner_kind), 0.f, clip_ls, klw, false, RED_PLAIN, nullptr, 0, nullptr, c->scal_tmp)) return -2;
+    PassReq q;
+    q.hvp = true; q.theta = c->theta_tasks; q.theta_stride = NP; q.loss_kind = loss_kind_inner(inner_kind); q.clip_ls = clip_ls; q.klw = klw;
+    if (launch_pass(c, S, q)) return -2;
     return params_out(c, out, c->lam, (size_t)M);
 }
 
@@ -2579,19 +2537,20 @@ int promp_debug_phase_stamps(promp_ctx* c, int step, int hvp, unsigned long long
     StepScope scope_(c, S, false);
     if (scope_.rc) return -2;
     if (tasks_materialize(c)) return -2;
+    PassReq q;
+    q.theta = c->theta_tasks; q.theta_stride = c->NP; q.clip_eps = 0.3f;
     if (hvp == 2) {               // the cache-reading R-operator pass: fill the step's primal cache first (unstamped)
-        if (c->wide || !policy_shape_chain(&c->d)) return fail(-1, "no primal cache for this shape");
-        if (!S.hcache && dev_alloc(&S.hcache, ((size_t)c->d.max_rows + 16 * (size_t)c->d.n_tasks) * chain_cache_row(c->d.hidden1, c->d.hidden2))) return -2;
-        c->pass_cache = 1;
-        const int rc0 = launch_pass(c, S, false, c->theta_tasks, c->NP, LOSS_RATIO, 0.3f, 0, 0.f, false, RED_PLAIN, nullptr, 0, nullptr, c->scal_tmp);
-        c->pass_cache = 0;
+        if (c->family != PassFamily::Chain) return fail(-1, "no primal cache for this shape");
+        if (ensure_primal_cache(c, S)) return -2;
+        q.cache = 1;
+        const int rc0 = launch_pass(c, S, q);
         if (rc0) return rc0;
     }
     HIPCHECK(hipMemsetAsync(c->dbg, 0, sizeof(unsigned long long) * (256 + 4 * 1024), c->stream));
     c->dbg_enabled = true;
-    c->pass_cache = hvp == 2 ? 2 : 0;
-    const int rc = launch_pass(c, S, hvp != 0, c->theta_tasks, c->NP, LOSS_RATIO, 0.3f, 0, 0.f, false, RED_PLAIN, nullptr, 0, nullptr, c->scal_tmp);
-    c->pass_cache = 0;
+    q.hvp = hvp != 0;
+    q.cache = hvp == 2 ? 2 : 0;
+    const int rc = launch_pass(c, S, q);
     c->dbg_enabled = false;
     if (rc) return rc;
     HIPCHECK(hipMemcpyAsync(out, c->dbg, sizeof(unsigned long long) * (256 + 4 * 1024), hipMemcpyDeviceToHost, c->stream));
