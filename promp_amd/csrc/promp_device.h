@@ -48,21 +48,6 @@ PROMP_DEV f64x4 mfma16d(double a, double b, f64x4 c) { return __builtin_amdgcn_m
 // 2 048).  lane l holds A[i = l & 15][k = 8 (l >> 4) .. + 7] and B[k = 8 (l >> 4) .. + 7][j = l & 15], 8 bf16 each;
 // D as mfma16.  Exact products, float32 accumulation (layout and error: tools/micro/bf16_layout_probe.hip).
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-PROMP_DEV f32x4 mfma16_bf16(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-// Error-compensated split of eight float32 values into three BF16 terms each: x = t0 + t1 + t2 up to 2^-24 |x|
-// (v_cvt_pk_bf16_f32 rounds to nearest even; the residuals are exact in float32).
-PROMP_DEV void bf16_split3(const float (&x)[8], bf16x8 (&t)[3]) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const __bf16 h0 = (__bf16)x[e];
-        const float r1 = x[e] - (float)h0;
-        const __bf16 h1 = (__bf16)r1;
-        const float r2 = r1 - (float)h1;
-        t[0][e] = h0;
-        t[1][e] = h1;
-        t[2][e] = (__bf16)r2;
-    }
-}
 // ---- BF16 fragments as raw 32-bit words ---------------------------------------------------------------------------------
 // The pass kernel moves its BF16 operands around as words of two bf16 (low half = the element with the lower index) and turns
 // them into bf16 vectors only at the MFMA call, by whole-vector bit casts (building a bf16x8 element by element from 16-bit
@@ -205,10 +190,6 @@ PROMP_DEV void pair_post(float* flags, int mine, int seq, int lane) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (lane == 0) ((volatile int*)flags)[mine] = seq;
 }
-PROMP_DEV void pair_wait(float* flags, int other, int seq) {
-    while (__builtin_amdgcn_readfirstlane(((volatile int*)flags)[other]) < seq) __builtin_amdgcn_s_sleep(1);
-    asm volatile("" ::: "memory");
-}
 // Agent-scope hand-off between workgroups (MI355X_MICROARCH.md, inter-workgroup visibility): the producer writes its
 // data, releases (L2 write-back + drain), then bumps a counter with a relaxed agent-scope atomic; the workgroup that
 // reads the final count acquires (L1 invalidate) before it loads the others' data.
@@ -235,22 +216,8 @@ PROMP_DEV int opaque_zero() {
     asm volatile("" : "+v"(z));
     return z;
 }
-// An LDS address the optimiser cannot see through: accesses at small constant offsets from it keep those offsets as instruction
-// immediates off ONE address register (folded into an absolute address they may not fit the offset field of ds_read2 / ds_write2).
-PROMP_DEV double* opaque_lds(double* p) {
-    unsigned a = (unsigned)(size_t)p;
-    asm volatile("" : "+v"(a));
-    return (double*)(__attribute__((address_space(3))) double*)(size_t)a;
-}
 // Tells the compiler a value is the same in every lane of the wave (e.g. the wave index threadIdx.x >> 6), so that
 // everything derived from it lives in scalar registers.
-// Pins a value into the accumulator half of the register file (AGPRs: usable as MFMA operands and load / store data
-// only).  At one wave per SIMD a lane has 256 + 256 registers; weights that only ever feed MFMAs belong in the second
-// half, where they do not compete with the activations and epilogue temporaries for the 256 VALU-visible registers.
-PROMP_DEV f32x4 pin_agpr(f32x4 v) {
-    asm volatile("" : "+a"(v));
-    return v;
-}
 // Pins: zero-instruction pass-throughs the optimiser cannot see through.  A value that went through one exists, in a register of
 // the named file, at that point of the instruction stream; together with sched_fence() they decide which stage of a software
 // pipeline a piece of pure arithmetic belongs to (instruction selection otherwise sinks it to its first use, across any
@@ -258,7 +225,6 @@ PROMP_DEV f32x4 pin_agpr(f32x4 v) {
 PROMP_DEV void pin_v(float& x) { asm volatile("" : "+v"(x)); }
 PROMP_DEV void pin_v(unsigned& x) { asm volatile("" : "+v"(x)); }
 PROMP_DEV void pin_v(int& x) { asm volatile("" : "+v"(x)); }
-PROMP_DEV void pin_s(unsigned& x) { asm volatile("" : "+s"(x)); }
 PROMP_DEV void pin_v(f32x4& x) { asm volatile("" : "+v"(x)); }
 PROMP_DEV void pin_v(u32x4& x) { asm volatile("" : "+v"(x)); }
 PROMP_DEV void pin_a(f32x4& x) { asm volatile("" : "+a"(x)); }
@@ -283,13 +249,6 @@ PROMP_DEV int xcd_item(int b, int G) {
     return off + (b >> 3);
 }
 PROMP_DEV int wave_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-// issue priority of this wave among the waves of its SIMD (s_setprio takes an immediate: 0..3)
-PROMP_DEV void wave_priority(int p) {
-    if (p >= 3) __builtin_amdgcn_s_setprio(3);
-    else if (p == 2) __builtin_amdgcn_s_setprio(2);
-    else if (p == 1) __builtin_amdgcn_s_setprio(1);
-    else __builtin_amdgcn_s_setprio(0);
-}
 PROMP_DEV unsigned long long promp_clock() { return (unsigned long long)clock64(); }
 PROMP_DEV unsigned long long promp_wall_clock() { return (unsigned long long)wall_clock64(); }   // constant 100 MHz
 PROMP_DEV float fast_exp(float x) { return __expf(x); }
@@ -335,185 +294,9 @@ PROMP_DEV double wave_min_f64(double v) {
     return v;
 }
 
-// The primal / tangent pair of one layer in a single pass over k (R-operator kernels):
-//     P[i][j] += A0_i B0_j                       T[i][j] += A1_i B0_j + s1 * A0_i B1_j
-// One software pipeline instead of three: the A0 / B0 operands are loaded once, a k-step issues 3 NA NB independent
-// MFMAs (enough to cover the LDS latency of the next step's operands), and two pipeline ramp-ups disappear.
-// a1 == nullptr drops the A1 term (first layer: the input has no tangent).
-template <int NA, int NB, bool HAS_A1>
-PROMP_DEV void outer16_pt(f32x4 (&P)[NA][NB], f32x4 (&T)[NA][NB], const float* a0, const float* a1, int a_ss, int a_bs,
-                          const float* b0, const float* b1, int b_ss, int b_bs, int NS, float s1) {
-    float x0[NA], x1[NA], y0[NB], y1[NB];
-    f32x4 T2[NA][NB];          // the A1 B0 term accumulates apart from the A0 B1 term and joins T at the end
-#pragma unroll
-    for (int i = 0; i < NA; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j) T2[i][j] = zero4();
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-        x0[i] = a0[i * a_bs];
-        x1[i] = HAS_A1 ? a1[i * a_bs] : 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-        y0[j] = b0[j * b_bs];
-        y1[j] = s1 * b1[j * b_bs];
-    }
-#pragma unroll 2
-    for (int s = 1; s <= NS; ++s) {
-        float nx0[NA], nx1[NA], ny0[NB], ny1[NB];
-        const int sn = s < NS ? s : 0;          // the last step re-reads step 0 (harmless) instead of branching
-#pragma unroll
-        for (int i = 0; i < NA; ++i) {
-            nx0[i] = a0[sn * a_ss + i * a_bs];
-            nx1[i] = HAS_A1 ? a1[sn * a_ss + i * a_bs] : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            ny0[j] = b0[sn * b_ss + j * b_bs];
-            ny1[j] = s1 * b1[sn * b_ss + j * b_bs];
-        }
-        // three independent accumulator sets, each walked completely before the next: no MFMA waits for its predecessor
-#pragma unroll
-        for (int i = 0; i < NA; ++i)
-#pragma unroll
-            for (int j = 0; j < NB; ++j) P[i][j] = mfma16(x0[i], y0[j], P[i][j]);
-#pragma unroll
-        for (int i = 0; i < NA; ++i)
-#pragma unroll
-            for (int j = 0; j < NB; ++j) T[i][j] = mfma16(x0[i], y1[j], T[i][j]);
-        if (HAS_A1) {
-#pragma unroll
-            for (int i = 0; i < NA; ++i)
-#pragma unroll
-                for (int j = 0; j < NB; ++j) T2[i][j] = mfma16(x1[i], y0[j], T2[i][j]);
-        }
-#pragma unroll
-        for (int i = 0; i < NA; ++i) {
-            x0[i] = nx0[i];
-            x1[i] = nx1[i];
-        }
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            y0[j] = ny0[j];
-            y1[j] = ny1[j];
-        }
-    }
-    if (HAS_A1) {
-#pragma unroll
-        for (int i = 0; i < NA; ++i)
-#pragma unroll
-            for (int j = 0; j < NB; ++j) T[i][j] += T2[i][j];
-    }
-}
-
-// acc[i][j] += s0 * A0_i B0_j + A1_i B1_j   (the two gradient terms of one kernel in the R-operator pass)
-template <int NA, int NB>
-PROMP_DEV void outer16_two(f32x4 (&acc)[NA][NB], const float* a0, const float* a1, int a_ss, int a_bs, const float* b0,
-                           const float* b1, int b_ss, int b_bs, int NS, float s0) {
-    float x0[NA], x1[NA], y0[NB], y1[NB];
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-        x0[i] = a0[i * a_bs];
-        x1[i] = a1[i * a_bs];
-    }
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-        y0[j] = s0 * b0[j * b_bs];
-        y1[j] = b1[j * b_bs];
-    }
-#pragma unroll 2
-    for (int s = 1; s <= NS; ++s) {
-        float nx0[NA], nx1[NA], ny0[NB], ny1[NB];
-        const int sn = s < NS ? s : 0;
-#pragma unroll
-        for (int i = 0; i < NA; ++i) {
-            nx0[i] = a0[sn * a_ss + i * a_bs];
-            nx1[i] = a1[sn * a_ss + i * a_bs];
-        }
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            ny0[j] = s0 * b0[sn * b_ss + j * b_bs];
-            ny1[j] = b1[sn * b_ss + j * b_bs];
-        }
-#pragma unroll
-        for (int i = 0; i < NA; ++i)
-#pragma unroll
-            for (int j = 0; j < NB; ++j) acc[i][j] = mfma16(x0[i], y0[j], acc[i][j]);
-#pragma unroll
-        for (int i = 0; i < NA; ++i)
-#pragma unroll
-            for (int j = 0; j < NB; ++j) acc[i][j] = mfma16(x1[i], y1[j], acc[i][j]);
-#pragma unroll
-        for (int i = 0; i < NA; ++i) {
-            x0[i] = nx0[i];
-            x1[i] = nx1[i];
-        }
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            y0[j] = ny0[j];
-            y1[j] = ny1[j];
-        }
-    }
-}
-
 // tanh(x) = 1 - 2/(exp(2x)+1): absolute error ~1e-7, saturates correctly at +-1.
 PROMP_DEV float fast_tanh(float x) { return 1.f - 2.f * fast_rcp(fast_exp(2.f * x) + 1.f); }
 
-// The same for a pre-activation that arrives already scaled by PROMP_TANH_PRESCALE = 2 log2(e) (the kernels fold the
-// factor into the staged kernel / bias of the layer): tanh(x) = 1 - 2 / (2^y + 1), y = 2 log2(e) x.  Two elements at a time:
-// v_exp_f32, v_add_f32, v_rcp_f32 each and ONE v_pk_fma_f32 for the pair.
+// The kernels that take a pre-activation already scaled by PROMP_TANH_PRESCALE = 2 log2(e) fold the factor into the staged kernel /
+// bias of the layer: tanh(x) = 1 - 2 / (2^y + 1), y = 2 log2(e) x.
 #define PROMP_TANH_PRESCALE 2.8853900817779268f
-PROMP_DEV f32x2 tanh2_prescaled(float y0, float y1) {
-    f32x2 r;
-    r[0] = fast_rcp(fast_exp2(y0) + 1.f);
-    r[1] = fast_rcp(fast_exp2(y1) + 1.f);
-    f32x2 m2, one;
-    m2[0] = m2[1] = -2.f;
-    one[0] = one[1] = 1.f;
-    return pk_fma(r, m2, one);
-}
-// h^2 - 1 (the NEGATED tanh derivative) for two elements in one v_pk_fma_f32; the caller's multiply takes the sign back
-// as a source modifier (negating h first would cost a v_xor per element)
-PROMP_DEV f32x2 neg_dtanh2(float h0, float h1) {
-    f32x2 h, m1;
-    h[0] = h0; h[1] = h1;
-    m1[0] = m1[1] = -1.f;
-    return pk_fma(h, h, m1);
-}
-
-// acc[ia][ib] (16x16 tiles) += sgn * A_ia * B_ib over NS k-steps of 16x16x4 MFMAs.
-// Operand streams: at step s, A block ia feeds a[s*a_ss + ia*a_bs], B block ib feeds b[s*b_ss + ib*b_bs] (pointers
-// already offset for this lane).  Which four k values a step contracts is the caller's choice (any bijection of K
-// onto (step, lane>>4) works as long as A and B agree) - the kernels pick it per GEMM for conflict-free LDS banks.
-// NA*NB independent accumulators hide the 40-cycle dependent latency; the operands of step s+1 are requested before
-// the MFMAs of step s issue.
-template <int NA, int NB>
-PROMP_DEV void outer16(f32x4 (&acc)[NA][NB], const float* a, int a_ss, int a_bs, const float* b, int b_ss, int b_bs, int NS,
-                       float sgn) {
-    float a0[NA], b0[NB];
-#pragma unroll
-    for (int i = 0; i < NA; ++i) a0[i] = a[i * a_bs];
-#pragma unroll
-    for (int j = 0; j < NB; ++j) b0[j] = b[j * b_bs];
-#pragma unroll 2
-    for (int s = 1; s < NS; ++s) {
-        float a1[NA], b1[NB];
-#pragma unroll
-        for (int i = 0; i < NA; ++i) a1[i] = a[s * a_ss + i * a_bs];
-#pragma unroll
-        for (int j = 0; j < NB; ++j) b1[j] = b[s * b_ss + j * b_bs];
-#pragma unroll
-        for (int i = 0; i < NA; ++i)
-#pragma unroll
-            for (int j = 0; j < NB; ++j) acc[i][j] = mfma16(sgn * a0[i], b0[j], acc[i][j]);
-#pragma unroll
-        for (int i = 0; i < NA; ++i) a0[i] = a1[i];
-#pragma unroll
-        for (int j = 0; j < NB; ++j) b0[j] = b1[j];
-    }
-#pragma unroll
-    for (int i = 0; i < NA; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j) acc[i][j] = mfma16(sgn * a0[i], b0[j], acc[i][j]);
-}

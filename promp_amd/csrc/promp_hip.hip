@@ -44,6 +44,61 @@ int fail(int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return fail(-2, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
+// ---- owners: every device allocation, page-locked host block, event and stream is released by the member that holds it ----
+// Move-only; converts to the raw pointer / handle, so use sites read as if they held one.
+template <class T, bool PINNED>
+struct Buf {
+    T* p = nullptr;
+    size_t cap = 0;                    // reserve(): elements held
+    Buf() = default;
+    Buf(Buf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    Buf& operator=(Buf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~Buf() { (void)release(); }
+    operator T*() const { return p; }
+    hipError_t release() {
+        T* q = p;
+        p = nullptr; cap = 0;
+        return !q ? hipSuccess : PINNED ? hipHostFree(q) : hipFree(q);
+    }
+    // n elements (at least one) in place of what it held; device memory arrives zero-filled
+    int alloc(size_t n) {
+        const size_t bytes = (n ? n : 1) * sizeof(T);
+        HIPCHECK(release());
+        if (PINNED) HIPCHECK(hipHostMalloc((void**)&p, bytes, hipHostMallocDefault));
+        else {
+            HIPCHECK(hipMalloc((void**)&p, bytes));
+            HIPCHECK(hipMemset(p, 0, bytes));
+        }
+        return 0;
+    }
+    // room for n elements, contents not kept and not zeroed; a buffer that has to grow is replaced by one of slack * n
+    int reserve(size_t n, size_t slack) {
+        if (n <= cap) return 0;
+        HIPCHECK(release());
+        if (PINNED) HIPCHECK(hipHostMalloc((void**)&p, sizeof(T) * slack * n, hipHostMallocDefault));
+        else HIPCHECK(hipMalloc((void**)&p, sizeof(T) * slack * n));
+        cap = slack * n;
+        return 0;
+    }
+};
+template <class T> using DevBuf = Buf<T, false>;
+template <class T> using PinBuf = Buf<T, true>;
+template <class H, hipError_t (*DESTROY)(H)>
+struct Handle {
+    H h = nullptr;
+    Handle() = default;
+    Handle(Handle&& o) noexcept : h(o.h) { o.h = nullptr; }
+    Handle& operator=(Handle&& o) noexcept { std::swap(h, o.h); return *this; }
+    ~Handle() { if (h) (void)DESTROY(h); }
+    operator H() const { return h; }
+};
+using Event = Handle<hipEvent_t, hipEventDestroy>;
+using Stream = Handle<hipStream_t, hipStreamDestroy>;
+
+// first line of an entry point that takes nothing but the context
+#define NEED_CTX(c) \
+    if (!(c)) return fail(-1, "ctx is NULL")
+
 struct StepData {
     int n_paths = 0, n_rows = 0;
     int n_work[2] = {0, 0};            // [0]: one workgroup per CU (wide passes, gram, fit), [1]: two per CU (k_normalize)
@@ -55,34 +110,34 @@ struct StepData {
     unsigned long long cache_tag = 0;      // identity of the primal cache's contents (every storing pass draws a new one)
     int ls_per_row = 0;
     int feat_dim = 0;
-    float *obs = nullptr, *act = nullptr, *rew = nullptr, *old_mean = nullptr, *old_ls = nullptr;
-    unsigned* obs_absmax = nullptr;    // [tasks]: bits of the largest |observation| of each task's rows (k_obs_range; the FP16 split's scale)
+    DevBuf<float> obs, act, rew, old_mean, old_ls;
+    DevBuf<unsigned> obs_absmax;       // [tasks]: bits of the largest |observation| of each task's rows (k_obs_range; the FP16 split's scale)
     bool obs_range_valid = false;      // false from every entry point that writes S.obs until k_obs_range has been enqueued behind it
-    double* rew64 = nullptr;           // promp_set_rewards_f64 (allocated on first use); valid while has_rew64
+    DevBuf<double> rew64;              // promp_set_rewards_f64 (allocated on first use); valid while has_rew64
     // DiCE (promp_set_dice_rewards; allocated on first use): per-row adjusted rewards, row tangents of the R-operator pass,
     // coupling weights, scan scratch
-    float *dice_rw = nullptr, *dice_c = nullptr, *dice_u = nullptr;
-    double* dice_tmp = nullptr;
+    DevBuf<float> dice_rw, dice_c, dice_u;
+    DevBuf<double> dice_tmp;
     bool has_dice = false;
     bool has_rew64 = false;
-    float *ret32 = nullptr, *adv32 = nullptr;
-    double *ret64 = nullptr, *adv64 = nullptr;
-    float* hcache = nullptr;           // primal cache (promp_kernels_chain.h: chain_cache_row), allocated on first use
-    int *path_row_offsets = nullptr, *path_task = nullptr, *row_t = nullptr;
-    int *task_row_offsets = nullptr, *task_path_offsets = nullptr;
-    int* task_wg_offsets[2] = {nullptr, nullptr};
-    ChainSeg* chain_segs = nullptr;                          // segment table of k_pass / k_chain_hvp
-    int* chain_wg_offsets = nullptr;                         // [workgroups+1]
-    int* chain_slot_offsets = nullptr;                       // [tasks+1]: partial rows (= segments) of each task
-    double *path_ret0 = nullptr, *path_undisc = nullptr, *path_rsq = nullptr, *path_mom = nullptr;
-    double* coeffs = nullptr;
-    WorkItem* work[2] = {nullptr, nullptr};
+    DevBuf<float> ret32, adv32;
+    DevBuf<double> ret64, adv64;
+    DevBuf<float> hcache;              // primal cache (promp_kernels_chain.h: chain_cache_row), allocated on first use
+    DevBuf<int> path_row_offsets, path_task, row_t;
+    DevBuf<int> task_row_offsets, task_path_offsets;
+    DevBuf<int> task_wg_offsets[2];
+    DevBuf<ChainSeg> chain_segs;                             // segment table of k_pass / k_chain_hvp
+    DevBuf<int> chain_wg_offsets;                            // [workgroups+1]
+    DevBuf<int> chain_slot_offsets;                          // [tasks+1]: partial rows (= segments) of each task
+    DevBuf<double> path_ret0, path_undisc, path_rsq, path_mom;
+    DevBuf<double> coeffs;
+    DevBuf<WorkItem> work[2];
     // second-stream sample processing (promp_process_samples of steps >= 1, see stage_a_stream):
-    hipEvent_t ev_use = nullptr;       // main stream: the last enqueued work that reads or writes this step's slabs
-    hipEvent_t ev_done = nullptr;      // side stream: the step's processed outputs are complete
+    Event ev_use;                      // main stream: the last enqueued work that reads or writes this step's slabs
+    Event ev_done;                     // side stream: the step's processed outputs are complete
     bool use_set = false, side_pending = false, dirty = false;
     // staged uploads (promp_stage_step / promp_commit_step): the slab set is written by the copy stream
-    hipEvent_t ev_ready = nullptr;     // copy stream: every array of this slab set has arrived
+    Event ev_ready;                    // copy stream: every array of this slab set has arrived
     bool ready_set = false, wait_ready_main = false, wait_ready_side = false, staged = false;
     std::shared_ptr<void> host_tables; // host-side sources of the asynchronous table copies, alive until the next staging
     std::vector<int> lay_tpo, lay_pro; // the offsets the set's device-side tables were built from (set_step_layout)
@@ -98,6 +153,9 @@ int chain_ksteps(int obs_dim) { return obs_dim <= 8 ? 2 : obs_dim <= 20 ? 5 : 8;
 #define PROMP_CHAIN_ALL(X) X(2, 2, 2) X(2, 2, 5) X(2, 2, 8) X(2, 4, 2) X(2, 4, 5) X(2, 4, 8) X(4, 2, 2) X(4, 2, 5) X(4, 2, 8) X(4, 4, 2) X(4, 4, 5) X(4, 4, 8)
 // k_wide_* instances: (hidden width, observation blocks of 16)
 #define PROMP_WIDE_ALL(X) X(128, 2) X(128, 4) X(128, 8) X(64, 2) X(64, 4) X(64, 8)
+// k_gram<NBLK> instances (feature blocks of 16) and k_fit_wave<DT> instances (ascending: the first with D + 1 <= DT runs)
+#define PROMP_GRAM_ALL(X) X(1) X(2) X(3) X(4) X(5)
+#define PROMP_FITWV_ALL(X) X(12) X(45) X(48) X(64)
 int wide_nob(int obs_dim) { return obs_dim <= 32 ? 2 : obs_dim <= 64 ? 4 : 8; }
 
 // which kernels run the policy passes of a context (promp_ctx_create chooses once, from the padded dims)
@@ -131,7 +189,7 @@ struct PassReq {
 };
 
 struct ProfSlot {
-    std::vector<hipEvent_t> ev;  // start/stop pairs
+    std::vector<Event> ev;       // start/stop pairs
     size_t used = 0;
     double total_ms = 0.0;
     long long launches = 0, rows = 0;
@@ -147,40 +205,39 @@ struct promp_ctx {
     promp_dims du;                       // the caller's dims (d holds the instantiated, possibly zero-padded hidden widths)
     int NPu = 0;                         // parameter count in the caller's layout
     bool padded = false;
-    hipStream_t stream = nullptr;
-    hipStream_t side = nullptr;          // sample processing of steps >= 1 runs here, under the main stream's step-0 work
-    hipStream_t copy = nullptr;          // promp_stage_step: host -> device copies of the NEXT batch, under the current one's compute
+    // (members are released in reverse order of declaration: the streams outlive every buffer and event below)
+    Stream stream;
+    Stream side;                         // sample processing of steps >= 1 runs here, under the main stream's step-0 work
+    Stream copy;                         // promp_stage_step: host -> device copies of the NEXT batch, under the current one's compute
     std::vector<StepData> back;          // the slab sets being staged (swapped with `steps` entries by promp_commit_step)
     bool overlap = true;
-    double *gram_partials_side = nullptr, *fit_scratch_side = nullptr;
+    DevBuf<double> gram_partials_side, fit_scratch_side;
     std::vector<StepData> steps;
-    float *theta = nullptr, *step_sizes = nullptr, *adam_m = nullptr, *adam_v = nullptr;
+    DevBuf<float> theta, step_sizes, adam_m, adam_v;
     long long adam_t = 0;
-    float *theta_tasks = nullptr, *chain = nullptr, *lam = nullptr, *vbuf = nullptr;
+    DevBuf<float> theta_tasks, chain, lam, vbuf;
     bool tasks_shared = false;           // switch_to_pre_update: every task's parameters ARE theta; theta_tasks is written when somebody reads it
-    float* wbuf = nullptr;               // promp_constraint_hvp: [tasks][Theta], allocated on first use
-    float *partials = nullptr, *scal_inner = nullptr, *scal_outer = nullptr, *scal_tmp = nullptr;
-    float *red = nullptr, *grad_mean = nullptr, *stats = nullptr;
+    DevBuf<float> wbuf;                  // promp_constraint_hvp: [tasks][Theta], allocated on first use
+    DevBuf<float> partials, scal_inner, scal_outer, scal_tmp;
+    DevBuf<float> red, grad_mean, stats;
     float eta_last[PROMP_ETA_MAX] = {};
-    double *gram_partials = nullptr, *red64 = nullptr;
-    void* rollout_buf = nullptr;         // goals, start states and noise of a device rollout
-    float* stage_rows = nullptr;         // promp_begin_collection: staging rows [steps][tasks * B] of observations | actions | means
-    size_t stage_capacity = 0;           // floats
-    size_t rollout_capacity = 0;
-    double* fit_scratch = nullptr;       // k_fit_wide: [tasks][2][(D+1)^2] when the matrices do not fit in LDS
+    DevBuf<double> gram_partials, red64;
+    DevBuf<char> rollout_buf;            // goals, start states and noise of a device rollout (bytes)
+    DevBuf<float> stage_rows;            // promp_begin_collection: staging rows [steps][tasks * B] of observations | actions | means
+    DevBuf<double> fit_scratch;          // k_fit_wide: [tasks][2][(D+1)^2] when the matrices do not fit in LDS
     size_t smem_fwd = 0, smem_hvp = 0;
     PassFamily family = PassFamily::Chain;
     int wb_cls = 0;                      // CoopSplit: the observation class 1..3 = (NKO, NXB) = (4,2) (7,4) (8,4): obs_dim <= 63 / 111 / 127
     size_t smem_wb_fwd = 0, smem_wb_bwd = 0, smem_wb_hvp = 0;
-    unsigned *wb_planes = nullptr, *wb_vplanes = nullptr;   // [tasks][wb_planes_words]: k_wb_planes' output for theta / the direction
+    DevBuf<unsigned> wb_planes, wb_vplanes;                 // [tasks][wb_planes_words]: k_wb_planes' output for theta / the direction
     // The planes of the META-parameters (theta itself, stride 0) have their own block: an epoch passes over step 0 at theta twice --
     // the inner gradient pass and, two passes later, the R-operator pass -- and the second finds the first one's planes (same
     // parameters, same slab, same observation scales): one k_wb_planes launch less per epoch.
-    unsigned* wb_planes_meta = nullptr;
-    float* cg_buf = nullptr;             // promp_cg_solve: x, r, d, (H + reg I) d, the gradient ahead, theta0 [+ the gradient at theta0]
-    double* cg_scal = nullptr;           // [4] r.r, d.Hd, converged, x.Hx
+    DevBuf<unsigned> wb_planes_meta;
+    DevBuf<float> cg_buf;                // promp_cg_solve: x, r, d, (H + reg I) d, the gradient ahead, theta0 [+ the gradient at theta0]
+    DevBuf<double> cg_scal;              // [4] r.r, d.Hd, converged, x.Hx
     struct { bool valid = false; unsigned long long theta_version = 0, data_version = 0, sizes_version = 0; const void* step = nullptr; } wbp;
-    unsigned* vdir_absmax = nullptr;     // [tasks]: k_vec_absmax's output for the direction (FP16 split)
+    DevBuf<unsigned> vdir_absmax;        // [tasks]: k_vec_absmax's output for the direction (FP16 split)
     // layer-by-layer kernels (promp_kernels_generic.h) for every other shape: layer table, and one set of activation / tangent /
     // cotangent buffers for the whole context (the passes of a context run one after another on its stream)
     bool gramt_single = false;           // PROMP_GRAMT_SINGLE=1: k_gram_tiled with one feature tile (A/B runs against the double-buffered rounds)
@@ -189,16 +246,16 @@ struct promp_ctx {
     GramtMap gramt_map;                  // one-slice k_gram_tiled launches: wave -> rectangle
     bool fit_one_launch = false;         // PROMP_FIT_ONE_LAUNCH=1: k_fit_wide alone at every width (A/B runs against the per-phase launches)
     bool gen_bf16 = true;                // Layered: the GEMMs on the BF16 matrix pipe (promp_kernels_generic_bf16.h); PROMP_GEN_FP32=1: the exact-FP32 kernels (A/B runs)
-    unsigned short *gb_wplanes = nullptr, *gb_vplanes = nullptr;   // [tasks][gb_plane_stride]: k_gb_planes' output for theta / minus the direction
+    DevBuf<unsigned short> gb_wplanes, gb_vplanes;                 // [tasks][gb_plane_stride]: k_gb_planes' output for theta / minus the direction
     long long gb_plane_stride = 0;
     int gb_pf_off[GEN_MAX_LIN] = {}, gb_pb_off[GEN_MAX_LIN] = {};
     int n_lin = 0, g_maxw = 0;
     GenLin lin[GEN_MAX_LIN];
-    float *g_act[GEN_MAX_LIN] = {}, *g_ract[GEN_MAX_LIN] = {}, *g_mu = nullptr, *g_rmu = nullptr, *g_dz[2] = {}, *g_qz[2] = {};
-    unsigned long long* dbg = nullptr;   // cycle stamps (developer tooling, tools/phase_timing.py)
+    DevBuf<float> g_act[GEN_MAX_LIN], g_ract[GEN_MAX_LIN], g_mu, g_rmu, g_dz[2], g_qz[2];
+    DevBuf<unsigned long long> dbg;      // cycle stamps (developer tooling, tools/phase_timing.py)
     bool dbg_enabled = false;
-    int* task_counters = nullptr;        // [tasks] arrival counters of the chain kernels' fused reductions (zero between launches)
-    int* split_events = nullptr;         // [2] see PassArgs::split_events
+    DevBuf<int> task_counters;           // [tasks] arrival counters of the chain kernels' fused reductions (zero between launches)
+    DevBuf<int> split_events;            // [2] see PassArgs::split_events
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1;
     float min_log_std = -13.815510558f;  // log(1e-6): GaussianMLPPolicy's default min_std
@@ -225,30 +282,21 @@ struct promp_ctx {
     long long adapt_passes_skipped = 0;
     bool force_split = false;            // take the multi-rank launch sequence (reduce / all-reduce / Adam) on one rank too
     bool fixed_order = false;            // exchange = ncclAllGather + sum in rank order (bitwise-identical replicas) instead of ncclAllReduce
-    float* gather = nullptr;             // [nranks][Theta + K + 2]: every rank's sums side by side (fixed_order)
-    size_t gather_len = 0;
+    DevBuf<float> gather;                // [nranks][Theta + K + 2]: every rank's sums side by side (fixed_order)
     bool prof = false;
     ProfSlot prof_slots[PROMP_KERNEL_COUNT];
-    float* stats_host = nullptr;         // pinned: promp_optimize_begin parks both statistics slots here (async copy)
-    double* small_host = nullptr;        // pinned: promp_download_processed gathers the per-path sums and coefficients here
-    size_t small_host_len = 0;
-    unsigned* stats_seq_host = nullptr;  // pinned: sequence number the last launch of an optimisation writes behind the statistics
+    PinBuf<float> stats_host;            // pinned: promp_optimize_begin parks both statistics slots here (async copy)
+    PinBuf<double> small_host;           // pinned: promp_download_processed gathers the per-path sums and coefficients here
+    PinBuf<unsigned> stats_seq_host;     // pinned: sequence number the last launch of an optimisation writes behind the statistics
     unsigned stats_seq = 0;              // the number the pending optimisation will write
     bool publish_next = false;           // enqueue_meta: this launch is the one that publishes
     bool opt_pending = false;
     int opt_epochs = 0;
-    float* fwd_buf = nullptr;            // staging for promp_policy_forward
-    size_t fwd_capacity = 0;
+    DevBuf<float> fwd_buf;               // staging for promp_policy_forward
 };
 
 namespace {
 
-template <class T>
-int dev_alloc(T** p, size_t n) {
-    HIPCHECK(hipMalloc((void**)p, (n ? n : 1) * sizeof(T)));
-    HIPCHECK(hipMemset(*p, 0, (n ? n : 1) * sizeof(T)));
-    return 0;
-}
 // lets each kernel take up to `bytes` of dynamic LDS
 template <class... Kernels>
 int allow_lds(int bytes, Kernels... kernels) {
@@ -291,15 +339,33 @@ int settle_others(promp_ctx* c, const StepData* touched) {
         if (&S != touched && mark_use(c, S)) return -2;
     return 0;
 }
+// The prologue of an entry point that works on one step: the context and step checks, then open(): the join with the step's
+// pending side-stream / copy-stream work, the other steps' use marks, and the check that the step holds data.  rc is what the
+// entry point returns if any of it failed.  An entry point with checks of its own between the two halves calls open() itself.
 struct StepScope {
     promp_ctx* c;
-    StepData& S;
-    int rc;
-    // writes: the entry point may change what a policy pass reads from the step (slabs, advantages, layout); pure readers say so
-    StepScope(promp_ctx* c_, StepData& S_, bool writes = true) : c(c_), S(S_), rc(join_side(c_, S_) | settle_others(c_, &S_)) {
-        if (writes) S.data_version = ++c->version_counter;
+    int step;
+    StepData* s = nullptr;
+    int rc = 0;
+    bool opened = false;
+    StepScope(promp_ctx* c_, int step_) : c(c_), step(step_) {
+        if (!c) rc = fail(-1, "ctx is NULL");
+        else if (step < 0 || step > c->d.num_inner_steps) rc = fail(-1, "step %d out of range", step);
+        else s = &c->steps[step];
     }
-    ~StepScope() { S.dirty = true; }
+    StepScope(promp_ctx* c_, int step, bool writes, bool needs_data) : StepScope(c_, step) {
+        if (!rc) open(writes, needs_data);
+    }
+    // writes: the entry point may change what a policy pass reads from the step (slabs, advantages, layout); pure readers say so
+    int open(bool writes, bool needs_data) {
+        opened = true;
+        rc = join_side(c, *s) | settle_others(c, s);
+        if (writes) s->data_version = ++c->version_counter;
+        if (!rc && needs_data && s->n_rows == 0) rc = fail(-3, "step %d has no data", step);
+        return rc;
+    }
+    ~StepScope() { if (opened) s->dirty = true; }
+    StepData& S() const { return *s; }
 };
 
 // hidden_sizes of a context: promp_dims carries up to four widths (n_hidden == 0: the two-layer struct of ABI 2)
@@ -370,11 +436,11 @@ int prof_begin(promp_ctx* c, int id, long long rows) {
     if (!c->prof) return 0;
     ProfSlot& s = c->prof_slots[id];
     if (s.used + 2 > s.ev.size()) {
-        hipEvent_t a, b;
-        HIPCHECK(hipEventCreate(&a));
-        HIPCHECK(hipEventCreate(&b));
-        s.ev.push_back(a);
-        s.ev.push_back(b);
+        Event a, b;
+        HIPCHECK(hipEventCreate(&a.h));
+        HIPCHECK(hipEventCreate(&b.h));
+        s.ev.push_back(std::move(a));
+        s.ev.push_back(std::move(b));
     }
     HIPCHECK(hipEventRecord(s.ev[s.used], c->stream));
     s.rows += rows;
@@ -427,12 +493,17 @@ void gen_wgrad(promp_ctx* c, const StepData& S, const GenArgs& g, int li, int pp
 #define PROMP_GEN_NBW(nbw, ...) \
     switch (nbw) { case 1: { constexpr int NBW = 1; __VA_ARGS__ } break; case 2: { constexpr int NBW = 2; __VA_ARGS__ } break; \
                    case 3: { constexpr int NBW = 3; __VA_ARGS__ } break; default: { constexpr int NBW = 4; __VA_ARGS__ } break; }
+// the context's layer table into the arguments of a layer-by-layer kernel
+template <class Args>
+void copy_layers(Args& dst, const promp_ctx* c) {
+    dst.n_lin = c->n_lin;
+    for (int l = 0; l < c->n_lin; ++l) dst.lin[l] = c->lin[l];
+}
 int launch_pass_generic(promp_ctx* c, StepData& S, const PassArgs& a, bool hvp, bool fwd_only) {
     GenArgs g;
     memset(&g, 0, sizeof g);
     g.work = a.work; g.task_row_offsets = a.task_row_offsets;
-    g.n_lin = c->n_lin;
-    for (int l = 0; l < c->n_lin; ++l) g.lin[l] = c->lin[l];
+    copy_layers(g, c);
     g.O = a.O; g.A = a.A; g.NP = c->NP; g.act_kind = gen_act_kinds(&c->d);
     g.theta = a.theta; g.theta_task_stride = a.theta_task_stride; g.vdir = a.vdir;
     g.act[0] = a.obs;
@@ -516,7 +587,7 @@ static bool primal_cache_on(const promp_ctx* c) { return c->family == PassFamily
 // the step's primal cache (promp_kernels_chain.h: chain_cache_row), allocated on first use
 static int ensure_primal_cache(promp_ctx* c, StepData& S) {
     if (S.hcache) return 0;
-    return dev_alloc(&S.hcache, ((size_t)c->d.max_rows + 16 * (size_t)c->d.n_tasks) * chain_cache_row(c->d.hidden1, c->d.hidden2));
+    return S.hcache.alloc(((size_t)c->d.max_rows + 16 * (size_t)c->d.n_tasks) * chain_cache_row(c->d.hidden1, c->d.hidden2));
 }
 
 // Chain: k_chain_hvp reduces in-launch when a.fuse_reduce says so; k_pass is followed by k_reduce_task
@@ -582,7 +653,7 @@ static void launch_coop_split(promp_ctx* c, StepData& S, PassArgs& a, const Pass
         va.src = c->vbuf; va.stride = c->NP; va.n = c->NP; va.out = c->vdir_absmax;
         va.n_w1 = c->d.obs_dim * c->d.hidden1; va.obs_absmax = a.obs_absmax;
         PROMP_LAUNCH(k_vec_absmax, dim3(c->d.n_tasks), 1024, 64, c->stream, va);
-        a.vdir_absmax = (const float*)c->vdir_absmax;
+        a.vdir_absmax = (const float*)c->vdir_absmax.p;
         pa.src = c->vbuf; pa.src_stride = c->NP; pa.dst = c->wb_vplanes; pa.vec_absmax = a.vdir_absmax;
         PROMP_LAUNCH(k_wb_planes, dim3((4 * (nko + 16) * 64 + 256 + 255) / 256, c->d.n_tasks), 256, 0, c->stream, pa);
         a.wb_v_planes = c->wb_vplanes;
@@ -606,11 +677,11 @@ int launch_pass(promp_ctx* c, StepData& S, const PassReq& q) {
     const bool chain = c->family == PassFamily::Chain;
     PassArgs a;
     memset(&a, 0, sizeof a);
-    a.obs_absmax = (const float*)S.obs_absmax;
+    a.obs_absmax = (const float*)S.obs_absmax.p;
     a.obs = S.obs; a.act = S.act; a.adv = q.adv ? q.adv : S.adv32; a.old_mean = S.old_mean; a.old_log_std = S.old_ls;
     a.row_tan = q.hvp ? q.row_tan : nullptr;
     const int cache = (!chain || q.fwd_only || !S.hcache) ? 0 : q.cache;
-    a.hcache = cache ? S.hcache : nullptr;
+    a.hcache = cache ? S.hcache.p : nullptr;
     if (cache == 1) S.cache_tag = ++c->cache_counter;
     a.ls_per_row = S.ls_per_row;
     a.task_row_offsets = S.task_row_offsets;
@@ -633,7 +704,7 @@ int launch_pass(promp_ctx* c, StepData& S, const PassReq& q) {
     float* scal = q.scal ? q.scal : c->scal_tmp;
     a.red_mode = q.red_mode; a.step_sizes = c->step_sizes; a.cur = q.cur; a.cur_task_stride = q.cur_stride; a.next = q.next;
     a.lam = c->lam; a.v = c->vbuf; a.scal = scal;
-    a.dbg = c->dbg_enabled ? c->dbg : nullptr;
+    a.dbg = c->dbg_enabled ? c->dbg.p : nullptr;
     a.split_events = c->split_events;
     const int id = q.hvp ? PROMP_KERNEL_HVP : q.fwd_only ? PROMP_KERNEL_FWD : PROMP_KERNEL_FWD_BWD;
     // (the timed slot covers the pass with the small launches that prepare its operands: k_wb_planes, k_vec_absmax)
@@ -694,13 +765,7 @@ static int exchange_sums(promp_ctx* c, float* buf, size_t n) {
 }
 static int exchange_sums_raw(promp_ctx* c, float* buf, size_t n) {
     if (c->fixed_order) {
-        const size_t need = (size_t)c->nranks * n;
-        if (c->gather_len < need) {
-            if (c->gather) HIPCHECK(hipFree(c->gather));
-            c->gather = nullptr;
-            HIPCHECK(hipMalloc((void**)&c->gather, sizeof(float) * need));
-            c->gather_len = need;
-        }
+        if (c->gather.reserve((size_t)c->nranks * n, 1)) return -2;
         ncclResult_t r = ncclAllGather(buf, c->gather, n, ncclFloat, c->comm, c->stream);
         if (r != ncclSuccess) return fail(-4, "ncclAllGather failed: %s", ncclGetErrorString(r));
         PROMP_LAUNCH(k_sum_ranks, dim3((unsigned)((n + 255) / 256)), 256, 0, c->stream, (const float*)c->gather, buf, (int)n, c->nranks);
@@ -767,7 +832,7 @@ int enqueue_meta(promp_ctx* c, float clip_eps, const float* eta_host, int inner_
             PassReq q;
             q.hvp = true; q.theta = th; q.theta_stride = st; q.loss_kind = loss_kind_inner(inner_kind); q.clip_eps = clip_eps; q.clip_ls = k == 0;
             q.klw = dice ? 0.f : eta_host[k] / (float)K; q.red_mode = RED_HVP;
-            q.cache = filled[k] ? 2 : 0; q.row_tan = dice ? Sk.dice_c : nullptr;
+            q.cache = filled[k] ? 2 : 0; q.row_tan = dice ? Sk.dice_c.p : nullptr;
             if (launch_pass(c, Sk, q)) return -2;
             if (dice) {
                 // The magic box couples the time steps of a path: H v = H_loglik(w) v + grad_loglik(u(v)), u from the row tangents
@@ -798,7 +863,7 @@ int enqueue_meta(promp_ctx* c, float clip_eps, const float* eta_host, int inner_
     ad.theta = c->theta; ad.m = c->adam_m; ad.v = c->adam_v; ad.red = c->red; ad.grad_mean = c->grad_mean;
     ad.stats = c->stats + (size_t)c->stats_slot * (K + 2); ad.NP = NP; ad.K = K; ad.A = c->d.act_dim;
     for (int k = 0; k < PROMP_ETA_MAX; ++k) ad.eta[k] = k < K ? eta_host[k] : 0.f;
-    ad.host_stats = c->publish_next ? c->stats_host : nullptr; ad.host_seq = c->stats_seq_host; ad.seq = c->stats_seq;
+    ad.host_stats = c->publish_next ? c->stats_host.p : nullptr; ad.host_seq = c->stats_seq_host; ad.seq = c->stats_seq;
     ad.inv_tasks = 1.0f / (float)c->d.n_tasks_global;
     ad.do_update = do_adam ? 1 : 0;
     ad.n_trainable = c->learn_std ? NP : NP - c->d.act_dim;
@@ -823,36 +888,24 @@ int upload_eta(promp_ctx* c, const float* eta) {
     return 0;
 }
 
-void free_step(StepData& S) {
-    void* ptrs[] = {S.obs_absmax, S.hcache, S.dice_rw, S.dice_c, S.dice_u, S.dice_tmp, S.rew64, S.obs, S.act, S.rew, S.old_mean, S.old_ls, S.ret32, S.adv32, S.ret64, S.adv64, S.path_row_offsets,
-                    S.path_task, S.row_t, S.task_row_offsets, S.task_path_offsets, S.task_wg_offsets[0], S.task_wg_offsets[1], S.chain_segs, S.chain_wg_offsets,
-                    S.chain_slot_offsets, S.path_ret0,
-                    S.path_undisc, S.path_rsq, S.path_mom, S.coeffs, S.work[0], S.work[1]};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-}
-
 int alloc_step(promp_ctx* c, StepData& S) {
     const promp_dims* dims = &c->d;
     const int M = dims->n_tasks;
     const size_t R = dims->max_rows, P = dims->max_paths, A = dims->act_dim, O = dims->obs_dim;
-    int rc = 0;
-    rc |= dev_alloc(&S.obs, R * O); rc |= dev_alloc(&S.act, R * A); rc |= dev_alloc(&S.rew, R);
-    rc |= dev_alloc(&S.obs_absmax, (size_t)M);
-    rc |= dev_alloc(&S.old_mean, R * A); rc |= dev_alloc(&S.old_ls, R * A);
-    rc |= dev_alloc(&S.ret32, R); rc |= dev_alloc(&S.adv32, R); rc |= dev_alloc(&S.ret64, R); rc |= dev_alloc(&S.adv64, R);
-    rc |= dev_alloc(&S.path_row_offsets, P + 1); rc |= dev_alloc(&S.path_task, P); rc |= dev_alloc(&S.row_t, R);
-    rc |= dev_alloc(&S.task_row_offsets, (size_t)M + 1); rc |= dev_alloc(&S.task_path_offsets, (size_t)M + 1);
-    rc |= dev_alloc(&S.task_wg_offsets[0], (size_t)M + 1); rc |= dev_alloc(&S.task_wg_offsets[1], (size_t)M + 1);
-    rc |= dev_alloc(&S.chain_segs, (size_t)c->max_work); rc |= dev_alloc(&S.chain_wg_offsets, (size_t)c->max_work + 1);
-    rc |= dev_alloc(&S.chain_slot_offsets, (size_t)M + 1);
-    rc |= dev_alloc(&S.path_ret0, P); rc |= dev_alloc(&S.path_undisc, P); rc |= dev_alloc(&S.path_rsq, P);
-    rc |= dev_alloc(&S.path_mom, 3 * P); rc |= dev_alloc(&S.coeffs, (size_t)M * c->coeff_stride);
-    rc |= dev_alloc(&S.work[0], (size_t)c->max_work); rc |= dev_alloc(&S.work[1], (size_t)c->max_work);
-    if (hipEventCreateWithFlags(&S.ev_use, hipEventDisableTiming) != hipSuccess) rc |= 1;
-    if (hipEventCreateWithFlags(&S.ev_done, hipEventDisableTiming) != hipSuccess) rc |= 1;
-    if (hipEventCreateWithFlags(&S.ev_ready, hipEventDisableTiming) != hipSuccess) rc |= 1;
-    return rc ? -2 : 0;
+    if (S.obs.alloc(R * O) || S.act.alloc(R * A) || S.rew.alloc(R)) return -2;
+    if (S.obs_absmax.alloc((size_t)M)) return -2;
+    if (S.old_mean.alloc(R * A) || S.old_ls.alloc(R * A)) return -2;
+    if (S.ret32.alloc(R) || S.adv32.alloc(R) || S.ret64.alloc(R) || S.adv64.alloc(R)) return -2;
+    if (S.path_row_offsets.alloc(P + 1) || S.path_task.alloc(P) || S.row_t.alloc(R)) return -2;
+    if (S.task_row_offsets.alloc((size_t)M + 1) || S.task_path_offsets.alloc((size_t)M + 1)) return -2;
+    if (S.task_wg_offsets[0].alloc((size_t)M + 1) || S.task_wg_offsets[1].alloc((size_t)M + 1)) return -2;
+    if (S.chain_segs.alloc((size_t)c->max_work) || S.chain_wg_offsets.alloc((size_t)c->max_work + 1)) return -2;
+    if (S.chain_slot_offsets.alloc((size_t)M + 1)) return -2;
+    if (S.path_ret0.alloc(P) || S.path_undisc.alloc(P) || S.path_rsq.alloc(P)) return -2;
+    if (S.path_mom.alloc(3 * P) || S.coeffs.alloc((size_t)M * c->coeff_stride)) return -2;
+    if (S.work[0].alloc((size_t)c->max_work) || S.work[1].alloc((size_t)c->max_work)) return -2;
+    for (Event* ev : {&S.ev_use, &S.ev_done, &S.ev_ready}) HIPCHECK(hipEventCreateWithFlags(&ev->h, hipEventDisableTiming));
+    return 0;
 }
 
 }  // namespace
@@ -921,12 +974,14 @@ int promp_ctx_create(promp_ctx** out, int device_id, const promp_dims* user_dims
         return fail(-2, "no HIP device available (%s): libpromp_hip has no CPU fallback", e != hipSuccess ? hipGetErrorString(e) : "0 devices");
     if (device_id < 0 || device_id >= ndev) return fail(-1, "device_id %d out of range (%d devices)", device_id, ndev);
     HIPCHECK(hipSetDevice(device_id));
-    promp_ctx* c = new promp_ctx();
+    // every exit below but the last releases the context and what it holds by then
+    std::unique_ptr<promp_ctx, void (*)(promp_ctx*)> guard(new promp_ctx(), promp_ctx_destroy);
+    promp_ctx* c = guard.get();
+    c->device = device_id;
     c->d = *dims;
     c->du = *user_dims;
     c->NPu = param_count(user_dims);
     c->padded = c->NPu != param_count(dims);
-    c->device = device_id;
     { const char* e = getenv("PROMP_FIT_ONE_LAUNCH"); c->fit_one_launch = e && e[0] == '1'; }
     { const char* e = getenv("PROMP_GRAM_UNTILED"); c->gram_untiled = e && e[0] == '1'; }
     { const char* e = getenv("PROMP_GRAMT_SINGLE"); c->gramt_single = e && e[0] == '1'; }
@@ -940,15 +995,15 @@ int promp_ctx_create(promp_ctx** out, int device_id, const promp_dims* user_dims
     }
     c->clock_mhz = prop.clockRate / 1000;
     snprintf(c->dev_name, sizeof c->dev_name, "%s", prop.name[0] ? prop.name : PROMP_ARCH_NAME(prop));
-    HIPCHECK(hipStreamCreate(&c->stream));
+    HIPCHECK(hipStreamCreate(&c->stream.h));
     {   // sample processing of steps >= 1 is a string of small latency-bound kernels under a chip-filling pass: with the
         // higher priority their workgroups are placed first, the string finishes before the main stream needs its result
         int lo = 0, hi = 0;
         HIPCHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
         // (PROMP_SIDE_PRIO=lo / none: the A/B switch)
         const char* e = getenv("PROMP_SIDE_PRIO");
-        if (e && e[0] == 'n') HIPCHECK(hipStreamCreate(&c->side));
-        else HIPCHECK(hipStreamCreateWithPriority(&c->side, hipStreamDefault, (e && e[0] == 'l') ? lo : hi));
+        if (e && e[0] == 'n') HIPCHECK(hipStreamCreate(&c->side.h));
+        else HIPCHECK(hipStreamCreateWithPriority(&c->side.h, hipStreamDefault, (e && e[0] == 'l') ? lo : hi));
     }
     const int K = dims->num_inner_steps, M = dims->n_tasks;
     c->NP = param_count(dims);
@@ -1009,7 +1064,6 @@ int promp_ctx_create(promp_ctx** out, int device_id, const promp_dims* user_dims
     }
     if (c->smem_hvp > 160 * 1024 || c->smem_fwd > 160 * 1024) {
         const size_t need = c->smem_hvp > c->smem_fwd ? c->smem_hvp : c->smem_fwd;
-        promp_ctx_destroy(c);
         return fail(-1, "LDS budget exceeded (%zu bytes)", need);
     }
     {   // dynamic LDS past the default limit, for every instance of every family
@@ -1034,52 +1088,54 @@ int promp_ctx_create(promp_ctx** out, int device_id, const promp_dims* user_dims
         PROMP_GEN_LDS(1) PROMP_GEN_LDS(2) PROMP_GEN_LDS(3) PROMP_GEN_LDS(4)
 #undef PROMP_GEN_LDS
         if (allow_lds((int)gen_loss_smem(GEN_MAX_A), k_gen_loss<true, true>, k_gen_loss<false, true>, k_gen_loss<false, false>)) return -2;
-        if (allow_lds(lds, k_gram<1>, k_gram<2>, k_gram<3>, k_gram<4>, k_gram<5>, k_fit, k_fit_wave<12>, k_fit_wave<48>, k_fit_wave<64>,
-                      k_fit_wave<45>, k_gram_wide, k_gram_tiled<GRAMT_TB, GRAMT_NWV, GRAMT_NLD>, k_fitw_panel<32>, k_fitw_panel<16>,
+#define PROMP_GRAM_INST(NBLK) k_gram<NBLK>,
+#define PROMP_FITWV_INST(DT) k_fit_wave<DT>,
+        if (allow_lds(lds, PROMP_GRAM_ALL(PROMP_GRAM_INST) PROMP_FITWV_ALL(PROMP_FITWV_INST) k_fit, k_gram_wide, k_gram_tiled<GRAMT_TB, GRAMT_NWV, GRAMT_NLD>, k_fitw_panel<32>, k_fitw_panel<16>,
                       k_fitw_update<32>, k_fitw_update<16>, k_fitw_back<32>, k_fitw_back<16>, k_fit_wide<32>, k_fit_wide<16>)) return -2;
+#undef PROMP_GRAM_INST
+#undef PROMP_FITWV_INST
     }
     const size_t NP = c->NP, MNP = (size_t)M * NP;
-    int rc = 0;
-    rc |= dev_alloc(&c->theta, NP); rc |= dev_alloc(&c->step_sizes, NP);
-    rc |= dev_alloc(&c->adam_m, NP); rc |= dev_alloc(&c->adam_v, NP);
-    rc |= dev_alloc(&c->theta_tasks, MNP); rc |= dev_alloc(&c->chain, (size_t)(K + 1) * MNP);
-    rc |= dev_alloc(&c->lam, MNP); rc |= dev_alloc(&c->vbuf, MNP);
+    if (c->theta.alloc(NP) || c->step_sizes.alloc(NP)) return -2;
+    if (c->adam_m.alloc(NP) || c->adam_v.alloc(NP)) return -2;
+    if (c->theta_tasks.alloc(MNP) || c->chain.alloc((size_t)(K + 1) * MNP)) return -2;
+    if (c->lam.alloc(MNP) || c->vbuf.alloc(MNP)) return -2;
     if (c->family == PassFamily::CoopSplit) {
         const size_t pw = (size_t)M * wb_planes_words(wb_nko(c->wb_cls));
-        rc |= dev_alloc(&c->wb_planes, pw); rc |= dev_alloc(&c->wb_vplanes, pw); rc |= dev_alloc(&c->wb_planes_meta, pw);
-        rc |= dev_alloc(&c->vdir_absmax, (size_t)M);
+        if (c->wb_planes.alloc(pw) || c->wb_vplanes.alloc(pw) || c->wb_planes_meta.alloc(pw)) return -2;
+        if (c->vdir_absmax.alloc((size_t)M)) return -2;
     }
-    rc |= dev_alloc(&c->partials, (size_t)c->max_work * c->partial_stride);
-    rc |= dev_alloc(&c->scal_inner, (size_t)K * M * 2); rc |= dev_alloc(&c->scal_outer, (size_t)M * 2);
-    rc |= dev_alloc(&c->scal_tmp, (size_t)M * 2);
-    rc |= dev_alloc(&c->red, NP + K + 2); rc |= dev_alloc(&c->grad_mean, NP);
-    rc |= dev_alloc(&c->stats, (size_t)2 * (K + 2));
+    if (c->partials.alloc((size_t)c->max_work * c->partial_stride)) return -2;
+    if (c->scal_inner.alloc((size_t)K * M * 2) || c->scal_outer.alloc((size_t)M * 2)) return -2;
+    if (c->scal_tmp.alloc((size_t)M * 2)) return -2;
+    if (c->red.alloc(NP + K + 2) || c->grad_mean.alloc(NP)) return -2;
+    if (c->stats.alloc((size_t)2 * (K + 2))) return -2;
     // (the baseline fit's partial Gram blocks and scratch matrices -- 2.7 GB per set at Humanoid's 757 columns -- are allocated by the
     //  first promp_process_samples that fits a baseline on that stream: fit_buffers())
-    rc |= dev_alloc(&c->red64, 64);
+    if (c->red64.alloc(64)) return -2;
     if (c->family == PassFamily::Layered) {
         const size_t R = (size_t)dims->max_rows;
-        for (int l = 1; l < c->n_lin; ++l) {
-            rc |= dev_alloc(&c->g_act[l], R * c->lin[l].K);
-            rc |= dev_alloc(&c->g_ract[l], R * c->lin[l].K);
-        }
-        rc |= dev_alloc(&c->g_mu, R * dims->act_dim); rc |= dev_alloc(&c->g_rmu, R * dims->act_dim);
-        for (int i = 0; i < 2; ++i) { rc |= dev_alloc(&c->g_dz[i], R * c->g_maxw); rc |= dev_alloc(&c->g_qz[i], R * c->g_maxw); }
-        if (c->gen_bf16) { rc |= dev_alloc(&c->gb_wplanes, (size_t)M * c->gb_plane_stride); rc |= dev_alloc(&c->gb_vplanes, (size_t)M * c->gb_plane_stride); }
+        for (int l = 1; l < c->n_lin; ++l)
+            if (c->g_act[l].alloc(R * c->lin[l].K) || c->g_ract[l].alloc(R * c->lin[l].K)) return -2;
+        if (c->g_mu.alloc(R * dims->act_dim) || c->g_rmu.alloc(R * dims->act_dim)) return -2;
+        for (int i = 0; i < 2; ++i)
+            if (c->g_dz[i].alloc(R * c->g_maxw) || c->g_qz[i].alloc(R * c->g_maxw)) return -2;
+        if (c->gen_bf16 && (c->gb_wplanes.alloc((size_t)M * c->gb_plane_stride) || c->gb_vplanes.alloc((size_t)M * c->gb_plane_stride))) return -2;
     }
-    rc |= dev_alloc(&c->task_counters, (size_t)M);
-    rc |= dev_alloc(&c->dbg, 256 + 4 * 1024);
-    rc |= dev_alloc(&c->split_events, 4);
-    if (hipHostMalloc((void**)&c->stats_host, sizeof(float) * (2 * (K + 2) + 1), hipHostMallocDefault) != hipSuccess) rc |= 1;
-    if (hipHostMalloc((void**)&c->stats_seq_host, sizeof(unsigned), hipHostMallocDefault) != hipSuccess) rc |= 1;
-    else *c->stats_seq_host = 0;
+    if (c->task_counters.alloc((size_t)M)) return -2;
+    if (c->dbg.alloc(256 + 4 * 1024)) return -2;
+    if (c->split_events.alloc(4)) return -2;
+    if (c->stats_host.alloc(2 * (K + 2) + 1)) return -2;
+    if (c->stats_seq_host.alloc(1)) return -2;
+    *c->stats_seq_host = 0;
     c->steps.resize(K + 1);
-    for (int s = 0; s <= K && !rc; ++s) rc |= alloc_step(c, c->steps[s]);
-    if (rc) { promp_ctx_destroy(c); return -2; }
-    *out = c;
+    for (auto& S : c->steps)
+        if (alloc_step(c, S)) return -2;
+    *out = guard.release();
     return 0;
 }
 
+// (delete releases what the context's members own, in reverse order of declaration: buffers and events first, the streams last)
 void promp_ctx_destroy(promp_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
@@ -1087,38 +1143,11 @@ void promp_ctx_destroy(promp_ctx* c) {
     if (c->side) (void)hipStreamSynchronize(c->side);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->comm) ncclCommDestroy(c->comm);
-    if (c->gather) (void)hipFree(c->gather);
-    for (auto* set : {&c->steps, &c->back})
-        for (auto& S : *set) {
-            free_step(S);
-            if (S.ev_use) (void)hipEventDestroy(S.ev_use);
-            if (S.ev_done) (void)hipEventDestroy(S.ev_done);
-            if (S.ev_ready) (void)hipEventDestroy(S.ev_ready);
-        }
-    void* ptrs[] = {c->cg_buf, c->cg_scal, c->vdir_absmax, c->gb_wplanes, c->gb_vplanes, c->wb_planes, c->wb_vplanes, c->wb_planes_meta, c->wbuf, c->gram_partials_side, c->fit_scratch_side, c->theta, c->step_sizes, c->adam_m, c->adam_v, c->theta_tasks, c->chain, c->lam, c->vbuf,
-                    c->partials, c->scal_inner, c->scal_outer, c->scal_tmp, c->red, c->grad_mean, c->stats,
-                    c->gram_partials, c->red64, c->fwd_buf, c->stage_rows, c->task_counters, c->split_events, c->dbg, c->fit_scratch, c->rollout_buf};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    for (int l = 0; l < GEN_MAX_LIN; ++l) {
-        if (c->g_act[l]) (void)hipFree(c->g_act[l]);
-        if (c->g_ract[l]) (void)hipFree(c->g_ract[l]);
-    }
-    for (float* p : {c->g_mu, c->g_rmu, c->g_dz[0], c->g_dz[1], c->g_qz[0], c->g_qz[1]})
-        if (p) (void)hipFree(p);
-    if (c->stats_host) (void)hipHostFree(c->stats_host);
-    if (c->small_host) (void)hipHostFree(c->small_host);
-    if (c->stats_seq_host) (void)hipHostFree(c->stats_seq_host);
-    for (auto& s : c->prof_slots)
-        for (auto ev : s.ev) (void)hipEventDestroy(ev);
-    if (c->copy) (void)hipStreamDestroy(c->copy);
-    if (c->side) (void)hipStreamDestroy(c->side);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
 int promp_sync(promp_ctx* c) {
-    if (!c) return fail(-1, "ctx is NULL");
+    NEED_CTX(c);
     if (c->copy) HIPCHECK(hipStreamSynchronize(c->copy));
     HIPCHECK(hipStreamSynchronize(c->side));
     HIPCHECK(hipStreamSynchronize(c->stream));
@@ -1320,12 +1349,10 @@ static int copy_step_data(promp_ctx* c, StepData& S, hipStream_t st, const float
 
 int promp_upload_step(promp_ctx* c, int step, int n_paths, const int32_t* tpo, const int32_t* pro, const float* obs,
                       const float* act, const float* rew, const float* old_mean, const float* old_ls, int ls_per_row) {
-    if (!c) return fail(-1, "ctx is NULL");
-    if (!obs || !rew) return fail(-1, "offsets, obs and rew are required");
-    if (step < 0 || step > c->d.num_inner_steps) return fail(-1, "step %d out of range", step);
-    StepData& S = c->steps[step];
-    StepScope scope_(c, S);
-    if (scope_.rc) return -2;
+    if (c && (!obs || !rew)) return fail(-1, "offsets, obs and rew are required");
+    StepScope sc(c, step, /*writes=*/true, /*needs_data=*/false);
+    if (sc.rc) return sc.rc;
+    StepData& S = sc.S();
     if (set_step_layout(c, S, c->stream, false, n_paths, tpo, pro)) return -2;
     return copy_step_data(c, S, c->stream, obs, act, rew, old_mean, old_ls, ls_per_row);
 }
@@ -1345,10 +1372,10 @@ void promp_host_free(void* p) {
 
 int promp_stage_step(promp_ctx* c, int step, int n_paths, const int32_t* tpo, const int32_t* pro, const float* obs,
                      const float* act, const float* rew, const float* old_mean, const float* old_ls, int ls_per_row) {
-    if (!c) return fail(-1, "ctx is NULL");
+    NEED_CTX(c);
     if (!obs || !rew) return fail(-1, "offsets, obs and rew are required");
     if (step < 0 || step > c->d.num_inner_steps) return fail(-1, "step %d out of range", step);
-    if (!c->copy) HIPCHECK(hipStreamCreate(&c->copy));
+    if (!c->copy) HIPCHECK(hipStreamCreate(&c->copy.h));
     if (c->back.empty()) {
         c->back.resize(c->steps.size());
         for (auto& B : c->back)
@@ -1373,7 +1400,7 @@ int promp_stage_step(promp_ctx* c, int step, int n_paths, const int32_t* tpo, co
 }
 
 int promp_commit_step(promp_ctx* c, int step) {
-    if (!c) return fail(-1, "ctx is NULL");
+    NEED_CTX(c);
     if (step < 0 || step > c->d.num_inner_steps) return fail(-1, "step %d out of range", step);
     if (c->back.empty() || !c->back[step].staged) return fail(-3, "step %d has nothing staged", step);
     // uses of the outgoing set that are still unmarked get their mark now, while "everything enqueued so far" is tight
@@ -1385,7 +1412,7 @@ int promp_commit_step(promp_ctx* c, int step) {
 }
 
 int promp_stage_wait(promp_ctx* c) {
-    if (!c) return fail(-1, "ctx is NULL");
+    NEED_CTX(c);
     if (c->copy) HIPCHECK(hipStreamSynchronize(c->copy));
     return 0;
 }
@@ -1428,21 +1455,31 @@ void gramt_balance(int nblk, int nwv, GramtMap* map) {
 }
 
 int fit_buffers(promp_ctx* c, bool on_side) {
-    double*& gp = on_side ? c->gram_partials_side : c->gram_partials;
-    double*& fs = on_side ? c->fit_scratch_side : c->fit_scratch;
-    if (!gp && dev_alloc(&gp, (size_t)c->max_work * c->gram_stride)) return -2;
+    DevBuf<double>& gp = on_side ? c->gram_partials_side : c->gram_partials;
+    DevBuf<double>& fs = on_side ? c->fit_scratch_side : c->fit_scratch;
+    if (!gp && gp.alloc((size_t)c->max_work * c->gram_stride)) return -2;
     const int nblk_max = (c->Dmax + 1 + 15) / 16;
-    if (!fs && (nblk_max > 5 || c->d.obs_dim > 32) && dev_alloc(&fs, (size_t)c->d.n_tasks * 2 * (c->Dmax + 1) * (c->Dmax + 1) + c->d.n_tasks)) return -2;   // (+ k_fitw_back's flags)
+    if (!fs && (nblk_max > 5 || c->d.obs_dim > 32) && fs.alloc((size_t)c->d.n_tasks * 2 * (c->Dmax + 1) * (c->Dmax + 1) + c->d.n_tasks)) return -2;   // (+ k_fitw_back's flags)
     return 0;
+}
+
+// What every sample kernel reads of a step (promp_predict_baseline's k_gae needs no more); everything else is zero and the caller
+// sets what its kernels use
+static SampleArgs sample_args(const promp_ctx* c, const StepData& S, int kind) {
+    SampleArgs a;
+    memset(&a, 0, sizeof a);
+    a.obs = S.obs; a.rew = S.rew; a.rew64 = S.has_rew64 ? S.rew64.p : nullptr; a.path_row_offsets = S.path_row_offsets; a.path_task = S.path_task; a.row_t = S.row_t;
+    a.task_row_offsets = S.task_row_offsets; a.task_path_offsets = S.task_path_offsets;
+    a.O = c->d.obs_dim; a.kind = kind; a.D = feature_dim(&c->d, kind);
+    a.adv64 = S.adv64; a.path_mom = S.path_mom; a.coeffs = S.coeffs; a.coeff_stride = c->coeff_stride;
+    return a;
 }
 
 int promp_process_samples(promp_ctx* c, int step, const promp_proc_opts* o) {
     if (!c || !o) return fail(-1, "NULL argument");
-    if (step < 0 || step > c->d.num_inner_steps) return fail(-1, "step %d out of range", step);
-    StepData& S = c->steps[step];
-    StepScope scope_(c, S);
-    if (scope_.rc) return -2;
-    if (S.n_rows == 0) return fail(-3, "step %d has no data", step);
+    StepScope sc(c, step, /*writes=*/true, /*needs_data=*/true);
+    if (sc.rc) return sc.rc;
+    StepData& S = sc.S();
     if (!(o->discount >= 0 && o->discount <= 1)) return fail(-1, "discount factor must be in [0,1]");      // samplers/base.py:57
     if (!(o->gae_lambda >= 0 && o->gae_lambda <= 1)) return fail(-1, "gae_lambda must be in [0,1]");       // samplers/base.py:58
     if (o->baseline_kind < 0 || o->baseline_kind > 2) return fail(-1, "unknown baseline kind %d", o->baseline_kind);
@@ -1450,18 +1487,13 @@ int promp_process_samples(promp_ctx* c, int step, const promp_proc_opts* o) {
         return fail(-1, "LinearFeatureBaseline's fit is sized for obs_dim <= %d (%d here: %d feature columns); fit LinearTimeBaseline / no "
                     "baseline on the device, or hand advantages in through promp_set_advantages", PROMP_LINFEAT_MAX_O, c->d.obs_dim,
                     2 * c->d.obs_dim + 5);
-    SampleArgs a;
-    a.obs = S.obs; a.rew = S.rew; a.rew64 = S.has_rew64 ? S.rew64 : nullptr; a.path_row_offsets = S.path_row_offsets; a.path_task = S.path_task; a.row_t = S.row_t;
-    a.task_row_offsets = S.task_row_offsets; a.task_path_offsets = S.task_path_offsets;
+    SampleArgs a = sample_args(c, S, o->baseline_kind);
     a.work = S.work[0];                         // k_gram / k_fit: one workgroup per CU
     a.task_wg_offsets = S.task_wg_offsets[0];
-    a.O = c->d.obs_dim; a.kind = o->baseline_kind; a.D = feature_dim(&c->d, o->baseline_kind);
     a.gamma = o->discount; a.lam = o->gae_lambda; a.reg = o->reg_coeff;
     a.normalize = o->normalize_adv; a.positive = o->positive_adv;
-    a.ret64 = S.ret64; a.ret32 = S.ret32; a.adv64 = S.adv64; a.adv32 = S.adv32;
-    a.path_ret0 = S.path_ret0; a.path_undisc = S.path_undisc; a.path_rsq = S.path_rsq; a.path_mom = S.path_mom;
-    a.coeffs = S.coeffs; a.coeff_stride = c->coeff_stride;
-    a.bl64 = nullptr;
+    a.ret64 = S.ret64; a.ret32 = S.ret32; a.adv32 = S.adv32;
+    a.path_ret0 = S.path_ret0; a.path_undisc = S.path_undisc; a.path_rsq = S.path_rsq;
     S.feat_dim = a.D;
     // Steps >= 1 go to the second stream (no data dependence on the step-0 work the host enqueued just before: their
     // samples are resident), behind the last main-stream work that touched this step's slabs.  Per-kernel timing
@@ -1485,11 +1517,10 @@ int promp_process_samples(promp_ctx* c, int step, const promp_proc_opts* o) {
         // k_gram<NBLK> stages raw observation rows of at most 32 floats (LinearTimeBaseline reads no observations: any obs_dim)
         const bool small = nblk <= 5 && (a.O <= 32 || a.kind != BASE_LINFEAT);
         switch (small ? nblk : 0) {
-            case 1: { auto k = k_gram<1>; PROMP_LAUNCH(k, dim3(S.n_work[0]), 64 * GramCfg<1>::NW, GramCfg<1>::SMEM_BYTES, st, a); } break;
-            case 2: { auto k = k_gram<2>; PROMP_LAUNCH(k, dim3(S.n_work[0]), 64 * GramCfg<2>::NW, GramCfg<2>::SMEM_BYTES, st, a); } break;
-            case 3: { auto k = k_gram<3>; PROMP_LAUNCH(k, dim3(S.n_work[0]), 64 * GramCfg<3>::NW, GramCfg<3>::SMEM_BYTES, st, a); } break;
-            case 4: { auto k = k_gram<4>; PROMP_LAUNCH(k, dim3(S.n_work[0]), 64 * GramCfg<4>::NW, GramCfg<4>::SMEM_BYTES, st, a); } break;
-            case 5: { auto k = k_gram<5>; PROMP_LAUNCH(k, dim3(S.n_work[0]), 64 * GramCfg<5>::NW, GramCfg<5>::SMEM_BYTES, st, a); } break;
+#define PROMP_GRAM_CASE(NBLK) \
+    case NBLK: { auto k = k_gram<NBLK>; PROMP_LAUNCH(k, dim3(S.n_work[0]), 64 * GramCfg<NBLK>::NW, GramCfg<NBLK>::SMEM_BYTES, st, a); } break;
+            PROMP_GRAM_ALL(PROMP_GRAM_CASE)
+#undef PROMP_GRAM_CASE
             default:
                 // 13 blocks and more (obs_dim >= 94; Ant: 15, Humanoid: 48): a square of 3 x 3 blocks per wave, operands reused in
                 // registers (k_gram_tiled); fewer blocks make too few squares to fill a compute unit: k_gram_wide
@@ -1513,11 +1544,12 @@ int promp_process_samples(promp_ctx* c, int step, const promp_proc_opts* o) {
         if (small) {
             const size_t fit_smem = sizeof(double) * ((size_t)2 * DA * DA + 3 * DA + 2 + fitwv_aux(64));      // (k_fit / k_fit_wave<DT <= 64>)
             // one wave per task while a row of the work matrix fits a wave's lanes (D + 1 <= 64); else one workgroup per task
-            if (DA <= 12) { auto k = k_fit_wave<12>; PROMP_LAUNCH(k, dim3(c->d.n_tasks), FITWV_NT, fit_smem, st, a, nblk); }
-            else if (DA <= 45) { auto k = k_fit_wave<45>; PROMP_LAUNCH(k, dim3(c->d.n_tasks), FITWV_NT, fit_smem, st, a, nblk); }    // obs_dim 20
-            else if (DA <= 48) { auto k = k_fit_wave<48>; PROMP_LAUNCH(k, dim3(c->d.n_tasks), FITWV_NT, fit_smem, st, a, nblk); }
-            else if (DA <= 64) { auto k = k_fit_wave<64>; PROMP_LAUNCH(k, dim3(c->d.n_tasks), FITWV_NT, fit_smem, st, a, nblk); }
+            // (45: obs_dim 20)
+#define PROMP_FITWV_CASE(DT) else if (DA <= DT) { auto k = k_fit_wave<DT>; PROMP_LAUNCH(k, dim3(c->d.n_tasks), FITWV_NT, fit_smem, st, a, nblk); }
+            if (false) {}                       // (head of the chain the list expands to)
+            PROMP_FITWV_ALL(PROMP_FITWV_CASE)
             else PROMP_LAUNCH(k_fit, dim3(c->d.n_tasks), 256, fit_smem, st, a, nblk);
+#undef PROMP_FITWV_CASE
         } else {
             PROMP_LAUNCH(k_gram_sum_wide, dim3(c->d.n_tasks * fitw_sum_split(nblk)), 256, 0, st, a, nblk, fit_scratch, fitw_sum_split(nblk));
             HIPCHECK(hipGetLastError());
@@ -1555,11 +1587,9 @@ int promp_process_samples(promp_ctx* c, int step, const promp_proc_opts* o) {
 
 int promp_download_processed(promp_ctx* c, int step, float* returns, float* adv, double* coeffs, double* ret0,
                              double* undisc, double* rsq) {
-    if (!c) return fail(-1, "ctx is NULL");
-    if (step < 0 || step > c->d.num_inner_steps) return fail(-1, "step %d out of range", step);
-    StepData& S = c->steps[step];
-    StepScope scope_(c, S, false);
-    if (scope_.rc) return -2;
+    StepScope sc(c, step, /*writes=*/false, /*needs_data=*/false);
+    if (sc.rc) return sc.rc;
+    StepData& S = sc.S();
     if (!S.processed) return fail(-3, "step %d has not been processed", step);
     hipStream_t st = c->stream;
     if (returns) HIPCHECK(hipMemcpyAsync(returns, S.ret32, sizeof(float) * S.n_rows, hipMemcpyDeviceToHost, st));
@@ -1568,13 +1598,7 @@ int promp_download_processed(promp_ctx* c, int step, float* returns, float* adv,
     // synchronisation and are copied out from there: the caller's arrays are pageable, and a device-to-pageable copy is a
     // synchronous bounce each (the plugin classes make this call once per sampling step)
     const size_t P = (size_t)S.n_paths, NC = (coeffs && S.feat_dim > 0) ? (size_t)c->d.n_tasks * c->coeff_stride : 0;
-    const size_t need = 3 * P + NC;
-    if (c->small_host_len < need) {
-        if (c->small_host) HIPCHECK(hipHostFree(c->small_host));
-        c->small_host = nullptr; c->small_host_len = 0;
-        HIPCHECK(hipHostMalloc((void**)&c->small_host, sizeof(double) * need, hipHostMallocDefault));
-        c->small_host_len = need;
-    }
+    if (c->small_host.reserve(3 * P + NC, 1)) return -2;
     double* h = c->small_host;
     if (ret0) HIPCHECK(hipMemcpyAsync(h, S.path_ret0, sizeof(double) * P, hipMemcpyDeviceToHost, st));
     if (undisc) HIPCHECK(hipMemcpyAsync(h + P, S.path_undisc, sizeof(double) * P, hipMemcpyDeviceToHost, st));
@@ -1591,11 +1615,9 @@ int promp_download_processed(promp_ctx* c, int step, float* returns, float* adv,
 }
 
 int promp_download_raw(promp_ctx* c, int step, double* ret64, double* adv64) {
-    if (!c) return fail(-1, "ctx is NULL");
-    if (step < 0 || step > c->d.num_inner_steps) return fail(-1, "step %d out of range", step);
-    StepData& S = c->steps[step];
-    StepScope scope_(c, S, false);
-    if (scope_.rc) return -2;
+    StepScope sc(c, step, /*writes=*/false, /*needs_data=*/false);
+    if (sc.rc) return sc.rc;
+    StepData& S = sc.S();
     if (!S.processed) return fail(-3, "step %d has not been processed", step);
     if (ret64) HIPCHECK(hipMemcpyAsync(ret64, S.ret64, sizeof(double) * S.n_rows, hipMemcpyDeviceToHost, c->stream));
     if (adv64) HIPCHECK(hipMemcpyAsync(adv64, S.adv64, sizeof(double) * S.n_rows, hipMemcpyDeviceToHost, c->stream));
@@ -1605,11 +1627,11 @@ int promp_download_raw(promp_ctx* c, int step, double* ret64, double* adv64) {
 
 int promp_set_coeffs(promp_ctx* c, int step, int kind, const double* coeffs) {
     if (!c || !coeffs) return fail(-1, "NULL argument");
-    if (step < 0 || step > c->d.num_inner_steps) return fail(-1, "step %d out of range", step);
+    StepScope sc(c, step);
+    if (sc.rc) return sc.rc;
     if (kind < 1 || kind > 2) return fail(-1, "coefficients exist for the linear baselines only");
-    StepData& S = c->steps[step];
-    StepScope scope_(c, S);
-    if (scope_.rc) return -2;
+    if (sc.open(/*writes=*/true, /*needs_data=*/false)) return sc.rc;
+    StepData& S = sc.S();
     const int D = feature_dim(&c->d, kind), M = c->d.n_tasks;
     std::vector<double> tmp((size_t)M * c->coeff_stride, 0.0);
     for (int i = 0; i < M; ++i) memcpy(tmp.data() + (size_t)i * c->coeff_stride, coeffs + (size_t)i * D, sizeof(double) * D);
@@ -1621,19 +1643,13 @@ int promp_set_coeffs(promp_ctx* c, int step, int kind, const double* coeffs) {
 
 int promp_predict_baseline(promp_ctx* c, int step, int kind, double* out) {
     if (!c || !out) return fail(-1, "NULL argument");
-    if (step < 0 || step > c->d.num_inner_steps) return fail(-1, "step %d out of range", step);
+    StepScope sc(c, step);
+    if (sc.rc) return sc.rc;
     if (kind < 0 || kind > 2) return fail(-1, "unknown baseline kind %d", kind);
-    StepData& S = c->steps[step];
-    StepScope scope_(c, S, false);
-    if (scope_.rc) return -2;
-    if (S.n_rows == 0) return fail(-3, "step %d has no data", step);
-    SampleArgs a;
-    memset(&a, 0, sizeof a);
-    a.obs = S.obs; a.rew = S.rew; a.rew64 = S.has_rew64 ? S.rew64 : nullptr; a.path_row_offsets = S.path_row_offsets; a.path_task = S.path_task; a.row_t = S.row_t;
-    a.task_row_offsets = S.task_row_offsets; a.task_path_offsets = S.task_path_offsets;
-    a.O = c->d.obs_dim; a.kind = kind; a.D = feature_dim(&c->d, kind);
+    if (sc.open(/*writes=*/false, /*needs_data=*/true)) return sc.rc;
+    StepData& S = sc.S();
+    SampleArgs a = sample_args(c, S, kind);
     a.gamma = 1.0; a.lam = 1.0;
-    a.adv64 = S.adv64; a.path_mom = S.path_mom; a.coeffs = S.coeffs; a.coeff_stride = c->coeff_stride;
     a.bl64 = S.ret64;                              // scratch: returns of this step are recomputed by process_samples
     if (kind == PROMP_BASELINE_ZERO) HIPCHECK(hipMemsetAsync(S.ret64, 0, sizeof(double) * S.n_rows, c->stream));
     PROMP_LAUNCH(k_gae, dim3(S.n_paths), 64, sizeof(double) * (size_t)(a.D > 0 ? a.D : 1), c->stream, a);
@@ -1647,11 +1663,9 @@ int promp_predict_baseline(promp_ctx* c, int step, int kind, double* out) {
 
 int promp_set_advantages(promp_ctx* c, int step, const float* adv) {
     if (!c || !adv) return fail(-1, "NULL argument");
-    if (step < 0 || step > c->d.num_inner_steps) return fail(-1, "step %d out of range", step);
-    StepData& S = c->steps[step];
-    StepScope scope_(c, S);
-    if (scope_.rc) return -2;
-    if (S.n_rows == 0) return fail(-3, "step %d has no data", step);
+    StepScope sc(c, step, /*writes=*/true, /*needs_data=*/true);
+    if (sc.rc) return sc.rc;
+    StepData& S = sc.S();
     HIPCHECK(hipMemcpyAsync(S.adv32, adv, sizeof(float) * S.n_rows, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipStreamSynchronize(c->stream));
     S.has_adv = true;
@@ -1660,17 +1674,15 @@ int promp_set_advantages(promp_ctx* c, int step, const float* adv) {
 
 int promp_set_dice_rewards(promp_ctx* c, int step, const float* rw) {
     if (!c || !rw) return fail(-1, "NULL argument");
-    if (step < 0 || step > c->d.num_inner_steps) return fail(-1, "step %d out of range", step);
+    StepScope sc(c, step);
+    if (sc.rc) return sc.rc;
     if (c->family != PassFamily::Chain) return fail(-1, "the DiCE objective is built on the register-chained kernels (hidden sizes from {32,64}, obs_dim <= 32)");
-    StepData& S = c->steps[step];
-    StepScope scope_(c, S);
-    if (scope_.rc) return -2;
-    if (S.n_rows == 0) return fail(-3, "step %d has no data", step);
+    if (sc.open(/*writes=*/true, /*needs_data=*/true)) return sc.rc;
+    StepData& S = sc.S();
     if (!S.dice_rw) {
         const size_t R = c->d.max_rows;
-        int rc = dev_alloc(&S.dice_rw, R);
-        rc |= dev_alloc(&S.dice_c, R); rc |= dev_alloc(&S.dice_u, R); rc |= dev_alloc(&S.dice_tmp, R);
-        if (rc) return -2;
+        // (dice_rw last: the guard above stands for all four)
+        if (S.dice_c.alloc(R) || S.dice_u.alloc(R) || S.dice_tmp.alloc(R) || S.dice_rw.alloc(R)) return -2;
     }
     HIPCHECK(hipMemcpyAsync(S.dice_rw, rw, sizeof(float) * S.n_rows, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipStreamSynchronize(c->stream));      // (the source may be a temporary of the caller)
@@ -1722,27 +1734,30 @@ int promp_set_theta(promp_ctx* c, const float* th) {
     c->ls_known = true;
     return params_in(c, c->theta, th, 1);
 }
-int promp_get_theta(promp_ctx* c, float* th) { return c ? params_out(c, th, c->theta, 1) : fail(-1, "ctx is NULL"); }
+int promp_get_theta(promp_ctx* c, float* th) {
+    NEED_CTX(c);
+    return params_out(c, th, c->theta, 1);
+}
 static int mask_log_std_step_sizes(promp_ctx* c) {
     if (c->learn_std) return 0;
     HIPCHECK(hipMemsetAsync(c->step_sizes + (c->NP - c->d.act_dim), 0, sizeof(float) * c->d.act_dim, c->stream));
     return 0;
 }
 int promp_set_step_sizes(promp_ctx* c, const float* s) {
-    if (!c) return fail(-1, "ctx is NULL");
+    NEED_CTX(c);
     c->sizes_version = ++c->version_counter;
     if (params_in(c, c->step_sizes, s, 1)) return -2;
     return mask_log_std_step_sizes(c);
 }
 int promp_set_min_std(promp_ctx* c, float min_std) {
-    if (!c) return fail(-1, "ctx is NULL");
+    NEED_CTX(c);
     if (!(min_std > 0.f)) return fail(-1, "min_std must be positive");
     c->min_log_std = logf(min_std);
     c->version_counter += 1;
     return 0;
 }
 int promp_set_schedule(promp_ctx* c, int stage_overlap, int fuse_min_tasks) {
-    if (!c) return fail(-1, "ctx is NULL");
+    NEED_CTX(c);
     if (stage_overlap >= 0) {
         HIPCHECK(hipStreamSynchronize(c->side));
         c->overlap = stage_overlap != 0;
@@ -1751,7 +1766,7 @@ int promp_set_schedule(promp_ctx* c, int stage_overlap, int fuse_min_tasks) {
     return 0;
 }
 int promp_set_reuse_adapt(promp_ctx* c, int on) {
-    if (!c) return fail(-1, "ctx is NULL");
+    NEED_CTX(c);
     c->reuse_adapt = on != 0;
     c->adapt0.valid = false;
     return 0;
@@ -1760,12 +1775,12 @@ long long promp_adapt_passes_skipped(promp_ctx* c) { return c ? c->adapt_passes_
 long long promp_constraint_hvp_cached_passes(promp_ctx* c) { return c ? c->chvp_cached_passes : -1; }
 long long promp_state_version(promp_ctx* c) { return c ? (long long)c->version_counter : -1; }
 int promp_set_primal_cache(promp_ctx* c, int on) {
-    if (!c) return fail(-1, "ctx is NULL");
+    NEED_CTX(c);
     c->primal_cache = on < 0 ? -1 : on != 0;
     return 0;
 }
 int promp_set_learn_std(promp_ctx* c, int on) {
-    if (!c) return fail(-1, "ctx is NULL");
+    NEED_CTX(c);
     if (on && !c->learn_std) return fail(-3, "learn_std cannot be switched back on: the log_std step sizes were zeroed (set the step sizes again)");
     c->learn_std = on != 0;
     c->sizes_version = ++c->version_counter;
@@ -1773,24 +1788,24 @@ int promp_set_learn_std(promp_ctx* c, int on) {
 }
 static int tasks_materialize(promp_ctx* c);
 int promp_set_task_thetas(promp_ctx* c, const float* t) {
-    if (!c) return fail(-1, "ctx is NULL");
+    NEED_CTX(c);
     c->tasks_shared = false;
     return params_in(c, c->theta_tasks, t, (size_t)c->d.n_tasks);
 }
 int promp_get_task_thetas(promp_ctx* c, float* t) {
-    if (!c) return fail(-1, "ctx is NULL");
+    NEED_CTX(c);
     if (tasks_materialize(c)) return -2;
     return params_out(c, t, c->theta_tasks, (size_t)c->d.n_tasks);
 }
 
 int promp_set_adam_state(promp_ctx* c, const float* m, const float* v, int64_t t) {
-    if (!c) return fail(-1, "ctx is NULL");
+    NEED_CTX(c);
     if (params_in(c, c->adam_m, m, 1) || params_in(c, c->adam_v, v, 1)) return -2;
     c->adam_t = t;
     return 0;
 }
 int promp_get_adam_state(promp_ctx* c, float* m, float* v, int64_t* t) {
-    if (!c) return fail(-1, "ctx is NULL");
+    NEED_CTX(c);
     if (m && params_out(c, m, c->adam_m, 1)) return -2;
     if (v && params_out(c, v, c->adam_v, 1)) return -2;
     if (t) *t = c->adam_t;
@@ -1801,7 +1816,7 @@ int promp_get_adam_state(promp_ctx* c, float* m, float* v, int64_t* t) {
 // launched here: the inner step reads theta with a task stride of zero, and the per-task copies are only written
 // (tasks_materialize) for the entry points that hand them out or index them per task.
 int promp_switch_to_pre_update(promp_ctx* c) {
-    if (!c) return fail(-1, "ctx is NULL");
+    NEED_CTX(c);
     c->tasks_shared = true;
     return 0;
 }
@@ -1814,12 +1829,9 @@ static int tasks_materialize(promp_ctx* c) {
 }
 
 int promp_inner_adapt(promp_ctx* c, int step, int inner_kind) {
-    if (!c) return fail(-1, "ctx is NULL");
-    if (step < 0 || step > c->d.num_inner_steps) return fail(-1, "step %d out of range", step);
-    StepData& S = c->steps[step];
-    StepScope scope_(c, S, false);
-    if (scope_.rc) return -2;
-    if (S.n_rows == 0) return fail(-3, "step %d has no data", step);
+    StepScope sc(c, step, /*writes=*/false, /*needs_data=*/true);
+    if (sc.rc) return sc.rc;
+    StepData& S = sc.S();
     // pre-update mode: all tasks start from theta itself (stride 0); the step writes every task's row of theta_tasks
     const float* cur = c->tasks_shared ? c->theta : c->theta_tasks;
     const long long st = c->tasks_shared ? 0 : c->NP;
@@ -1857,12 +1869,7 @@ int promp_policy_forward(promp_ctx* c, const float* obs, int batch, float* mean_
     const int M = c->d.n_tasks, O = c->d.obs_dim, A = c->d.act_dim;
     const size_t n_obs = (size_t)M * batch * O, n_out = (size_t)M * batch * A;
     const size_t n_scr = c->family == PassFamily::Layered ? (size_t)M * batch * 2 * c->g_maxw : 0;
-    if (n_obs + n_out + n_scr > c->fwd_capacity) {
-        if (c->fwd_buf) (void)hipFree(c->fwd_buf);
-        c->fwd_buf = nullptr;
-        c->fwd_capacity = 2 * (n_obs + n_out + n_scr);
-        HIPCHECK(hipMalloc((void**)&c->fwd_buf, sizeof(float) * c->fwd_capacity));
-    }
+    if (c->fwd_buf.reserve(n_obs + n_out + n_scr, 2)) return -2;
     float* d_obs = c->fwd_buf;
     float* d_out = c->fwd_buf + n_obs;
     HIPCHECK(hipMemcpyAsync(d_obs, obs, sizeof(float) * n_obs, hipMemcpyHostToDevice, c->stream));
@@ -1873,8 +1880,8 @@ int promp_policy_forward(promp_ctx* c, const float* obs, int batch, float* mean_
     if (c->family == PassFamily::Layered) {
         GenForwardArgs gf;
         gf.obs = d_obs; gf.theta_tasks = c->theta_tasks; gf.mean = d_out; gf.scratch = d_out + n_out;
-        gf.B = batch; gf.NP = c->NP; gf.n_lin = c->n_lin; gf.maxw = c->g_maxw; gf.act_kind = gen_act_kinds(&c->d);
-        for (int l = 0; l < c->n_lin; ++l) gf.lin[l] = c->lin[l];
+        gf.B = batch; gf.NP = c->NP; gf.maxw = c->g_maxw; gf.act_kind = gen_act_kinds(&c->d);
+        copy_layers(gf, c);
         PROMP_LAUNCH(k_gen_policy_forward, dim3(M), 256, 0, c->stream, gf);
     } else
     PROMP_LAUNCH(k_policy_forward, dim3(M), 256, 0, c->stream, f);
@@ -1885,9 +1892,10 @@ int promp_policy_forward(promp_ctx* c, const float* obs, int batch, float* mean_
 }
 
 // fixed-length layout of a device-side rollout: path p of task i is rows [(i B + p) T, (i B + p + 1) T)
-static int begin_fixed_rollout(promp_ctx* c, int step, int B, int T) {
-    if (!c) return fail(-1, "ctx is NULL");
-    if (step < 0 || step > c->d.num_inner_steps) return fail(-1, "step %d out of range", step);
+// (sc: the caller's scope, checked but not yet open)
+static int begin_fixed_rollout(StepScope& sc, int B, int T) {
+    if (sc.rc) return sc.rc;
+    promp_ctx* c = sc.c;
     if (B < 1 || T < 1) return fail(-1, "envs_per_task and path_length must be positive");
     const int M = c->d.n_tasks;
     const long long rows = (long long)M * B * T;
@@ -1895,9 +1903,8 @@ static int begin_fixed_rollout(promp_ctx* c, int step, int B, int T) {
     std::vector<int32_t> tpo(M + 1), pro((size_t)M * B + 1);
     for (int i = 0; i <= M; ++i) tpo[i] = i * B;
     for (int p = 0; p <= M * B; ++p) pro[p] = p * T;
-    StepData& S = c->steps[step];
-    StepScope scope_(c, S);
-    if (scope_.rc) return -2;
+    if (sc.open(/*writes=*/true, /*needs_data=*/false)) return sc.rc;
+    StepData& S = sc.S();
     if (set_step_layout(c, S, c->stream, false, M * B, tpo.data(), pro.data())) return -2;
     S.has_policy = true;
     S.ls_per_row = 0;
@@ -1905,31 +1912,21 @@ static int begin_fixed_rollout(promp_ctx* c, int step, int B, int T) {
     return 0;
 }
 
-static int ensure_rollout_buf(promp_ctx* c, size_t need) {
-    if (need > c->rollout_capacity) {
-        if (c->rollout_buf) (void)hipFree(c->rollout_buf);
-        c->rollout_buf = nullptr;
-        c->rollout_capacity = 2 * need;
-        HIPCHECK(hipMalloc((void**)&c->rollout_buf, c->rollout_capacity));
-    }
-    return 0;
-}
-
 int promp_rollout_point_env(promp_ctx* c, int step, int envs_per_task, int path_length, const double* goals,
                             const double* start, const float* noise, const promp_point_env_opts* o) {
     if (!c || !goals || !start || !o) return fail(-1, "NULL argument");
-    if (step < 0 || step > c->d.num_inner_steps) return fail(-1, "step %d out of range", step);
+    StepScope sc(c, step);
+    if (sc.rc) return sc.rc;
     if (c->d.obs_dim != 2 || c->d.act_dim != 2) return fail(-1, "the point environment has obs_dim = act_dim = 2 (context: %d, %d)", c->d.obs_dim, c->d.act_dim);
     if (o->reward_type < 0 || o->reward_type > 2) return fail(-1, "unknown reward type %d", o->reward_type);
-    if (begin_fixed_rollout(c, step, envs_per_task, path_length)) return -2;
+    if (begin_fixed_rollout(sc, envs_per_task, path_length)) return -2;
     const int M = c->d.n_tasks, B = envs_per_task, T = path_length;
     const long long rows = (long long)M * B * T;
-    StepData& S = c->steps[step];
-    StepScope scope_(c, S);
-    if (scope_.rc) return -2;
+    StepData& S = sc.S();
+    S.data_version = ++c->version_counter;       // (the rollout's own bump behind the layout's: promp_state_version counts both)
     const size_t need = sizeof(double) * ((size_t)M * 2 + (size_t)M * B * 2) + sizeof(float) * (size_t)rows * 2;
-    if (ensure_rollout_buf(c, need)) return -2;
-    double* d_goals = (double*)c->rollout_buf;
+    if (c->rollout_buf.reserve(need, 2)) return -2;
+    double* d_goals = (double*)c->rollout_buf.p;
     double* d_start = d_goals + (size_t)M * 2;
     float* d_noise = (float*)(d_start + (size_t)M * B * 2);
     hipStream_t st = c->stream;
@@ -1946,8 +1943,8 @@ int promp_rollout_point_env(promp_ctx* c, int step, int envs_per_task, int path_
     a.normalization_scale = o->normalization_scale; a.max_step = o->max_step; a.reward_type = o->reward_type; a.sparse_radius = o->sparse_radius;
     if (c->family == PassFamily::Layered) {          // any layer table: one workgroup per environment (promp_kernels_generic.h)
         GenPointRolloutArgs g;
-        g.p = a; g.n_lin = c->n_lin; g.act_kind = gen_act_kinds(&c->d);
-        for (int l = 0; l < c->n_lin; ++l) g.lin[l] = c->lin[l];
+        g.p = a; g.act_kind = gen_act_kinds(&c->d);
+        copy_layers(g, c);
         PROMP_LAUNCH(k_gen_point_rollout, dim3(B, M), 256, gen_rollout_smem(2), st, g);
     } else
     PROMP_LAUNCH(k_point_rollout, dim3(M), 64, 0, st, a);
@@ -1957,26 +1954,21 @@ int promp_rollout_point_env(promp_ctx* c, int step, int envs_per_task, int path_
 }
 
 int promp_begin_rollout(promp_ctx* c, int step, int envs_per_task, int path_length) {
-    if (!c) return fail(-1, "ctx is NULL");
-    if (begin_fixed_rollout(c, step, envs_per_task, path_length)) return -2;
-    c->steps[step].rollout_ragged = false;
+    NEED_CTX(c);
+    StepScope sc(c, step);
+    if (begin_fixed_rollout(sc, envs_per_task, path_length)) return -2;
+    sc.S().rollout_ragged = false;
     return 0;
 }
 
 int promp_begin_collection(promp_ctx* c, int step, int envs_per_task, int max_steps) {
-    if (!c) return fail(-1, "ctx is NULL");
-    if (step < 0 || step > c->d.num_inner_steps) return fail(-1, "step %d out of range", step);
+    StepScope sc(c, step);
+    if (sc.rc) return sc.rc;
     if (envs_per_task < 1 || max_steps < 1) return fail(-1, "envs_per_task and max_steps must be positive");
-    StepData& S = c->steps[step];
-    StepScope scope_(c, S);
-    if (scope_.rc) return -2;
+    if (sc.open(/*writes=*/true, /*needs_data=*/false)) return sc.rc;
+    StepData& S = sc.S();
     const size_t need = (size_t)max_steps * c->d.n_tasks * envs_per_task * (c->d.obs_dim + 2 * c->d.act_dim);
-    if (need > c->stage_capacity) {
-        if (c->stage_rows) (void)hipFree(c->stage_rows);
-        c->stage_rows = nullptr;
-        c->stage_capacity = need;
-        HIPCHECK(hipMalloc((void**)&c->stage_rows, sizeof(float) * need));
-    }
+    if (c->stage_rows.reserve(need, 1)) return -2;
     S.rollout_B = envs_per_task; S.rollout_T = max_steps; S.rollout_ragged = true;
     S.has_policy = false; S.processed = false; S.has_adv = false;
     return 0;
@@ -1985,8 +1977,9 @@ int promp_begin_collection(promp_ctx* c, int step, int envs_per_task, int max_st
 int promp_end_collection(promp_ctx* c, int step, int n_paths, const int32_t* task_path_offsets, const int32_t* path_env,
                          const int32_t* path_start, const int32_t* path_len, const float* rewards) {
     if (!c || !task_path_offsets || !path_env || !path_start || !path_len || !rewards) return fail(-1, "NULL argument");
-    if (step < 0 || step > c->d.num_inner_steps) return fail(-1, "step %d out of range", step);
-    StepData& S = c->steps[step];
+    StepScope sc(c, step);
+    if (sc.rc) return sc.rc;
+    StepData& S = sc.S();
     if (!S.rollout_ragged || S.rollout_B < 1) return fail(-3, "promp_begin_collection has not been called for step %d", step);
     const int M = c->d.n_tasks, B = S.rollout_B, O = c->d.obs_dim, A = c->d.act_dim;
     if (n_paths < 1 || n_paths > c->d.max_paths) return fail(-1, "%d paths outside [1, max_paths = %d]", n_paths, c->d.max_paths);
@@ -1997,12 +1990,11 @@ int promp_end_collection(promp_ctx* c, int step, int n_paths, const int32_t* tas
         pro[p + 1] = pro[p] + path_len[p];
     }
     if (pro[n_paths] > c->d.max_rows) return fail(-1, "%d collected rows exceed max_rows = %d", pro[n_paths], c->d.max_rows);
-    StepScope scope_(c, S);
-    if (scope_.rc) return -2;
+    if (sc.open(/*writes=*/true, /*needs_data=*/false)) return sc.rc;
     if (set_step_layout(c, S, c->stream, false, n_paths, task_path_offsets, pro.data())) return -2;
     // the finished episodes: staging rows -> slab rows in path order
-    if (ensure_rollout_buf(c, sizeof(int32_t) * 2 * (size_t)n_paths)) return -2;
-    int32_t* d_env = (int32_t*)c->rollout_buf;
+    if (c->rollout_buf.reserve(sizeof(int32_t) * 2 * (size_t)n_paths, 2)) return -2;
+    int32_t* d_env = (int32_t*)c->rollout_buf.p;
     int32_t* d_start = d_env + n_paths;
     HIPCHECK(hipMemcpyAsync(d_env, path_env, sizeof(int32_t) * n_paths, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipMemcpyAsync(d_start, path_start, sizeof(int32_t) * n_paths, hipMemcpyHostToDevice, c->stream));
@@ -2024,16 +2016,15 @@ int promp_end_collection(promp_ctx* c, int step, int n_paths, const int32_t* tas
 
 int promp_policy_step(promp_ctx* c, int step, int t, const float* obs, uint64_t seed, int clip_infos, float* actions_out) {
     if (!c || !obs || !actions_out) return fail(-1, "NULL argument");
-    if (step < 0 || step > c->d.num_inner_steps) return fail(-1, "step %d out of range", step);
-    StepData& S = c->steps[step];
-    StepScope scope_(c, S);
-    if (scope_.rc) return -2;
+    StepScope sc(c, step, /*writes=*/true, /*needs_data=*/false);
+    if (sc.rc) return sc.rc;
+    StepData& S = sc.S();
     if (S.rollout_B < 1) return fail(-3, "promp_begin_rollout has not been called for step %d", step);
     const int M = c->d.n_tasks, B = S.rollout_B, T = S.rollout_T, O = c->d.obs_dim, A = c->d.act_dim;
     if (t < 0 || t >= T) return fail(-1, "time step %d outside the horizon %d", t, T);
     const size_t n_obs = (size_t)M * B * O, n_act = (size_t)M * B * A;
-    if (ensure_rollout_buf(c, sizeof(float) * (n_obs + n_act))) return -2;
-    float* d_obs = (float*)c->rollout_buf;
+    if (c->rollout_buf.reserve(sizeof(float) * (n_obs + n_act), 2)) return -2;
+    float* d_obs = (float*)c->rollout_buf.p;
     float* d_act = d_obs + n_obs;
     hipStream_t st = c->stream;
     HIPCHECK(hipMemcpyAsync(d_obs, obs, sizeof(float) * n_obs, hipMemcpyHostToDevice, st));
@@ -2052,8 +2043,8 @@ int promp_policy_step(promp_ctx* c, int step, int t, const float* obs, uint64_t 
     a.seed = seed; a.stream = (unsigned)step;
     if (c->family == PassFamily::Layered) {          // any layer table: one workgroup per environment (promp_kernels_generic.h)
         GenPolicyStepArgs g;
-        g.p = a; g.n_lin = c->n_lin; g.act_kind = gen_act_kinds(&c->d);
-        for (int l = 0; l < c->n_lin; ++l) g.lin[l] = c->lin[l];
+        g.p = a; g.act_kind = gen_act_kinds(&c->d);
+        copy_layers(g, c);
         PROMP_LAUNCH(k_gen_policy_step, dim3(B, M), 256, gen_rollout_smem(O), st, g);
     } else
     PROMP_LAUNCH(k_policy_step, dim3((B + 63) / 64, M), 64, 0, st, a);
@@ -2066,11 +2057,9 @@ int promp_policy_step(promp_ctx* c, int step, int t, const float* obs, uint64_t 
 
 int promp_set_rewards(promp_ctx* c, int step, const float* rew) {
     if (!c || !rew) return fail(-1, "NULL argument");
-    if (step < 0 || step > c->d.num_inner_steps) return fail(-1, "step %d out of range", step);
-    StepData& S = c->steps[step];
-    StepScope scope_(c, S);
-    if (scope_.rc) return -2;
-    if (S.n_rows == 0) return fail(-3, "step %d has no data", step);
+    StepScope sc(c, step, /*writes=*/true, /*needs_data=*/true);
+    if (sc.rc) return sc.rc;
+    StepData& S = sc.S();
     HIPCHECK(hipMemcpyAsync(S.rew, rew, sizeof(float) * S.n_rows, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipStreamSynchronize(c->stream));
     S.processed = false;
@@ -2080,12 +2069,10 @@ int promp_set_rewards(promp_ctx* c, int step, const float* rew) {
 
 int promp_set_rewards_f64(promp_ctx* c, int step, const double* rew) {
     if (!c || !rew) return fail(-1, "NULL argument");
-    if (step < 0 || step > c->d.num_inner_steps) return fail(-1, "step %d out of range", step);
-    StepData& S = c->steps[step];
-    StepScope scope_(c, S);
-    if (scope_.rc) return -2;
-    if (S.n_rows == 0) return fail(-3, "step %d has no data", step);
-    if (!S.rew64 && dev_alloc(&S.rew64, (size_t)c->d.max_rows)) return -2;
+    StepScope sc(c, step, /*writes=*/true, /*needs_data=*/true);
+    if (sc.rc) return sc.rc;
+    StepData& S = sc.S();
+    if (!S.rew64 && S.rew64.alloc((size_t)c->d.max_rows)) return -2;
     std::vector<float> r32((size_t)S.n_rows);
     for (int i = 0; i < S.n_rows; ++i) r32[i] = (float)rew[i];
     HIPCHECK(hipMemcpyAsync(S.rew64, rew, sizeof(double) * S.n_rows, hipMemcpyHostToDevice, c->stream));
@@ -2097,12 +2084,9 @@ int promp_set_rewards_f64(promp_ctx* c, int step, const double* rew) {
 }
 
 int promp_download_step(promp_ctx* c, int step, float* obs, float* act, float* rew, float* old_mean, float* old_log_std) {
-    if (!c) return fail(-1, "ctx is NULL");
-    if (step < 0 || step > c->d.num_inner_steps) return fail(-1, "step %d out of range", step);
-    StepData& S = c->steps[step];
-    StepScope scope_(c, S, false);
-    if (scope_.rc) return -2;
-    if (S.n_rows == 0) return fail(-3, "step %d has no data", step);
+    StepScope sc(c, step, /*writes=*/false, /*needs_data=*/true);
+    if (sc.rc) return sc.rc;
+    StepData& S = sc.S();
     const size_t R = S.n_rows, O = c->d.obs_dim, A = c->d.act_dim, M = c->d.n_tasks;
     hipStream_t st = c->stream;
     if (obs) HIPCHECK(hipMemcpyAsync(obs, S.obs, sizeof(float) * R * O, hipMemcpyDeviceToHost, st));
@@ -2142,7 +2126,7 @@ static int enqueue_constraint_hvp(promp_ctx* c, int inner_kind, int refresh_chai
         if (c->steps[k].n_rows == 0) return fail(-3, "step %d has no data", k);
         if (join_side(c, c->steps[k])) return -2;
     }
-    if (!c->wbuf && dev_alloc(&c->wbuf, MNP)) return -2;
+    if (!c->wbuf && c->wbuf.alloc(MNP)) return -2;
     auto theta_of = [&](int k, long long* stride) -> const float* {
         *stride = (k == 0) ? 0 : NP;
         return (k == 0) ? c->theta : c->chain + (size_t)k * MNP;
@@ -2241,8 +2225,8 @@ int promp_cg_solve(promp_ctx* c, int inner_kind, const float* b, int cg_iters, f
                         "(promp_comm_init first)", c->d.n_tasks, c->d.n_tasks_global);
     const int NP = c->NP;
     // (one guard each: a call whose second allocation failed must not leave the next one running k_cg_step without its scalars)
-    if (!c->cg_buf && dev_alloc(&c->cg_buf, (size_t)7 * NP)) return -2;
-    if (!c->cg_scal && dev_alloc(&c->cg_scal, 4)) return -2;
+    if (!c->cg_buf && c->cg_buf.alloc((size_t)7 * NP)) return -2;
+    if (!c->cg_scal && c->cg_scal.alloc(4)) return -2;
     float *x = c->cg_buf, *r = x + NP, *d = r + NP, *hd = d + NP, *ga = hd + NP, *th0 = ga + NP;
     if (params_in(c, r, b, 1)) return -2;                       // (blocking: b is the caller's)
     float eta[PROMP_ETA_MAX] = {};
@@ -2309,7 +2293,7 @@ int promp_cg_solve(promp_ctx* c, int inner_kind, const float* b, int cg_iters, f
 }
 
 int promp_adam_step(promp_ctx* c, float lr) {
-    if (!c) return fail(-1, "ctx is NULL");
+    NEED_CTX(c);
     // red still holds the (all-reduced) sums of the last promp_meta_grad
     AdamArgs ad;
     ad.theta = c->theta; ad.m = c->adam_m; ad.v = c->adam_v; ad.red = c->red; ad.grad_mean = c->grad_mean;
@@ -2364,16 +2348,16 @@ int promp_optimize_begin(promp_ctx* c, int num_epochs, float lr, float clip_eps,
 }
 
 int promp_optimize_end(promp_ctx* c, float* loss_before, float* stats_after) {
-    if (!c) return fail(-1, "ctx is NULL");
+    NEED_CTX(c);
     if (!c->opt_pending) return fail(-1, "promp_optimize_end without promp_optimize_begin");
     c->opt_pending = false;
     // poll the sequence number (the stream is queried now and then: a failed launch must not turn into an endless wait)
     for (unsigned long long spins = 0;; ++spins) {
-        if (__atomic_load_n(c->stats_seq_host, __ATOMIC_ACQUIRE) == c->stats_seq) break;
+        if (__atomic_load_n(c->stats_seq_host.p, __ATOMIC_ACQUIRE) == c->stats_seq) break;
         if ((spins & 0xfff) == 0xfff) {
             const hipError_t q = hipStreamQuery(c->stream);
             if (q == hipSuccess) {
-                if (__atomic_load_n(c->stats_seq_host, __ATOMIC_ACQUIRE) == c->stats_seq) break;
+                if (__atomic_load_n(c->stats_seq_host.p, __ATOMIC_ACQUIRE) == c->stats_seq) break;
                 return fail(-2, "promp_optimize_end: the stream drained without publishing the statistics");
             }
             if (q != hipErrorNotReady) return fail(-2, "promp_optimize_end: %s", hipGetErrorString(q));
@@ -2399,33 +2383,31 @@ int promp_optimize(promp_ctx* c, int num_epochs, float lr, float clip_eps, const
 
 int promp_eval_loss_grad(promp_ctx* c, int step, int kind, float clip_eps, int clip_ls, float* grads_out, float* loss_out,
                          float* kl_out) {
-    if (!c) return fail(-1, "ctx is NULL");
-    if (step < 0 || step > c->d.num_inner_steps) return fail(-1, "step %d out of range", step);
+    StepScope sc(c, step);
+    if (sc.rc) return sc.rc;
     if (kind < 0 || kind > 3) return fail(-1, "unknown objective kind %d", kind);
-    StepData& S = c->steps[step];
-    StepScope scope_(c, S, false);
-    if (scope_.rc) return -2;
+    if (sc.open(/*writes=*/false, /*needs_data=*/false)) return sc.rc;
+    StepData& S = sc.S();
     const int M = c->d.n_tasks;
     if (tasks_materialize(c)) return -2;
     PassReq q;
     q.theta = c->theta_tasks; q.theta_stride = c->NP; q.loss_kind = kind; q.clip_eps = clip_eps; q.clip_ls = clip_ls;
     if (launch_pass(c, S, q)) return -2;
     if (grads_out && params_out(c, grads_out, c->lam, (size_t)M)) return -2;
-    std::vector<float> sc((size_t)M * 2);
-    if (copy_out(c, sc.data(), c->scal_tmp, sc.size())) return -2;
+    std::vector<float> scal((size_t)M * 2);
+    if (copy_out(c, scal.data(), c->scal_tmp, scal.size())) return -2;
     for (int i = 0; i < M; ++i) {
-        if (loss_out) loss_out[i] = sc[2 * i];
-        if (kl_out) kl_out[i] = sc[2 * i + 1];
+        if (loss_out) loss_out[i] = scal[2 * i];
+        if (kl_out) kl_out[i] = scal[2 * i + 1];
     }
     return 0;
 }
 
 int promp_eval_hvp(promp_ctx* c, int step, int inner_kind, int clip_ls, float klw, const float* v, float* out) {
     if (!c || !v || !out) return fail(-1, "NULL argument");
-    if (step < 0 || step > c->d.num_inner_steps) return fail(-1, "step %d out of range", step);
-    StepData& S = c->steps[step];
-    StepScope scope_(c, S, false);
-    if (scope_.rc) return -2;
+    StepScope sc(c, step, /*writes=*/false, /*needs_data=*/false);
+    if (sc.rc) return sc.rc;
+    StepData& S = sc.S();
     const int M = c->d.n_tasks, NP = c->NP;
     if (params_in(c, c->vbuf, v, (size_t)M)) return -2;
     HIPCHECK(hipMemsetAsync(c->lam, 0, sizeof(float) * (size_t)M * NP, c->stream));
@@ -2447,7 +2429,7 @@ int promp_comm_unique_id(void* id_out, size_t id_bytes) {
 }
 
 int promp_comm_init(promp_ctx* c, int rank, int nranks, const void* id, size_t id_bytes) {
-    if (!c) return fail(-1, "ctx is NULL");
+    NEED_CTX(c);
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail(-1, "bad rank %d / nranks %d", rank, nranks);
     if (!id || id_bytes < sizeof(ncclUniqueId)) return fail(-1, "id buffer must hold %zu bytes", sizeof(ncclUniqueId));
     HIPCHECK(hipSetDevice(c->device));
@@ -2461,7 +2443,7 @@ int promp_comm_init(promp_ctx* c, int rank, int nranks, const void* id, size_t i
 }
 
 int promp_comm_info(promp_ctx* c, int32_t* nranks, int32_t* rank, int32_t* fixed_order, char* bus_id_out, size_t bus_id_bytes) {
-    if (!c) return fail(-1, "ctx is NULL");
+    NEED_CTX(c);
     int n = 1, r = 0;
     if (c->comm) {        // what the communicator itself says, not what the caller passed to promp_comm_init
         ncclResult_t e = ncclCommCount(c->comm, &n);
@@ -2479,13 +2461,13 @@ int promp_comm_info(promp_ctx* c, int32_t* nranks, int32_t* rank, int32_t* fixed
 }
 
 int promp_comm_fixed_order(promp_ctx* c, int on) {
-    if (!c) return fail(-1, "ctx is NULL");
+    NEED_CTX(c);
     c->fixed_order = on != 0;
     return 0;
 }
 
 int promp_comm_split_path(promp_ctx* c, int on) {
-    if (!c) return fail(-1, "ctx is NULL");
+    NEED_CTX(c);
     c->force_split = on != 0;
     return 0;
 }
@@ -2533,9 +2515,9 @@ int promp_allreduce_f64(promp_ctx* c, double* buf, int n, int op) {
 int promp_debug_phase_stamps(promp_ctx* c, int step, int hvp, unsigned long long* out) {
     if (!c || !out) return fail(-1, "NULL argument");
     if (!PROMP_STAMPS_ON) return fail(-3, "phase stamps need a build with -DPROMP_DEV_STAMPS");
-    StepData& S = c->steps[step];
-    StepScope scope_(c, S, false);
-    if (scope_.rc) return -2;
+    StepScope sc(c, step, /*writes=*/false, /*needs_data=*/false);
+    if (sc.rc) return sc.rc;
+    StepData& S = sc.S();
     if (tasks_materialize(c)) return -2;
     PassReq q;
     q.theta = c->theta_tasks; q.theta_stride = c->NP; q.clip_eps = 0.3f;
@@ -2559,7 +2541,7 @@ int promp_debug_phase_stamps(promp_ctx* c, int step, int hvp, unsigned long long
 }
 
 int promp_prof_enable(promp_ctx* c, int on) {
-    if (!c) return fail(-1, "ctx is NULL");
+    NEED_CTX(c);
     if (prof_collect(c)) return -2;
     c->prof = on != 0;
     if (on)
@@ -2568,7 +2550,7 @@ int promp_prof_enable(promp_ctx* c, int on) {
 }
 
 int promp_prof_read(promp_ctx* c, int id, double* total_ms, int64_t* launches, int64_t* rows) {
-    if (!c) return fail(-1, "ctx is NULL");
+    NEED_CTX(c);
     if (id < 0 || id >= PROMP_KERNEL_COUNT) return fail(-1, "kernel id %d out of range", id);
     if (prof_collect(c)) return -2;
     if (total_ms) *total_ms = c->prof_slots[id].total_ms;
@@ -2588,7 +2570,7 @@ int promp_split_events(promp_ctx* c, int64_t* out2) {
 }
 
 int promp_device_info(promp_ctx* c, char* name_out, size_t name_bytes, int32_t* n_cus, int32_t* clock_mhz) {
-    if (!c) return fail(-1, "ctx is NULL");
+    NEED_CTX(c);
     if (name_out && name_bytes) snprintf(name_out, name_bytes, "%s", c->dev_name);
     if (n_cus) *n_cus = c->n_cus;
     if (clock_mhz) *clock_mhz = c->clock_mhz;

@@ -682,13 +682,6 @@ PROMP_DEV void chain_load_xN(float (&xN)[NOB][4], const float* obs, long long ro
         }
 }
 
-PROMP_DEV f32x4 tanh4(f32x4 z) {
-    f32x4 h;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) h[r] = fast_tanh(z[r]);
-    return h;
-}
-
 // Cross-wave, fixed-order sum of the waves' gradient tiles -> one partial row in global memory.
 // Every wave stores its tiles to its own LDS slab of [NP + 2] floats (plain stores, every entry written exactly once);
 // then all threads add the slabs in wave order.  (NW x [NP + 2] floats alias the parameter / transpose regions.)

@@ -88,7 +88,6 @@ PROMP_CX int pass_unit(int P, int kk, int e) { return 16 * (2 * P + (e >> 2)) + 
 
 // tanh of a pre-activation that arrives scaled by PROMP_TANH_PRESCALE, and h^2 - 1 (the NEGATED derivative): unpacked float32
 // instructions (packed-f32 VALU beside MFMAs costs more than the issue slot it saves: MI355X_MICROARCH.md)
-PROMP_DEV float pass_tanh(float y) { return __builtin_fmaf(fast_rcp(fast_exp2(y) + 1.f), -2.f, 1.f); }
 // four at a time, stage by stage: a transcendental's result is not consumed by the very next instruction (no hazard s_nop)
 PROMP_DEV f32x4 pass_tanh4(f32x4 y) {
     f32x4 e, r, h;

@@ -255,16 +255,6 @@ PROMP_DEV void wb_park(float* blk, const f32x16& v, int lane) {
         sts4(blk + 256 * g + 4 * lane, q);
     }
 }
-PROMP_DEV f32x16 wb_fetch(const float* blk, int lane) {
-    f32x16 v;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const f32x4 q = lds4(blk + 256 * g + 4 * lane);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[4 * g + i] = q[i];
-    }
-    return v;
-}
 // the bias of the wave's own units in D-fragment order
 PROMP_DEV f32x16 wb_bias16(const float* bs, int h, int w) {
     f32x16 z;

@@ -10,6 +10,7 @@
 // promp_amd (the product binds libpromp_hip.so only and has no CPU path).
 #pragma once
 #include <algorithm>
+#include <atomic>
 #include <barrier>
 #include <chrono>
 #include <cmath>
@@ -172,15 +173,6 @@ inline float emu_bf2f(unsigned short h) {
     float x;
     memcpy(&x, &u, 4);
     return x;
-}
-inline void bf16_split3(const float (&x)[8], bf16x8 (&t)[3]) {
-    for (int e = 0; e < 8; ++e) {
-        float r = x[e];
-        for (int s = 0; s < 3; ++s) {
-            t[s].h[e] = emu_f2bf(r);
-            r -= emu_bf2f(t[s].h[e]);
-        }
-    }
 }
 inline f32x4 mfma16_bf16(bf16x8 a, bf16x8 b, f32x4 c) {
     emu::Wave& W = emu::wave();
@@ -395,10 +387,6 @@ inline void pair_post(float* flags, int mine, int seq, int lane) {
     emu::wave().bar.arrive_and_wait();
     if (lane == 0) __atomic_store_n((int*)flags + mine, seq, __ATOMIC_SEQ_CST);
 }
-inline void pair_wait(float* flags, int other, int seq) {
-    while (__atomic_load_n((int*)flags + other, __ATOMIC_SEQ_CST) < seq) std::this_thread::yield();
-    emu::wave().bar.arrive_and_wait();
-}
 inline void fence_release_agent() { __atomic_thread_fence(__ATOMIC_SEQ_CST); }
 inline void fence_acquire_agent() { __atomic_thread_fence(__ATOMIC_SEQ_CST); }
 inline int atomic_add_agent(int* p, int v) { return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST); }
@@ -409,8 +397,6 @@ inline void atomic_max_agent(unsigned* p, unsigned v) {
 }
 inline void sched_fence() {}
 inline int opaque_zero() { return 0; }
-inline double* opaque_lds(double* p) { return p; }
-inline f32x4 pin_agpr(f32x4 v) { return v; }
 inline int wave_uniform(int v) { return v; }
 // the product's XCD-aware work-item bijection (promp_device.h), so that the emulated kernels take the same items
 inline int xcd_item(int b, int G) {
@@ -425,7 +411,6 @@ inline int xcd_item(int b, int G) {
 #define PROMP_SCHED_DSWRITE(n) ((void)0)
 template <class T> inline void pin_v(T&) {}
 template <class T> inline void pin_a(T&) {}
-template <class T> inline void pin_s(T&) {}
 inline unsigned long long promp_clock() { return 0; }
 inline unsigned long long promp_wall_clock() { return 0; }
 inline double rsqrt(double x) { return 1.0 / sqrt(x); }
@@ -435,7 +420,6 @@ inline double rsq_finish(double r0, double e) { return fma(r0 * e, fma(e, 0.375,
 inline float fast_exp(float x) { return expf(x); }
 inline float fast_rcp(float x) { return 1.0f / x; }
 inline float fast_exp2(float x) { return exp2f(x); }
-inline void wave_priority(int) {}
 inline void release_store_system(unsigned* p, unsigned v) { __atomic_store_n(p, v, __ATOMIC_RELEASE); }
 inline f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { f32x2 r; r[0] = fmaf(a[0], b[0], c[0]); r[1] = fmaf(a[1], b[1], c[1]); return r; }
 
@@ -470,22 +454,31 @@ constexpr unsigned hipStreamDefault = 0;
 inline hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { *s = (void*)1; return 0; }
 inline hipError_t hipStreamDestroy(hipStream_t) { return 0; }
 inline hipError_t hipStreamSynchronize(hipStream_t) { return 0; }
-inline hipError_t hipMalloc(void** p, size_t n) { *p = aligned_alloc(64, (n + 63) / 64 * 64); return *p ? 0 : 1; }
-inline hipError_t hipFree(void* p) { free(p); return 0; }
+// live objects of the three kinds the host code owns: device allocations, page-locked host blocks, events (tests: emu_live_counts)
+inline std::atomic<int64_t> emu_live[3];
+inline hipError_t hipMalloc(void** p, size_t n) {
+    *p = aligned_alloc(64, (n + 63) / 64 * 64);
+    emu_live[0] += *p ? 1 : 0;
+    return *p ? 0 : 1;
+}
+inline hipError_t hipFree(void* p) { emu_live[0] -= p ? 1 : 0; free(p); return 0; }
 inline hipError_t hipMemset(void* p, int v, size_t n) { memset(p, v, n); return 0; }
 inline hipError_t hipMemsetAsync(void* p, int v, size_t n, hipStream_t) { memset(p, v, n); return 0; }
 inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { memcpy(d, s, n); return 0; }
 inline hipError_t hipGetLastError() { return 0; }
 inline hipError_t hipFuncSetAttribute(const void*, int, int) { return 0; }
-inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new EmuEvent(); return 0; }
+inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new EmuEvent(); emu_live[2] += 1; return 0; }
 enum { hipEventDisableTiming = 2 };
-inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = new EmuEvent(); return 0; }
+inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCreate(e); }
 inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return 0; }
 inline hipError_t hipEventSynchronize(hipEvent_t) { return 0; }
 enum { hipHostMallocDefault = 0 };
-inline hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = malloc(n); return *p ? 0 : 2; }
-inline hipError_t hipHostFree(void* p) { free(p); return 0; }
-inline hipError_t hipEventDestroy(hipEvent_t e) { delete e; return 0; }
+inline hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = malloc(n); emu_live[1] += *p ? 1 : 0; return *p ? 0 : 2; }
+inline hipError_t hipHostFree(void* p) { emu_live[1] -= p ? 1 : 0; free(p); return 0; }
+inline hipError_t hipEventDestroy(hipEvent_t e) { emu_live[2] -= e ? 1 : 0; delete e; return 0; }
+extern "C" inline __attribute__((used, visibility("default"))) void emu_live_counts(int64_t out[3]) {
+    for (int i = 0; i < 3; ++i) out[i] = emu_live[i];
+}
 inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t) { e->t = std::chrono::steady_clock::now(); return 0; }
 inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
     *ms = std::chrono::duration<float, std::milli>(b->t - a->t).count();

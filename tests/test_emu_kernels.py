@@ -321,3 +321,96 @@ def test_cg_solve_matches_a_bit_exact_mirror(lib, two_cus):
 
 def test_trpo_maml_step_rejects_a_zero_gradient(lib, two_cus):
     pc.check_trpo_zero_gradient(lib, 20, M=2, P=1, T=16, O=4, A=2, hidden=(32, 32), cg_iters=2, max_backtracks=1)
+
+
+def _live_counts(lib):
+    import ctypes
+    out = (ctypes.c_int64 * 3)()
+    lib.cdll.emu_live_counts(out)
+    return list(out)
+
+
+def test_destroy_releases_every_allocation(lib, two_cus):
+    """Live device allocations / page-locked host blocks / events of the emulated runtime (hip_emu.h: emu_live_counts) are back at
+    their starting values once the contexts are destroyed, after every buffer that is allocated on first use has been: float64
+    rewards, DiCE rows, the fit's buffers of both streams, primal caches, promp_constraint_hvp's and promp_cg_solve's vectors, the
+    staged slab sets, the all-gather buffer, profiling events, the forward / rollout / collection staging areas (the rollout's
+    grown twice) and the pinned download area -- on a fused (32,32) point-environment shape and on a layer-by-layer one."""
+    import gc
+
+    import numpy as np
+
+    from promp_amd import _lib
+    gc.collect()                       # (a context some earlier test left to the collector must not be released in between)
+    before = _live_counts(lib)
+    kw = dict(discount=0.99, gae_lambda=0.97, normalize_adv=True)
+    eta = np.array([5e-4], np.float32)
+    rng = np.random.RandomState(3)
+
+    def flat(paths, f64=False):
+        fl = _lib.flatten_paths(paths)
+        rew = fl['rew'].astype(np.float64) if f64 else fl['rew']
+        return (fl['task_path_offsets'], fl['path_row_offsets'], fl['obs'], rew, fl['act'], fl['old_mean'], fl['old_log_std'])
+
+    # ---- the fused kernels: two layers of 32 units, obs_dim = act_dim = 2
+    M, O, A, hidden = 2, 2, 2, (32, 32)
+    theta, all_slabs, all_paths = helpers.make_promp_case(5, M, 2, 12, O, A, hidden, 1)
+    ctx = _lib.Context(M, O, A, hidden, 1, max_rows=M * 4 * 20, max_paths=M * 4, lib=lib)
+    ctx.set_theta(theta)
+    ctx.set_step_sizes(np.full(ctx.n_params, 0.1, np.float32))
+    for k in range(2):
+        ctx.upload_step(k, *flat(all_paths[k], f64=True))                   # float64 rewards: promp_set_rewards_f64
+    ctx.set_dice_rewards(0, rng.randn(ctx.step_rows[0]).astype(np.float32))
+    for k in range(2):                                                       # step 1: the side stream's fit buffers
+        ctx.process_samples(k, baseline_kind=pc.KIND['linear_feature'], **kw)
+    # (promp_download_processed into plain arrays: Context.download_processed draws page-locked ones from the process-wide host pool,
+    #  which keeps them -- they are the pool's, not the context's)
+    R, P = ctx.step_rows[1], ctx.step_paths[1]
+    out = dict(returns=np.empty(R, np.float32), advantages=np.empty(R, np.float32), coeffs=np.zeros((M, 2 * O + 4)),
+               path_returns0=np.empty(P), path_undiscounted=np.empty(P), path_reward_sumsq=np.empty(P))
+    assert np.all(np.isfinite(ctx.fetch_processed(1, out)['advantages']))
+    ctx.set_primal_cache(True)
+    ctx.switch_to_pre_update()
+    ctx.inner_adapt(0)
+    v = rng.randn(ctx.n_params).astype(np.float32)
+    assert np.all(np.isfinite(ctx.constraint_hvp(v)))
+    x, xhx = ctx.cg_solve(v, cg_iters=1)
+    assert np.all(np.isfinite(x)) and np.isfinite(xhx)
+    ctx.comm_init(0, 1, _lib.comm_unique_id(lib))
+    ctx.comm_fixed_order(True)
+    ctx.comm_split_path(True)
+    ctx.prof_enable(True)
+    ctx.optimize(1, 1e-3, 0.3, eta)
+    ctx.prof_enable(False)
+    for k in range(2):
+        ctx.stage_step(k, *flat(all_paths[1 - k]))
+        ctx.commit_step(k)
+    ctx.switch_to_pre_update()
+    assert ctx.policy_forward(rng.randn(M, 3, O)).shape == (M, 3, A)
+    ctx.begin_rollout(0, 2, 5)
+    ctx.policy_step(0, 0, rng.randn(M, 2, O))
+    ctx.begin_collection(0, 2, 6)
+    for t in range(2):
+        ctx.policy_step(0, t, rng.randn(M, 2, O))
+    ctx.end_collection(0, [0, 2, 4], [0, 1, 2, 3], [0, 0, 0, 0], [2, 1, 2, 2], rng.randn(7))
+    assert ctx.step_rows[0] == 7
+    # (the noise of 2 x 4 x 20 rows needs more than twice what the calls above reserved: the rollout buffer grows again)
+    ctx.rollout_point_env(0, rng.randn(M, 2), rng.randn(M, 4, 2), noise=rng.randn(M, 4, 20, 2))
+    assert ctx.download_step(0)['obs'].shape == (M * 4 * 20, O)
+    ctx.close()
+
+    # ---- the layer-by-layer kernels: three hidden layers
+    O, A, hidden = 5, 3, (16, 16, 16)
+    theta, all_slabs, all_paths = helpers.make_promp_case(6, M, 2, 12, O, A, hidden, 1)
+    ctx = pc.make_ctx(lib, M, O, A, hidden, 1, all_paths)
+    helpers.upload_slabs(ctx, all_paths, all_slabs)
+    ctx.set_task_thetas(np.tile(theta, (M, 1)))
+    ctx.process_samples(0, baseline_kind=pc.KIND['linear_feature'], **kw)
+    g, _, _ = ctx.eval_loss_grad(1, 0, clip_eps=0.3)
+    assert np.all(np.isfinite(g))
+    assert ctx.policy_forward(rng.randn(M, 3, O)).shape == (M, 3, A)
+    ctx.begin_rollout(0, 2, 5)
+    ctx.policy_step(0, 0, rng.randn(M, 2, O))
+    ctx.close()
+
+    assert _live_counts(lib) == before
