@@ -168,8 +168,7 @@ int promp_set_advantages(promp_ctx* ctx, int step, const float* advantages);
  * rows / (paths * max_path_length) of its task so that the slab mean equals the reference's mean over the zero-padded
  * [paths, max_path_length] array (samplers/dice_sample_processor.py:165-191).  Computes the suffix sums within each path
  * that weight the log-likelihood gradient and installs them as the step's advantages; PROMP_INNER_DICE additionally
- * couples the time steps of a path in the second-order term (two extra launches per R-operator pass).
- * Register-chained kernels only (hidden sizes from {32,64}, obs_dim <= 32). */
+ * couples the time steps of a path in the second-order term (two extra launches per R-operator pass). */
 int promp_set_dice_rewards(promp_ctx* ctx, int step, const float* rewards);
 
 /* ---- parameters (rows a14: policies/base.py:173-203, 234-240, 262-286) ---------------------- */

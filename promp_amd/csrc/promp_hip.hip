@@ -1676,7 +1676,6 @@ int promp_set_dice_rewards(promp_ctx* c, int step, const float* rw) {
     if (!c || !rw) return fail(-1, "NULL argument");
     StepScope sc(c, step);
     if (sc.rc) return sc.rc;
-    if (c->family != PassFamily::Chain) return fail(-1, "the DiCE objective is built on the register-chained kernels (hidden sizes from {32,64}, obs_dim <= 32)");
     if (sc.open(/*writes=*/true, /*needs_data=*/true)) return sc.rc;
     StepData& S = sc.S();
     if (!S.dice_rw) {

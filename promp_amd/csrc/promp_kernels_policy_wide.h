@@ -666,6 +666,8 @@ __global__ void __launch_bounds__(4 * H, 2) k_wide_hvp(PassArgs a) {
             dlp += shfl_xor_f32(dlp, 1);  dlp += shfl_xor_f32(dlp, 2);
             Rlp += shfl_xor_f32(Rlp, 1);  Rlp += shfl_xor_f32(Rlp, 2);
             kl += shfl_xor_f32(kl, 1);  kl += shfl_xor_f32(kl, 2);
+            // DiCE coupling (PassArgs::row_tan, k_chain_hvp's convention): dlogpi_row . (-v) -- this kernel runs on +v and negates its outputs
+            if (a.row_tan != nullptr && rvalid && q == 0) a.row_tan[n] = -Rlp;
             float c = 0.f, Rc = 0.f, km = 0.f;
             if (rvalid) {
                 km = 1.f;

@@ -1306,6 +1306,9 @@ __global__ void __launch_bounds__(256, 1) k_wb_hvp(PassArgs a) {
                 Rlp += shfl_xor_f32(Rlp, m);
                 kl += shfl_xor_f32(kl, m);
             }
+            // DiCE coupling (PassArgs::row_tan, k_chain_hvp's convention): dlogpi_row . (-v) at the direction's true magnitude -- this
+            // kernel runs on +vs v and negates its outputs (a walk repeated by `attempt` stores again, with that walk's scale)
+            if (a.row_tan != nullptr && rvalid && eq == 0) a.row_tan[(long long)base + erow] = -Rlp * ivs;
             float c = 0.f, Rc = 0.f, km = 0.f;
             if (rvalid) {
                 km = 1.f;
