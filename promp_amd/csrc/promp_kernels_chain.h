@@ -30,6 +30,7 @@
 // the other (restaging the parameters in between).  Every (workgroup, segment) writes one partial row.
 #pragma once
 #include "promp_device.h"
+#include "promp_objective.h"
 
 #define PROMP_PASS_TPLANE 512    // words per plane of a [16 samples][64 units] tile of 16-bit halves
 #define PROMP_PASS_XPLANE 256    // [16][32 observation slots]
@@ -39,8 +40,6 @@
 #define PROMP_CH_DS 20          // row stride of the [16 samples][16 action slots] cotangent tile
 #define PROMP_CH_ROW 68         // floats per lane-group row of a hidden_1 fragment block (64 + 4 pad)
 #define PROMP_CH_BLK (4 * PROMP_CH_ROW)
-
-enum { LOSS_RATIO = 0, LOSS_CLIP = 1, LOSS_LOGLIK = 2, LOSS_KL = 3 };   // LOSS_KL: mean KL(old || new) itself (TRPO constraint)
 
 // Which entry of the workgroup -> segments table a workgroup of k_pass / k_chain_hvp takes.  The table is ordered by task, and the
 // dispatcher deals consecutive workgroups out over the eight XCDs: with the identity (0) the ~6 workgroups of a task sit on different
@@ -1347,14 +1346,14 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) k_chain_hvp(PassArgs a) {
             // ---- loss-level R-operator: lane (i16, kk) = sample i16, actions 2 kk and 2 kk + 1
             float d0, d1, qm0, qm1;
             {
-                const float z0 = (ac0 - mu0) * e0, z1 = (ac1 - mu1) * e1;
-                const float zo0 = (ac0 - mo0) * fast_exp(-so0), zo1 = (ac1 - mo1) * fast_exp(-so1);
-                const float num0 = (mo0 - mu0) * (mo0 - mu0) + fast_exp(2.f * so0) - sn20;
-                const float num1 = (mo1 - mu1) * (mo1 - mu1) + fast_exp(2.f * so1) - sn21;
-                const float den0 = 2.f * sn20 + 1e-8f, den1 = 2.f * sn21 + 1e-8f;
-                float dlp = (own0 ? (so0 - s0) - 0.5f * (z0 * z0 - zo0 * zo0) : 0.f) + (own1 ? (so1 - s1) - 0.5f * (z1 * z1 - zo1 * zo1) : 0.f);
-                float Rlp = (own0 ? z0 * e0 * Rmu0 + (z0 * z0 - 1.f) * Rs0 : 0.f) + (own1 ? z1 * e1 * Rmu1 + (z1 * z1 - 1.f) * Rs1 : 0.f);
-                float kl = (own0 ? num0 * rden0 + s0 - so0 : 0.f) + (own1 ? num1 * rden1 + s1 - so1 : 0.f);
+                const float z0 = gauss_z(ac0, mu0, e0), z1 = gauss_z(ac1, mu1, e1);
+                const float zo0 = gauss_z(ac0, mo0, fast_exp(-so0)), zo1 = gauss_z(ac1, mo1, fast_exp(-so1));
+                const float num0 = gauss_kl_num(mo0 - mu0, sn20, fast_exp(2.f * so0));
+                const float num1 = gauss_kl_num(mo1 - mu1, sn21, fast_exp(2.f * so1));
+                const float den0 = gauss_kl_den(sn20), den1 = gauss_kl_den(sn21);
+                float dlp = (own0 ? gauss_log_ratio(z0, zo0, s0, so0) : 0.f) + (own1 ? gauss_log_ratio(z1, zo1, s1, so1) : 0.f);
+                float Rlp = (own0 ? gauss_row_tangent(z0, e0, Rmu0, Rs0) : 0.f) + (own1 ? gauss_row_tangent(z1, e1, Rmu1, Rs1) : 0.f);
+                float kl = (own0 ? gauss_kl(num0, rden0, s0, so0) : 0.f) + (own1 ? gauss_kl(num1, rden1, s1, so1) : 0.f);
                 dlp = fold_groups16(dlp);      // sums over the row's actions (the four lane groups): lane swaps, no LDS round trip
                 Rlp = fold_groups16(Rlp);
                 kl = fold_groups16(kl);
@@ -1364,9 +1363,9 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) k_chain_hvp(PassArgs a) {
                     km = 1.f;
                     c = (a.loss_kind == LOSS_RATIO) ? -advn * expf(dlp) * invN : -advn * invN;
                 }
-                const float dklm0 = -2.f * (mo0 - mu0) * rden0 * invN, dklm1 = -2.f * (mo1 - mu1) * rden1 * invN;
-                const float dkls0 = ((-2.f * sn20 * den0 - 4.f * num0 * sn20) * (rden0 * rden0) + 1.f) * invN;
-                const float dkls1 = ((-2.f * sn21 * den1 - 4.f * num1 * sn21) * (rden1 * rden1) + 1.f) * invN;
+                const GaussKlGrad k0 = gauss_kl_grad(mo0 - mu0, sn20, num0, den0, rden0), k1 = gauss_kl_grad(mo1 - mu1, sn21, num1, den1, rden1);
+                const float dklm0 = k0.dklm * invN, dklm1 = k1.dklm * invN;
+                const float dkls0 = k0.dkls * invN, dkls1 = k1.dkls * invN;
                 const bool is_kl = a.loss_kind == LOSS_KL;
                 const float Rc = (a.loss_kind == LOSS_RATIO) ? c * Rlp : 0.f;
                 const float klv = klw * vs;          // (the KL cotangents carry no factor of the direction: they take its scale here)
@@ -1374,46 +1373,25 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) k_chain_hvp(PassArgs a) {
                 // cotangents of log_std, os
                 float os0, os1;
                 if (is_kl) {
-                    // The objective is the mean KL itself (the TRPO constraint): primal cotangent dKL/dmu, tangent cotangents
-                    // R'{dKL/dmu}, R'{dKL/ds}.  With D = mu_old - mu, den = 2 e^{2s} + 1e-8, num = D^2 + e^{2 s_old} - e^{2s}:
-                    //   dKL/dmu = -2 D / den                     R'{.} = 2 R'mu / den + 8 D e^{2s} R's / den^2
-                    //   dKL/ds  = 1 - 2 P / den^2, P = e^{2s} (den + 2 num)
-                    //   R'{P}   = 2 e^{2s} R's (den + 2 num) - 4 e^{2s} D R'mu ;  R'{dKL/ds} = -2 R'{P} / den^2 + 16 P e^{2s} R's / den^3
-                    {
-                        const float D = mo0 - mu0, P = sn20 * (den0 + 2.f * num0);
-                        const float RP = 2.f * sn20 * Rs0 * (den0 + 2.f * num0) - 4.f * sn20 * D * Rmu0;
-                        const float Rdm = 2.f * Rmu0 * rden0 + 8.f * D * sn20 * Rs0 * (rden0 * rden0);
-                        const float Rds = (-2.f * RP + 16.f * P * sn20 * Rs0 * rden0) * (rden0 * rden0);
-                        d0 = own0 ? km * dklm0 : 0.f;
-                        qm0 = own0 ? km * Rdm * invN : 0.f;
-                        os0 = own0 ? km * Rds * invN : 0.f;
-                    }
-                    {
-                        const float D = mo1 - mu1, P = sn21 * (den1 + 2.f * num1);
-                        const float RP = 2.f * sn21 * Rs1 * (den1 + 2.f * num1) - 4.f * sn21 * D * Rmu1;
-                        const float Rdm = 2.f * Rmu1 * rden1 + 8.f * D * sn21 * Rs1 * (rden1 * rden1);
-                        const float Rds = (-2.f * RP + 16.f * P * sn21 * Rs1 * rden1) * (rden1 * rden1);
-                        d1 = own1 ? km * dklm1 : 0.f;
-                        qm1 = own1 ? km * Rdm * invN : 0.f;
-                        os1 = own1 ? km * Rds * invN : 0.f;
-                    }
+                    // the objective is the mean KL itself (the TRPO constraint): primal cotangent dKL/dmu, tangent cotangents
+                    // R'{dKL/dmu}, R'{dKL/ds}
+                    const KlTangent t0 = kl_tangent(mo0 - mu0, sn20, num0, den0, rden0, Rmu0, Rs0);
+                    d0 = own0 ? km * dklm0 : 0.f;
+                    qm0 = own0 ? km * t0.Rdm * invN : 0.f;
+                    os0 = own0 ? km * t0.Rds * invN : 0.f;
+                    const KlTangent t1 = kl_tangent(mo1 - mu1, sn21, num1, den1, rden1, Rmu1, Rs1);
+                    d1 = own1 ? km * dklm1 : 0.f;
+                    qm1 = own1 ? km * t1.Rdm * invN : 0.f;
+                    os1 = own1 ? km * t1.Rds * invN : 0.f;
                 } else {
-                    {
-                        const float Rz = -Rmu0 * e0 - z0 * Rs0;
-                        const float Rd = Rc * z0 * e0 + c * (Rz * e0 - z0 * e0 * Rs0);
-                        const float Rds = Rc * (z0 * z0 - 1.f) + 2.f * c * z0 * Rz;
-                        d0 = own0 ? c * z0 * e0 : 0.f;
-                        qm0 = own0 ? km * (Rd + klv * dklm0) : 0.f;
-                        os0 = own0 ? km * (Rds + klv * dkls0) : 0.f;
-                    }
-                    {
-                        const float Rz = -Rmu1 * e1 - z1 * Rs1;
-                        const float Rd = Rc * z1 * e1 + c * (Rz * e1 - z1 * e1 * Rs1);
-                        const float Rds = Rc * (z1 * z1 - 1.f) + 2.f * c * z1 * Rz;
-                        d1 = own1 ? c * z1 * e1 : 0.f;
-                        qm1 = own1 ? km * (Rd + klv * dklm1) : 0.f;
-                        os1 = own1 ? km * (Rds + klv * dkls1) : 0.f;
-                    }
+                    const LikTangent t0 = lik_tangent(c, Rc, z0, e0, Rmu0, Rs0);
+                    d0 = own0 ? c * z0 * e0 : 0.f;
+                    qm0 = own0 ? km * (t0.Rd + klv * dklm0) : 0.f;
+                    os0 = own0 ? km * (t0.Rds + klv * dkls0) : 0.f;
+                    const LikTangent t1 = lik_tangent(c, Rc, z1, e1, Rmu1, Rs1);
+                    d1 = own1 ? c * z1 * e1 : 0.f;
+                    qm1 = own1 ? km * (t1.Rd + klv * dklm1) : 0.f;
+                    os1 = own1 ? km * (t1.Rds + klv * dkls1) : 0.f;
                 }
                 if (PROMP_NT == 2) {
                     // FP16 has a range (promp_kernels_pass.h: pass_cotangent_scale): the wave's first tile with a cotangent sets the
@@ -1424,13 +1402,10 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) k_chain_hvp(PassArgs a) {
                     const float am = fmaxf(fmaxf(fabsf(d0), fabsf(d1)), (1.f / (float)(1 << CHAIN_Q_OVER_D)) * fmaxf(fabsf(qm0), fabsf(qm1)));
                     amax = fmaxf(amax, am);
                     if (wave_uniform(prov)) {
-                        const float mx = wave_absmax_f32(am);
-                        const bool okm = mx > 0.f && mx < 3.0e38f;
-                        int k = scale_exp(okm ? mx : invN, okm ? ct : -4);
-                        k = k < -100 ? -100 : k > 100 ? 100 : k;
-                        cs = pow2f(k);
+                        const CotangentScale k = cotangent_scale(wave_absmax_f32(am), invN, ct);
+                        cs = k.cs;
                         qs = cs * vs;
-                        prov = okm ? 0 : 1;
+                        prov = k.prov;
                     }
                     d0 *= cs; d1 *= cs; qm0 *= cs; qm1 *= cs; os0 *= cs; os1 *= cs;
                 }

@@ -374,7 +374,7 @@ PROMP_DEV float gen_block_sum(float v, float* red, int tid) {
 
 // k_gen_loss: objective / KL of the work item's rows, the cotangents of the means (-> dz[pp], [rows][A]) and the log_std gradient;
 // one thread per row, the row's actions in a loop.  HVP: also the tangents along u = -v (-> qz[pp]) and R'{d objective / d s},
-// with kl_weight x the KL cotangents joined in (k_chain_hvp's loss level).  Writes P[oS .. oS + A), P[NP], P[NP + 1].
+// with kl_weight x the KL cotangents joined in (formulas: promp_objective.h).  Writes P[oS .. oS + A), P[NP], P[NP + 1].
 // What depends on the action only (the clipped log_std, its exponentials, the direction's entry; the old distribution's when it is
 // per task) is tabulated in LDS once per workgroup.  The rows' log_std terms go through an LDS tile [256][A | 1], 256 rows at a
 // time, and are summed per action by 4 x 64 threads (thread (q, j): rows q, q + 4, ... in row order; the four parts combined in
@@ -439,17 +439,18 @@ __global__ void __launch_bounds__(256) k_gen_loss(GenArgs a, int pp) {
             float so, eo, so2;
             if (a.ls_per_row) { so = olsp[j]; eo = expf(-so); so2 = expf(2.f * so); }
             else { so = cst[5 * GEN_MAX_A + j]; eo = cst[6 * GEN_MAX_A + j]; so2 = cst[7 * GEN_MAX_A + j]; }
-            const float z = (ac - mu) * e, zo = (ac - mo) * eo;
-            const float num = (mo - mu) * (mo - mu) + so2 - sn2, rden = 1.0f / (2.f * sn2 + 1e-8f);
-            dlp += (so - s) - 0.5f * (z * z - zo * zo);
+            const float z = gauss_z(ac, mu, e), zo = gauss_z(ac, mo, eo);
+            const float num = gauss_kl_num(mo - mu, sn2, so2), rden = 1.0f / gauss_kl_den(sn2);
+            dlp += gauss_log_ratio(z, zo, s, so);
             sumz2 += z * z;
-            kl += num * rden + s - so;
-            if (HVP) Rlp += z * e * g_rmu[(long long)n * A + j] + (z * z - 1.f) * cst[4 * GEN_MAX_A + j];
+            kl += gauss_kl(num, rden, s, so);
+            if (HVP) Rlp += gauss_row_tangent(z, e, g_rmu[(long long)n * A + j], cst[4 * GEN_MAX_A + j]);
         }
         if (HVP && a.row_tan != nullptr && rv) a.row_tan[n] = Rlp;
+        // (row_objective_weight_first's values, as overriding assignments: on its selects this kernel's register counts move)
         const float rho = expf(dlp), aw = advn * invN;
-        const float x = rho * advn, y = fminf(fmaxf(rho, 1.f - a.clip_eps), 1.f + a.clip_eps) * advn;
-        const float lp = -ssum - 0.5f * sumz2 - 0.5f * (float)A * 1.8378770664093453f;
+        const float x = clip_x(rho, advn), y = clip_y(rho, advn, a.clip_eps);
+        const float lp = gauss_log_lik(ssum, sumz2, A);
         float c = -aw, lrow = -lp * aw;                                  // log-likelihood
         if (is_clip) { c = (x <= y) ? -aw * rho : 0.f; lrow = -fminf(x, y) * invN; }
         if (is_ratio) { c = -aw * rho; lrow = -rho * aw; }
@@ -465,10 +466,10 @@ __global__ void __launch_bounds__(256) k_gen_loss(GenArgs a, int pp) {
             const float e = cst[GEN_MAX_A + j], sn2 = cst[2 * GEN_MAX_A + j], lmask = cst[3 * GEN_MAX_A + j];
             const float mu = g_mu[(long long)n * A + j], ac = g_act[(long long)n * A + j], mo = g_om[(long long)n * A + j];
             const float so2 = a.ls_per_row ? expf(2.f * olsp[j]) : cst[7 * GEN_MAX_A + j];
-            const float z = (ac - mu) * e;
-            const float num = (mo - mu) * (mo - mu) + so2 - sn2, den = 2.f * sn2 + 1e-8f, rden = 1.0f / den;
-            const float dklm = -2.f * (mo - mu) * rden * invN;
-            const float dkls = ((-2.f * sn2 * den - 4.f * num * sn2) * (rden * rden) + 1.f) * invN;
+            const float z = gauss_z(ac, mu, e);
+            const float num = gauss_kl_num(mo - mu, sn2, so2), den = gauss_kl_den(sn2), rden = 1.0f / den;
+            const GaussKlGrad k = gauss_kl_grad(mo - mu, sn2, num, den, rden);
+            const float dklm = k.dklm * invN, dkls = k.dkls * invN;
             float d, q = 0.f, os;
             if (!HVP) {
                 d = c * z * e + (is_kl ? dklm : 0.f);
@@ -477,21 +478,16 @@ __global__ void __launch_bounds__(256) k_gen_loss(GenArgs a, int pp) {
                 const float Rs = cst[4 * GEN_MAX_A + j];
                 const float Rmu = g_rmu[(long long)n * A + j];
                 if (is_kl) {
-                    // the objective is the mean KL itself (TRPO's constraint): see k_chain_hvp for the derivation
-                    const float D = mo - mu, Pq = sn2 * (den + 2.f * num);
-                    const float RP = 2.f * sn2 * Rs * (den + 2.f * num) - 4.f * sn2 * D * Rmu;
-                    const float Rdm = 2.f * Rmu * rden + 8.f * D * sn2 * Rs * (rden * rden);
-                    const float Rds = (-2.f * RP + 16.f * Pq * sn2 * Rs * rden) * (rden * rden);
+                    // the objective is the mean KL itself (TRPO's constraint)
+                    const KlTangent t = kl_tangent(mo - mu, sn2, num, den, rden, Rmu, Rs);
                     d = dklm;
-                    q = Rdm * invN;
-                    os = Rds * invN;
+                    q = t.Rdm * invN;
+                    os = t.Rds * invN;
                 } else {
-                    const float Rz = -Rmu * e - z * Rs;
-                    const float Rd = Rc * z * e + c * (Rz * e - z * e * Rs);
-                    const float Rds = Rc * (z * z - 1.f) + 2.f * c * z * Rz;
+                    const LikTangent t = lik_tangent(c, Rc, z, e, Rmu, Rs);
                     d = c * z * e;
-                    q = Rd + a.kl_weight * dklm;
-                    os = Rds + a.kl_weight * dkls;
+                    q = t.Rd + a.kl_weight * dklm;
+                    os = t.Rds + a.kl_weight * dkls;
                 }
             }
             if (out_kind != GEN_ACT_IDENTITY) {      // output_nonlinearity (mlp.py:114-117): mu = f(z), d / dz = f'(z) d / dmu, and its R-operator

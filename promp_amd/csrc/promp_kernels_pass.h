@@ -351,22 +351,15 @@ struct PassSums {                // what a wave accumulates over its tiles of a 
 // for backward gains beyond 2^5: PASS_CT_RETRY lower).  One such segment doubles the launch's duration: the other workgroups wait.  Guarded in-tile variants (rescaling
 // the sums in place; abandoning the tile and walking it again) were built and measured: +3.4 / +4.7 us per launch for an event that
 // does not occur at PPO's operating point.
-#ifndef PROMP_CT_ATTEMPTS
-#define PROMP_CT_ATTEMPTS 3
-#endif
 #ifndef PROMP_PASS_CT_TARGET
 #define PROMP_PASS_CT_TARGET 5
 #endif
 PROMP_CX int PASS_CT_TARGET = PROMP_PASS_CT_TARGET, PASS_CT_REDO = 10, PASS_CT_RETRY = 12, PASS_CT_ATTEMPTS = PROMP_CT_ATTEMPTS;
-// the scale a largest |mean cotangent| of mx asks for (mx = 0 / not finite: 2^-4 N, for adv / N, and `prov`)
+// the scale a largest |mean cotangent| of mx asks for (cotangent_scale, promp_objective.h)
 template <int NC1, int NC2>
 PROMP_DEV void pass_cotangent_scale(PassSums<NC1, NC2>& S, float mx, float invN, int target) {
-    const bool okm = mx > 0.f && mx < 3.0e38f;
-    int k = scale_exp(okm ? mx : invN, okm ? target : -4);
-    k = k < -100 ? -100 : k > 100 ? 100 : k;
-    S.cs = pow2f(k);
-    S.ics = pow2f(-k);
-    S.prov = okm ? 0 : 1;
+    const CotangentScale k = cotangent_scale(mx, invN, target);
+    S.cs = k.cs; S.ics = k.ics; S.prov = k.prov;
 }
 
 // constants of a wave's walk through a segment
@@ -578,41 +571,30 @@ PROMP_DEV void pass_tile(PassSums<NC1, NC2>& S, PassPending<NC1>& Q, u32x4 (&w1f
     float d0, d1;
     {   // lane (i16, kk) = sample i16, actions 2 kk and 2 kk + 1
         const float o0 = W.own0 ? 1.f : 0.f, o1 = W.own1 ? 1.f : 0.f, rv = rvalid ? 1.f : 0.f;
-        const float z0 = (ac0 - mu0) * W.e0, z1 = (ac1 - mu1) * W.e1;
-        const float zo0 = (ac0 - mo0) * fast_exp(-so0), zo1 = (ac1 - mo1) * fast_exp(-so1);
-        const float num0 = (mo0 - mu0) * (mo0 - mu0) + fast_exp(2.f * so0) - W.sn20;
-        const float num1 = (mo1 - mu1) * (mo1 - mu1) + fast_exp(2.f * so1) - W.sn21;
-        const float den0 = 2.f * W.sn20 + 1e-8f, den1 = 2.f * W.sn21 + 1e-8f;
-        float dlp = o0 * ((so0 - W.s0) - 0.5f * (z0 * z0 - zo0 * zo0)) + o1 * ((so1 - W.s1) - 0.5f * (z1 * z1 - zo1 * zo1));
-        float sumz2 = o0 * (z0 * z0) + o1 * (z1 * z1);
-        float kl = o0 * (num0 * W.rden0 + W.s0 - so0) + o1 * (num1 * W.rden1 + W.s1 - so1);
+        const GaussTerms g0 = gauss_terms(ac0, mu0, W.s0, W.e0, W.sn20, W.rden0, mo0, so0, fast_exp(-so0), fast_exp(2.f * so0));
+        const GaussTerms g1 = gauss_terms(ac1, mu1, W.s1, W.e1, W.sn21, W.rden1, mo1, so1, fast_exp(-so1), fast_exp(2.f * so1));
+        float dlp = o0 * g0.dlp + o1 * g1.dlp;
+        float sumz2 = o0 * (g0.z * g0.z) + o1 * (g1.z * g1.z);
+        float kl = o0 * g0.kl + o1 * g1.kl;
         dlp = fold_groups16(dlp);          // sums over the row's actions (the four lane groups)
         sumz2 = fold_groups16(sumz2);
         kl = fold_groups16(kl);
         const float rho = expf(rvalid ? dlp : 0.f);        // (padding rows: a finite ratio with zero weight)
-        const float aw = advn * W.invN;
-        const float x = rho * advn, y = fminf(fmaxf(rho, 1.f - W.clip_eps), 1.f + W.clip_eps) * advn;
-        const float lp = -W.sums - 0.5f * sumz2 - 0.5f * (float)W.A * 1.8378770664093453f;
-        const bool is_kl = W.loss_kind == LOSS_KL, is_ratio = W.loss_kind == LOSS_RATIO, is_clip = W.loss_kind == LOSS_CLIP;
         // d loss / d logpi (c), the weight of the KL cotangents (ck; LOSS_KL only), the row's objective term
-        const float c = is_kl ? 0.f : is_ratio ? -aw * rho : is_clip ? ((x <= y) ? -aw * rho : 0.f) : -aw;
-        const float ck = is_kl ? rv * W.invN : 0.f;
-        const float lrow = is_kl ? kl * W.invN : is_ratio ? -rho * aw : is_clip ? -fminf(x, y) * W.invN : -lp * aw;
+        const RowObjective r = row_objective_weight_first(W.loss_kind, rho, kl, advn, W.invN, rv, W.clip_eps, W.sums, sumz2, W.A);
+        const float c = r.c, ck = r.ck;
         const float first = (kk == 0) ? rv : 0.f;          // one lane per row carries the row's scalars
-        const float dklm0 = -2.f * (mo0 - mu0) * W.rden0, dklm1 = -2.f * (mo1 - mu1) * W.rden1;
-        const float dkls0 = (-2.f * W.sn20 * den0 - 4.f * num0 * W.sn20) * (W.rden0 * W.rden0) + 1.f;
-        const float dkls1 = (-2.f * W.sn21 * den1 - 4.f * num1 * W.sn21) * (W.rden1 * W.rden1) + 1.f;
-        d0 = o0 * (c * z0 * W.e0 + ck * dklm0);
-        d1 = o1 * (c * z1 * W.e1 + ck * dklm1);
+        d0 = o0 * (c * g0.z * W.e0 + ck * g0.dklm);
+        d1 = o1 * (c * g1.z * W.e1 + ck * g1.dklm);
         if (BWD && PROMP_NT == 2) {
             const float am = fmaxf(fabsf(d0), fabsf(d1));
             S.amax = fmaxf(S.amax, am);
             if (wave_uniform(S.prov)) pass_cotangent_scale<NC1, NC2>(S, wave_absmax_f32(am), W.invN, W.ct_target);
         }
-        S.loss += first * lrow;
+        S.loss += first * r.lrow;
         S.klsum += first * (kl * W.invN);
-        S.gs0 += o0 * (c * (z0 * z0 - 1.f) + ck * dkls0);
-        S.gs1 += o1 * (c * (z1 * z1 - 1.f) + ck * dkls1);
+        S.gs0 += o0 * (c * (g0.z * g0.z - 1.f) + ck * g0.dkls);
+        S.gs1 += o1 * (c * (g1.z * g1.z - 1.f) + ck * g1.dkls);
         S.gb30 += d0;
         S.gb31 += d1;
         if (BWD && PROMP_NT == 2) {

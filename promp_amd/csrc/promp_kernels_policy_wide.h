@@ -254,7 +254,7 @@ __global__ void __launch_bounds__(4 * H, 2) k_wide_fwd_bwd(PassArgs a) {
             for (int r = 0; r < 4; ++r) Mss[(16 * w + 4 * kk + r) * MS + i16] = acc[r];
         }
         __syncthreads();
-        // ---- distribution + objective epilogue (same arithmetic as k_pass)
+        // ---- distribution + objective epilogue (promp_objective.h)
         if (epi) {
             const bool rvalid = erow < nrows;
             const long long n = (long long)base + (rvalid ? erow : 0);
@@ -266,32 +266,28 @@ __global__ void __launch_bounds__(4 * H, 2) k_wide_fwd_bwd(PassArgs a) {
             float dlp = 0.f, sumz2 = 0.f, sums = 0.f, kl = 0.f;
             float z0 = 0.f, z1 = 0.f, e0 = 0.f, e1 = 0.f, dklm0 = 0.f, dklm1 = 0.f, dkls0 = 0.f, dkls1 = 0.f;
             if (own0) {
-                const float s = lss[q], mu = Mss[erow * MS + q];
+                const float s = lss[q], mu = Mss[erow * MS + q], sn2 = sn2s[q];
                 e0 = ess[q];
-                z0 = (ac0 - mu) * e0;
-                const float zo = (ac0 - mo0) * fast_exp(-so0);
-                dlp += (so0 - s) - 0.5f * (z0 * z0 - zo * zo);
+                const GaussTerms g = gauss_terms(ac0, mu, s, e0, sn2, fast_rcp(gauss_kl_den(sn2)), mo0, so0, fast_exp(-so0), fast_exp(2.f * so0));
+                z0 = g.z;
+                dlp += g.dlp;
                 sumz2 += z0 * z0;
                 sums += s;
-                const float sn2 = sn2s[q], num = (mo0 - mu) * (mo0 - mu) + fast_exp(2.f * so0) - sn2, den = 2.f * sn2 + 1e-8f;
-                const float rden = fast_rcp(den);
-                kl += num * rden + s - so0;
-                dklm0 = -2.f * (mo0 - mu) * rden;
-                dkls0 = (-2.f * sn2 * den - 4.f * num * sn2) * (rden * rden) + 1.f;
+                kl += g.kl;
+                dklm0 = g.dklm;
+                dkls0 = g.dkls;
             }
             if (own1) {
-                const float s = lss[q + 4], mu = Mss[erow * MS + q + 4];
+                const float s = lss[q + 4], mu = Mss[erow * MS + q + 4], sn2 = sn2s[q + 4];
                 e1 = ess[q + 4];
-                z1 = (ac1 - mu) * e1;
-                const float zo = (ac1 - mo1) * fast_exp(-so1);
-                dlp += (so1 - s) - 0.5f * (z1 * z1 - zo * zo);
+                const GaussTerms g = gauss_terms(ac1, mu, s, e1, sn2, fast_rcp(gauss_kl_den(sn2)), mo1, so1, fast_exp(-so1), fast_exp(2.f * so1));
+                z1 = g.z;
+                dlp += g.dlp;
                 sumz2 += z1 * z1;
                 sums += s;
-                const float sn2 = sn2s[q + 4], num = (mo1 - mu) * (mo1 - mu) + fast_exp(2.f * so1) - sn2, den = 2.f * sn2 + 1e-8f;
-                const float rden = fast_rcp(den);
-                kl += num * rden + s - so1;
-                dklm1 = -2.f * (mo1 - mu) * rden;
-                dkls1 = (-2.f * sn2 * den - 4.f * num * sn2) * (rden * rden) + 1.f;
+                kl += g.kl;
+                dklm1 = g.dklm;
+                dkls1 = g.dkls;
             }
             dlp += shfl_xor_f32(dlp, 1);  dlp += shfl_xor_f32(dlp, 2);
             sumz2 += shfl_xor_f32(sumz2, 1);  sumz2 += shfl_xor_f32(sumz2, 2);
@@ -299,26 +295,11 @@ __global__ void __launch_bounds__(4 * H, 2) k_wide_fwd_bwd(PassArgs a) {
             kl += shfl_xor_f32(kl, 1);  kl += shfl_xor_f32(kl, 2);
             float c = 0.f, ck = 0.f;
             if (rvalid) {
-                const float rho = expf(dlp);
-                float lrow;
-                if (a.loss_kind == LOSS_KL) {
-                    lrow = kl * invN;
-                    ck = invN;
-                } else if (a.loss_kind == LOSS_RATIO) {
-                    lrow = -rho * advn * invN;
-                    c = -advn * rho * invN;
-                } else if (a.loss_kind == LOSS_CLIP) {
-                    const float x = rho * advn;
-                    const float y = fminf(fmaxf(rho, 1.f - a.clip_eps), 1.f + a.clip_eps) * advn;
-                    lrow = -fminf(x, y) * invN;
-                    c = (x <= y) ? -advn * rho * invN : 0.f;
-                } else {
-                    const float lp = -sums - 0.5f * sumz2 - 0.5f * (float)A * 1.8378770664093453f;
-                    lrow = -lp * advn * invN;
-                    c = -advn * invN;
-                }
+                const RowObjective r = row_objective_invn_last(a.loss_kind, expf(dlp), kl, advn, invN, a.clip_eps, sums, sumz2, A);
+                c = r.c;
+                ck = r.ck;
                 if (q == 0) {
-                    loss += lrow;
+                    loss += r.lrow;
                     klsum += kl * invN;
                 }
             }
@@ -611,7 +592,7 @@ __global__ void __launch_bounds__(4 * H, 2) k_wide_hvp(PassArgs a) {
             }
         }
         __syncthreads();
-        // ---- loss-level R-operator (same arithmetic as k_hvp)
+        // ---- loss-level R-operator (promp_objective.h)
         if (epi) {
             const bool rvalid = erow < nrows;
             const long long n = (long long)base + (rvalid ? erow : 0);
@@ -623,45 +604,39 @@ __global__ void __launch_bounds__(4 * H, 2) k_wide_hvp(PassArgs a) {
             float dlp = 0.f, Rlp = 0.f, kl = 0.f;
             float z0 = 0.f, z1 = 0.f, e0 = 0.f, e1 = 0.f, Rmu0 = 0.f, Rmu1 = 0.f, dklm0 = 0.f, dklm1 = 0.f, dkls0 = 0.f,
                   dkls1 = 0.f, Rs0 = 0.f, Rs1 = 0.f;
-            // objective = the mean KL itself (the TRPO constraint, LOSS_KL): R{dKL/dmu}, R{dKL/ds} along v (formulas: k_chain_hvp)
+            // objective = the mean KL itself (the TRPO constraint, LOSS_KL): R{dKL/dmu}, R{dKL/ds} along v
             float kRdm0 = 0.f, kRdm1 = 0.f, kRds0 = 0.f, kRds1 = 0.f;
             if (own0) {
-                const float s = lss[q], mu = Mss[erow * MS + q];
+                const float s = lss[q], mu = Mss[erow * MS + q], sn2 = sn2s[q], rden = fast_rcp(gauss_kl_den(sn2));
                 Rmu0 = Ms2s[erow * MS + q];
                 Rs0 = vls[q];
                 e0 = ess[q];
-                z0 = (ac0 - mu) * e0;
-                const float zo = (ac0 - mo0) * fast_exp(-so0);
-                dlp += (so0 - s) - 0.5f * (z0 * z0 - zo * zo);
-                Rlp += z0 * e0 * Rmu0 + (z0 * z0 - 1.f) * Rs0;
-                const float sn2 = sn2s[q], num = (mo0 - mu) * (mo0 - mu) + fast_exp(2.f * so0) - sn2, den = 2.f * sn2 + 1e-8f;
-                const float rden = fast_rcp(den);
-                kl += num * rden + s - so0;
-                dklm0 = -2.f * (mo0 - mu) * rden * invN;
-                dkls0 = ((-2.f * sn2 * den - 4.f * num * sn2) * (rden * rden) + 1.f) * invN;
-                const float D = mo0 - mu, Pk = sn2 * (den + 2.f * num);
-                const float RP = 2.f * sn2 * Rs0 * (den + 2.f * num) - 4.f * sn2 * D * Rmu0;
-                kRdm0 = (2.f * Rmu0 * rden + 8.f * D * sn2 * Rs0 * (rden * rden)) * invN;
-                kRds0 = (-2.f * RP + 16.f * Pk * sn2 * Rs0 * rden) * (rden * rden) * invN;
+                const GaussTerms g = gauss_terms(ac0, mu, s, e0, sn2, rden, mo0, so0, fast_exp(-so0), fast_exp(2.f * so0));
+                const KlTangent t = kl_tangent(mo0 - mu, sn2, g.num, g.den, rden, Rmu0, Rs0);
+                z0 = g.z;
+                dlp += g.dlp;
+                Rlp += gauss_row_tangent(z0, e0, Rmu0, Rs0);
+                kl += g.kl;
+                dklm0 = g.dklm * invN;
+                dkls0 = g.dkls * invN;
+                kRdm0 = t.Rdm * invN;
+                kRds0 = t.Rds * invN;
             }
             if (own1) {
-                const float s = lss[q + 4], mu = Mss[erow * MS + q + 4];
+                const float s = lss[q + 4], mu = Mss[erow * MS + q + 4], sn2 = sn2s[q + 4], rden = fast_rcp(gauss_kl_den(sn2));
                 Rmu1 = Ms2s[erow * MS + q + 4];
                 Rs1 = vls[q + 4];
                 e1 = ess[q + 4];
-                z1 = (ac1 - mu) * e1;
-                const float zo = (ac1 - mo1) * fast_exp(-so1);
-                dlp += (so1 - s) - 0.5f * (z1 * z1 - zo * zo);
-                Rlp += z1 * e1 * Rmu1 + (z1 * z1 - 1.f) * Rs1;
-                const float sn2 = sn2s[q + 4], num = (mo1 - mu) * (mo1 - mu) + fast_exp(2.f * so1) - sn2, den = 2.f * sn2 + 1e-8f;
-                const float rden = fast_rcp(den);
-                kl += num * rden + s - so1;
-                dklm1 = -2.f * (mo1 - mu) * rden * invN;
-                dkls1 = ((-2.f * sn2 * den - 4.f * num * sn2) * (rden * rden) + 1.f) * invN;
-                const float D = mo1 - mu, Pk = sn2 * (den + 2.f * num);
-                const float RP = 2.f * sn2 * Rs1 * (den + 2.f * num) - 4.f * sn2 * D * Rmu1;
-                kRdm1 = (2.f * Rmu1 * rden + 8.f * D * sn2 * Rs1 * (rden * rden)) * invN;
-                kRds1 = (-2.f * RP + 16.f * Pk * sn2 * Rs1 * rden) * (rden * rden) * invN;
+                const GaussTerms g = gauss_terms(ac1, mu, s, e1, sn2, rden, mo1, so1, fast_exp(-so1), fast_exp(2.f * so1));
+                const KlTangent t = kl_tangent(mo1 - mu, sn2, g.num, g.den, rden, Rmu1, Rs1);
+                z1 = g.z;
+                dlp += g.dlp;
+                Rlp += gauss_row_tangent(z1, e1, Rmu1, Rs1);
+                kl += g.kl;
+                dklm1 = g.dklm * invN;
+                dkls1 = g.dkls * invN;
+                kRdm1 = t.Rdm * invN;
+                kRds1 = t.Rds * invN;
             }
             dlp += shfl_xor_f32(dlp, 1);  dlp += shfl_xor_f32(dlp, 2);
             Rlp += shfl_xor_f32(Rlp, 1);  Rlp += shfl_xor_f32(Rlp, 2);
@@ -681,25 +656,21 @@ __global__ void __launch_bounds__(4 * H, 2) k_wide_hvp(PassArgs a) {
             }
             const bool klobj = a.loss_kind == LOSS_KL;      // the outputs are MINUS the tangent of the gradient (see the header)
             if (own0) {
-                const float Rz = -Rmu0 * e0 - z0 * Rs0;
-                const float Rd = Rc * z0 * e0 + c * (Rz * e0 - z0 * e0 * Rs0);
-                const float Rds = Rc * (z0 * z0 - 1.f) + 2.f * c * z0 * Rz;
+                const LikTangent t = lik_tangent(c, Rc, z0, e0, Rmu0, Rs0);
                 const float d = klobj ? km * dklm0 : c * z0 * e0;
-                const float qm = klobj ? -km * kRdm0 : km * (-Rd + klw * dklm0);
+                const float qm = klobj ? -km * kRdm0 : km * (-t.Rd + klw * dklm0);
                 Mss[erow * MS + q] = d;
                 Ms2s[erow * MS + q] = qm;
-                outs0 += klobj ? -km * kRds0 : km * (-Rds + klw * dkls0);
+                outs0 += klobj ? -km * kRds0 : km * (-t.Rds + klw * dkls0);
                 outb30 += qm;
             }
             if (own1) {
-                const float Rz = -Rmu1 * e1 - z1 * Rs1;
-                const float Rd = Rc * z1 * e1 + c * (Rz * e1 - z1 * e1 * Rs1);
-                const float Rds = Rc * (z1 * z1 - 1.f) + 2.f * c * z1 * Rz;
+                const LikTangent t = lik_tangent(c, Rc, z1, e1, Rmu1, Rs1);
                 const float d = klobj ? km * dklm1 : c * z1 * e1;
-                const float qm = klobj ? -km * kRdm1 : km * (-Rd + klw * dklm1);
+                const float qm = klobj ? -km * kRdm1 : km * (-t.Rd + klw * dklm1);
                 Mss[erow * MS + q + 4] = d;
                 Ms2s[erow * MS + q + 4] = qm;
-                outs1 += klobj ? -km * kRds1 : km * (-Rds + klw * dkls1);
+                outs1 += klobj ? -km * kRds1 : km * (-t.Rds + klw * dkls1);
                 outb31 += qm;
             }
         }

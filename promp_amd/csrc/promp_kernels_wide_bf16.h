@@ -698,24 +698,22 @@ __global__ void __launch_bounds__(256, 1) k_wb_fwd_bwd(PassArgs a) {
         WB_STAMP(6);
         __syncthreads();
         WB_STAMP(7);
-        // ---- distribution + objective epilogue (the arithmetic of k_wide_fwd_bwd, one (row, action) pair per thread: the sums over a
+        // ---- distribution + objective epilogue (promp_objective.h; one (row, action) pair per thread: the sums over a
         //      row's actions run over its 8 lanes)
         {
             float dlp = 0.f, sumz2 = 0.f, sums = 0.f, kl = 0.f, z = 0.f, ee = 0.f, dklm = 0.f, dkls = 0.f;
             if (eown) {
                 const float mu = b3s[eq] + ((Mp[(0 * R + erow) * 8 + eq] + Mp[(1 * R + erow) * 8 + eq]) + (Mp[(2 * R + erow) * 8 + eq] + Mp[(3 * R + erow) * 8 + eq]));
-                const float s = lss[eq];
+                const float s = lss[eq], sn2 = sn2s[eq];
                 ee = ess[eq];
-                z = (eac - mu) * ee;
-                const float zo = (eac - emo) * fast_exp(-eso);
-                dlp = (eso - s) - 0.5f * (z * z - zo * zo);
+                const GaussTerms g = gauss_terms(eac, mu, s, ee, sn2, fast_rcp(gauss_kl_den(sn2)), emo, eso, fast_exp(-eso), fast_exp(2.f * eso));
+                z = g.z;
+                dlp = g.dlp;
                 sumz2 = z * z;
                 sums = s;
-                const float sn2 = sn2s[eq], num = (emo - mu) * (emo - mu) + fast_exp(2.f * eso) - sn2, den = 2.f * sn2 + 1e-8f;
-                const float rden = fast_rcp(den);
-                kl = num * rden + s - eso;
-                dklm = -2.f * (emo - mu) * rden;
-                dkls = (-2.f * sn2 * den - 4.f * num * sn2) * (rden * rden) + 1.f;
+                kl = g.kl;
+                dklm = g.dklm;
+                dkls = g.dkls;
             }
 #pragma unroll
             for (int m = 1; m <= 4; m <<= 1) {
@@ -726,26 +724,11 @@ __global__ void __launch_bounds__(256, 1) k_wb_fwd_bwd(PassArgs a) {
             }
             float c = 0.f, ck = 0.f;
             if (rvalid) {
-                const float rho = expf(dlp);
-                float lrow;
-                if (a.loss_kind == LOSS_KL) {
-                    lrow = kl * invN;
-                    ck = invN;
-                } else if (a.loss_kind == LOSS_RATIO) {
-                    lrow = -rho * advn * invN;
-                    c = -advn * rho * invN;
-                } else if (a.loss_kind == LOSS_CLIP) {
-                    const float x = rho * advn;
-                    const float y = fminf(fmaxf(rho, 1.f - a.clip_eps), 1.f + a.clip_eps) * advn;
-                    lrow = -fminf(x, y) * invN;
-                    c = (x <= y) ? -advn * rho * invN : 0.f;
-                } else {
-                    const float lp = -sums - 0.5f * sumz2 - 0.5f * (float)A * 1.8378770664093453f;
-                    lrow = -lp * advn * invN;
-                    c = -advn * invN;
-                }
+                const RowObjective r = row_objective_invn_last(a.loss_kind, expf(dlp), kl, advn, invN, a.clip_eps, sums, sumz2, A);
+                c = r.c;
+                ck = r.ck;
                 if (eq == 0) {
-                    loss += lrow;
+                    loss += r.lrow;
                     klsum += kl * invN;
                 }
             }
@@ -761,13 +744,10 @@ __global__ void __launch_bounds__(256, 1) k_wb_fwd_bwd(PassArgs a) {
                     const float m = wave_absmax_f32(d);
                     if (lane == 0) red[w] = m;
                     __syncthreads();
-                    const float mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-                    const bool okm = mx > 0.f && mx < 3.0e38f;
-                    int k = scale_exp(okm ? mx : invN, okm ? PASS_CT_TARGET : -4);
-                    k = k < -100 ? -100 : k > 100 ? 100 : k;
-                    cs = pow2f(k);
-                    ics = pow2f(-k);
-                    prov = okm ? 0 : 1;
+                    const CotangentScale k = cotangent_scale(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])), invN, PASS_CT_TARGET);
+                    cs = k.cs;
+                    ics = k.ics;
+                    prov = k.prov;
                 }
                 d *= cs;
             }
@@ -1275,7 +1255,7 @@ __global__ void __launch_bounds__(256, 1) k_wb_hvp(PassArgs a) {
         WB_STAMP(6);
         __syncthreads();
         WB_STAMP(7);
-        // ---- loss-level R-operator (the arithmetic of k_wide_hvp, one (row, action) pair per thread)
+        // ---- loss-level R-operator (promp_objective.h; one (row, action) pair per thread)
         {
             float dlp = 0.f, Rlp = 0.f, kl = 0.f;
             float z = 0.f, ee = 0.f, Rmu = 0.f, dklm = 0.f, dkls = 0.f, Rs = 0.f, kRdm = 0.f, kRds = 0.f;
@@ -1285,20 +1265,19 @@ __global__ void __launch_bounds__(256, 1) k_wb_hvp(PassArgs a) {
                 const float s = lss[eq];
                 Rs = vls[eq];
                 ee = ess[eq];
-                z = (eac - mu) * ee;
-                const float zo = (eac - emo) * fast_exp(-eso);
-                dlp = (eso - s) - 0.5f * (z * z - zo * zo);
-                Rlp = z * ee * Rmu + (z * z - 1.f) * Rs;
-                const float sn2 = sn2s[eq], num = (emo - mu) * (emo - mu) + fast_exp(2.f * eso) - sn2, den = 2.f * sn2 + 1e-8f;
+                z = gauss_z(eac, mu, ee);
+                dlp = gauss_log_ratio(z, gauss_z(eac, emo, fast_exp(-eso)), s, eso);
+                Rlp = gauss_row_tangent(z, ee, Rmu, Rs);
+                const float sn2 = sn2s[eq], num = gauss_kl_num(emo - mu, sn2, fast_exp(2.f * eso)), den = gauss_kl_den(sn2);
                 const float rden = fast_rcp(den);
-                kl = num * rden + s - eso;
-                dklm = -2.f * (emo - mu) * rden * invN;
-                dkls = ((-2.f * sn2 * den - 4.f * num * sn2) * (rden * rden) + 1.f) * invN;
-                // objective = the mean KL itself (LOSS_KL): R{dKL/dmu}, R{dKL/ds} along v (formulas: k_chain_hvp)
-                const float D = emo - mu, Pk = sn2 * (den + 2.f * num);
-                const float RP = 2.f * sn2 * Rs * (den + 2.f * num) - 4.f * sn2 * D * Rmu;
-                kRdm = (2.f * Rmu * rden + 8.f * D * sn2 * Rs * (rden * rden)) * invN;
-                kRds = (-2.f * RP + 16.f * Pk * sn2 * Rs * rden) * (rden * rden) * invN;
+                kl = gauss_kl(num, rden, s, eso);
+                const GaussKlGrad k = gauss_kl_grad(emo - mu, sn2, num, den, rden);
+                dklm = k.dklm * invN;
+                dkls = k.dkls * invN;
+                // objective = the mean KL itself (LOSS_KL): R{dKL/dmu}, R{dKL/ds} along v
+                const KlTangent t = kl_tangent(emo - mu, sn2, num, den, rden, Rmu, Rs);
+                kRdm = t.Rdm * invN;
+                kRds = t.Rds * invN;
             }
 #pragma unroll
             for (int m = 1; m <= 4; m <<= 1) {
@@ -1323,12 +1302,10 @@ __global__ void __launch_bounds__(256, 1) k_wb_hvp(PassArgs a) {
             const bool klobj = a.loss_kind == LOSS_KL;      // the outputs are MINUS the tangent of the gradient
             float d = 0.f, qm = 0.f;                        // (the tangent quantities at the direction's scale vs)
             if (eown) {
-                const float Rz = -Rmu * ee - z * Rs;
-                const float Rd = Rc * z * ee + c * (Rz * ee - z * ee * Rs);
-                const float Rds = Rc * (z * z - 1.f) + 2.f * c * z * Rz;
+                const LikTangent t = lik_tangent(c, Rc, z, ee, Rmu, Rs);
                 d = klobj ? km * dklm : c * z * ee;
-                qm = klobj ? -km * kRdm : km * (-Rd + klv * dklm);
-                outs += klobj ? -km * kRds : km * (-Rds + klv * dkls);
+                qm = klobj ? -km * kRdm : km * (-t.Rd + klv * dklm);
+                outs += klobj ? -km * kRds : km * (-t.Rds + klv * dkls);
                 outb3 += qm;
             }
             if (PROMP_NT == 2) {
@@ -1338,12 +1315,9 @@ __global__ void __launch_bounds__(256, 1) k_wb_hvp(PassArgs a) {
                     const float m = wave_absmax_f32(am);
                     if (lane == 0) red[w] = m;
                     __syncthreads();
-                    const float mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-                    const bool okm = mx > 0.f && mx < 3.0e38f;
-                    int k = scale_exp(okm ? mx : invN, okm ? CHAIN_CT_TARGET : -4);
-                    k = k < -100 ? -100 : k > 100 ? 100 : k;
-                    cs = pow2f(k);
-                    prov = okm ? 0 : 1;
+                    const CotangentScale k = cotangent_scale(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])), invN, CHAIN_CT_TARGET);
+                    cs = k.cs;
+                    prov = k.prov;
                 }
                 d *= cs;
                 qm *= cs;
