@@ -94,8 +94,9 @@ const char* promp_last_error(void);
 /* 3.  The version moves when an existing entry point changes its meaning or signature: 3 = promp_dims grew by n_hidden,
  * hidden3, hidden4 (hidden_sizes of any length 1..4; a v2 caller's two-layer struct is the same prefix, but the library reads the
  * new fields, so bindings must be rebuilt).  Entry points added since the first v2 header -- round 3: promp_set_reuse_adapt,
- * promp_begin_collection / promp_end_collection, promp_state_version, the two pass counters; round 4: promp_comm_fixed_order --
- * were additions and did not move it. */
+ * promp_begin_collection / promp_end_collection, promp_state_version, the two pass counters; round 4: promp_comm_fixed_order;
+ * later: promp_set_train_step_sizes with promp_get_step_sizes / promp_get_step_size_grad / promp_{set,get}_step_size_adam_state
+ * and promp_reduced_count -- were additions and did not move it. */
 int promp_abi_version(void);
 /* Theta = O*H1+H1 + H1*H2+H2 + H2*A+A + A */
 int promp_param_count(const promp_dims* dims);
@@ -175,6 +176,25 @@ int promp_set_dice_rewards(promp_ctx* ctx, int step, const float* rewards);
 int promp_set_theta(promp_ctx* ctx, const float* theta);                 /* [Theta] meta-parameters     */
 int promp_get_theta(promp_ctx* ctx, float* theta);
 int promp_set_step_sizes(promp_ctx* ctx, const float* step_sizes);       /* [Theta], base.py:303-313     */
+/* The step sizes as they are now (base.py:203-211,303-313): what promp_set_step_sizes stored, the log_std entries zeroed under
+ * learn_std = False, and -- trained -- moved by every Adam step since. */
+int promp_get_step_sizes(promp_ctx* ctx, float* step_sizes);             /* [Theta]                      */
+/* trainable_inner_step_size (base.py:203-211,303-313: the reference creates the step-size variables trainable and leaves them out
+ * of its optimiser's var_list; here they are trained).  On: every gradient evaluation of the meta-objective (promp_meta_grad,
+ * promp_optimize, promp_optimize_begin) also leaves d objective / d step sizes = mean over tasks of sum_k -lam_{k+1} * g_k, and
+ * every Adam step (promp_adam_step and the two above) updates the step sizes together with theta: same beta_1, beta_2, epsilon,
+ * bias-corrected learning rate and step count, slots of their own; entries of log_std under learn_std = False stay as they
+ * are.  The one exchange per epoch then moves 2 Theta + K + 2 floats.  promp_constraint_hvp, promp_cg_solve and promp_eval_*
+ * treat the step sizes as constants.  Costs (K + 1) x n_tasks x Theta floats of device memory, allocated when first switched on
+ * (the sums a promp_meta_grad left for promp_reduced_get do not survive that).  Off (default): nothing is launched, allocated
+ * or exchanged that a library without this entry point would not. */
+int promp_set_train_step_sizes(promp_ctx* ctx, int on);
+/* [Theta] the task-mean step-size gradient the last gradient evaluation left (base.py:203-211,303-313; entries that are not
+ * trained report 0); needs promp_set_train_step_sizes(1) */
+int promp_get_step_size_grad(promp_ctx* ctx, float* grad);
+/* Adam slots of the step sizes (base.py:203-211,303-313; the step count is promp_set_adam_state's); need promp_set_train_step_sizes(1) */
+int promp_set_step_size_adam_state(promp_ctx* ctx, const float* m, const float* v);
+int promp_get_step_size_adam_state(promp_ctx* ctx, float* m, float* v);
 /* GaussianMLPPolicy(learn_std=False) (policies/gaussian_mlp_policy.py:63-69: log_std_var created with trainable=False):
  * the trailing act_dim parameters are neither adapted by the inner step (their step sizes are forced to 0) nor updated
  * by Adam.  Default: learned. */
@@ -374,6 +394,9 @@ int promp_comm_fixed_order(promp_ctx* ctx, int on);
  * n_tasks_global). */
 int promp_reduced_get(promp_ctx* ctx, float* out);
 int promp_reduced_set(promp_ctx* ctx, const float* in);
+/* The length the two above act on: Theta + K + 2, and with trainable step sizes (base.py:203-211,303-313) 2 Theta + K + 2 --
+ * the task sums of the step-size gradient follow the scalars. */
+int promp_reduced_count(promp_ctx* ctx);
 
 /* ---- evaluation hooks used by the parity tests and by alternative optimizers (TRPO-MAML's
  * conjugate-gradient loop calls these per evaluation): per-task objective, mean-KL and their

@@ -72,6 +72,11 @@ SIGNATURES = {
     'promp_set_theta': (C.c_int, [_P, _F]),
     'promp_get_theta': (C.c_int, [_P, _F]),
     'promp_set_step_sizes': (C.c_int, [_P, _F]),
+    'promp_get_step_sizes': (C.c_int, [_P, _F]),
+    'promp_set_train_step_sizes': (C.c_int, [_P, C.c_int]),
+    'promp_get_step_size_grad': (C.c_int, [_P, _F]),
+    'promp_set_step_size_adam_state': (C.c_int, [_P, _F, _F]),
+    'promp_get_step_size_adam_state': (C.c_int, [_P, _F, _F]),
     'promp_set_learn_std': (C.c_int, [_P, C.c_int]),
     'promp_set_primal_cache': (C.c_int, [_P, C.c_int]),
     'promp_set_reuse_adapt': (C.c_int, [_P, C.c_int]),
@@ -116,6 +121,7 @@ SIGNATURES = {
     'promp_comm_fixed_order': (C.c_int, [_P, C.c_int]),
     'promp_reduced_get': (C.c_int, [_P, _F]),
     'promp_reduced_set': (C.c_int, [_P, _F]),
+    'promp_reduced_count': (C.c_int, [_P]),
     'promp_allreduce_f64': (C.c_int, [_P, _D, C.c_int, C.c_int]),
     'promp_eval_loss_grad': (C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_int, _F, _F, _F]),
     'promp_eval_hvp': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, _F, _F]),
@@ -653,6 +659,30 @@ class Context:
         s = _f32(np.broadcast_to(np.asarray(s, dtype=np.float32), (self.n_params,)))
         self._call('promp_set_step_sizes', _ptr(s, C.c_float))
 
+    def get_step_sizes(self):
+        out = np.empty(self.n_params, np.float32)
+        self._call('promp_get_step_sizes', _ptr(out, C.c_float))
+        return out
+
+    def set_train_step_sizes(self, on=True):
+        """trainable_inner_step_size: gradient evaluations also leave the step sizes' gradient, Adam steps update them with theta"""
+        self._call('promp_set_train_step_sizes', int(bool(on)))
+
+    def get_step_size_grad(self):
+        out = np.empty(self.n_params, np.float32)
+        self._call('promp_get_step_size_grad', _ptr(out, C.c_float))
+        return out
+
+    def set_step_size_adam_state(self, m, v):
+        m, v = _f32(m), _f32(v)
+        assert m.shape == v.shape == (self.n_params,)
+        self._call('promp_set_step_size_adam_state', _ptr(m, C.c_float), _ptr(v, C.c_float))
+
+    def get_step_size_adam_state(self):
+        m, v = np.empty(self.n_params, np.float32), np.empty(self.n_params, np.float32)
+        self._call('promp_get_step_size_adam_state', _ptr(m, C.c_float), _ptr(v, C.c_float))
+        return m, v
+
     def set_adam_state(self, m, v, t):
         m, v = _f32(m), _f32(v)
         self._call('promp_set_adam_state', _ptr(m, C.c_float), _ptr(v, C.c_float), int(t))
@@ -895,14 +925,18 @@ class Context:
     def comm_split_path(self, on=True):
         self._call('promp_comm_split_path', int(bool(on)))
 
+    def reduced_count(self):
+        """floats promp_reduced_get / promp_reduced_set act on: Theta + K + 2, with trainable step sizes 2 Theta + K + 2"""
+        return self._call('promp_reduced_count')
+
     def reduced_get(self):
-        out = np.empty(self.n_params + self.K + 2, np.float32)
+        out = np.empty(self.reduced_count(), np.float32)
         self._call('promp_reduced_get', _ptr(out, C.c_float))
         return out
 
     def reduced_set(self, values):
         v = _f32(values)
-        assert v.shape == (self.n_params + self.K + 2,)
+        assert v.shape == (self.reduced_count(),)
         self._call('promp_reduced_set', _ptr(v, C.c_float))
 
     def allreduce_f64(self, values, op='sum'):

@@ -186,6 +186,7 @@ struct PassReq {
     float* row_tan = nullptr;          // R-operator pass: where the rows' log-likelihood tangents go (DiCE)
     float* next2 = nullptr;            // RED_STEP: second destinations of next and scal (see adapt0)
     float* scal2 = nullptr;
+    float* ginner = nullptr;           // RED_STEP: where the summed gradient itself goes (trainable step sizes)
 };
 
 struct ProfSlot {
@@ -293,6 +294,11 @@ struct promp_ctx {
     bool opt_pending = false;
     int opt_epochs = 0;
     DevBuf<float> fwd_buf;               // staging for promp_policy_forward
+    // promp_set_train_step_sizes (promp_kernels_step_sizes.h), all allocated when the flag is first switched on: the inner
+    // gradients g_k [K][tasks][Theta], the per-task step-size gradients [tasks][Theta], their task mean, alpha's Adam slots
+    bool train_sizes = false;
+    bool red_has_sizes = false;          // red's last Theta columns hold the step-size gradient's sums (promp_adam_step needs them)
+    DevBuf<float> ginner, galpha, ss_grad, ss_m, ss_v;
 };
 
 namespace {
@@ -727,7 +733,9 @@ int launch_pass(promp_ctx* c, StepData& S, const PassReq& q) {
     r.cur = q.cur; r.cur_task_stride = q.cur_stride; r.next = q.next;
     r.lam = c->lam; r.v = c->vbuf; r.scal = scal;
     r.next2 = q.red_mode == RED_STEP ? q.next2 : nullptr; r.scal2 = q.red_mode == RED_STEP ? q.scal2 : nullptr;
-    PROMP_LAUNCH(k_reduce_task, dim3((c->NP + 2 + 255) / 256, c->d.n_tasks), 256, 0, c->stream, r);
+    float* ginner = q.red_mode == RED_STEP ? q.ginner : nullptr;
+    if (ginner) PROMP_LAUNCH(k_reduce_task_keep, dim3((c->NP + 2 + 255) / 256, c->d.n_tasks), 256, 0, c->stream, r, ginner);
+    else PROMP_LAUNCH(k_reduce_task, dim3((c->NP + 2 + 255) / 256, c->d.n_tasks), 256, 0, c->stream, r);
     HIPCHECK(hipGetLastError());
     return 0;
 }
@@ -782,11 +790,24 @@ static int exchange_sums_raw(promp_ctx* c, float* buf, size_t n) {
 // exchange buffer); the ones that would go on to USE a mean (an Adam step, a conjugate-gradient product) refuse instead.
 static bool sharded_without_comm(const promp_ctx* c) { return c->d.n_tasks_global > c->d.n_tasks && c->comm == nullptr; }
 
-// One evaluation of the meta-objective (+ gradient, + Adam) enqueued on the stream.
+// the floats of c->red one exchange moves: [grad Theta | K + 2 scalars], and behind them the step-size gradient's Theta sums
+static size_t red_count(const promp_ctx* c, bool with_sizes) {
+    return (size_t)(with_sizes ? 2 : 1) * c->NP + c->d.num_inner_steps + 2;
+}
+// what the *_ss instances of the final stage take beside theta's arguments (promp_kernels_step_sizes.h)
+static StepSizeArgs step_size_args(const promp_ctx* c) {
+    StepSizeArgs s;
+    s.galpha = c->galpha; s.alpha = c->step_sizes; s.alpha_m = c->ss_m; s.alpha_v = c->ss_v; s.alpha_grad_mean = c->ss_grad;
+    return s;
+}
+
+// One evaluation of the meta-objective (+ gradient, + Adam) enqueued on the stream.  sizes_grad: with trainable step sizes the
+// gradient evaluation also leaves the step sizes' gradient (and Adam steps them); promp_cg_solve's evaluations say no.
 int enqueue_meta(promp_ctx* c, float clip_eps, const float* eta_host, int inner_kind, int outer_kind, bool want_grad,
-                 bool do_adam, float lr) {
+                 bool do_adam, float lr, bool sizes_grad = true) {
     const int K = c->d.num_inner_steps, M = c->d.n_tasks, NP = c->NP;
     const size_t MNP = (size_t)M * NP;
+    const bool ag = c->train_sizes && want_grad && sizes_grad;
     for (int k = 0; k <= K; ++k)
         if (c->steps[k].n_rows == 0) return fail(-3, "step %d has no data", k);
     // a step's second-stream sample processing is waited for right in front of the first pass that reads its advantages:
@@ -803,7 +824,7 @@ int enqueue_meta(promp_ctx* c, float clip_eps, const float* eta_host, int inner_
         // promp_inner_adapt has left exactly this pass's results behind (see there) if nothing it read has changed since and
         // the clip of log_std at log(min_std) -- the one difference between the two -- is not active
         const bool reuse = k == 0 && adapt0_stands(c, inner_kind, cached);
-        if (reuse) {
+        if (reuse) {                               // (with trainable step sizes it left its gradient in ginner[0] as well)
             c->adapt_passes_skipped += 1;
             filled[k] = cached;
             continue;
@@ -812,6 +833,7 @@ int enqueue_meta(promp_ctx* c, float clip_eps, const float* eta_host, int inner_
         q.theta = th; q.theta_stride = st; q.loss_kind = loss_kind_inner(inner_kind); q.clip_eps = clip_eps; q.clip_ls = k == 0;
         q.red_mode = RED_STEP; q.cur = th; q.cur_stride = st; q.next = c->chain + (size_t)(k + 1) * MNP; q.scal = c->scal_inner + (size_t)k * M * 2;
         q.cache = cached ? 1 : 0;
+        q.ginner = ag ? c->ginner + (size_t)k * MNP : nullptr;
         if (launch_pass(c, c->steps[k], q)) return -2;
         filled[k] = cached;
     }
@@ -829,6 +851,12 @@ int enqueue_meta(promp_ctx* c, float clip_eps, const float* eta_host, int inner_
             StepData& Sk = c->steps[k];
             const bool dice = inner_kind == PROMP_INNER_DICE;
             if (dice && !Sk.has_dice) return fail(-3, "step %d has no DiCE rewards: call promp_set_dice_rewards first", k);
+            if (ag) {
+                // lam is the complete multiplier of theta_{k+1} here, both pieces of a DiCE step included
+                PROMP_LAUNCH(k_step_size_grad, dim3((NP + 255) / 256, M), 256, 0, c->stream, c->galpha.p, (const float*)c->lam,
+                             (const float*)(c->ginner + (size_t)k * MNP), NP, k == K - 1 ? 1 : 0);
+                HIPCHECK(hipGetLastError());
+            }
             PassReq q;
             q.hvp = true; q.theta = th; q.theta_stride = st; q.loss_kind = loss_kind_inner(inner_kind); q.clip_eps = clip_eps; q.clip_ls = k == 0;
             q.klw = dice ? 0.f : eta_host[k] / (float)K; q.red_mode = RED_HVP;
@@ -852,12 +880,15 @@ int enqueue_meta(promp_ctx* c, float clip_eps, const float* eta_host, int inner_
     FinalArgs f;
     f.lam = c->lam; f.NP = NP; f.K = K; f.n_tasks = M;
     f.scal_inner = c->scal_inner; f.scal_outer = c->scal_outer; f.red = c->red; f.want_grad = want_grad ? 1 : 0;
+    c->red_has_sizes = ag;
+    const unsigned final_blocks = (unsigned)((red_count(c, ag) + 63) / 64);
     // several ranks (or an external collective: more global than local tasks): sums first, mean + Adam after the exchange
     const bool split = c->nranks > 1 || c->force_split || c->d.n_tasks_global != c->d.n_tasks;
     if (split) {
-        PROMP_LAUNCH(k_reduce_final, dim3((NP + K + 2 + 63) / 64), 256, 0, c->stream, f);
+        if (ag) PROMP_LAUNCH(k_reduce_final_ss, dim3(final_blocks), 256, 0, c->stream, f, (const float*)c->galpha);
+        else PROMP_LAUNCH(k_reduce_final, dim3(final_blocks), 256, 0, c->stream, f);
         HIPCHECK(hipGetLastError());
-        if (exchange_sums(c, c->red, (size_t)(NP + K + 2))) return -4;
+        if (exchange_sums(c, c->red, red_count(c, ag))) return -4;      // (one exchange per epoch, with or without the step sizes)
     }
     AdamArgs ad;
     ad.theta = c->theta; ad.m = c->adam_m; ad.v = c->adam_v; ad.red = c->red; ad.grad_mean = c->grad_mean;
@@ -870,13 +901,18 @@ int enqueue_meta(promp_ctx* c, float clip_eps, const float* eta_host, int inner_
     ad.lr_t = 0.f;
     if (do_adam) {
         c->theta_version = ++c->version_counter;     // (the smallest log_std entry is unknown until the next publication)
+        if (ag) c->sizes_version = ++c->version_counter;
         c->ls_known = false;
         c->adam_t += 1;
         const double t = (double)c->adam_t;
         ad.lr_t = (float)((double)lr * std::sqrt(1.0 - std::pow(0.999, t)) / (1.0 - std::pow(0.9, t)));
     }
-    if (split) PROMP_LAUNCH(k_mean_adam, dim3((NP + 1 + 255) / 256), 256, 0, c->stream, ad);
-    else PROMP_LAUNCH(k_final_adam, dim3((NP + K + 2 + 63) / 64 + 1), 256, 0, c->stream, f, ad);   // one rank: nothing in between
+    if (ag) {
+        const StepSizeArgs ss = step_size_args(c);
+        if (split) PROMP_LAUNCH(k_mean_adam_ss, dim3((2 * NP + 1 + 255) / 256), 256, 0, c->stream, ad, ss);
+        else PROMP_LAUNCH(k_final_adam_ss, dim3(final_blocks + 1), 256, 0, c->stream, f, ad, ss);
+    } else if (split) PROMP_LAUNCH(k_mean_adam, dim3((NP + 1 + 255) / 256), 256, 0, c->stream, ad);
+    else PROMP_LAUNCH(k_final_adam, dim3(final_blocks + 1), 256, 0, c->stream, f, ad);   // one rank: nothing in between
     HIPCHECK(hipGetLastError());
     for (int k = 0; k <= K; ++k) c->steps[k].dirty = true;
     return 0;
@@ -1748,6 +1784,53 @@ int promp_set_step_sizes(promp_ctx* c, const float* s) {
     if (params_in(c, c->step_sizes, s, 1)) return -2;
     return mask_log_std_step_sizes(c);
 }
+int promp_get_step_sizes(promp_ctx* c, float* s) {
+    NEED_CTX(c);
+    return params_out(c, s, c->step_sizes, 1);
+}
+// Trainable step sizes (meta_algos/base.py:203-211,303-313).  Switching on allocates what the feature needs -- (K + 1) tasks x Theta
+// floats for the inner gradients and the per-task step-size gradients, three Theta vectors, and an exchange buffer of
+// 2 Theta + K + 2 floats in place of the one of Theta + K + 2 (the sums of an earlier evaluation do not survive that); switching
+// off keeps the buffers and alpha's Adam slots, and every launch is again the one of a context that never had the flag on.
+int promp_set_train_step_sizes(promp_ctx* c, int on) {
+    NEED_CTX(c);
+    if ((on != 0) == c->train_sizes) return 0;
+    if (on && !c->ginner) {
+        const size_t MNP = (size_t)c->d.n_tasks * c->NP;
+        HIPCHECK(hipStreamSynchronize(c->stream));
+        if (c->ss_grad.alloc(c->NP) || c->ss_m.alloc(c->NP) || c->ss_v.alloc(c->NP) || c->galpha.alloc(MNP)) return -2;
+        {   // (into a temporary: a failed allocation leaves the context with the exchange buffer it had)
+            DevBuf<float> red;
+            if (red.alloc(red_count(c, true))) return -2;
+            c->red = std::move(red);
+        }
+        // (ginner last: the guard above stands for all six)
+        if (c->ginner.alloc((size_t)c->d.num_inner_steps * MNP)) return -2;
+    }
+    c->train_sizes = on != 0;
+    c->red_has_sizes = false;
+    c->adapt0.valid = false;            // (the pass promp_inner_adapt left behind has no ginner[0] / no use for one)
+    c->version_counter += 1;
+    return 0;
+}
+int promp_get_step_size_grad(promp_ctx* c, float* out) {
+    NEED_CTX(c);
+    if (!c->train_sizes) return fail(-3, "the step sizes are not trained (promp_set_train_step_sizes)");
+    return params_out(c, out, c->ss_grad, 1);
+}
+int promp_set_step_size_adam_state(promp_ctx* c, const float* m, const float* v) {
+    NEED_CTX(c);
+    if (!c->train_sizes) return fail(-3, "the step sizes are not trained (promp_set_train_step_sizes)");
+    if (params_in(c, c->ss_m, m, 1) || params_in(c, c->ss_v, v, 1)) return -2;
+    return 0;
+}
+int promp_get_step_size_adam_state(promp_ctx* c, float* m, float* v) {
+    NEED_CTX(c);
+    if (!c->train_sizes) return fail(-3, "the step sizes are not trained (promp_set_train_step_sizes)");
+    if (m && params_out(c, m, c->ss_m, 1)) return -2;
+    if (v && params_out(c, v, c->ss_v, 1)) return -2;
+    return 0;
+}
 int promp_set_min_std(promp_ctx* c, float min_std) {
     NEED_CTX(c);
     if (!(min_std > 0.f)) return fail(-1, "min_std must be positive");
@@ -1850,6 +1933,7 @@ int promp_inner_adapt(promp_ctx* c, int step, int inner_kind) {
     if (leave) {
         q.next2 = c->chain + (size_t)c->d.n_tasks * c->NP;
         q.scal2 = c->scal_inner;
+        q.ginner = c->train_sizes ? c->ginner.p : nullptr;     // ... and the gradient itself, the step sizes' first factor
     }
     c->tasks_shared = false;
     const int rc = launch_pass(c, S, q);
@@ -2193,6 +2277,7 @@ static int enqueue_constraint_hvp(promp_ctx* c, int inner_kind, int refresh_chai
     FinalArgs f;
     f.lam = c->wbuf; f.NP = NP; f.K = K; f.n_tasks = M;
     f.scal_inner = c->scal_inner; f.scal_outer = c->scal_outer; f.red = c->red; f.want_grad = 1;
+    c->red_has_sizes = false;
     PROMP_LAUNCH(k_reduce_final, dim3((NP + K + 2 + 63) / 64), 256, 0, c->stream, f);
     HIPCHECK(hipGetLastError());
     if (exchange_sums(c, c->red, (size_t)NP)) return -4;
@@ -2241,12 +2326,12 @@ int promp_cg_solve(promp_ctx* c, int inner_kind, const float* b, int cg_iters, f
         PROMP_LAUNCH(k_cg_displace, dim3((NP + 255) / 256), 256, 0, c->stream, c->theta, th0, v, s, NP);
         c->theta_version = ++c->version_counter;
         c->ls_known = false;
-        return enqueue_meta(c, 0.f, eta, inner_kind, PROMP_OUTER_KL, true, false, 0.f);
+        return enqueue_meta(c, 0.f, eta, inner_kind, PROMP_OUTER_KL, true, false, 0.f, /*sizes_grad=*/false);
     };
     if (!exact) {
         HIPCHECK(hipMemcpyAsync(th0, c->theta, sizeof(float) * NP, hipMemcpyDeviceToDevice, c->stream));
         if (hvp_mode == 1) {                                      // one-sided: the gradient at theta0 itself, once
-            if (enqueue_meta(c, 0.f, eta, inner_kind, PROMP_OUTER_KL, true, false, 0.f)) return -2;
+            if (enqueue_meta(c, 0.f, eta, inner_kind, PROMP_OUTER_KL, true, false, 0.f, /*sizes_grad=*/false)) return -2;
             HIPCHECK(hipMemcpyAsync(th0 + NP, c->grad_mean, sizeof(float) * NP, hipMemcpyDeviceToDevice, c->stream));
         }
     }
@@ -2294,6 +2379,9 @@ int promp_cg_solve(promp_ctx* c, int inner_kind, const float* b, int cg_iters, f
 int promp_adam_step(promp_ctx* c, float lr) {
     NEED_CTX(c);
     // red still holds the (all-reduced) sums of the last promp_meta_grad
+    if (c->train_sizes && !c->red_has_sizes)
+        return fail(-3, "promp_adam_step: the step sizes are trained, but the exchange buffer holds no step-size gradient: the last "
+                        "evaluation ran with the flag off, or was promp_constraint_hvp / promp_cg_solve (promp_meta_grad first)");
     AdamArgs ad;
     ad.theta = c->theta; ad.m = c->adam_m; ad.v = c->adam_v; ad.red = c->red; ad.grad_mean = c->grad_mean;
     ad.stats = c->stats; ad.NP = c->NP; ad.K = c->d.num_inner_steps;
@@ -2304,11 +2392,13 @@ int promp_adam_step(promp_ctx* c, float lr) {
     ad.n_trainable = c->learn_std ? c->NP : c->NP - c->d.act_dim;
     ad.A = c->d.act_dim;
     c->theta_version = ++c->version_counter;
+    if (c->train_sizes) c->sizes_version = ++c->version_counter;
     c->ls_known = false;
     c->adam_t += 1;
     const double t = (double)c->adam_t;
     ad.lr_t = (float)((double)lr * std::sqrt(1.0 - std::pow(0.999, t)) / (1.0 - std::pow(0.9, t)));
-    PROMP_LAUNCH(k_mean_adam, dim3((c->NP + 1 + 255) / 256), 256, 0, c->stream, ad);
+    if (c->train_sizes) PROMP_LAUNCH(k_mean_adam_ss, dim3((2 * c->NP + 1 + 255) / 256), 256, 0, c->stream, ad, step_size_args(c));
+    else PROMP_LAUNCH(k_mean_adam, dim3((c->NP + 1 + 255) / 256), 256, 0, c->stream, ad);
     HIPCHECK(hipGetLastError());
     return 0;
 }
@@ -2489,12 +2579,24 @@ int promp_reduced_get(promp_ctx* c, float* out) {
     if (!c || !out) return fail(-1, "NULL argument");
     // [grad Theta | K + 2 scalars]: the gradient part in the caller's layout, like every parameter vector that crosses the ABI
     if (params_out(c, out, c->red, 1)) return -2;
-    return copy_out(c, out + c->NPu, c->red + c->NP, (size_t)c->d.num_inner_steps + 2);
+    const size_t ns = (size_t)c->d.num_inner_steps + 2;
+    if (copy_out(c, out + c->NPu, c->red + c->NP, ns)) return -2;
+    // trainable step sizes: [... | step-size gradient Theta], in the caller's layout as well
+    return c->train_sizes ? params_out(c, out + c->NPu + ns, c->red + c->NP + ns, 1) : 0;
 }
 int promp_reduced_set(promp_ctx* c, const float* in) {
     if (!c || !in) return fail(-1, "NULL argument");
     if (params_in(c, c->red, in, 1)) return -2;
-    return copy_in(c, c->red + c->NP, in + c->NPu, (size_t)c->d.num_inner_steps + 2);
+    const size_t ns = (size_t)c->d.num_inner_steps + 2;
+    if (copy_in(c, c->red + c->NP, in + c->NPu, ns)) return -2;
+    if (!c->train_sizes) return 0;
+    if (params_in(c, c->red + c->NP + ns, in + c->NPu + ns, 1)) return -2;
+    c->red_has_sizes = true;
+    return 0;
+}
+int promp_reduced_count(promp_ctx* c) {
+    NEED_CTX(c);
+    return (c->train_sizes ? 2 : 1) * c->NPu + c->d.num_inner_steps + 2;
 }
 
 int promp_allreduce_f64(promp_ctx* c, double* buf, int n, int op) {

@@ -857,7 +857,7 @@ PROMP_DEV void chain_task_sum(TaskRedArgs r, int tid) {
                 continue;
             }
             const long long tj = (long long)task * NP + j;
-            if (mode == RED_STEP) {
+            if (mode == RED_STEP) {       // (unreachable: launch_pass fuses R-operator passes only, so no ReduceArgs::ginner store here)
                 r.next[tj] = old[u] - al[u] * g[u];
                 continue;
             }

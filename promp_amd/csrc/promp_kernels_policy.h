@@ -5,11 +5,14 @@
 //   k_reduce_final : task sum of the per-task gradients and scalars                          (K14)
 //   k_mean_adam    : mean over the global meta-batch + tf.train.AdamOptimizer step            (K14)
 //   k_final_adam   : the two above in one launch (single rank)
+//                    (their *_ss instances carry Theta more columns: trainable step sizes, promp_kernels_step_sizes.h;
+//                    the plain ones are the launches and arguments of a library without the feature)
 //   k_policy_forward : mean network under each task's current parameters (get_actions)
 #pragma once
 #include "promp_device.h"
 #include "promp_kernels_chain.h"
 #include "promp_kernels_pass.h"
+#include "promp_kernels_step_sizes.h"
 
 // ---------------------------------------------------------------------------------------------
 // Reductions over the per-workgroup partials of each task (fixed order => reproducible).
@@ -39,7 +42,11 @@ struct ReduceArgs {
     float* scal2;
 };
 
-__global__ void __launch_bounds__(256) k_reduce_task(ReduceArgs a) {
+// KEEP_G (k_reduce_task_keep, mode 0): the summed gradient itself goes to ginner [tasks][Theta] as well (trainable step sizes,
+// promp_kernels_step_sizes.h: the backward sweep multiplies it with the multiplier of the step behind it).  k_reduce_task is
+// the instance without, with the arguments it always had.
+template <bool KEEP_G>
+PROMP_DEV void reduce_task_body(const ReduceArgs& a, float* ginner) {
     const int j = blockIdx.x * 256 + threadIdx.x;
     const int task = blockIdx.y;
     if (j >= a.NP + 2) return;
@@ -69,6 +76,7 @@ __global__ void __launch_bounds__(256) k_reduce_task(ReduceArgs a) {
         const float nx = a.cur[(long long)task * a.cur_task_stride + j] - a.step_sizes[j] * g;
         a.next[tj] = nx;
         if (a.next2 != nullptr) a.next2[tj] = nx;
+        if (KEEP_G) ginner[tj] = g;
         return;
     }
     float lam = g;
@@ -77,12 +85,15 @@ __global__ void __launch_bounds__(256) k_reduce_task(ReduceArgs a) {
     if (a.mode == 3) return;
     a.v[tj] = a.step_sizes[j] * lam;
 }
+__global__ void __launch_bounds__(256) k_reduce_task(ReduceArgs a) { reduce_task_body<false>(a, nullptr); }
+__global__ void __launch_bounds__(256) k_reduce_task_keep(ReduceArgs a, float* ginner) { reduce_task_body<true>(a, ginner); }
 
 // Task sum of lam (gradient) and of the per-task scalars -> red[NP + K + 2]
 //   red[0..NP)      = sum_i lam[i][j]
 //   red[NP]         = sum_i J_i                     (outer surrogate)
 //   red[NP+1+k]     = sum_i KL^k_i
 //   red[NP+1+K]     = sum_i outer KL_i
+//   red[NP+K+2+j]   = sum_i galpha[i][j]            (trainable step sizes only: Theta more columns behind the others)
 // grid = ceil((NP+K+2)/256)
 struct FinalArgs {
     const float* lam;
@@ -92,28 +103,42 @@ struct FinalArgs {
     float* red;
     int want_grad;
 };
+// trainable step sizes: what the *_ss instances of the final stage take beside the arguments above
+struct StepSizeArgs {
+    const float* galpha;      // [tasks][NP] per-task step-size gradients (k_step_size_grad)
+    float* alpha;             // the step sizes and their Adam slots: the same Adam step as theta's (lr_t, do_update, n_trainable)
+    float* alpha_m;
+    float* alpha_v;
+    float* alpha_grad_mean;   // [NP] task-mean step-size gradient (promp_get_step_size_grad)
+};
 
-// grid = ceil((NP + K + 2) / 64), block = 256: 64 columns x 4 task quarters.  Thread (c, q) adds the tasks i = q, q+4, ...
+// One task quarter of a [tasks][NP] column: thread (c, q) adds the tasks i = q, q + 4, ... of column j
+// (up to 12 tasks of the quarter requested together, clamped + masked like k_reduce_task; order i = q, q + 4, ...)
+PROMP_DEV float final_quarter_sum(const float* rows, int NP, int n_tasks, int j, int q) {
+    float s = 0.f;
+    for (int ib = q; ib < n_tasks; ib += 48) {
+        float x[12];
+#pragma unroll
+        for (int u = 0; u < 12; ++u) {
+            const int i = ib + 4 * u;
+            x[u] = rows[(long long)(i < n_tasks ? i : q) * NP + j] * (i < n_tasks ? 1.f : 0.f);
+        }
+#pragma unroll
+        for (int u = 0; u < 12; ++u) s += x[u];
+    }
+    return s;
+}
+
+// grid = ceil((NP + K + 2) / 64) -- k_reduce_final_ss: ceil((2 NP + K + 2) / 64) --, block = 256: 64 columns x 4 task quarters.  Thread (c, q) adds the tasks i = q, q+4, ...
 // of column c (10 dependent-latency steps instead of 40 at M = 40); the four quarter sums are added in a fixed order.
-__global__ void __launch_bounds__(256) k_reduce_final(FinalArgs a) {
-    __shared__ float part[4][64];
+template <bool SS>
+PROMP_DEV void reduce_final_body(const FinalArgs& a, const float* galpha, float (*part)[64]) {
     const int c = threadIdx.x & 63, q = threadIdx.x >> 6;
     const int j = blockIdx.x * 64 + c;
+    const int jend = a.NP + a.K + 2 + (SS ? a.NP : 0);
     float s = 0.f;
     if (j < a.NP) {
-        if (a.want_grad) {
-            // (up to 12 tasks of the quarter requested together, clamped + masked like k_reduce_task; order i = q, q + 4, ...)
-            for (int ib = q; ib < a.n_tasks; ib += 48) {
-                float x[12];
-#pragma unroll
-                for (int u = 0; u < 12; ++u) {
-                    const int i = ib + 4 * u;
-                    x[u] = a.lam[(long long)(i < a.n_tasks ? i : q) * a.NP + j] * (i < a.n_tasks ? 1.f : 0.f);
-                }
-#pragma unroll
-                for (int u = 0; u < 12; ++u) s += x[u];
-            }
-        }
+        if (a.want_grad) s = final_quarter_sum(a.lam, a.NP, a.n_tasks, j, q);
     } else if (j == a.NP) {
         for (int i = q; i < a.n_tasks; i += 4) s += a.scal_outer[i * 2 + 0];
     } else if (j <= a.NP + a.K) {
@@ -121,10 +146,20 @@ __global__ void __launch_bounds__(256) k_reduce_final(FinalArgs a) {
         for (int i = q; i < a.n_tasks; i += 4) s += a.scal_inner[((long long)k * a.n_tasks + i) * 2 + 1];
     } else if (j == a.NP + a.K + 1) {
         for (int i = q; i < a.n_tasks; i += 4) s += a.scal_outer[i * 2 + 1];
+    } else if (SS && j < jend) {
+        s = final_quarter_sum(galpha, a.NP, a.n_tasks, j - (a.NP + a.K + 2), q);
     }
     part[q][c] = s;
     __syncthreads();
-    if (q == 0 && j < a.NP + a.K + 2) a.red[j] = (part[0][c] + part[1][c]) + (part[2][c] + part[3][c]);
+    if (q == 0 && j < jend) a.red[j] = (part[0][c] + part[1][c]) + (part[2][c] + part[3][c]);
+}
+__global__ void __launch_bounds__(256) k_reduce_final(FinalArgs a) {
+    __shared__ float part[4][64];
+    reduce_final_body<false>(a, nullptr, part);
+}
+__global__ void __launch_bounds__(256) k_reduce_final_ss(FinalArgs a, const float* galpha) {
+    __shared__ float part[4][64];
+    reduce_final_body<true>(a, galpha, part);
 }
 
 // Mean over the global meta-batch + Adam.  red holds SUMS over all tasks (after the all-reduce).
@@ -161,7 +196,9 @@ PROMP_DEV void publish_stats(const AdamArgs& a) {
     release_store_system(a.host_seq, a.seq);
 }
 
-__global__ void __launch_bounds__(256) k_mean_adam(AdamArgs a) {
+// SS (k_mean_adam_ss, grid = ceil((2 NP + 1) / 256)): the step sizes' Adam step from red[NP + K + 2 + j] behind theta's
+template <bool SS>
+PROMP_DEV void mean_adam_body(const AdamArgs& a, const StepSizeArgs& ss) {
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j < a.NP) {
         const float g = a.red[j] * a.inv_tasks;
@@ -183,8 +220,14 @@ __global__ void __launch_bounds__(256) k_mean_adam(AdamArgs a) {
         a.stats[0] = a.red[a.NP] * a.inv_tasks + pen / (float)a.K;
         a.stats[1 + a.K] = a.red[a.NP + 1 + a.K] * a.inv_tasks;
         publish_stats(a);
+    } else if (SS && j <= 2 * a.NP) {
+        const int ja = j - a.NP - 1;
+        step_size_adam(ss.alpha, ss.alpha_m, ss.alpha_v, ss.alpha_grad_mean, ja, a.red[a.NP + a.K + 2 + ja] * a.inv_tasks,
+                       a.do_update && ja < a.n_trainable, ja < a.n_trainable, a.lr_t);
     }
 }
+__global__ void __launch_bounds__(256) k_mean_adam(AdamArgs a) { mean_adam_body<false>(a, StepSizeArgs{}); }
+__global__ void __launch_bounds__(256) k_mean_adam_ss(AdamArgs a, StepSizeArgs ss) { mean_adam_body<true>(a, ss); }
 
 // Fixed-order exchange: the ranks' vectors side by side ([nranks][n], ncclAllGather) added in rank order -- the same additions in
 // the same order on every rank.
@@ -199,28 +242,16 @@ __global__ void __launch_bounds__(256) k_sum_ranks(const float* gathered, float*
 // k_reduce_final + k_mean_adam in one launch, for the single-rank case (no all-reduce in between).  Column sums in the
 // same order as k_reduce_final (bitwise the same red[]); the thread that finishes a parameter column applies its Adam
 // update; one extra workgroup re-sums the K + 2 scalar columns and writes the statistics.
-// grid = ceil((NP + K + 2) / 64) + 1, block = 256
-__global__ void __launch_bounds__(256) k_final_adam(FinalArgs a, AdamArgs ad) {
-    __shared__ float part[4][64];
-    __shared__ float sums[64];
+// grid = ceil((NP + K + 2) / 64) + 1 -- k_final_adam_ss: ceil((2 NP + K + 2) / 64) + 1 --, block = 256
+template <bool SS>
+PROMP_DEV void final_adam_body(const FinalArgs& a, const AdamArgs& ad, const StepSizeArgs& ss, float (*part)[64], float* sums) {
     const int c = threadIdx.x & 63, q = threadIdx.x >> 6;
     const bool stats_block = blockIdx.x == gridDim.x - 1;
     const int j = stats_block ? a.NP + c : blockIdx.x * 64 + c;
+    const int jend = a.NP + a.K + 2 + (SS && !stats_block ? a.NP : 0);
     float s = 0.f;
     if (j < a.NP) {
-        if (a.want_grad) {
-            // (up to 12 tasks of the quarter requested together, clamped + masked like k_reduce_task; order i = q, q + 4, ...)
-            for (int ib = q; ib < a.n_tasks; ib += 48) {
-                float x[12];
-#pragma unroll
-                for (int u = 0; u < 12; ++u) {
-                    const int i = ib + 4 * u;
-                    x[u] = a.lam[(long long)(i < a.n_tasks ? i : q) * a.NP + j] * (i < a.n_tasks ? 1.f : 0.f);
-                }
-#pragma unroll
-                for (int u = 0; u < 12; ++u) s += x[u];
-            }
-        }
+        if (a.want_grad) s = final_quarter_sum(a.lam, a.NP, a.n_tasks, j, q);
     } else if (j == a.NP) {
         for (int i = q; i < a.n_tasks; i += 4) s += a.scal_outer[i * 2 + 0];
     } else if (j <= a.NP + a.K) {
@@ -228,10 +259,12 @@ __global__ void __launch_bounds__(256) k_final_adam(FinalArgs a, AdamArgs ad) {
         for (int i = q; i < a.n_tasks; i += 4) s += a.scal_inner[((long long)k * a.n_tasks + i) * 2 + 1];
     } else if (j == a.NP + a.K + 1) {
         for (int i = q; i < a.n_tasks; i += 4) s += a.scal_outer[i * 2 + 1];
+    } else if (SS && j < jend) {
+        s = final_quarter_sum(ss.galpha, a.NP, a.n_tasks, j - (a.NP + a.K + 2), q);
     }
     part[q][c] = s;
     __syncthreads();
-    if (q == 0 && j < a.NP + a.K + 2) {
+    if (q == 0 && j < jend) {
         const float t = (part[0][c] + part[1][c]) + (part[2][c] + part[3][c]);
         if (!stats_block) a.red[j] = t;
         sums[c] = t;
@@ -245,6 +278,10 @@ __global__ void __launch_bounds__(256) k_final_adam(FinalArgs a, AdamArgs ad) {
                 ad.v[j] = v;
                 ad.theta[j] -= ad.lr_t * m / (sqrtf(v) + 1e-8f);
             }
+        } else if (SS && !stats_block && j >= a.NP + a.K + 2) {
+            const int ja = j - (a.NP + a.K + 2);
+            step_size_adam(ss.alpha, ss.alpha_m, ss.alpha_v, ss.alpha_grad_mean, ja, t * ad.inv_tasks,
+                           ad.do_update && ja < ad.n_trainable, ja < ad.n_trainable, ad.lr_t);
         }
     }
     if (!stats_block) return;
@@ -260,6 +297,16 @@ __global__ void __launch_bounds__(256) k_final_adam(FinalArgs a, AdamArgs ad) {
         ad.stats[1 + a.K] = sums[1 + a.K] * ad.inv_tasks;
         publish_stats(ad);
     }
+}
+__global__ void __launch_bounds__(256) k_final_adam(FinalArgs a, AdamArgs ad) {
+    __shared__ float part[4][64];
+    __shared__ float sums[64];
+    final_adam_body<false>(a, ad, StepSizeArgs{}, part, sums);
+}
+__global__ void __launch_bounds__(256) k_final_adam_ss(FinalArgs a, AdamArgs ad, StepSizeArgs ss) {
+    __shared__ float part[4][64];
+    __shared__ float sums[64];
+    final_adam_body<true>(a, ad, ss, part, sums);
 }
 
 // dst[i][:] = src[:] for i < n_tasks   (MetaPolicy.switch_to_pre_update)

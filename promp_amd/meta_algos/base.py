@@ -3,6 +3,7 @@ bookkeeping that maps processed samples onto device-resident slabs."""
 import numpy as np
 
 from .. import _lib
+from ..utils import logger
 
 
 class MetaAlgo(object):
@@ -18,6 +19,7 @@ class MAMLAlgo(MetaAlgo):
     trainable_inner_step_size=False
     """
     inner_kind = _lib.INNER_RATIO
+    trains_step_sizes = True      # trainable_inner_step_size is honoured (TRPOMAML: its step is over theta alone)
 
     def __init__(self, policy, inner_lr=0.1, meta_batch_size=20, num_inner_grad_steps=1, trainable_inner_step_size=False):
         super(MAMLAlgo, self).__init__(policy)
@@ -27,13 +29,28 @@ class MAMLAlgo(MetaAlgo):
         self.inner_lr = float(inner_lr)
         self.meta_batch_size = meta_batch_size
         self.num_inner_grad_steps = num_inner_grad_steps
-        self.trainable_inner_step_size = trainable_inner_step_size   # never trained in the reference either (base.py:109,203)
+        # The reference creates the step-size variables with trainable=... (base.py:303-313) and then leaves them out of its
+        # optimiser's var_list (base.py:203, maml_first_order_optimizer.py:64): there the flag changes nothing.  Here True trains
+        # them: the outer Adam steps update one step size per parameter together with theta (Meta-SGD).
+        self.trainable_inner_step_size = bool(trainable_inner_step_size)
         self.session = policy.session
         self.session.set_num_inner_steps(num_inner_grad_steps)
         # per-parameter step-size tensors initialised to inner_lr (base.py:303-313)
-        self.step_sizes = np.full(self.session.theta.size, self.inner_lr, dtype=np.float32)
-        self.session.set_step_sizes(self.step_sizes)
+        self.session.set_step_sizes(np.full(self.session.theta.size, self.inner_lr, dtype=np.float32))
+        self.session.set_train_step_sizes(self.trainable_inner_step_size and self.trains_step_sizes)
         self._adapt_count = 0
+
+    @property
+    def step_sizes(self):
+        """[Theta] inner step sizes: np.full(Theta, inner_lr) unless trainable_inner_step_size moves them"""
+        return self.session.get_step_sizes()
+
+    def _log_step_sizes(self):
+        if self.session.train_step_sizes:
+            s = self.step_sizes
+            logger.logkv('InnerStepSize-Mean', float(np.mean(s)))
+            logger.logkv('InnerStepSize-Min', float(np.min(s)))
+            logger.logkv('InnerStepSize-Max', float(np.max(s)))
 
     def _slot_of(self, samples, default_slot):
         """device slot that holds `samples` (uploading them if they did not come from our sample processor)"""

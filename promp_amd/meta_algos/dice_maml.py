@@ -95,5 +95,6 @@ class DICEMAML(MAMLAlgo):
         if log:
             logger.logkv('LossBefore', loss)
             logger.logkv('LossAfter', loss)
+            self._log_step_sizes()
         self.last_stats = dict(loss_before=loss, loss_after=loss)
         self.session.param_version += 1

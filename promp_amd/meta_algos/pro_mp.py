@@ -56,6 +56,7 @@ class ProMP(MAMLAlgo):
             logger.logkv('LossAfter', loss_after)
             logger.logkv('KLInner', np.mean(inner_kls))
             logger.logkv('KLCoeffInner', np.mean(self.inner_kl_coeff))
+            self._log_step_sizes()
         self.last_stats = res
 
     def adapt_kl_coeff(self, kl_coeff, kl_values, kl_target):

@@ -119,7 +119,11 @@ class TRPOMAML(MAMLAlgo):
     Args (trpo_maml.py:23-31): policy, name, step_size (trust region), inner_type in {'log_likelihood',
     'likelihood_ratio'}, exploration (E-MAML), inner_lr, meta_batch_size, num_inner_grad_steps,
     trainable_inner_step_size; plus hvp_approach in {'finite_difference' (the reference's, default), 'exact'}
+
+    trainable_inner_step_size is accepted and, as in the reference, changes nothing here: the conjugate-gradient step is over
+    theta, the step sizes stay np.full(Theta, inner_lr) and are constants of the objective, its gradient and the constraint.
     """
+    trains_step_sizes = False
 
     def __init__(self, *args, name='trpo_maml', step_size=0.01, inner_type='likelihood_ratio', exploration=False,
                  hvp_approach='finite_difference', **kwargs):

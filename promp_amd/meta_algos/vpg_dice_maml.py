@@ -51,5 +51,6 @@ class VPG_DICEMAML(DICEMAML):
         if log:
             logger.logkv('LossBefore', res['loss_before'])
             logger.logkv('LossAfter', res['loss_after'])
+            self._log_step_sizes()
         self.last_stats = dict(loss_before=res['loss_before'], loss_after=res['loss_after'])
         self.session.param_version += 1

@@ -72,5 +72,6 @@ class VPGMAML(MAMLAlgo):
         if log:
             logger.logkv('LossBefore', loss_before)
             logger.logkv('LossAfter', loss_after)
+            self._log_step_sizes()
         self.last_stats = dict(loss_before=loss_before, loss_after=loss_after)
         self.session.param_version += 1

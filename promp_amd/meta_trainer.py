@@ -90,7 +90,7 @@ class Trainer(object):
 
     def load_snapshot(self, snapshot):
         """Resume from what get_itr_snapshot wrote (a dict, or the path of a params.pkl / itr_<n>.pkl file): policy parameters,
-        Adam moments and step count, inner KL coefficients, baseline coefficients; training continues at the next iteration."""
+        Adam moments and step count, trained inner step sizes with their Adam slots, inner KL coefficients, baseline coefficients; training continues at the next iteration."""
         if isinstance(snapshot, str):
             snapshot = logger.load_params(snapshot)
         self.policy.set_params(snapshot['policy_params'])
@@ -100,6 +100,13 @@ class Trainer(object):
             sess.adam = (snapshot['adam_m'], snapshot['adam_v'], int(snapshot['adam_t']))
             if sess.ctx is not None:
                 sess.ctx.set_adam_state(*sess.adam)
+        if snapshot.get('inner_step_sizes') is not None:       # (absent in snapshots of runs with constant step sizes)
+            if not sess.train_step_sizes:
+                raise ValueError('the snapshot holds trained inner step sizes, but the algorithm was built with '
+                                 'trainable_inner_step_size=False (or is TRPOMAML): it would adapt with step sizes it cannot train')
+            sess.set_step_sizes(snapshot['inner_step_sizes'])
+            if snapshot.get('step_adam_m') is not None:
+                sess.set_step_adam(snapshot['step_adam_m'], snapshot['step_adam_v'])
         if snapshot.get('inner_kl_coeff') is not None and hasattr(self.algo, 'inner_kl_coeff'):
             self.algo.inner_kl_coeff = snapshot['inner_kl_coeff']
         if snapshot.get('baseline') is not None:
@@ -111,8 +118,12 @@ class Trainer(object):
         sess = self.policy.session
         ctx = sess.ctx
         adam_m, adam_v, adam_t = ctx.get_adam_state() if ctx is not None else (sess.adam or (None, None, 0))
-        return dict(itr=itr, policy_params=self.policy.get_param_values(), adam_m=adam_m, adam_v=adam_v, adam_t=adam_t,
+        snap = dict(itr=itr, policy_params=self.policy.get_param_values(), adam_m=adam_m, adam_v=adam_v, adam_t=adam_t,
                     inner_kl_coeff=getattr(self.algo, 'inner_kl_coeff', None), baseline=self.baseline.get_param_values())
+        if sess.train_step_sizes:          # trainable_inner_step_size: the step sizes and their Adam slots are state too
+            step_adam = sess.get_step_adam() or (None, None)
+            snap.update(inner_step_sizes=sess.get_step_sizes(), step_adam_m=step_adam[0], step_adam_v=step_adam[1])
+        return snap
 
     def log_diagnostics(self, paths, prefix):
         for reporter in (self.env, self.policy, self.baseline):

@@ -67,8 +67,12 @@ class MAMLFirstOrderOptimizer(Optimizer):
         return clip_eps, eta
 
     def _key(self, clip_eps, eta):
+        # the context's own counter covers what param_version does not see: set_theta / set_step_sizes, advantages, min_std /
+        # learn_std, trained step sizes (as _DeviceEvaluator._key, meta_algos/trpo_maml.py)
         s = self._algo.session
-        return (s.param_version, tuple(s.upload_serial), clip_eps, eta.tobytes(), self._algo.inner_kind, self._algo.outer_kind)
+        ctx = s.ctx
+        return (s.param_version, tuple(s.upload_serial), clip_eps, eta.tobytes(), self._algo.inner_kind, self._algo.outer_kind,
+                id(ctx), None if ctx is None else ctx.state_version())
 
     def _place(self, input_val_dict):
         if isinstance(input_val_dict, (list, tuple)):          # all_samples_data: sampling step k into slot k

@@ -41,6 +41,8 @@ class DeviceSession:
         self.capacity = (0, 0)
         self.theta = None
         self.step_sizes = None
+        self.train_step_sizes = False  # trainable_inner_step_size: Adam moves the step sizes with theta (slots: step_adam)
+        self.step_adam = None
         self.adam = None
         self.task_thetas = None
         self.step_cursor = 0
@@ -81,7 +83,8 @@ class DeviceSession:
         ctx.reduced_set(red)                                                # every rank now holds the meta-batch's sums
         K, n = self.K, float(self.M_global)
         eta = np.asarray(eta, dtype=np.float64)
-        J, kls, okl = red[-(K + 2)] / n, red[-(K + 1):-1].astype(np.float64) / n, red[-1] / n
+        sc = red[ctx.n_params:ctx.n_params + K + 2]         # (trainable step sizes: their gradient's sums follow the scalars)
+        J, kls, okl = sc[0] / n, sc[1:-1].astype(np.float64) / n, sc[-1] / n
         return dict(loss=float(J + np.mean(eta * kls)), inner_kl=kls.astype(np.float32), outer_kl=float(okl))
 
     def optimize(self, num_epochs, lr, clip_eps, inner_kl_coeff, inner_kind=_lib.INNER_RATIO, outer_kind=_lib.OUTER_CLIP):
@@ -89,6 +92,8 @@ class DeviceSession:
         `collective` -- the same epochs with the [Theta + K + 2] buffer crossing the ranks on the host
         (promp_meta_grad -> promp_reduced_get -> collective -> promp_reduced_set -> promp_adam_step)."""
         ctx = self.ensure()
+        if self.train_step_sizes and int(num_epochs) > 0:
+            self.param_version += 1       # the step sizes move with theta: what the tasks adapt with is no longer what it was
         if not self.external():
             return ctx.optimize(num_epochs, lr, clip_eps, inner_kl_coeff, inner_kind, outer_kind)
         eta = np.asarray(inner_kl_coeff, dtype=np.float32)
@@ -125,6 +130,9 @@ class DeviceSession:
             self.theta = self.ctx.get_theta()
             self.adam = self.ctx.get_adam_state()
             self.task_thetas = self.ctx.get_task_thetas()
+            if self.train_step_sizes:
+                self.step_sizes = self.ctx.get_step_sizes()
+                self.step_adam = self.ctx.get_step_size_adam_state()
 
     def ensure(self, rows=1, paths=1):
         """Context with room for `rows` rows / `paths` paths per sampling step (grown geometrically)."""
@@ -151,6 +159,10 @@ class DeviceSession:
             self.ctx.set_min_std(self.min_std)
             if self.adam is not None:
                 self.ctx.set_adam_state(*self.adam)
+            if self.train_step_sizes:
+                self.ctx.set_train_step_sizes(True)
+                if self.step_adam is not None:
+                    self.ctx.set_step_size_adam_state(*self.step_adam)
             if self.task_thetas is not None:
                 self.ctx.set_task_thetas(self.task_thetas)
             if self.world > 1 and not self._comm_ready and self.collective is None:
@@ -175,6 +187,27 @@ class DeviceSession:
         self.step_sizes = np.ascontiguousarray(s, dtype=np.float32)
         if self.ctx is not None:
             self.ctx.set_step_sizes(self.step_sizes)
+
+    def set_train_step_sizes(self, on=True):
+        self.train_step_sizes = bool(on)
+        if self.ctx is not None:
+            self.ctx.set_train_step_sizes(self.train_step_sizes)
+
+    def get_step_sizes(self):
+        """the step sizes as they are on the device (trained: moved by every Adam step since set_step_sizes)"""
+        if self.ctx is not None and self.train_step_sizes:
+            self.step_sizes = self.ctx.get_step_sizes()
+        return self.step_sizes
+
+    def set_step_adam(self, m, v):
+        self.step_adam = (np.ascontiguousarray(m, dtype=np.float32), np.ascontiguousarray(v, dtype=np.float32))
+        if self.ctx is not None and self.train_step_sizes:
+            self.ctx.set_step_size_adam_state(*self.step_adam)
+
+    def get_step_adam(self):
+        if self.ctx is not None and self.train_step_sizes:
+            self.step_adam = self.ctx.get_step_size_adam_state()
+        return self.step_adam
 
     def next_slot(self):
         slot = self.step_cursor % (self.K + 1)
