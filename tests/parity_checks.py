@@ -6,6 +6,9 @@ Stated tolerances (float32 device arithmetic vs float64 oracle; BASELINE.md sect
   advantages   : rtol 1e-4, atol 1e-5  (after normalisation)
   coefficients : predictions compared, not raw coefficients (normal equations are ill-conditioned);
                  raw coefficients rtol 1e-6 on well-conditioned fixtures
+  float64 results (download_raw, predict_baseline; check_sample_processing_edges):
+                 returns and per-path sums rtol 1e-12; raw advantages and baseline predictions within fit_allowance(), derived
+                 per task from two float64 solves of the reference's ridge system
   loss / KL    : rtol 1e-4
   gradients    : 1e-4 of the max-norm (meta-gradient: 1e-3 in BASELINE.md; we hold 1e-4)
 """
@@ -69,6 +72,127 @@ def check_sample_processing_oracle(lib, seed, M, P, T, O, ragged, kwargs, baseli
     np.testing.assert_allclose(out['returns'], np.concatenate([r['returns'] for r in ref]), rtol=1e-6, atol=1e-6)
     np.testing.assert_allclose(out['advantages'], np.concatenate([r['advantages'] for r in ref]), rtol=1e-4, atol=1e-5)
     return out
+
+
+def feature_columns(O, baseline):
+    """columns of the baseline's feature matrix (linear_baseline.py:101-106, 122-126)"""
+    return {'zero': 0, 'linear_feature': 2 * O + 4, 'linear_time': 4}[baseline]
+
+
+def fit_allowance(plist, baseline, reg_coeff):
+    """What a float64 solve of one task's ridge system may differ by in the baseline predictions, from the reference's side alone:
+    (G + reg I) w = Phi^T R is solved twice in float64 -- numpy.linalg.lstsq as the oracle does, and a Cholesky factorisation of
+    the same matrix -- and the predictions Phi w of the two are compared.  The device eliminates in a third order: ten times that
+    disagreement (one decimal), and never less than 1e-9 of the task's largest |return| (float64 sums of a few hundred terms
+    through the features, the Gram matrix and the scans).  `plist`: the task's paths after the oracle has added 'returns'.
+    -> (allowance, max |returns|); both absolute, in units of the returns."""
+    rets = np.concatenate([p['returns'] for p in plist])
+    rmax = float(np.max(np.abs(rets)))
+    if baseline == 'zero':
+        return 1e-9 * rmax, rmax
+    Phi = np.concatenate([sp._features(p['observations'], KIND[baseline]) for p in plist], axis=0)
+    G, rhs = Phi.T.dot(Phi), Phi.T.dot(rets)
+    eye = np.identity(G.shape[0])
+    w_lstsq = np.linalg.lstsq(G + reg_coeff * eye, rhs, rcond=-1)[0]
+    reg = reg_coeff
+    for _ in range(5):       # a factorisation that meets a non-positive pivot is linear_baseline.py:68-77's NaN: reg *= 10
+        try:
+            L = np.linalg.cholesky(G + reg * eye)
+            break
+        except np.linalg.LinAlgError:
+            reg *= 10
+    w_chol = np.linalg.solve(L.T, np.linalg.solve(L, rhs))
+    disagreement = float(np.max(np.abs(Phi.dot(w_lstsq - w_chol))))
+    return max(10.0 * disagreement, 1e-9 * rmax), rmax
+
+
+def check_sample_processing_edges(lib, seed, O, lengths_per_task, kwargs, baseline='linear_feature', reward_offset=None,
+                                  compare_coeffs=False):
+    """promp_process_samples against oracle.sample_processing.process_samples_meta on a batch with explicit path lengths
+    (helpers.make_paths_with_lengths), in what the kernels compute -- float64 -- and in what they hand on:
+      returns (download_raw), per-path sums      rtol 1e-12
+      raw advantages (download_raw), predictions fit_allowance() of the task: derived from two float64 solves of the reference's
+                                                 system, never from the device's output
+      processed float32 advantages               rtol 1e-4 / atol 1e-5, on tasks with at least as many rows as feature columns.
+          A task with fewer rows is interpolated by the fit: its raw advantages are ~1e-8 and (adv - mean) / (std + 1e-8) turns
+          solver noise into O(1).  At most ONE such task per batch may be left out (asserted); its raw values are judged above.
+          A one-row task is never left out: its mean is its only value, so it comes out as 0 (1e-8 with positive_adv) whatever
+          the fit gave.
+      coefficients (compare_coeffs)              rtol 1e-5 / atol 1e-7 as on the reference's fixtures; the caller asks for it only
+                                                 where every task has four times as many rows as columns (asserted)
+    reward_offset: float64 rewards reward_offset + N(0,1) instead of the synthetic float32 ones.
+    -> dict of the worst errors per quantity, relative to max |returns| of the task, beside the allowance on the same scale."""
+    from promp_amd import synthetic
+    rng = np.random.RandomState(seed)
+    theta = synthetic.init_theta(rng, O, (8, 8), 2)
+    paths = helpers.make_paths_with_lengths(rng, theta, lengths_per_task, O, 2, (8, 8))
+    if reward_offset is not None:
+        for plist in paths.values():
+            for p in plist:
+                p['rewards'] = reward_offset + rng.randn(len(p['rewards']))          # float64
+    reg = kwargs.get('reg_coeff', 1e-5)
+    fl = _lib.flatten_paths(paths)
+    assert [int(n) for n in np.diff(fl['path_row_offsets'])] == [int(n) for lens in lengths_per_task for n in lens]
+    M = len(paths)
+    ctx = _lib.Context(M, O, 2, (32, 32), 1, max_rows=len(fl['rew']), max_paths=len(fl['path_row_offsets']) - 1, lib=lib)
+    try:
+        ctx.upload_step(0, fl['task_path_offsets'], fl['path_row_offsets'], fl['obs'], fl['rew'])
+        ctx.process_samples(0, baseline_kind=KIND[baseline], **kwargs)
+        out = ctx.download_processed(0)
+        ret64, adv64 = (np.array(x) for x in ctx.download_raw(0))
+        bl64 = ctx.predict_baseline(0, KIND[baseline])       # (last: it takes the step's returns buffer as scratch)
+    finally:
+        ctx.close()
+
+    ref, coeffs, _ = sp.process_samples_meta(paths, baseline_kind=KIND[baseline], **kwargs)
+    np.testing.assert_allclose(ret64, np.concatenate([r['returns'] for r in ref]), rtol=1e-12)
+    flat = [p for plist in paths.values() for p in plist]
+    np.testing.assert_allclose(out['path_returns0'], [p['returns'][0] for p in flat], rtol=1e-12)
+    np.testing.assert_allclose(out['path_undiscounted'], [np.sum(np.asarray(p['rewards'], np.float64)) for p in flat], rtol=1e-12)
+    np.testing.assert_allclose(out['path_reward_sumsq'], [np.sum(np.asarray(p['rewards'], np.float64) ** 2) for p in flat], rtol=1e-12)
+    np.testing.assert_allclose(out['returns'], ret64, rtol=1e-6, atol=1e-6)
+
+    cols = feature_columns(O, baseline)
+    worst = dict(allowance=0.0, adv_raw=0.0, baseline=0.0, adv_over_allowance=0.0, baseline_over_allowance=0.0, adv_processed=0.0,
+                 left_out=0)
+    tro = np.concatenate([[0], np.cumsum([sum(lens) for lens in lengths_per_task])]).astype(int)
+    failures = []
+    for i, plist in enumerate(paths.values()):
+        a, b = tro[i], tro[i + 1]
+        allow, rmax = fit_allowance(plist, baseline, reg)
+        adv_ref = np.concatenate([p['advantages'] for p in plist])            # raw: compute_samples_data normalises a copy
+        bl_ref = (np.zeros(b - a) if baseline == 'zero' else
+                  np.concatenate([sp.predict_linear_baseline(p['observations'], coeffs[i], KIND[baseline]) for p in plist]))
+        e_adv, e_bl = float(np.max(np.abs(adv64[a:b] - adv_ref))), float(np.max(np.abs(bl64[a:b] - bl_ref)))
+        worst['allowance'] = max(worst['allowance'], allow / rmax)
+        worst['adv_raw'] = max(worst['adv_raw'], e_adv / rmax)
+        worst['baseline'] = max(worst['baseline'], e_bl / rmax)
+        worst['adv_over_allowance'] = max(worst['adv_over_allowance'], e_adv / allow)
+        worst['baseline_over_allowance'] = max(worst['baseline_over_allowance'], e_bl / allow)
+        if not (e_adv <= allow and e_bl <= allow):
+            failures.append('task %d (%d rows, %d columns): raw advantages off by %.3e, predictions by %.3e, allowance %.3e '
+                            '(max |returns| %.3e)' % (i, b - a, cols, e_adv, e_bl, allow, rmax))
+        if kwargs.get('normalize_adv') and 1 < (b - a) < cols:         # (without normalisation nothing amplifies the fit's noise)
+            worst['left_out'] += 1
+            continue
+        got, want = out['advantages'][a:b], ref[i]['advantages']
+        worst['adv_processed'] = max(worst['adv_processed'], float(np.max(np.abs(got - want) / (1e-5 + 1e-4 * np.abs(want)))))
+        np.testing.assert_allclose(got, want, rtol=1e-4, atol=1e-5, err_msg='processed advantages of task %d' % i)
+        if b - a == 1 and kwargs.get('normalize_adv'):           # n = 1: (adv - adv) / (0 + 1e-8), then - min + 1e-8
+            assert got[0] == np.float32(1e-8 if kwargs.get('positive_adv') else 0.0) == np.float32(want[0]), (got[0], want[0])
+        if compare_coeffs and baseline != 'zero':
+            assert (b - a) >= 4 * cols, (b - a, cols)
+            np.testing.assert_allclose(out['coeffs'][i], coeffs[i], rtol=1e-5, atol=1e-7, err_msg='coefficients of task %d' % i)
+    print('sample_edges O=%d %s lengths=%s %s: allowance %.2e  raw advantages %.2e  predictions %.2e  (of max |returns|; '
+          'worst error / allowance %.3f)  processed advantages %.3f of tolerance  left out %d'
+          % (O, baseline, 'x'.join(str(len(l)) for l in lengths_per_task) + ':' + str(int(tro[-1])) + 'rows',
+             ','.join('%s=%g' % kv for kv in sorted(kwargs.items())) + ('' if reward_offset is None else ',rewards=%g+N(0,1)' % reward_offset)
+             + ''.join(' %s=%s' % (k, os.environ[k]) for k in ('PROMP_GRAM_UNTILED', 'PROMP_FIT_ONE_LAUNCH') if os.environ.get(k)),
+             worst['allowance'], worst['adv_raw'], worst['baseline'],
+             max(worst['adv_over_allowance'], worst['baseline_over_allowance']), worst['adv_processed'], worst['left_out']))
+    assert worst['left_out'] <= 1, 'more than one task with fewer rows than columns'
+    assert not failures, '\n'.join(failures)
+    return worst
 
 
 def check_layout_reuse(lib, seed, M=3, P=3, T=40, O=5, order=('X', 'X2', 'Y', 'X', 'Y', 'Y', 'X2')):
@@ -1168,9 +1292,16 @@ def upload_dice_slabs(ctx, all_slabs):
 def check_dice(lib, name, tol=1e-4):
     """DICE-MAML on the device (PROMP_INNER_DICE / PROMP_OUTER_LOGLIK) against the oracle and, through the committed fixture,
     against torch.autograd on the reference's forward graph: gradient weights, inner step, exact meta-gradient."""
-    from oracle import dice
     g = np.load(os.path.join(helpers.GOLDEN, 'dice_autograd_%s.npz' % name))
     c, t64, all_slabs = helpers.dice_case_from_golden(g)
+    return check_dice_case(lib, c, t64, all_slabs, tol, golden_grad=g['grad'])
+
+
+def check_dice_case(lib, c, t64, all_slabs, tol=1e-4, golden_grad=None):
+    """check_dice's comparison on a case in hand: c (M, K, O, A, hidden, alpha), theta float64, slabs of steps 0..K in
+    oracle/dice.py:to_slab form.  golden_grad: torch.autograd's gradient where a fixture holds one.
+    -> the meta-gradient's error against the oracle (of its max-norm)."""
+    from oracle import dice
     spec = op.PolicySpec(c['O'], c['A'], c['hidden'])
     M, K = c['M'], c['K']
     R = max(sum(len(sl['dice_rw']) for sl in step) for step in all_slabs)
@@ -1189,12 +1320,50 @@ def check_dice(lib, name, tol=1e-4):
     # exact meta-gradient through the adaptation, incl. the path-coupled second-order term
     grad, _ = ctx.meta_grad(0.0, np.zeros(K, np.float32), _lib.INNER_DICE, _lib.OUTER_LOGLIK)
     r = dice.meta_objective_and_grad(spec, t64, all_slabs, alpha.astype(np.float64))
-    assert rel_max(grad, r['grad']) < tol
-    assert rel_max(grad, g['grad']) < tol                      # torch.autograd on the padded magic-box graph
+    err = rel_max(grad, r['grad'])
+    assert err < tol, err
+    if golden_grad is not None:
+        assert rel_max(grad, golden_grad) < tol                # torch.autograd on the padded magic-box graph
     # without the coupling term the gradient is measurably different (the check above is not vacuous)
     grad_ll, _ = ctx.meta_grad(0.0, np.zeros(K, np.float32), _lib.INNER_LOGLIK, _lib.OUTER_LOGLIK)
     assert rel_max(grad_ll, r['grad']) > 10 * tol
     ctx.close()
+    return err
+
+
+def check_dice_path_lengths(lib, seed, lengths_per_task, O=5, A=3, hidden=(32, 32), K=1, alpha=0.1, tol=1e-4):
+    """DICE-MAML's inner step and meta-gradient on paths of the given lengths (k_dice_scan's 64-row chunks: lengths on both sides
+    of one and two chunks), against the float64 oracle (oracle/dice.py) alone.  The inputs follow oracle/gen_golden.py's
+    make_dice_inputs: seeded paths per step, N(0,1) adjusted rewards, padded to the longest path."""
+    from oracle import dice
+    from promp_amd import synthetic
+    rng = np.random.RandomState(seed)
+    theta = synthetic.init_theta(rng, O, hidden, A)
+    theta = (theta + 0.05 * rng.randn(theta.size)).astype(np.float32)
+    Tmax = max(n for lens in lengths_per_task for n in lens)
+    all_slabs = []
+    for k in range(K + 1):
+        paths = helpers.make_paths_with_lengths(rng, theta, lengths_per_task, O, A, hidden)
+        step = []
+        for plist in paths.values():
+            def pad(a):
+                a = np.asarray(a)
+                return np.pad(a, ((0, Tmax - a.shape[0]),) + ((0, 0),) * (a.ndim - 1), mode='constant')
+            sd = dict(mask=np.stack([pad(np.ones(len(p['rewards']))) for p in plist]),
+                      observations=np.stack([pad(p['observations']) for p in plist]),
+                      actions=np.stack([pad(p['actions']) for p in plist]),
+                      adjusted_rewards=rng.randn(len(plist), Tmax),
+                      agent_infos=dict(mean=np.stack([pad(p['agent_infos']['mean']) for p in plist]),
+                                       log_std=np.stack([pad(p['agent_infos']['log_std']) for p in plist])))
+            step.append(dice.to_slab(sd))
+        all_slabs.append(step)
+    for step in all_slabs:
+        assert [list(np.diff(sl['path_row_offsets'])) for sl in step] == [list(lens) for lens in lengths_per_task]
+    c = dict(M=len(lengths_per_task), K=K, O=O, A=A, hidden=tuple(hidden), alpha=alpha)
+    err = check_dice_case(lib, c, theta.astype(np.float64), all_slabs, tol)
+    print('sample_edges dice O=%d hidden=%s K=%d lengths=%s: meta-gradient %.2e of its max-norm against the oracle (tolerance %.0e)'
+          % (O, 'x'.join(map(str, hidden)), K, lengths_per_task, err, tol))
+    return err
 
 
 def check_vpg_dice(lib, name, tol=1e-4):

@@ -179,7 +179,40 @@ def test_loss_grad_clipped_log_std_values_at_benign_min_std(lib):
 
 
 def test_fit_retries_with_larger_reg_on_rank_deficient_features(lib):
-    pc.check_fit_retry_on_rank_deficient_features(lib, 21)
+    pc.check_fit_retry_on_rank_deficient_features(lib, 21)          # obs_dim 4: k_fit_wave<45>
+
+
+@pytest.mark.parametrize('O', [pytest.param(21, id='obs21-k_fit_wave<48>'), pytest.param(29, id='obs29-k_fit_wave<64>'),
+                               pytest.param(30, id='obs30-k_fit')])
+def test_fit_retries_in_every_small_fit_kernel(lib, O):
+    # the NaN -> reg *= 10 loop of the other two wave-per-task instantiations and of the workgroup-per-task kernel
+    pc.check_fit_retry_on_rank_deficient_features(lib, 21 + O, M=2, P=2, T=40, O=O)
+
+
+# ---- sample processing at the scans' chunk edges and in the fit / Gram kernels between obs_dim 21 and 32 (the GPU tests of the
+#      same names in test_gpu_parity.py hold the full list of widths and lengths, and the table obs_dim -> kernels)
+@pytest.mark.parametrize('O', [pytest.param(21, id='obs21-k_gram<3>-k_fit_wave<48>'), pytest.param(29, id='obs29-k_gram<4>-k_fit_wave<64>'),
+                               pytest.param(30, id='obs30-k_gram<5>-k_fit')])
+def test_sample_processing_edges_fit_and_gram_families(lib, two_cus, O):
+    # paths of 65, 1, 64 and 2 rows: one chunk + one row, a single row, exactly one chunk, two rows; 66 rows per task against
+    # 46 / 62 / 64 feature columns
+    pc.check_sample_processing_edges(lib, 400 + O, O, [[65, 1], [64, 2]], dict(discount=0.99, gae_lambda=0.97, normalize_adv=True))
+
+
+@pytest.mark.parametrize('discount,gae_lambda', [(1.0, 0.0), (0.0, 1.0)])
+def test_sample_processing_edges_scan_weights_zero_and_one(lib, two_cus, discount, gae_lambda):
+    # scan weights exactly 0 / exactly 1 (the range check admits them); a task of the eight lengths around the 64-row chunks and
+    # a task that is one one-row path (normalisation with n = 1: 0, and 1e-8 with positive_adv)
+    lengths = [[1, 2, 63, 64, 65, 127, 128, 129], [1]]
+    for baseline in ('linear_feature', 'zero'):
+        for norm, pos in ((True, False), (True, True)):
+            pc.check_sample_processing_edges(lib, 431, 5, lengths, dict(discount=discount, gae_lambda=gae_lambda, normalize_adv=norm,
+                                                                        positive_adv=pos), baseline=baseline)
+
+
+def test_dice_maml_gradient_at_the_scan_chunk_edges(lib, two_cus):
+    # k_dice_scan: paths of 1, 64, 65, 129 and of 2, 63, 128 rows (oracle only: no autograd fixture)
+    pc.check_dice_path_lengths(lib, 441, [[1, 64, 65, 129], [2, 63, 128]])
 
 
 def test_hvp_h64(lib):

@@ -3,7 +3,33 @@
   * torch.autograd goldens of the TF graph's arithmetic (tests/golden/promp_autograd_*.npz),
   * the float64 oracle on seeded inputs (sizes the oracle finishes in seconds),
   * size-independent properties at BASELINE.json's full config-3 size.
-Tolerances are stated in tests/parity_checks.py."""
+Tolerances are stated in tests/parity_checks.py.
+
+Sample processing picks its Gram and fit kernels from LinearFeatureBaseline's column count (promp_process_samples): D = 2 obs_dim + 4
+features, D + 1 columns with the target, nblk = ceil((D + 1) / 16) blocks of 16.  The test_sample_processing_edges_* tests below run
+every one of them; their ids name the kernels:
+
+  obs_dim   D+1  nblk  Gram kernel                     fit kernel
+  1, 3      7,11   1   k_gram<1>                       k_fit_wave<12>
+  4, 5     13,15   1   k_gram<1>                       k_fit_wave<45>
+  6, 13    17,31   2   k_gram<2>                       k_fit_wave<45>
+  14, 20   33,45   3   k_gram<3>                       k_fit_wave<45>
+  21         47    3   k_gram<3>                       k_fit_wave<48>
+  22, 29   49,63   4   k_gram<4>                       k_fit_wave<64>
+  30, 32   65,69   5   k_gram<5>                       k_fit (a workgroup per task: a row no longer fits a wave's lanes)
+  33         71    5   k_gram_wide, one pair slice     k_fit_wide<32>     (obs_dim > 32: k_gram<NBLK> stages at most 32 observations)
+  93        191   12   k_gram_wide, one pair slice     k_fit_wide<32>
+  94        193   13   k_gram_tiled (GRAMT_MIN_NBLK)   k_fit_wide<32>
+  133       271   17   k_gram_tiled | PROMP_GRAM_UNTILED=1: k_gram_wide, one pair slice (153 pairs <= 160)     k_fit_wide<32>
+  134       273   18   k_gram_tiled | PROMP_GRAM_UNTILED=1: k_gram_wide, two pair slices (171 pairs)           k_fit_wide<32>
+  197       399   25   k_gram_tiled                    k_fit_wide<32>     (D = 398 < FITW_ML_MIN_D)
+  198       401   26   k_gram_tiled                    k_fitw_panel/update/back<32>, k_fit_wide<32> behind them (D = 400)
+  274       553   35   k_gram_tiled                    k_fitw_panel/update/back<32>, k_fit_wide<32>: the last width whose 32-column
+                                                       panel fits LDS: fitw_smem(D, 32) = 8 (36 D + 598) bytes <= 160 KiB <=> D <= 552
+  275       555   35   k_gram_tiled                    k_fitw_panel/update/back<16>, k_fit_wide<16>   (fitw_nb(554) = 16)
+  480       965   61   k_gram_tiled                    k_fitw_panel/update/back<16>, k_fit_wide<16>   (PROMP_LINFEAT_MAX_O)
+  481                  refused: LinearFeatureBaseline's fit is sized for obs_dim <= 480
+"""
 import os
 
 import numpy as np
@@ -175,11 +201,18 @@ def test_loss_grad_clipped_log_std(lib):
 
 
 def test_fit_retries_with_larger_reg_on_rank_deficient_features(lib):
-    pc.check_fit_retry_on_rank_deficient_features(lib, 39)
-    pc.check_fit_retry_on_rank_deficient_features(lib, 40, M=3, P=4, T=120, O=20)       # k_fit_wave<48>
+    pc.check_fit_retry_on_rank_deficient_features(lib, 39)                              # obs_dim 4: k_fit_wave<45>
+    pc.check_fit_retry_on_rank_deficient_features(lib, 40, M=3, P=4, T=120, O=20)       # k_fit_wave<45> (its last width: 45 columns)
     pc.check_fit_retry_on_rank_deficient_features(lib, 41, M=2, P=4, T=100, O=40)       # k_fit_wide
     pc.check_fit_retry_on_rank_deficient_features(lib, 42, M=2, P=4, T=150, O=200)      # one launch per phase, then k_fit_wide<32>(only_bad)
     pc.check_fit_retry_on_rank_deficient_features(lib, 43, M=2, P=4, T=200, O=300)      # ... 16-column panels
+
+
+@pytest.mark.parametrize('O', [pytest.param(21, id='obs21-k_fit_wave<48>'), pytest.param(29, id='obs29-k_fit_wave<64>'),
+                               pytest.param(30, id='obs30-k_fit')])
+def test_fit_retries_in_every_small_fit_kernel(lib, O):
+    # the NaN -> reg *= 10 loop of the other two wave-per-task instantiations and of the workgroup-per-task kernel
+    pc.check_fit_retry_on_rank_deficient_features(lib, 21 + O, M=2, P=3, T=60, O=O)
 
 
 def test_fit_with_one_launch_per_phase_equals_the_single_launch(lib):
@@ -616,3 +649,117 @@ def test_dice_maml_gradient_vs_oracle_and_autograd(lib, name):
 def test_vpg_dice_maml_gradient_vs_oracle_and_autograd(lib, name):
     """VPG_DICEMAML (vpg_dice_maml.py:35-113): DiCE inner steps, log-likelihood x advantage outer objective"""
     pc.check_vpg_dice(lib, name)
+
+
+# ---- sample processing: every Gram / fit kernel, the dispatch boundaries, the scans' chunk edges (table in the module docstring) ----
+EDGE_KW = dict(discount=0.99, gae_lambda=0.97, normalize_adv=True)
+EDGE_LENGTHS = [1, 2, 63, 64, 65, 127, 128, 129]      # k_returns / k_gae / k_dice_scan walk a path from its end in 64-row chunks
+
+
+@pytest.mark.parametrize('O', [
+    pytest.param(1, id='obs1-k_gram<1>-k_fit_wave<12>'), pytest.param(3, id='obs3-k_gram<1>-k_fit_wave<12>'),
+    pytest.param(4, id='obs4-k_gram<1>-k_fit_wave<45>'), pytest.param(5, id='obs5-k_gram<1>-k_fit_wave<45>'),
+    pytest.param(6, id='obs6-k_gram<2>-k_fit_wave<45>'), pytest.param(13, id='obs13-k_gram<2>-k_fit_wave<45>'),
+    pytest.param(14, id='obs14-k_gram<3>-k_fit_wave<45>'), pytest.param(20, id='obs20-k_gram<3>-k_fit_wave<45>'),
+    pytest.param(21, id='obs21-k_gram<3>-k_fit_wave<48>'), pytest.param(22, id='obs22-k_gram<4>-k_fit_wave<64>'),
+    pytest.param(29, id='obs29-k_gram<4>-k_fit_wave<64>'), pytest.param(30, id='obs30-k_gram<5>-k_fit'),
+    pytest.param(32, id='obs32-k_gram<5>-k_fit'), pytest.param(33, id='obs33-k_gram_wide_one_slice-k_fit_wide<32>')])
+def test_sample_processing_edges_fit_and_gram_families(lib, O):
+    """every small Gram and fit kernel at its first and last obs_dim, on paths around the scans' 64-row chunks; tasks of 257,
+    322 and 365 rows (work items with a partial last 64-row tile).  Coefficients too where every task has four times as many
+    rows as columns (2 obs_dim + 4 <= 64)"""
+    lengths = [[64, 65, 1, 127], [128, 129, 63, 2], [200, 64, 64, 37]]
+    pc.check_sample_processing_edges(lib, 500 + O, O, lengths, EDGE_KW, compare_coeffs=4 * (2 * O + 4) <= 257)
+
+
+def _wide_lengths(O):
+    """two tasks; up to obs_dim 198 three paths each with more rows than the 2 obs_dim + 4 columns (the lengths grow with the
+    width: three paths of at most 130 rows stop at 390 rows), each batch with a path of 64 and one of 65 rows; beyond, one task with
+    enough rows and one without (the one the normalised comparison may leave out)"""
+    if O <= 94:
+        return [[40, 64, 127], [65, 130, 41]]              # 231, 236 rows / 190, 192 columns
+    if O <= 134:
+        return [[128, 65, 100], [64, 130, 127]]            # 293, 321 rows / 270, 272 columns
+    if O <= 198:
+        return [[64, 170, 170], [65, 170, 171]]            # 404, 406 rows / 398, 400 columns
+    if O <= 275:
+        return [[128, 129, 64, 127, 110], [65, 40, 130]]   # 558, 235 rows / 552, 554 columns
+    return [[128] * 8, [64, 65, 130]]                      # 1024, 259 rows / 964 columns
+
+
+@pytest.mark.parametrize('O,untiled', [
+    pytest.param(93, False, id='obs93-k_gram_wide_one_slice-k_fit_wide<32>'),
+    pytest.param(94, False, id='obs94-k_gram_tiled-k_fit_wide<32>'),
+    pytest.param(133, False, id='obs133-k_gram_tiled-k_fit_wide<32>'),
+    pytest.param(133, True, id='obs133-untiled-k_gram_wide_one_slice-k_fit_wide<32>'),
+    pytest.param(134, False, id='obs134-k_gram_tiled-k_fit_wide<32>'),
+    pytest.param(134, True, id='obs134-untiled-k_gram_wide_two_slices-k_fit_wide<32>'),
+    pytest.param(197, False, id='obs197-k_gram_tiled-k_fit_wide<32>'),
+    pytest.param(198, False, id='obs198-k_gram_tiled-k_fitw_panel_update_back<32>-k_fit_wide<32>'),
+    pytest.param(274, False, id='obs274-k_gram_tiled-k_fitw_panel_update_back<32>-k_fit_wide<32>'),
+    pytest.param(275, False, id='obs275-k_gram_tiled-k_fitw_panel_update_back<16>-k_fit_wide<16>'),
+    pytest.param(480, False, id='obs480-k_gram_tiled-k_fitw_panel_update_back<16>-k_fit_wide<16>')])
+def test_sample_processing_edges_wide_dispatch_boundaries(lib, monkeypatch, O, untiled):
+    """both sides of k_gram_wide | k_gram_tiled (93 | 94), of one | two pair slices of k_gram_wide (133 | 134 with
+    PROMP_GRAM_UNTILED=1), of k_fit_wide | one launch per phase (197 | 198), of the 32- | 16-column panel (274 | 275: fitw_smem(D, 32)
+    = 8 (36 D + 598) bytes <= 160 KiB holds up to D = 552 = 2 * 274 + 4) and the last accepted width"""
+    # fitw_smem(D, 32) = sizeof(double) * ((D + 1 + 16) * 33 + 3 * (D + 1) + 32 + 2)
+    assert 8 * (36 * (2 * 274 + 4) + 598) <= 160 * 1024 < 8 * (36 * (2 * 275 + 4) + 598)
+    if untiled:
+        monkeypatch.setenv('PROMP_GRAM_UNTILED', '1')
+    pc.check_sample_processing_edges(lib, 600 + O, O, _wide_lengths(O), EDGE_KW)
+
+
+def test_sample_processing_edges_obs481_refused(lib):
+    """one observation past PROMP_LINFEAT_MAX_O: promp_process_samples refuses LinearFeatureBaseline (and says what to do instead)"""
+    rng = np.random.RandomState(5)
+    paths = helpers.make_paths_with_lengths(rng, synthetic.init_theta(rng, 481, (8, 8), 2), [[64, 65], [40]], 481, 2, (8, 8))
+    fl = _lib.flatten_paths(paths)
+    ctx = _lib.Context(2, 481, 2, (32, 32), 1, max_rows=len(fl['rew']), max_paths=3, lib=lib)
+    try:
+        ctx.upload_step(0, fl['task_path_offsets'], fl['path_row_offsets'], fl['obs'], fl['rew'])
+        with pytest.raises(_lib.PrompError, match='LinearFeatureBaseline'):
+            ctx.process_samples(0, baseline_kind=pc.KIND['linear_feature'], **EDGE_KW)
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize('discount,gae_lambda', [(1.0, 1.0), (1.0, 0.0), (0.0, 1.0), (0.0, 0.0), (0.97, 0.9)])
+@pytest.mark.parametrize('O', [pytest.param(5, id='obs5-k_gram<1>-k_fit_wave<45>'), pytest.param(30, id='obs30-k_gram<5>-k_fit')])
+def test_sample_processing_edges_scan_parameters(lib, O, discount, gae_lambda):
+    """scan weights exactly 0 and exactly 1 (the range check admits them) and ordinary ones, every baseline, raw / normalised /
+    shifted: a task of the eight lengths around the chunks and a task that is ONE one-row path -- normalisation with n = 1 gives
+    0, and 1e-8 with positive_adv, as in the oracle; a work item shorter than one 64-row tile"""
+    for baseline in ('linear_feature', 'linear_time', 'zero'):
+        for norm, pos in ((False, False), (True, False), (True, True)):
+            pc.check_sample_processing_edges(lib, 700 + O, O, [EDGE_LENGTHS, [1]],
+                                             dict(discount=discount, gae_lambda=gae_lambda, normalize_adv=norm, positive_adv=pos),
+                                             baseline=baseline)
+
+
+@pytest.mark.parametrize('O,normalize', [pytest.param(20, True, id='obs20-k_gram<3>-k_fit_wave<45>'),
+                                         pytest.param(111, False, id='obs111-k_gram_tiled-k_fit_wide<32>')])
+def test_sample_processing_edges_task_size_mix(lib, O, normalize):
+    """a tiny task, a large one and a middling one in one batch: 1 path x 3 rows, 20 x 200, 2 x 64 (one work item of 3 rows beside
+    tasks of 63 and of two).  At obs_dim 20 the 3-row task has fewer rows than the 44 columns and is the one the normalised
+    comparison leaves out.  At obs_dim 111 (226 columns) the 128-row task has too few as well; only one task may be left out, so
+    that batch runs without normalisation: all three tasks are judged in float64, none in the amplified form."""
+    pc.check_sample_processing_edges(lib, 800 + O, O, [[3], [200] * 20, [64, 64]],
+                                     dict(discount=0.99, gae_lambda=0.97, normalize_adv=normalize))
+
+
+@pytest.mark.parametrize('c', [1e3, 1e5])
+def test_sample_processing_edges_offset_advantages(lib, c):
+    """ZeroBaseline, discount 0, float64 rewards c + N(0,1): the advantages ARE the rewards, and k_normalize forms their variance
+    in one pass as s2 / n - mean^2, which cancels c^2 against a variance of 1.  Both forms evaluated in float64 NumPy on
+    c + N(0,1), 580 values, 20 draws: the one-pass form is at 2e-6 of the advantage tolerance (rtol 1e-4 / atol 1e-5) at c = 1e3,
+    0.015 at 1e5, 0.23 at 3e5, and leaves it at c ~ 1e6 (2.9 x the tolerance, 5 draws of 20; 18 of 20 at 2e6).  The kernel is held
+    to the tolerance at 1e3 and 1e5, two orders below that."""
+    pc.check_sample_processing_edges(lib, 900, 5, [EDGE_LENGTHS, [200, 37]], dict(discount=0.0, gae_lambda=1.0, normalize_adv=True),
+                                     baseline='zero', reward_offset=c)
+
+
+def test_dice_maml_gradient_at_the_scan_chunk_edges(lib):
+    """k_dice_scan's suffix and prefix sums on paths of 1, 64, 65, 129 and of 2, 63, 128 rows: DICE-MAML's inner step and exact
+    meta-gradient against the float64 oracle (obs_dim 5, hidden (32, 32), K = 1)"""
+    pc.check_dice_path_lengths(lib, 441, [[1, 64, 65, 129], [2, 63, 128]], O=5, A=3, hidden=(32, 32), K=1)
