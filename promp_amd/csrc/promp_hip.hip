@@ -1,6 +1,7 @@
 // promp_hip.hip -- host side of libpromp_hip.so: context, device memory, launch sequences, C ABI.
 // See include/promp_hip.h for the contract.  gfx950 only; built by __graft_entry__.build():
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC promp_hip.hip -lrccl -o libpromp_hip.so
+#include "promp_plan.h"
 #include "promp_kernels_chain.h"
 #include "promp_kernels_pass.h"
 #include "promp_kernels_policy.h"
@@ -37,6 +38,9 @@ int fail(int code, const char* fmt, ...) {
     g_err = buf;
     return code;
 }
+
+// a plan function (promp_plan.h) refused: its code, its message
+int fail_plan(int code, const std::string& why) { return fail(code, "%s", why.c_str()); }
 
 #define HIPCHECK(expr)                                                                            \
     do {                                                                                          \
@@ -143,28 +147,12 @@ struct StepData {
     std::vector<int> lay_tpo, lay_pro; // the offsets the set's device-side tables were built from (set_step_layout)
 };
 
-// waves per workgroup of k_pass / k_chain_hvp (one per SIMD: 512 registers per lane)
-constexpr int CHAIN_NW_HVP = 4;
-// layer-1 k-steps k_chain_hvp is instantiated for (4 observation entries per step, zero-padded)
-int chain_ksteps(int obs_dim) { return obs_dim <= 8 ? 2 : obs_dim <= 20 ? 5 : 8; }
 // k_pass instances: (hidden_0 / 16, hidden_1 / 16)
 #define PROMP_PASS_ALL(X) X(2, 2) X(2, 4) X(4, 2) X(4, 4)
 #define PROMP_WB_ALL(X) X(1, 4, 2) X(2, 7, 4) X(3, 8, 4)
 #define PROMP_CHAIN_ALL(X) X(2, 2, 2) X(2, 2, 5) X(2, 2, 8) X(2, 4, 2) X(2, 4, 5) X(2, 4, 8) X(4, 2, 2) X(4, 2, 5) X(4, 2, 8) X(4, 4, 2) X(4, 4, 5) X(4, 4, 8)
 // k_wide_* instances: (hidden width, observation blocks of 16)
 #define PROMP_WIDE_ALL(X) X(128, 2) X(128, 4) X(128, 8) X(64, 2) X(64, 4) X(64, 8)
-// k_gram<NBLK> instances (feature blocks of 16) and k_fit_wave<DT> instances (ascending: the first with D + 1 <= DT runs)
-#define PROMP_GRAM_ALL(X) X(1) X(2) X(3) X(4) X(5)
-#define PROMP_FITWV_ALL(X) X(12) X(45) X(48) X(64)
-int wide_nob(int obs_dim) { return obs_dim <= 32 ? 2 : obs_dim <= 64 ? 4 : 8; }
-
-// which kernels run the policy passes of a context (promp_ctx_create chooses once, from the padded dims)
-enum class PassFamily {
-    Chain,       // register-chained k_pass / k_chain_hvp (promp_kernels_chain.h, promp_kernels_pass.h): widths from {32, 64}, obs_dim <= 32
-    CoopFp32,    // cooperative exact-FP32 k_wide_* (promp_kernels_policy_wide.h): (64,64) with obs_dim > 32, (128,128) outside CoopSplit
-    CoopSplit,   // cooperative k_wb_* on the BF16 matrix pipe (promp_kernels_wide_bf16.h): (128,128) with obs_dim <= 127
-    Layered,     // layer-by-layer k_gen_* / k_gb_* (promp_kernels_generic*.h): every shape policy_shape_generic() names
-};
 
 // One policy pass (launch_pass): the defaults are a first-order pass with the plain per-task reduction
 struct PassReq {
@@ -227,8 +215,9 @@ struct promp_ctx {
     DevBuf<float> stage_rows;            // promp_begin_collection: staging rows [steps][tasks * B] of observations | actions | means
     DevBuf<double> fit_scratch;          // k_fit_wide: [tasks][2][(D+1)^2] when the matrices do not fit in LDS
     size_t smem_fwd = 0, smem_hvp = 0;
+    PlanSwitches sw;                     // the PROMP_* switches, as promp_ctx_create found them
     PassFamily family = PassFamily::Chain;
-    int wb_cls = 0;                      // CoopSplit: the observation class 1..3 = (NKO, NXB) = (4,2) (7,4) (8,4): obs_dim <= 63 / 111 / 127
+    int wb_cls = 0;                      // CoopSplit: the observation class 1..3 (pass_family)
     size_t smem_wb_fwd = 0, smem_wb_bwd = 0, smem_wb_hvp = 0;
     DevBuf<unsigned> wb_planes, wb_vplanes;                 // [tasks][wb_planes_words]: k_wb_planes' output for theta / the direction
     // The planes of the META-parameters (theta itself, stride 0) have their own block: an epoch passes over step 0 at theta twice --
@@ -241,11 +230,8 @@ struct promp_ctx {
     DevBuf<unsigned> vdir_absmax;        // [tasks]: k_vec_absmax's output for the direction (FP16 split)
     // layer-by-layer kernels (promp_kernels_generic.h) for every other shape: layer table, and one set of activation / tangent /
     // cotangent buffers for the whole context (the passes of a context run one after another on its stream)
-    bool gramt_single = false;           // PROMP_GRAMT_SINGLE=1: k_gram_tiled with one feature tile (A/B runs against the double-buffered rounds)
-    bool gram_untiled = false;           // PROMP_GRAM_UNTILED=1: k_gram_wide at every width (A/B runs against k_gram_tiled)
     int gramt_map_nblk = -1;             // the block count c->gramt_map was balanced for
     GramtMap gramt_map;                  // one-slice k_gram_tiled launches: wave -> rectangle
-    bool fit_one_launch = false;         // PROMP_FIT_ONE_LAUNCH=1: k_fit_wide alone at every width (A/B runs against the per-phase launches)
     bool gen_bf16 = true;                // Layered: the GEMMs on the BF16 matrix pipe (promp_kernels_generic_bf16.h); PROMP_GEN_FP32=1: the exact-FP32 kernels (A/B runs)
     DevBuf<unsigned short> gb_wplanes, gb_vplanes;                 // [tasks][gb_plane_stride]: k_gb_planes' output for theta / minus the direction
     long long gb_plane_stride = 0;
@@ -374,67 +360,12 @@ struct StepScope {
     StepData& S() const { return *s; }
 };
 
-// hidden_sizes of a context: promp_dims carries up to four widths (n_hidden == 0: the two-layer struct of ABI 2)
-struct HiddenList {
-    int n;
-    int h[4];
-};
-static HiddenList hidden_list(const promp_dims* d) {
-    HiddenList L;
-    L.n = d->n_hidden > 0 ? d->n_hidden : 2;
-    L.h[0] = d->hidden1; L.h[1] = d->hidden2; L.h[2] = d->hidden3; L.h[3] = d->hidden4;
-    return L;
-}
-// which family of pass kernels serves a network shape (sample processing alone works for any obs_dim <= 128)
-#define PROMP_LINFEAT_MAX_O 480     // LinearFeatureBaseline on the device: 2 obs_dim + 5 <= 965 columns (16 feature rows + their observations in LDS)
 // what the layer-by-layer kernels read as GenArgs.act_kind: the hidden nonlinearity's code in the low byte, the output
 // nonlinearity's (mlp.py:53-60, 114-117; none = identity) above it
 static int gen_act_kinds(const promp_dims* d) {
     const int out = d->hidden_act >> PROMP_OUT_ACT_SHIFT;
     const int ok = out == PROMP_OUT_ACT_TANH ? GEN_ACT_TANH : out == PROMP_OUT_ACT_RELU ? GEN_ACT_RELU : GEN_ACT_IDENTITY;
     return (d->hidden_act & 0xff) | (ok << 8);
-}
-bool policy_shape_generic(const promp_dims* d) {   // layer-by-layer kernels (promp_kernels_generic.h): everything the fused ones do not cover
-    const HiddenList L = hidden_list(d);
-    return L.n != 2 || d->obs_dim > 128 || d->act_dim > 8 || d->hidden1 > 128 || d->hidden2 > 128 || d->hidden_act != PROMP_ACT_TANH;      // (an output nonlinearity sits in the upper bits: != too)
-}
-int wb_nko(int cls) { return cls == 1 ? 4 : cls == 2 ? 7 : 8; }      // K = 16 steps of the observation per class
-
-int check_dims(const promp_dims* d) {
-    if (!d) return fail(-1, "dims is NULL");
-    if (d->n_tasks < 1 || d->n_tasks_global < d->n_tasks) return fail(-1, "bad task counts (%d local, %d global)", d->n_tasks, d->n_tasks_global);
-    if (d->obs_dim < 1 || d->obs_dim > 1024) return fail(-1, "obs_dim %d unsupported (1..1024)", d->obs_dim);
-    if (d->act_dim < 1 || d->act_dim > GEN_MAX_A) return fail(-1, "act_dim %d unsupported (1..%d)", d->act_dim, GEN_MAX_A);
-    const HiddenList L = hidden_list(d);
-    if (d->n_hidden < 0 || L.n > 4) return fail(-1, "hidden_sizes of length %d unsupported (1..4 hidden layers)", L.n);
-    for (int l = 0; l < L.n; ++l)
-        if (L.h[l] < 1 || L.h[l] > GEN_MAX_N)
-            return fail(-1, "hidden size %d (layer %d) unsupported: tanh layers of 1..%d units.  Two layers of up to 128 units run on the fused "
-                        "kernels (narrower ones zero-padded on the instantiated widths: every combination of {32, 64} for obs_dim <= 32, "
-                        "(64,64) / (128,128) otherwise); wider layers and other depths on the layer-by-layer kernels", L.h[l], l, GEN_MAX_N);
-    if ((d->hidden_act & 0xff) > PROMP_ACT_IDENTITY || d->hidden_act < 0)
-        return fail(-1, "hidden_act %d unknown (0 tanh, 1 relu, 2 identity)", d->hidden_act & 0xff);
-    if ((d->hidden_act >> PROMP_OUT_ACT_SHIFT) > PROMP_OUT_ACT_RELU)
-        return fail(-1, "output nonlinearity %d unknown (0 none, 1 tanh, 2 relu)", d->hidden_act >> PROMP_OUT_ACT_SHIFT);
-    if (d->num_inner_steps < 1 || d->num_inner_steps > PROMP_ETA_MAX) return fail(-1, "num_inner_steps must be in [1, %d]", PROMP_ETA_MAX);
-    if (d->max_rows < 1 || d->max_paths < 1) return fail(-1, "max_rows / max_paths must be positive");
-    return 0;
-}
-
-int param_count(const promp_dims* d) {
-    const HiddenList L = hidden_list(d);
-    int n = 0, in = d->obs_dim;
-    for (int l = 0; l < L.n; ++l) {
-        n += in * L.h[l] + L.h[l];
-        in = L.h[l];
-    }
-    return n + in * d->act_dim + d->act_dim + d->act_dim;
-}
-
-int feature_dim(const promp_dims* d, int kind) {
-    if (kind == PROMP_BASELINE_LINEAR_FEATURE) return 2 * d->obs_dim + 4;
-    if (kind == PROMP_BASELINE_LINEAR_TIME) return 4;
-    return 0;
 }
 
 // ---- profiling helpers -------------------------------------------------------------------------
@@ -951,43 +882,6 @@ extern "C" {
 const char* promp_last_error(void) { return g_err.c_str(); }
 int promp_abi_version(void) { return 3; }
 
-// The kernels are instantiated for hidden widths from {32, 64} in any combination (obs_dim <= 32) and for (64,64) / (128,128).
-// Any other pair of widths up to 128 runs EMBEDDED in the next instantiated shape: the extra hidden units have zero incoming and
-// outgoing weights and zero bias, so they output tanh(0) = 0, receive a zero cotangent, and every gradient / Hessian-vector entry
-// that belongs to them is exactly zero -- they stay zero under the inner steps and under Adam.  Parameter vectors cross the C ABI in
-// the caller's (unpadded) layout (policies/networks/mlp.py:5-62 takes any hidden_sizes; policies/base.py:271-277 fixes the order).
-static void pad_dims(const promp_dims* u, promp_dims* p) {
-    *p = *u;
-    if (policy_shape_generic(u)) return;          // the layer-by-layer kernels take any width as it is
-    auto up = [](int h) { return h <= 32 ? 32 : h <= 64 ? 64 : 128; };
-    int a = up(u->hidden1), b = up(u->hidden2);
-    if (u->obs_dim > 32) a = b = std::max(std::max(a, b), 64);
-    else if (a == 128 || b == 128) a = b = 128;
-    p->hidden1 = a;
-    p->hidden2 = b;
-}
-// one parameter vector between the caller's layout (du) and the padded one (dp); to_padded: dst must arrive zeroed
-static void remap_params(const promp_dims& du, const promp_dims& dp, const float* src, float* dst, bool to_padded) {
-    const int O = du.obs_dim, A = du.act_dim, h1 = du.hidden1, h2 = du.hidden2, H1 = dp.hidden1, H2 = dp.hidden2;
-    size_t ou = 0, op = 0;
-    auto rows = [&](int nrows_u, int nrows_p, int cols_u, int cols_p) {
-        for (int r = 0; r < nrows_u; ++r)
-            for (int cc = 0; cc < cols_u; ++cc) {
-                if (to_padded) dst[op + (size_t)r * cols_p + cc] = src[ou + (size_t)r * cols_u + cc];
-                else dst[ou + (size_t)r * cols_u + cc] = src[op + (size_t)r * cols_p + cc];
-            }
-        ou += (size_t)nrows_u * cols_u;
-        op += (size_t)nrows_p * cols_p;
-    };
-    rows(O, O, h1, H1);      // hidden_0/kernel
-    rows(1, 1, h1, H1);      // hidden_0/bias
-    rows(h1, H1, h2, H2);    // hidden_1/kernel
-    rows(1, 1, h2, H2);      // hidden_1/bias
-    rows(h2, H2, A, A);      // output/kernel
-    rows(1, 1, A, A);        // output/bias
-    rows(1, 1, A, A);        // log_std
-}
-
 int promp_param_count(const promp_dims* d) {
     if (!d) return fail(-1, "dims is NULL");
     return param_count(d);
@@ -1000,7 +894,8 @@ int promp_feature_dim(const promp_dims* d, int kind) {
 int promp_ctx_create(promp_ctx** out, int device_id, const promp_dims* user_dims) {
     if (!out) return fail(-1, "out is NULL");
     *out = nullptr;
-    if (check_dims(user_dims)) return -1;
+    std::string why;
+    if (const int rc = check_dims(user_dims, &why)) return fail_plan(rc, why);
     promp_dims padded_dims;
     pad_dims(user_dims, &padded_dims);
     const promp_dims* dims = &padded_dims;        // everything below sees the instantiated shape
@@ -1018,17 +913,12 @@ int promp_ctx_create(promp_ctx** out, int device_id, const promp_dims* user_dims
     c->du = *user_dims;
     c->NPu = param_count(user_dims);
     c->padded = c->NPu != param_count(dims);
-    { const char* e = getenv("PROMP_FIT_ONE_LAUNCH"); c->fit_one_launch = e && e[0] == '1'; }
-    { const char* e = getenv("PROMP_GRAM_UNTILED"); c->gram_untiled = e && e[0] == '1'; }
-    { const char* e = getenv("PROMP_GRAMT_SINGLE"); c->gramt_single = e && e[0] == '1'; }
+    c->sw = plan_switches_from_env();
+    c->gen_bf16 = !c->sw.gen_fp32;
     hipDeviceProp_t prop;
     HIPCHECK(hipGetDeviceProperties(&prop, device_id));
     c->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    {   // tests: work tables for fewer workgroups than the chip has compute units (a wave then walks several tiles of a small batch)
-        const char* e = getenv("PROMP_MAX_CUS");
-        const int cap = e ? atoi(e) : 0;
-        if (cap > 0 && cap < c->n_cus) c->n_cus = cap;
-    }
+    if (c->sw.max_cus > 0 && c->sw.max_cus < c->n_cus) c->n_cus = c->sw.max_cus;
     c->clock_mhz = prop.clockRate / 1000;
     snprintf(c->dev_name, sizeof c->dev_name, "%s", prop.name[0] ? prop.name : PROMP_ARCH_NAME(prop));
     HIPCHECK(hipStreamCreate(&c->stream.h));
@@ -1052,15 +942,12 @@ int promp_ctx_create(promp_ctx** out, int device_id, const promp_dims* user_dims
     c->partial_stride = (c->NP + PROMP_PARTIAL_EXTRA + 3) & ~3;
     const int nblk_max = (c->Dmax + 1 + 15) / 16;
     c->gram_stride = nblk_max * (nblk_max + 1) / 2 * 256;
-    // The pass family, chosen once.  Every shape check_dims accepts falls into exactly one, so launch_pass has a kernel for every
-    // context:
-    //   - policy_shape_generic() (not two layers, obs_dim > 128, act_dim > 8, a width > 128, not tanh): Layered, dims as given;
-    //   - otherwise pad_dims has made the widths (32|64, 32|64) with obs_dim <= 32: Chain; or equal widths of 64 / 128 when
-    //     obs_dim > 32 or a width exceeded 64: the cooperative kernels, CoopSplit for (128,128) with obs_dim <= 127 unless
-    //     PROMP_WIDE_FP32=1 keeps the exact-FP32 CoopFp32 (the A/B switch of the measurements), CoopFp32 for the rest:
-    //     (128,128) with obs_dim 128 and (64,64) with obs_dim > 32.
-    if (policy_shape_generic(dims)) {
-        c->family = PassFamily::Layered;
+    // the pass family, chosen once (pass_family); what follows sizes its launches
+    const FamilyPlan fam = pass_family(dims, c->sw);
+    c->family = fam.family;
+    c->wb_cls = fam.wb_cls;
+    switch (c->family) {
+    case PassFamily::Layered: {
         const HiddenList L = hidden_list(dims);
         int in = dims->obs_dim, off = 0;
         c->n_lin = L.n + 1;
@@ -1072,31 +959,31 @@ int promp_ctx_create(promp_ctx** out, int device_id, const promp_dims* user_dims
             if (out > c->g_maxw) c->g_maxw = out;
             in = out;
         }
-        { const char* e = getenv("PROMP_GEN_FP32"); if (e && e[0] == '1') c->gen_bf16 = false; }
         for (int l = 0; l < c->n_lin; ++l) {
             c->gb_pf_off[l] = (int)c->gb_plane_stride; c->gb_plane_stride += gb_f_elems(c->lin[l].K, c->lin[l].N);
             c->gb_pb_off[l] = (int)c->gb_plane_stride; c->gb_plane_stride += gb_b_elems(c->lin[l].K, c->lin[l].N);
         }
-    } else if (dims->obs_dim > 32 || dims->hidden1 == 128) {
+        break;
+    }
+    case PassFamily::CoopFp32:
+    case PassFamily::CoopSplit: {
         const int nob = wide_nob(dims->obs_dim);
         c->smem_fwd = sizeof(float) * (size_t)make_layout_wide(dims->hidden1, 4, nob, false).total;
         c->smem_hvp = sizeof(float) * (size_t)make_layout_wide(dims->hidden1, 2, nob, true).total;
         // two layers of 128 units: the first-order pass on the BF16 matrix pipe (float32-equivalent 3-way split)
-        const char* fp32_env = getenv("PROMP_WIDE_FP32");
-        c->family = PassFamily::CoopFp32;
-        if (dims->hidden1 == 128 && dims->obs_dim <= 127 && !(fp32_env && atoi(fp32_env) != 0)) {
-            c->family = PassFamily::CoopSplit;
-            c->wb_cls = dims->obs_dim <= 63 ? 1 : dims->obs_dim <= 111 ? 2 : 3;
+        if (c->family == PassFamily::CoopSplit) {
             c->smem_wb_bwd = sizeof(float) * (size_t)wb_layout(false).total;
             c->smem_wb_fwd = c->smem_wb_bwd;
             c->smem_wb_hvp = sizeof(float) * (size_t)wb_layout(true).total;
         }
-    } else {
-        c->family = PassFamily::Chain;
+        break;
+    }
+    case PassFamily::Chain:
         c->smem_fwd = sizeof(float) * (size_t)pass_layout(dims->hidden1 / 16, dims->hidden2 / 16, CHAIN_NW_HVP, c->NP).total;
         // (one size for both instances: the cache-reading one lays LDS out with the backward planes)
         c->smem_hvp = sizeof(float) * (size_t)std::max(chain_layout(dims->hidden1 / 16, dims->hidden2 / 16, CHAIN_NW_HVP, true, c->NP).total,
                                                        chain_layout(dims->hidden1 / 16, dims->hidden2 / 16, CHAIN_NW_HVP, true, c->NP, true).total);
+        break;
     }
     if (c->smem_hvp > 160 * 1024 || c->smem_fwd > 160 * 1024) {
         const size_t need = c->smem_hvp > c->smem_fwd ? c->smem_hvp : c->smem_fwd;
@@ -1190,7 +1077,8 @@ int promp_sync(promp_ctx* c) {
     return 0;
 }
 
-// Offsets, time indices and the three work tables of one sampling step (everything of promp_upload_step but the data).
+// Offsets, time indices and the three work tables of one sampling step (everything of promp_upload_step but the data), built by
+// build_step_tables (promp_plan.h).
 // `S` is the slab set to describe and `st` the stream the table copies go to: the step's current set on the main stream
 // (promp_upload_step; synchronous), or its back set on the copy stream (promp_stage_step; the host-side tables are
 // then kept alive in S.host_tables until the set is staged again).
@@ -1198,153 +1086,25 @@ static int set_step_layout(promp_ctx* c, StepData& S, hipStream_t st, bool async
     if (!tpo || !pro) return fail(-1, "offsets are required");
     const int M = c->d.n_tasks;
     S.obs_range_valid = false;         // (whoever describes a slab anew is about to fill it)
-    if (n_paths < 1 || n_paths > c->d.max_paths) return fail(-1, "n_paths %d outside [1, max_paths=%d]", n_paths, c->d.max_paths);
-    if (tpo[0] != 0 || tpo[M] != n_paths) return fail(-1, "task_path_offsets must start at 0 and end at n_paths");
-    if (pro[0] != 0) return fail(-1, "path_row_offsets must start at 0");
-    const int R = pro[n_paths];
-    if (R < 1 || R > c->d.max_rows) return fail(-1, "rows %d outside [1, max_rows=%d]", R, c->d.max_rows);
     // Same offsets as the batch this set held before (fixed-horizon environments: every batch): the time indices and the
     // work tables on the device are already the right ones -- nothing to rebuild on the host (0.3 ms at 160 000 rows), no
     // table copies to enqueue.  (A set is only ever re-described after its previous table copies have completed.)
-    if ((int)S.lay_tpo.size() == M + 1 && (int)S.lay_pro.size() == n_paths + 1 && S.n_paths == n_paths && S.n_rows == R &&
+    // (A match also means the offsets are well-formed: the set was built from them.)
+    if ((int)S.lay_tpo.size() == M + 1 && (int)S.lay_pro.size() == n_paths + 1 && S.n_paths == n_paths &&
         memcmp(S.lay_tpo.data(), tpo, sizeof(int) * (M + 1)) == 0 && memcmp(S.lay_pro.data(), pro, sizeof(int) * (n_paths + 1)) == 0) {
         S.processed = false; S.has_adv = false; S.has_rew64 = false; S.has_dice = false;
         return 0;
     }
-    S.lay_tpo.clear(); S.lay_pro.clear();         // (rebuilt below; stays empty if anything fails half-way)
-    std::vector<int> path_task(n_paths), row_t(R), tro(M + 1);
-    for (int i = 0; i < M; ++i) {
-        if (tpo[i + 1] <= tpo[i]) return fail(-1, "task %d has no paths", i);
-        tro[i] = pro[tpo[i]];
-        for (int p = tpo[i]; p < tpo[i + 1]; ++p) {
-            if (pro[p + 1] < pro[p]) return fail(-1, "path_row_offsets must be non-decreasing");
-            path_task[p] = i;
-            for (int r = pro[p]; r < pro[p + 1]; ++r) row_t[r] = r - pro[p];
-        }
-        if (pro[tpo[i + 1]] == tro[i]) return fail(-1, "task %d has no rows", i);
-    }
-    tro[M] = R;
-    // work tables: contiguous ranges of 16-row wave tiles, workgroups shared out over tasks in proportion to their tiles
-    std::vector<int> tiles(M);
-    long long total_tiles = 0;
-    const int GR = 16;   // work granule = one wave tile (16 rows)
-    for (int i = 0; i < M; ++i) { tiles[i] = (tro[i + 1] - tro[i] + GR - 1) / GR; total_tiles += tiles[i]; }
-    std::vector<WorkItem> work[2];
-    std::vector<int> two[2];
-    for (int t = 0; t < 2; ++t) {
-        // table 0: the cooperative pass kernels (one workgroup per CU: measured faster than two shorter ones, the parameter
-        // staging and the end-of-kernel reduction amortise over twice the tiles); table 1: the sample-processing kernels
-        int target = (t + 1) * c->n_cus;
-        two[t].assign(M + 1, 0);
-        // largest-remainder split: sum of workgroups <= target (one more would cost a whole second round on the chip),
-        // every task gets at least one and at most one per tile
-        std::vector<long long> nw(M), rem(M);
-        long long used = 0;
-        for (int i = 0; i < M; ++i) {
-            const long long num = tiles[i] * (long long)target;
-            nw[i] = num / total_tiles;
-            rem[i] = num % total_tiles;
-            if (nw[i] < 1) { nw[i] = 1; rem[i] = 0; }
-            if (nw[i] > tiles[i]) { nw[i] = tiles[i]; rem[i] = 0; }
-            used += nw[i];
-        }
-        while (used < target) {
-            int best = -1;
-            for (int i = 0; i < M; ++i)
-                if (nw[i] < tiles[i] && rem[i] > 0 && (best < 0 || rem[i] > rem[best])) best = i;
-            if (best < 0) break;
-            nw[best] += 1;
-            rem[best] = 0;
-            used += 1;
-        }
-        for (int i = 0; i < M; ++i) {
-            const long long w = nw[i];
-            for (int g = 0; g < (int)w; ++g) {
-                const int t0 = (int)((long long)tiles[i] * g / w), t1 = (int)((long long)tiles[i] * (g + 1) / w);
-                WorkItem it;
-                it.task = i;
-                it.row_begin = tro[i] + t0 * GR;
-                it.row_end = tro[i] + t1 * GR;
-                if (it.row_end > tro[i + 1]) it.row_end = tro[i + 1];
-                it.pad = 0;
-                work[t].push_back(it);
-            }
-            two[t][i + 1] = (int)work[t].size();
-        }
-        if ((int)work[t].size() > c->max_work) return fail(-5, "internal: work table overflow (%zu > %d)", work[t].size(), c->max_work);
-    }
-    // chain kernels: the NW waves of a workgroup walk a segment's tiles round-robin, so a task of n tiles costs
-    // ceil(n / NW) rounds; the global list of rounds is cut into equal shares, one per CU; a share that straddles task
-    // boundaries becomes one segment per task (walked one after the other).  Segments are generated in task order, so a
-    // task's partial rows are the contiguous segment indices [slot_off[i], slot_off[i+1]).
-    struct ChainTable { std::vector<ChainSeg> segs; std::vector<int> wg_off, slot_off; };
-    ChainTable T;
-    {
-        const int NW = CHAIN_NW_HVP;
-        std::vector<long long> rounds(M);
-        long long total = 0;
-        for (int i = 0; i < M; ++i) { rounds[i] = (tiles[i] + NW - 1) / NW; total += rounds[i]; }
-        // A segment also costs its parameter staging and end reduction, about SEGC rounds' worth: workgroups are filled
-        // up to a common cost limit (rounds + SEGC per segment, in quarter rounds), the smallest limit that needs no more
-        // workgroups than there are CUs.
-        const long long SEGC = 2;                  // quarter rounds per segment
-        auto cut = [&](long long limit, bool emit) -> long long {
-            long long nwg = 0, cost = 0;
-            bool open = false;
-            for (int i = 0; i < M; ++i) {
-                long long done = 0;
-                while (done < rounds[i]) {
-                    long long room = open ? (limit - cost - SEGC) / 4 : 0;   // rounds of task i that still fit
-                    if (!open || room < 1) {
-                        if (open && emit) T.wg_off.push_back((int)T.segs.size());
-                        ++nwg; open = true; cost = 0;
-                        room = (limit - SEGC) / 4;
-                        if (room < 1) room = 1;
-                    }
-                    const long long take = std::min(room, rounds[i] - done);
-                    if (emit) {
-                        ChainSeg sg;
-                        sg.task = i;
-                        sg.tile0 = (int)(done * NW);
-                        sg.ntiles = (int)std::min<long long>(tiles[i], (done + take) * NW) - sg.tile0;
-                        sg.pad = 0;
-                        T.segs.push_back(sg);
-                        T.slot_off[i + 1] = (int)T.segs.size();
-                    }
-                    done += take;
-                    cost += 4 * take + SEGC;
-                }
-            }
-            if (open && emit) T.wg_off.push_back((int)T.segs.size());
-            return nwg;
-        };
-        long long lo = 4 + SEGC, hi = 4 * total + SEGC * M + 4;
-        while (lo < hi) {
-            const long long mid = (lo + hi) / 2;
-            if (cut(mid, false) <= c->n_cus) hi = mid; else lo = mid + 1;
-        }
-        T.slot_off.assign(M + 1, 0);
-        T.wg_off.assign(1, 0);
-        cut(lo, true);
-        for (int i = 0; i < M; ++i)
-            if (T.slot_off[i + 1] < T.slot_off[i]) T.slot_off[i + 1] = T.slot_off[i];
-        if ((int)T.segs.size() > c->max_work) return fail(-5, "internal: segment table overflow (%zu > %d)", T.segs.size(), c->max_work);
-    }
-    S.n_paths = n_paths; S.n_rows = R; S.n_work[0] = (int)work[0].size(); S.n_work[1] = (int)work[1].size();
+    // every source of the copies below lives in `keep` (asynchronous mode: until the set is staged again)
+    auto keep = std::make_shared<StepTables>();
+    std::string why;
+    if (const int rc = build_step_tables(c->n_cus, c->max_work, c->d.max_rows, c->d.max_paths, M, n_paths, tpo, pro, keep.get(), &why))
+        return fail_plan(rc, why);
+    const StepTables& k = *keep;
+    const int R = (int)k.row_t.size();
+    S.lay_tpo.clear(); S.lay_pro.clear();         // (set again at the end; stays empty if a copy fails half-way)
+    S.n_paths = n_paths; S.n_rows = R; S.n_work[0] = (int)k.work[0].size(); S.n_work[1] = (int)k.work[1].size();
     S.processed = false; S.has_adv = false; S.has_rew64 = false; S.has_dice = false;
-    // every source below lives in `keep` (asynchronous mode: until the set is staged again)
-    struct Keep {
-        std::vector<int> pro, tpo, path_task, row_t, tro, wg_off, slot_chain, two[2];
-        std::vector<ChainSeg> segs;
-        std::vector<WorkItem> work[2];
-    };
-    auto keep = std::make_shared<Keep>();
-    keep->pro.assign(pro, pro + n_paths + 1); keep->tpo.assign(tpo, tpo + M + 1);
-    keep->path_task = std::move(path_task); keep->row_t = std::move(row_t); keep->tro = std::move(tro);
-    keep->wg_off = std::move(T.wg_off); keep->slot_chain = std::move(T.slot_off);
-    keep->segs = std::move(T.segs);
-    for (int t = 0; t < 2; ++t) { keep->two[t] = std::move(two[t]); keep->work[t] = std::move(work[t]); }
-    const Keep& k = *keep;
     HIPCHECK(hipMemcpyAsync(S.path_row_offsets, k.pro.data(), sizeof(int) * (n_paths + 1), hipMemcpyHostToDevice, st));
     HIPCHECK(hipMemcpyAsync(S.task_path_offsets, k.tpo.data(), sizeof(int) * (M + 1), hipMemcpyHostToDevice, st));
     HIPCHECK(hipMemcpyAsync(S.path_task, k.path_task.data(), sizeof(int) * n_paths, hipMemcpyHostToDevice, st));
@@ -1455,47 +1215,11 @@ int promp_stage_wait(promp_ctx* c) {
 
 // The baseline fit's buffers of one stream (main / side), allocated on first use: contexts that never fit a LinearFeatureBaseline
 // (policy passes only, ZeroBaseline, advantages handed in) do not pay for them.
-// k_gram_tiled, one slice (at most GRAMT_NWV squares): share the squares out over the waves so that the four SIMDs of a compute
-// unit carry about the same number of matrix instructions per k-step (wave w of a workgroup runs on SIMD w mod 4).  Waves to
-// spare take halves of diagonal squares (first row of the triangle / the rest: 3 + 3 products at TB = 3) -- Ant's 15 squares on
-// 16 waves: 10 x 9 + 4 x 6 + 2 x 3 products = 30 per SIMD.  Longest first, each to the least loaded SIMD that still has a wave
-// free.  More squares than waves: slices in list order, diagonal squares whole (the kernel ignores the map).
-void gramt_balance(int nblk, int nwv, GramtMap* map) {
-    const int nb = gramt_nb(nblk), nr = gramt_nrect(nblk), TB = GRAMT_TB;
-    memset(map->rect, 255, sizeof map->rect);
-    memset(map->part, GRAMT_DIAG, sizeof map->part);
-    if (nr > nwv || nwv > 16) return;
-    struct Piece { int rect, part, cost; };
-    std::vector<Piece> pieces;
-    int spare = nwv - nr;
-    for (int bi = 0, r = 0; bi < nb; ++bi)
-        for (int bj = bi; bj < nb; ++bj, ++r) {
-            if (bi != bj) pieces.push_back({r, GRAMT_FULL, TB * TB});
-            else if (spare > 0) {
-                pieces.push_back({r, GRAMT_DIAG_TOP, TB});
-                pieces.push_back({r, GRAMT_DIAG_REST, TB * (TB + 1) / 2 - TB});
-                --spare;
-            } else pieces.push_back({r, GRAMT_DIAG, TB * (TB + 1) / 2});
-        }
-    std::stable_sort(pieces.begin(), pieces.end(), [](const Piece& x, const Piece& y) { return x.cost > y.cost; });
-    int slots[4] = {0, 0, 0, 0}, load[4] = {0, 0, 0, 0}, next[4] = {0, 1, 2, 3};
-    for (int w = 0; w < nwv; ++w) slots[w & 3]++;
-    for (const Piece& pc : pieces) {
-        int q = -1;
-        for (int t = 0; t < 4; ++t)
-            if (slots[t] > 0 && (q < 0 || load[t] < load[q])) q = t;
-        map->rect[next[q]] = (unsigned char)pc.rect;
-        map->part[next[q]] = (unsigned char)pc.part;
-        next[q] += 4; slots[q]--; load[q] += pc.cost;
-    }
-}
-
-int fit_buffers(promp_ctx* c, bool on_side) {
+int fit_buffers(promp_ctx* c, bool on_side, const SamplePlan& plan) {
     DevBuf<double>& gp = on_side ? c->gram_partials_side : c->gram_partials;
     DevBuf<double>& fs = on_side ? c->fit_scratch_side : c->fit_scratch;
     if (!gp && gp.alloc((size_t)c->max_work * c->gram_stride)) return -2;
-    const int nblk_max = (c->Dmax + 1 + 15) / 16;
-    if (!fs && (nblk_max > 5 || c->d.obs_dim > 32) && fs.alloc((size_t)c->d.n_tasks * 2 * (c->Dmax + 1) * (c->Dmax + 1) + c->d.n_tasks)) return -2;   // (+ k_fitw_back's flags)
+    if (!fs && plan.fit == FitKernel::Wide && fs.alloc((size_t)c->d.n_tasks * 2 * (c->Dmax + 1) * (c->Dmax + 1) + c->d.n_tasks)) return -2;   // (+ k_fitw_back's flags)
     return 0;
 }
 
@@ -1519,10 +1243,11 @@ int promp_process_samples(promp_ctx* c, int step, const promp_proc_opts* o) {
     if (!(o->discount >= 0 && o->discount <= 1)) return fail(-1, "discount factor must be in [0,1]");      // samplers/base.py:57
     if (!(o->gae_lambda >= 0 && o->gae_lambda <= 1)) return fail(-1, "gae_lambda must be in [0,1]");       // samplers/base.py:58
     if (o->baseline_kind < 0 || o->baseline_kind > 2) return fail(-1, "unknown baseline kind %d", o->baseline_kind);
-    if (o->baseline_kind == PROMP_BASELINE_LINEAR_FEATURE && c->d.obs_dim > PROMP_LINFEAT_MAX_O)
-        return fail(-1, "LinearFeatureBaseline's fit is sized for obs_dim <= %d (%d here: %d feature columns); fit LinearTimeBaseline / no "
-                    "baseline on the device, or hand advantages in through promp_set_advantages", PROMP_LINFEAT_MAX_O, c->d.obs_dim,
-                    2 * c->d.obs_dim + 5);
+    // which Gram and fit kernels run (promp_plan.h: sample_plan; the table in tests/test_gpu_parity.py)
+    SamplePlan plan;
+    std::string why;
+    if (const int rc = sample_plan(o->baseline_kind, c->d.obs_dim, feature_dim(&c->d, o->baseline_kind), c->sw, &plan, &why))
+        return fail_plan(rc, why);
     SampleArgs a = sample_args(c, S, o->baseline_kind);
     a.work = S.work[0];                         // k_gram / k_fit: one workgroup per CU
     a.task_wg_offsets = S.task_wg_offsets[0];
@@ -1536,7 +1261,7 @@ int promp_process_samples(promp_ctx* c, int step, const promp_proc_opts* o) {
     // (promp_profile) keeps everything on the one stream it brackets.
     const bool on_side = c->overlap && !c->prof && step >= 1;
     hipStream_t st = on_side ? c->side : c->stream;
-    if (o->baseline_kind != PROMP_BASELINE_ZERO && fit_buffers(c, on_side)) return -2;
+    if (o->baseline_kind != PROMP_BASELINE_ZERO && fit_buffers(c, on_side, plan)) return -2;
     a.gram_partials = on_side ? c->gram_partials_side : c->gram_partials;
     double* fit_scratch = on_side ? c->fit_scratch_side : c->fit_scratch;
     if (on_side) {
@@ -1547,66 +1272,66 @@ int promp_process_samples(promp_ctx* c, int step, const promp_proc_opts* o) {
     S.wait_ready_side = false;
     PROMP_LAUNCH(k_returns, dim3(S.n_paths), 64, 0, st, a);
     HIPCHECK(hipGetLastError());
-    if (a.kind != BASE_ZERO) {
-        const int nblk = (a.D + 1 + 15) / 16;
-        if (prof_begin(c, PROMP_KERNEL_GRAM, S.n_rows)) return -2;
-        // k_gram<NBLK> stages raw observation rows of at most 32 floats (LinearTimeBaseline reads no observations: any obs_dim)
-        const bool small = nblk <= 5 && (a.O <= 32 || a.kind != BASE_LINFEAT);
-        switch (small ? nblk : 0) {
+    const int nblk = plan.nblk, DA = a.D + 1, M = c->d.n_tasks;
+    if (plan.gram != GramKernel::None && prof_begin(c, PROMP_KERNEL_GRAM, S.n_rows)) return -2;
+    switch (plan.gram) {
+    case GramKernel::None: break;
+    case GramKernel::Small:
+        switch (plan.gram_nblk) {
 #define PROMP_GRAM_CASE(NBLK) \
     case NBLK: { auto k = k_gram<NBLK>; PROMP_LAUNCH(k, dim3(S.n_work[0]), 64 * GramCfg<NBLK>::NW, GramCfg<NBLK>::SMEM_BYTES, st, a); } break;
             PROMP_GRAM_ALL(PROMP_GRAM_CASE)
 #undef PROMP_GRAM_CASE
-            default:
-                // 13 blocks and more (obs_dim >= 94; Ant: 15, Humanoid: 48): a square of 3 x 3 blocks per wave, operands reused in
-                // registers (k_gram_tiled); fewer blocks make too few squares to fill a compute unit: k_gram_wide
-                if (nblk >= GRAMT_MIN_NBLK && !c->gram_untiled) {
-                    const int nr = gramt_nrect(nblk);
-                    int rows, db;
-                    gramt_cfg(nblk, a.O, 64 * GRAMT_NWV * GRAMT_NLD, c->gramt_single, &rows, &db);
-                    if (c->gramt_map_nblk != nblk) { gramt_balance(nblk, GRAMT_NWV, &c->gramt_map); c->gramt_map_nblk = nblk; }
-                    auto k = k_gram_tiled<GRAMT_TB, GRAMT_NWV, GRAMT_NLD>;
-                    PROMP_LAUNCH(k, dim3(S.n_work[0], (nr + GRAMT_NWV - 1) / GRAMT_NWV), 64 * GRAMT_NWV, gramt_smem(nblk, rows, db), st, a, nblk,
-                                 c->gramt_map, rows, db);
-                    break;
-                }
-                // (more than 17 blocks -- obs_dim > 133: the pair list is cut into slices of <= 160, one workgroup per work item and slice)
-                PROMP_LAUNCH(k_gram_wide, dim3(S.n_work[0], gramw_slices(nblk)), 512, gramw_smem(nblk, a.O, gramw_rows(nblk, a.O)), st, a, nblk,
-                             gramw_rows(nblk, a.O));
         }
-        HIPCHECK(hipGetLastError());
-        if (prof_end(c, PROMP_KERNEL_GRAM)) return -2;
-        const int DA = a.D + 1;
-        if (small) {
-            const size_t fit_smem = sizeof(double) * ((size_t)2 * DA * DA + 3 * DA + 2 + fitwv_aux(64));      // (k_fit / k_fit_wave<DT <= 64>)
-            // one wave per task while a row of the work matrix fits a wave's lanes (D + 1 <= 64); else one workgroup per task
-            // (45: obs_dim 20)
-#define PROMP_FITWV_CASE(DT) else if (DA <= DT) { auto k = k_fit_wave<DT>; PROMP_LAUNCH(k, dim3(c->d.n_tasks), FITWV_NT, fit_smem, st, a, nblk); }
-            if (false) {}                       // (head of the chain the list expands to)
+        break;
+    case GramKernel::Tiled: {
+        if (c->gramt_map_nblk != nblk) { gramt_balance(nblk, GRAMT_NWV, &c->gramt_map); c->gramt_map_nblk = nblk; }
+        auto k = k_gram_tiled<GRAMT_TB, GRAMT_NWV, GRAMT_NLD>;
+        PROMP_LAUNCH(k, dim3(S.n_work[0], plan.gram_slices), 64 * GRAMT_NWV, gramt_smem(nblk, plan.gram_rows, plan.gram_db), st, a, nblk,
+                     c->gramt_map, plan.gram_rows, plan.gram_db);
+        break;
+    }
+    case GramKernel::Wide:
+        PROMP_LAUNCH(k_gram_wide, dim3(S.n_work[0], plan.gram_slices), 512, gramw_smem(nblk, a.O, plan.gram_rows), st, a, nblk, plan.gram_rows);
+        break;
+    }
+    HIPCHECK(hipGetLastError());
+    if (plan.gram != GramKernel::None && prof_end(c, PROMP_KERNEL_GRAM)) return -2;
+    const size_t fit_smem = sizeof(double) * ((size_t)2 * DA * DA + 3 * DA + 2 + fitwv_aux(64));      // (k_fit / k_fit_wave<DT <= 64>)
+    switch (plan.fit) {
+    case FitKernel::None: break;
+    case FitKernel::Wave:
+        switch (plan.fit_arg) {
+#define PROMP_FITWV_CASE(DT) case DT: { auto k = k_fit_wave<DT>; PROMP_LAUNCH(k, dim3(M), FITWV_NT, fit_smem, st, a, nblk); } break;
             PROMP_FITWV_ALL(PROMP_FITWV_CASE)
-            else PROMP_LAUNCH(k_fit, dim3(c->d.n_tasks), 256, fit_smem, st, a, nblk);
 #undef PROMP_FITWV_CASE
-        } else {
-            PROMP_LAUNCH(k_gram_sum_wide, dim3(c->d.n_tasks * fitw_sum_split(nblk)), 256, 0, st, a, nblk, fit_scratch, fitw_sum_split(nblk));
-            HIPCHECK(hipGetLastError());
-            const int* none = nullptr;
-            int* bad = (int*)(fit_scratch + (size_t)c->d.n_tasks * 2 * (c->Dmax + 1) * (c->Dmax + 1));
-            const bool phases = a.D >= FITW_ML_MIN_D && !c->fit_one_launch;      // one launch per phase: all CUs in the trailing updates
+        }
+        break;
+    case FitKernel::Block: PROMP_LAUNCH(k_fit, dim3(M), 256, fit_smem, st, a, nblk); break;
+    case FitKernel::Wide: {
+        PROMP_LAUNCH(k_gram_sum_wide, dim3(M * plan.sum_split), 256, 0, st, a, nblk, fit_scratch, plan.sum_split);
+        HIPCHECK(hipGetLastError());
+        const int* none = nullptr;
+        int* bad = (int*)(fit_scratch + (size_t)M * 2 * (c->Dmax + 1) * (c->Dmax + 1));
 #define PROMP_FITW(NB)                                                                                                              \
-    if (phases) {                                                                                                                   \
+    if (plan.fit_phases) {                                                                                                          \
         auto kp = k_fitw_panel<NB>; auto ku = k_fitw_update<NB>; auto kb = k_fitw_back<NB>; auto kf = k_fit_wide<NB>;              \
         for (int k0 = 0; k0 < a.D; k0 += NB) {                                                                                      \
-            PROMP_LAUNCH(kp, dim3(c->d.n_tasks), FITW_NT, fitw_panel_smem(a.D, NB), st, a, fit_scratch, k0);                        \
-            if (k0 + NB < a.D) PROMP_LAUNCH(ku, dim3(c->d.n_tasks, FITW_UPD_SPLIT), FITW_NT, fitw_panel_smem(a.D, NB), st, a, fit_scratch, k0); \
+            PROMP_LAUNCH(kp, dim3(M), FITW_NT, fitw_panel_smem(a.D, NB), st, a, fit_scratch, k0);                                   \
+            if (k0 + NB < a.D) PROMP_LAUNCH(ku, dim3(M, FITW_UPD_SPLIT), FITW_NT, fitw_panel_smem(a.D, NB), st, a, fit_scratch, k0); \
         }                                                                                                                           \
-        PROMP_LAUNCH(kb, dim3(c->d.n_tasks), FITW_NT, fitw_back_smem(a.D, NB), st, a, fit_scratch, bad);                               \
-        PROMP_LAUNCH(kf, dim3(c->d.n_tasks), FITW_NT, fitw_smem(a.D, NB), st, a, nblk, fit_scratch, (const int*)bad);               \
-    } else { auto k = k_fit_wide<NB>; PROMP_LAUNCH(k, dim3(c->d.n_tasks), FITW_NT, fitw_smem(a.D, NB), st, a, nblk, fit_scratch, none); }
-            if (fitw_nb(a.D) == 32) { PROMP_FITW(32) } else { PROMP_FITW(16) }
-#undef PROMP_FITW
+        PROMP_LAUNCH(kb, dim3(M), FITW_NT, fitw_back_smem(a.D, NB), st, a, fit_scratch, bad);                                       \
+        PROMP_LAUNCH(kf, dim3(M), FITW_NT, fitw_smem(a.D, NB), st, a, nblk, fit_scratch, (const int*)bad);                          \
+    } else { auto k = k_fit_wide<NB>; PROMP_LAUNCH(k, dim3(M), FITW_NT, fitw_smem(a.D, NB), st, a, nblk, fit_scratch, none); }
+        switch (plan.fit_arg) {
+        case 32: PROMP_FITW(32) break;
+        case 16: PROMP_FITW(16) break;
         }
-        HIPCHECK(hipGetLastError());
+#undef PROMP_FITW
+        break;
     }
+    }
+    HIPCHECK(hipGetLastError());
     PROMP_LAUNCH(k_gae, dim3(S.n_paths), 64, sizeof(double) * (size_t)(a.D > 0 ? a.D : 1), st, a);
     HIPCHECK(hipGetLastError());
     a.work = S.work[1];                         // k_normalize: two workgroups per CU

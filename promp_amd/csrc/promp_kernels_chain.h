@@ -31,6 +31,7 @@
 #pragma once
 #include "promp_device.h"
 #include "promp_objective.h"
+#include "promp_plan.h"            // WorkItem, ChainSeg
 
 #define PROMP_PASS_TPLANE 512    // words per plane of a [16 samples][64 units] tile of 16-bit halves
 #define PROMP_PASS_XPLANE 256    // [16][32 observation slots]
@@ -51,9 +52,6 @@
 #ifndef PROMP_PASS_XCD
 #define PROMP_PASS_XCD 0
 #endif
-struct WorkItem {
-    int task, row_begin, row_end, pad;
-};
 
 // Primal cache.  The R-operator pass at theta on a step's slab recomputes what the gradient pass at the SAME theta on the
 // SAME slab computed moments earlier: the hidden activations and the means.  Both kernels are bound by the matrix pipe
@@ -68,9 +66,6 @@ struct WorkItem {
 // spare rows per task keep the next task's first block clear of it without a tile-offset table.
 PROMP_CX int chain_cache_row(int H1, int H2) { return 2 * H1 + H2 + 8; }     // floats per row
 
-struct ChainSeg {
-    int task, tile0, ntiles, pad;   // 16-row tiles [tile0, tile0 + ntiles) of the task; slot = index of the segment
-};
 
 // What the last-arriving workgroup of a task does with the task's summed partial row g (fixed slot order):
 //   RED_STEP  : next[i] = cur[i] - alpha * g                  ; scal[i] = {loss, kl}     (inner SGD step)

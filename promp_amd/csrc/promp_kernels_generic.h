@@ -19,14 +19,12 @@
 #pragma once
 #include "promp_kernels_policy.h"
 #include "promp_kernels_rollout.h"
+#include "promp_plan.h"            // GEN_MAX_LIN, GEN_MAX_N, GEN_MAX_A
 
-#define GEN_MAX_LIN 5          // linear layers: up to 4 hidden + the output layer
 #define GEN_R 64               // rows per chunk (4 row blocks of 16)
 #define GEN_KC 64              // contraction entries staged per chunk
 #define GEN_LD (GEN_KC + 16)   // LDS row stride of a staged chunk of k_gen_wgrad (4 rows x 16 columns of an operand read: 64 banks)
 #define GEN_RW 32              // rows per chunk of the weight-gradient kernel (its LDS also holds the cotangent rows)
-#define GEN_MAX_N 256          // widest layer output (4 waves x 4 column blocks of 16)
-#define GEN_MAX_A 64
 #define GEN_SPLIT 4            // workgroups per work item of k_gen_linear
 
 struct GenLin {

@@ -164,7 +164,6 @@ __global__ void __launch_bounds__(256) k_reduce_final_ss(FinalArgs a, const floa
 
 // Mean over the global meta-batch + Adam.  red holds SUMS over all tasks (after the all-reduce).
 // stats[0] = loss = mean_i J_i + mean_k(eta_k * mean_i KL^k_i); stats[1+k] = inner_kl[k]; stats[1+K] = outer_kl
-#define PROMP_ETA_MAX 8        // most inner gradient steps a context is created for
 struct AdamArgs {
     float* theta;
     float* m;

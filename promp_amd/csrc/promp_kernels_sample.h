@@ -15,7 +15,8 @@
 #pragma once
 #include <utility>
 #include "promp_device.h"
-#include "promp_kernels_policy.h"  // WorkItem
+#include "promp_plan.h"            // the constants and sizing helpers shared with the host's plan
+#include "promp_kernels_policy.h"
 
 enum { BASE_ZERO = 0, BASE_LINFEAT = 1, BASE_LINTIME = 2 };
 
@@ -354,9 +355,6 @@ __global__ void __launch_bounds__(256) k_fit(SampleArgs a, int NBLK) {
 
 // One column step of k_fit_wave's factorisation (J is a compile-time constant: the steps are instantiated one by one, which
 // keeps the row in registers whatever the unroller's size limits say).
-#define FITWV_CS 65        // doubles between the factor's columns in LDS (k_fit_wave: 64 lanes + 1: a lane walking down its own
-                           // column -- the back substitution's operands -- is then on its own pair of banks)
-PROMP_HD size_t fitwv_aux(int dt) { return (size_t)dt * FITWV_CS + 2 + 64; }     // the factor by columns + 1 / L[j][j]
 template <int J, int DT>
 PROMP_DEV void fitw_column(double (&W)[DT], double* colbuf, double* rsv, double& rs, int lane, int D) {
     if (J >= D) return;       // (wave-uniform)
@@ -633,19 +631,6 @@ __global__ void __launch_bounds__(256) k_normalize(SampleArgs a) {
 // its owner.  Rounds of GRAMW_ROWS rows; same partial layout as k_gram ([NPAIR][256] doubles per work item).
 // grid = work items (table 0) x pair slices, block = 512.  smem: the feature tile, ROWS * FS doubles.
 // ---------------------------------------------------------------------------------------------
-#define GRAMW_PPW 20     // pairs per wave: 8 * 20 >= 17 * 18 / 2 (NBLK <= 17, D <= 271) in one workgroup; more blocks: the pair list is
-                         // cut into gridDim.y slices of at most 160 (gramw_slices), one workgroup per work item and slice
-PROMP_HD int gramw_fs(int NBLK) { return (NBLK % 2 == 1) ? 16 * NBLK : 16 * NBLK + 16; }
-PROMP_HD size_t gramw_smem(int NBLK, int O, int rows) {
-    (void)O;
-    return sizeof(double) * (size_t)(rows * gramw_fs(NBLK));      // the feature tile
-}
-// rows per round: 64 where the feature tile + raw observations fit the 160 KB of LDS (Ant: 151 KB), else 32, else 16
-PROMP_HD int gramw_rows(int NBLK, int O) {
-    return gramw_smem(NBLK, O, 64) <= 160 * 1024 ? 64 : gramw_smem(NBLK, O, 32) <= 160 * 1024 ? 32 : 16;
-}
-PROMP_HD int gramw_slices(int NBLK) { return (NBLK * (NBLK + 1) / 2 + 8 * GRAMW_PPW - 1) / (8 * GRAMW_PPW); }
-
 __global__ void __launch_bounds__(512, 2) k_gram_wide(SampleArgs a, int NBLK, int GRAMW_ROWS) {
     PROMP_SMEM_DECL;
     const int tid = threadIdx.x, lane = tid & 63, w = wave_uniform(tid >> 6), i16 = lane & 15, kk = lane >> 4;
@@ -793,32 +778,6 @@ __global__ void __launch_bounds__(512, 2) k_gram_wide(SampleArgs a, int NBLK, in
 //   * A partial last round issues only the k-steps that hold rows.
 // grid = work items (table 0) x slices, block = 64 NWV.  ROWS / DB: gramt_cfg; smem: gramt_smem(NBLK, ROWS, DB).
 // ---------------------------------------------------------------------------------------------
-#define GRAMT_MIN_NBLK 13
-#define GRAMT_TB 3
-#define GRAMT_NWV 16
-#define GRAMT_NLD 8
-struct GramtMap {        // one-slice launches: wave -> square (255: none) and which part of a diagonal square (GRAMT_*)
-    unsigned char rect[16], part[16];
-};
-enum { GRAMT_FULL = 0, GRAMT_DIAG = 1, GRAMT_DIAG_TOP = 2, GRAMT_DIAG_REST = 3 };
-PROMP_HD int gramt_nb(int NBLK) { return (NBLK + GRAMT_TB - 1) / GRAMT_TB; }
-PROMP_HD int gramt_fs(int NBLK) {       // 16 x odd: the four k-rows of a step land on disjoint banks
-    const int nc = GRAMT_TB * gramt_nb(NBLK);
-    return (nc % 2 == 1) ? 16 * nc : 16 * nc + 16;
-}
-PROMP_HD int gramt_nrect(int NBLK) { return gramt_nb(NBLK) * (gramt_nb(NBLK) + 1) / 2; }
-// rows per round and single / double tile: two tiles of 32 or 16 rows where they fit LDS (and a round's observations the
-// threads' request registers: cap = NT * NLD elements) -- the build of round r + 1 then runs beside the products of round r
-// behind ONE barrier per round; `single` (PROMP_GRAMT_SINGLE=1, the A/B switch) or nothing fitting twice: one tile of 32 / 16 rows,
-// the build between two barriers.
-PROMP_HD void gramt_cfg(int NBLK, int O, int cap, bool single, int* rows, int* db) {
-    const size_t row_bytes = sizeof(double) * (size_t)gramt_fs(NBLK), lds = 160 * 1024;
-    if (!single)
-        for (int r = 32; r >= 16; r >>= 1)      // (two tiles of 8 rows measured slower than one of 16 at Humanoid's width: 2.37 vs 2.21 ms)
-            if (2 * r * row_bytes <= lds && r * O <= cap) { *rows = r; *db = 1; return; }
-    *rows = (32 * row_bytes <= lds && 32 * O <= cap) ? 32 : 16;
-    *db = 0;
-}
 PROMP_HD size_t gramt_smem(int NBLK, int rows, int db) { return sizeof(double) * (size_t)((db ? 2 : 1) * rows * gramt_fs(NBLK)); }
 
 // which of a square's TB x TB products a wave of shape SHAPE issues: all (off the diagonal); the upper triangle jj >= ii (a
@@ -1007,21 +966,12 @@ __global__ void __launch_bounds__(64 * NWV) k_gram_tiled(SampleArgs a, int NBLK,
 // (results agree to rounding, not bit for bit).
 // grid = tasks, block = FITW_NT.  smem: fitw_smem(D).
 // ---------------------------------------------------------------------------------------------
-#define FITW_NB 32         // panel width where the panel fits LDS (D <= ~580); wider matrices take 16-column panels
-#define FITW_NT 512        // 8 waves: two per SIMD, 256 registers each (a row of the diagonal block / of the solve lives in 64 of them)
-PROMP_HD size_t fitw_smem(int D, int nb) {
-    const size_t DA = D + 1, panel = (DA + 16) * (size_t)(nb + 1);       // (16 spare rows: the last 16-row tile of the update reads zeros)
-    return sizeof(double) * (panel + 3 * DA + nb + 2);
-}
-PROMP_HD int fitw_nb(int D) { return fitw_smem(D, FITW_NB) <= 160 * 1024 ? FITW_NB : 16; }
-
 // The task's partial Gram blocks summed in workgroup order and scattered into the symmetric matrix G -- and G + reg I into the
 // work matrix of the first factorisation attempt -- by the WHOLE chip (grid = tasks x fitw_sum_split(NBLK)): inside k_fit_wide the sum
 // ran on one compute unit per task (40 of 256 busy, a quarter of that kernel's time at Ant's size).
 // scratch: [tasks][2][(D+1)^2].  block = 256.
 // (the split grows with the matrix: Humanoid's 1176 blocks of 256 entries per task are 617 MB of partial blocks per launch, and with
 //  8 workgroups per task the loads in flight -- not the memory system -- set the pace; every entry is still one thread's sum in workgroup order)
-PROMP_HD int fitw_sum_split(int NBLK) { return NBLK >= 32 ? 32 : NBLK >= 13 ? 16 : 8; }
 __global__ void __launch_bounds__(256) k_gram_sum_wide(SampleArgs a, int NBLK, double* scratch, int FITW_SUM_SPLIT) {
     const int D = a.D, DA = D + 1;
     const int task = blockIdx.x / FITW_SUM_SPLIT, part = blockIdx.x % FITW_SUM_SPLIT;
@@ -1324,8 +1274,6 @@ __global__ void __launch_bounds__(FITW_NT) k_fit_wide(SampleArgs a, int NBLK, do
 // Same elimination order and the same arithmetic per entry as k_fit_wide (every trailing entry takes one 16-term MFMA sum per
 // panel whichever wave computes it): bit-identical coefficients.  The diagonal of the factor is kept on the work matrix' diagonal.
 // ---------------------------------------------------------------------------------------------
-#define FITW_UPD_SPLIT 6          // 40 tasks x 6 = 240 workgroups
-#define FITW_ML_MIN_D 400         // below: k_fit_wide (8 panels at Ant's 226 columns are a chain of dependent steps, not tile work)
 PROMP_HD size_t fitw_panel_smem(int D, int nb) { return sizeof(double) * ((size_t)(D + 1 + 16) * (nb + 1) + nb + 2); }
 PROMP_HD size_t fitw_back_smem(int D, int nb) { return sizeof(double) * ((size_t)3 * (D + 1) + 2 * nb * (nb + 1) + 2); }
 

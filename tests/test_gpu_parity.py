@@ -5,9 +5,10 @@
   * size-independent properties at BASELINE.json's full config-3 size.
 Tolerances are stated in tests/parity_checks.py.
 
-Sample processing picks its Gram and fit kernels from LinearFeatureBaseline's column count (promp_process_samples): D = 2 obs_dim + 4
+Sample processing picks its Gram and fit kernels from LinearFeatureBaseline's column count (promp_plan.h: sample_plan): D = 2 obs_dim + 4
 features, D + 1 columns with the target, nblk = ceil((D + 1) / 16) blocks of 16.  The test_sample_processing_edges_* tests below run
-every one of them; their ids name the kernels:
+every one of them; their ids name the kernels.  tests/host/plan_check.cpp (tests/test_plan_host.py) pins this table: it asks
+sample_plan for every row and fails if a row gets another kernel, slice count or panel width:
 
   obs_dim   D+1  nblk  Gram kernel                     fit kernel
   1, 3      7,11   1   k_gram<1>                       k_fit_wave<12>
