@@ -347,6 +347,28 @@ int promp_constraint_hvp(promp_ctx* ctx, int inner_kind, const float* v, int ref
  * are back at theta when the call returns.  b [Theta] = the loss gradient; x_out [Theta]; *xhx_out = x . (H + reg_coeff I) x. */
 int promp_cg_solve(promp_ctx* ctx, int inner_kind, const float* b, int cg_iters, float reg_coeff, float eps, int hvp_mode,
                    float residual_tol, float* x_out, double* xhx_out);
+/* Subsampled constraint products (ConjugateGradientOptimizer's subsample_factor, as in rllab's TRPO: the products x -> H x of
+ * the solve and the closing x . H x see a subset of the paths; the loss, its gradient and the line search see the whole batch).
+ * promp_set_step_selection: path_idx [n_sel] = indices into the step's paths, strictly increasing, at least one path of every
+ * task; n_sel = 0 or path_idx = NULL clears the step's selection.  A malformed selection is refused with a message and nothing
+ * is written.  The selected paths' rows (observations, actions, advantages, old means and log_std) are copied into a compact
+ * slab laid out exactly as promp_upload_step would lay out an upload of those paths alone, on first use and again whenever the
+ * step's data has moved (promp_process_samples / promp_set_advantages after the selection are seen); whatever replaces the
+ * step's layout (promp_upload_step, promp_commit_step, the rollout entry points, promp_end_collection) clears the selection.
+ * The constraint on a selection is the same function on fewer paths: the inner adaptation runs on the selected paths of steps
+ * 0..K-1, the KL mean over those of step K, the old distributions are the stored ones.  Its exact product J_S^T H_KL J_S is
+ * positive semi-definite but no longer the full Hessian: the adapted parameters on a subsample are not the ones step K was
+ * sampled with, so the dropped third-order term is not zero.
+ *   promp_cg_solve            runs every product (all three modes) on the selections when EVERY step has one; refuses when only
+ *                             some have.  Without any, it is bit for bit what it was.
+ *   promp_use_selection(on)   promp_meta_grad with PROMP_OUTER_KL and promp_constraint_hvp evaluate on the selections (every
+ *                             step must have one) until switched off: the host loop's and external collectives' way in.
+ *   promp_step_selection      the number of selected paths of a step, 0: none.
+ * The evaluations on selections keep a chain of adapted parameters, inner scalars and a primal-cache record of their own: what
+ * promp_inner_adapt and the last full-batch product left behind stays valid.  PROMP_INNER_DICE is refused on a selection. */
+int promp_set_step_selection(promp_ctx* ctx, int step, int n_sel, const int32_t* path_idx);
+int promp_step_selection(promp_ctx* ctx, int step);
+int promp_use_selection(promp_ctx* ctx, int on);
 /* tf.train.AdamOptimizer step on theta with the gradient left by promp_meta_grad
  * (optimizers/maml_first_order_optimizer.py:24,64; b1=.9 b2=.999 eps=1e-8, bias-corrected lr). */
 int promp_adam_step(promp_ctx* ctx, float learning_rate);

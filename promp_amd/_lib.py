@@ -93,6 +93,9 @@ SIGNATURES = {
     'promp_host_free': (None, [C.c_void_p]),
     'promp_constraint_hvp': (C.c_int, [_P, C.c_int, _F, C.c_int, _F]),
     'promp_cg_solve': (C.c_int, [_P, C.c_int, _F, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, _F, C.POINTER(C.c_double)]),
+    'promp_set_step_selection': (C.c_int, [_P, C.c_int, C.c_int, _I]),
+    'promp_step_selection': (C.c_int, [_P, C.c_int]),
+    'promp_use_selection': (C.c_int, [_P, C.c_int]),
     'promp_set_adam_state': (C.c_int, [_P, _F, _F, C.c_int64]),
     'promp_get_adam_state': (C.c_int, [_P, _F, _F, C.POINTER(C.c_int64)]),
     'promp_switch_to_pre_update': (C.c_int, [_P]),
@@ -470,6 +473,7 @@ class Context:
         self._wait_epoch = 0
         self.step_ls_rows = {}
         self.step_paths = {}
+        self.step_tpo = {}           # step -> task_path_offsets of the resident batch (set_step_selection's callers draw per task)
         self._lazy = {}              # step -> WeakSet of LazyResults that have not fetched yet
 
     def close(self):
@@ -547,6 +551,7 @@ class Context:
         self._retain_upload(step, (tpo, pro, obs, act, rew, old_mean, old_log_std, rew64))
         self.step_rows[step] = int(pro[-1])
         self.step_paths[step] = int(n_paths)
+        self.step_tpo[step] = np.array(tpo, dtype=np.int64)
         self.step_ls_rows[step] = int(pro[-1]) if per_row else self.n_tasks
         if rew64 is not None:        # float64 rewards stay float64 on the device (the reference scans the env's float64)
             self._call('promp_set_rewards_f64', int(step), _ptr(rew64, C.c_double))
@@ -567,7 +572,7 @@ class Context:
         self._call('promp_stage_step', int(step), int(n_paths), _ptr(tpo, C.c_int32), _ptr(pro, C.c_int32),
                    _ptr(obs, C.c_float), _ptr(act, C.c_float), _ptr(rew, C.c_float), _ptr(old_mean, C.c_float),
                    _ptr(old_log_std, C.c_float), per_row)
-        self._staged[step] = dict(rows=int(pro[-1]), paths=int(n_paths), ls_rows=int(pro[-1]) if per_row else self.n_tasks,
+        self._staged[step] = dict(rows=int(pro[-1]), paths=int(n_paths), tpo=np.array(tpo, dtype=np.int64), ls_rows=int(pro[-1]) if per_row else self.n_tasks,
                                   refs=(obs, rew, act, old_mean, old_log_std))
 
     def commit_step(self, step):
@@ -575,6 +580,7 @@ class Context:
         st = self._staged.pop(step)
         self._call('promp_commit_step', int(step))
         self.step_rows[step], self.step_paths[step], self.step_ls_rows[step] = st['rows'], st['paths'], st['ls_rows']
+        self.step_tpo[step] = st['tpo']
         self._live_refs[step] = st['refs']       # until the next commit: the copies may still be in flight
 
     def stage_wait(self):
@@ -734,6 +740,7 @@ class Context:
         self._call('promp_rollout_point_env', int(step), int(B), int(T), _ptr(goals, C.c_double), _ptr(start, C.c_double),
                    _ptr(noise, C.c_float) if noise is not None else None, C.byref(opts))
         self.step_rows[step], self.step_paths[step] = M * B * T, M * B
+        self.step_tpo[step] = np.arange(M + 1, dtype=np.int64) * B
         self.step_ls_rows[step] = M
 
     def begin_rollout(self, step, envs_per_task, path_length):
@@ -743,6 +750,7 @@ class Context:
         self._rollout_shape = (int(envs_per_task), int(path_length))
         self.step_rows[step] = self.n_tasks * envs_per_task * path_length
         self.step_paths[step] = self.n_tasks * envs_per_task
+        self.step_tpo[step] = np.arange(self.n_tasks + 1, dtype=np.int64) * int(envs_per_task)
         self.step_ls_rows[step] = self.n_tasks
 
     def begin_collection(self, step, envs_per_task, max_steps):
@@ -763,6 +771,7 @@ class Context:
         self._call('promp_end_collection', int(step), int(env.size), tpo.ctypes.data_as(C.c_void_p), env.ctypes.data_as(C.c_void_p),
                    start.ctypes.data_as(C.c_void_p), ln.ctypes.data_as(C.c_void_p), _ptr(rew, C.c_float))
         self.step_rows[step], self.step_paths[step], self.step_ls_rows[step] = int(ln.sum()), int(env.size), self.n_tasks
+        self.step_tpo[step] = np.array(tpo, dtype=np.int64)
 
     def policy_step(self, step, t, obs, seed=0, clip_infos=True):
         """obs [M, B, O] -> actions [M, B, A]; observation, action and mean land in the slab at row (task, env, t)"""
@@ -893,6 +902,25 @@ class Context:
         self._call('promp_cg_solve', int(inner_kind), _ptr(b, C.c_float), int(cg_iters), float(reg_coeff), float(eps), int(hvp_mode),
                    float(residual_tol), _ptr(x, C.c_float), C.byref(xhx))
         return x, float(xhx.value)
+
+    # ---- subsampled constraint products ----
+    def set_step_selection(self, step, path_idx=None):
+        """promp_set_step_selection: the paths of `step` (indices into its paths, strictly increasing, at least one per task) that
+        the constraint products keep; None or an empty list clears it.  cg_solve runs on the selections once every step has one."""
+        idx = np.ascontiguousarray([] if path_idx is None else path_idx, dtype=np.int32).reshape(-1)
+        self._call('promp_set_step_selection', int(step), int(idx.size), _ptr(idx, C.c_int32) if idx.size else None)
+
+    def clear_selections(self):
+        for k in range(self.K + 1):
+            self._call('promp_set_step_selection', k, 0, None)
+
+    def step_selection(self, step):
+        """number of selected paths of `step` (0: no selection)"""
+        return self._call('promp_step_selection', int(step))
+
+    def use_selection(self, on=True):
+        """promp_use_selection: meta_grad with OUTER_KL and constraint_hvp evaluate on the selections until switched off"""
+        self._call('promp_use_selection', int(bool(on)))
 
     def eval_hvp(self, step, v, inner_kind=INNER_RATIO, clip_log_std=False, kl_weight=0.0):
         v = _f32(v)

@@ -114,6 +114,7 @@ struct StepData {
     unsigned long long cache_tag = 0;      // identity of the primal cache's contents (every storing pass draws a new one)
     int ls_per_row = 0;
     int feat_dim = 0;
+    int cap_rows = 0;                  // a selection's compact slab: the rows its buffers hold (0: the context's max_rows)
     DevBuf<float> obs, act, rew, old_mean, old_ls;
     DevBuf<unsigned> obs_absmax;       // [tasks]: bits of the largest |observation| of each task's rows (k_obs_range; the FP16 split's scale)
     bool obs_range_valid = false;      // false from every entry point that writes S.obs until k_obs_range has been enqueued behind it
@@ -175,6 +176,38 @@ struct PassReq {
     float* next2 = nullptr;            // RED_STEP: second destinations of next and scal (see adapt0)
     float* scal2 = nullptr;
     float* ginner = nullptr;           // RED_STEP: where the summed gradient itself goes (trainable step sizes)
+};
+
+// promp_constraint_hvp: what its primal caches (one per step) were filled at; the products of one conjugate-gradient solve run
+// at the same parameters on the same slabs, so the 2K + 1 R-operator passes of every product after the first read them back
+struct ChvpRec {
+    bool valid = false;
+    unsigned long long theta_version = 0, sizes_version = 0, data_version[PROMP_ETA_MAX + 1] = {}, tag[PROMP_ETA_MAX + 1] = {};
+    int inner_kind = 0;
+    float min_log_std = 0.f;
+};
+
+// promp_set_step_selection: the paths of a step that the subsampled constraint products keep.  The compact slab that holds copies
+// of their rows (promp_ctx::sub) is filled by the first evaluation that needs it and again whenever the step's data has moved.
+struct Selection {
+    bool on = false;
+    SelectionLayout lay;
+    StepTables tables;                 // the compact slab's tables, as build_step_tables lays out an upload of the selected paths
+    DevBuf<int> idx;                   // lay.idx on the device
+    int cap_paths = 0;
+    bool tables_sent = false, gathered = false;
+    unsigned long long gathered_version = 0;   // the step's data_version the copies were taken at
+};
+
+// What an evaluation of the meta-objective or of the constraint product walks and leaves behind: the whole batch with the
+// context's chain of adapted parameters, or the selections' compact slabs with a chain, inner scalars and cache record of their
+// own (what promp_inner_adapt and the last full-batch product left behind stays valid under a subsampled solve)
+struct EvalSet {
+    std::vector<StepData>* steps;
+    float* chain;
+    float* scal_inner;
+    ChvpRec* chvp;
+    bool sub;
 };
 
 struct ProfSlot {
@@ -261,10 +294,14 @@ struct promp_ctx {
     bool reuse_adapt = true;             // promp_set_reuse_adapt
     bool ls_known = false;               // ls_min is the smallest log_std entry of the current theta
     float ls_min = 0.f;
-    // promp_constraint_hvp: what its primal caches (one per step) were filled at; the products of one conjugate-gradient solve run
-    // at the same parameters on the same slabs, so the 2K + 1 R-operator passes of every product after the first read them back
-    struct { bool valid = false; unsigned long long theta_version = 0, sizes_version = 0, data_version[PROMP_ETA_MAX + 1] = {},
-             tag[PROMP_ETA_MAX + 1] = {}; int inner_kind = 0; float min_log_std = 0.f; } chvp;
+    ChvpRec chvp;
+    // subsampled constraint products (promp_set_step_selection): per step the selection and its compact slab; the evaluations on
+    // them keep their own chain, inner scalars and cache record (EvalSet), all allocated with the first selection
+    std::vector<Selection> sel;
+    std::vector<StepData> sub;
+    DevBuf<float> sel_chain, sel_scal_inner;
+    ChvpRec chvp_sel;
+    bool use_sel = false;                // promp_use_selection: promp_meta_grad (outer kind KL) and promp_constraint_hvp run on the selections
     long long chvp_cached_passes = 0;          // R-operator passes of promp_constraint_hvp that read a primal cache (tests, tools)
     long long adapt_passes_skipped = 0;
     bool force_split = false;            // take the multi-rank launch sequence (reduce / all-reduce / Adam) on one rank too
@@ -524,7 +561,8 @@ static bool primal_cache_on(const promp_ctx* c) { return c->family == PassFamily
 // the step's primal cache (promp_kernels_chain.h: chain_cache_row), allocated on first use
 static int ensure_primal_cache(promp_ctx* c, StepData& S) {
     if (S.hcache) return 0;
-    return S.hcache.alloc(((size_t)c->d.max_rows + 16 * (size_t)c->d.n_tasks) * chain_cache_row(c->d.hidden1, c->d.hidden2));
+    const size_t rows = S.cap_rows ? S.cap_rows : c->d.max_rows;
+    return S.hcache.alloc((rows + 16 * (size_t)c->d.n_tasks) * chain_cache_row(c->d.hidden1, c->d.hidden2));
 }
 
 // Chain: k_chain_hvp reduces in-launch when a.fuse_reduce says so; k_pass is followed by k_reduce_task
@@ -732,29 +770,33 @@ static StepSizeArgs step_size_args(const promp_ctx* c) {
     return s;
 }
 
+static EvalSet full_set(promp_ctx* c) { return EvalSet{&c->steps, c->chain, c->scal_inner, &c->chvp, false}; }
+
 // One evaluation of the meta-objective (+ gradient, + Adam) enqueued on the stream.  sizes_grad: with trainable step sizes the
 // gradient evaluation also leaves the step sizes' gradient (and Adam steps them); promp_cg_solve's evaluations say no.
-int enqueue_meta(promp_ctx* c, float clip_eps, const float* eta_host, int inner_kind, int outer_kind, bool want_grad,
-                 bool do_adam, float lr, bool sizes_grad = true) {
+int enqueue_meta_on(promp_ctx* c, const EvalSet& E, float clip_eps, const float* eta_host, int inner_kind, int outer_kind,
+                    bool want_grad, bool do_adam, float lr, bool sizes_grad) {
+    std::vector<StepData>& W = *E.steps;
     const int K = c->d.num_inner_steps, M = c->d.n_tasks, NP = c->NP;
     const size_t MNP = (size_t)M * NP;
     const bool ag = c->train_sizes && want_grad && sizes_grad;
     for (int k = 0; k <= K; ++k)
-        if (c->steps[k].n_rows == 0) return fail(-3, "step %d has no data", k);
+        if (W[k].n_rows == 0) return fail(-3, "step %d has no data", k);
     // a step's second-stream sample processing is waited for right in front of the first pass that reads its advantages:
     // the passes on earlier steps run while it finishes
+    if (E.sub && ag) c->adapt0.valid = false;      // (ginner[0] is about to hold the selection's gradient)
     bool filled[PROMP_ETA_MAX] = {};      // steps whose primal cache this evaluation has written
     for (int k = 0; k < K; ++k) {
-        const float* th = (k == 0) ? c->theta : c->chain + (size_t)k * MNP;
+        const float* th = (k == 0) ? c->theta : E.chain + (size_t)k * MNP;
         const long long st = (k == 0) ? 0 : NP;
-        if (join_side(c, c->steps[k])) return -2;
+        if (join_side(c, W[k])) return -2;
         // the R-operator pass of this step (below) runs at these parameters on this slab: it reads the activations and means
         // back instead of recomputing them (primal cache, promp_kernels_chain.h)
         const bool cached = want_grad && primal_cache_on(c);
-        if (cached && ensure_primal_cache(c, c->steps[k])) return -2;
+        if (cached && ensure_primal_cache(c, W[k])) return -2;
         // promp_inner_adapt has left exactly this pass's results behind (see there) if nothing it read has changed since and
         // the clip of log_std at log(min_std) -- the one difference between the two -- is not active
-        const bool reuse = k == 0 && adapt0_stands(c, inner_kind, cached);
+        const bool reuse = k == 0 && !E.sub && adapt0_stands(c, inner_kind, cached);
         if (reuse) {                               // (with trainable step sizes it left its gradient in ginner[0] as well)
             c->adapt_passes_skipped += 1;
             filled[k] = cached;
@@ -762,24 +804,24 @@ int enqueue_meta(promp_ctx* c, float clip_eps, const float* eta_host, int inner_
         }
         PassReq q;
         q.theta = th; q.theta_stride = st; q.loss_kind = loss_kind_inner(inner_kind); q.clip_eps = clip_eps; q.clip_ls = k == 0;
-        q.red_mode = RED_STEP; q.cur = th; q.cur_stride = st; q.next = c->chain + (size_t)(k + 1) * MNP; q.scal = c->scal_inner + (size_t)k * M * 2;
+        q.red_mode = RED_STEP; q.cur = th; q.cur_stride = st; q.next = E.chain + (size_t)(k + 1) * MNP; q.scal = E.scal_inner + (size_t)k * M * 2;
         q.cache = cached ? 1 : 0;
         q.ginner = ag ? c->ginner + (size_t)k * MNP : nullptr;
-        if (launch_pass(c, c->steps[k], q)) return -2;
+        if (launch_pass(c, W[k], q)) return -2;
         filled[k] = cached;
     }
-    if (join_side(c, c->steps[K])) return -2;
+    if (join_side(c, W[K])) return -2;
     {
         PassReq q;
-        q.theta = c->chain + (size_t)K * MNP; q.theta_stride = NP; q.loss_kind = loss_kind_outer(outer_kind); q.clip_eps = clip_eps;
+        q.theta = E.chain + (size_t)K * MNP; q.theta_stride = NP; q.loss_kind = loss_kind_outer(outer_kind); q.clip_eps = clip_eps;
         q.fwd_only = !want_grad; q.red_mode = want_grad ? RED_OUTER : RED_SCAL; q.scal = c->scal_outer;
-        if (launch_pass(c, c->steps[K], q)) return -2;
+        if (launch_pass(c, W[K], q)) return -2;
     }
     if (want_grad) {
         for (int k = K - 1; k >= 0; --k) {
-            const float* th = (k == 0) ? c->theta : c->chain + (size_t)k * MNP;
+            const float* th = (k == 0) ? c->theta : E.chain + (size_t)k * MNP;
             const long long st = (k == 0) ? 0 : NP;
-            StepData& Sk = c->steps[k];
+            StepData& Sk = W[k];
             const bool dice = inner_kind == PROMP_INNER_DICE;
             if (dice && !Sk.has_dice) return fail(-3, "step %d has no DiCE rewards: call promp_set_dice_rewards first", k);
             if (ag) {
@@ -810,7 +852,7 @@ int enqueue_meta(promp_ctx* c, float clip_eps, const float* eta_host, int inner_
     }
     FinalArgs f;
     f.lam = c->lam; f.NP = NP; f.K = K; f.n_tasks = M;
-    f.scal_inner = c->scal_inner; f.scal_outer = c->scal_outer; f.red = c->red; f.want_grad = want_grad ? 1 : 0;
+    f.scal_inner = E.scal_inner; f.scal_outer = c->scal_outer; f.red = c->red; f.want_grad = want_grad ? 1 : 0;
     c->red_has_sizes = ag;
     const unsigned final_blocks = (unsigned)((red_count(c, ag) + 63) / 64);
     // several ranks (or an external collective: more global than local tasks): sums first, mean + Adam after the exchange
@@ -845,8 +887,12 @@ int enqueue_meta(promp_ctx* c, float clip_eps, const float* eta_host, int inner_
     } else if (split) PROMP_LAUNCH(k_mean_adam, dim3((NP + 1 + 255) / 256), 256, 0, c->stream, ad);
     else PROMP_LAUNCH(k_final_adam, dim3(final_blocks + 1), 256, 0, c->stream, f, ad);   // one rank: nothing in between
     HIPCHECK(hipGetLastError());
-    for (int k = 0; k <= K; ++k) c->steps[k].dirty = true;
+    for (int k = 0; k <= K; ++k) W[k].dirty = true;
     return 0;
+}
+int enqueue_meta(promp_ctx* c, float clip_eps, const float* eta_host, int inner_kind, int outer_kind, bool want_grad,
+                 bool do_adam, float lr, bool sizes_grad = true) {
+    return enqueue_meta_on(c, full_set(c), clip_eps, eta_host, inner_kind, outer_kind, want_grad, do_adam, lr, sizes_grad);
 }
 
 int upload_eta(promp_ctx* c, const float* eta) {
@@ -872,6 +918,91 @@ int alloc_step(promp_ctx* c, StepData& S) {
     if (S.path_mom.alloc(3 * P) || S.coeffs.alloc((size_t)M * c->coeff_stride)) return -2;
     if (S.work[0].alloc((size_t)c->max_work) || S.work[1].alloc((size_t)c->max_work)) return -2;
     for (Event* ev : {&S.ev_use, &S.ev_done, &S.ev_ready}) HIPCHECK(hipEventCreateWithFlags(&ev->h, hipEventDisableTiming));
+    return 0;
+}
+
+// ---- selections: subsampled constraint products -----------------------------------------------------------------------
+// Whatever replaces a step's layout drops its selection: old indices never address new rows.
+void clear_selection(promp_ctx* c, int step) {
+    if ((size_t)step >= c->sel.size() || !c->sel[step].on) return;
+    c->sel[step].on = false;
+    c->sel[step].gathered = false;
+    c->chvp_sel.valid = false;
+}
+int n_selected(const promp_ctx* c) {
+    int n = 0;
+    for (const Selection& L : c->sel) n += L.on ? 1 : 0;
+    return n;
+}
+// The compact slab of step k's selection, current: buffers sized by the selection, its tables on the device, and copies of the
+// selected paths' rows taken at the step's present data_version (promp_process_samples / promp_set_advantages after the
+// selection are seen).  On the main stream, behind the step's pending side-stream / copy-stream work.
+int ensure_sub(promp_ctx* c, int k) {
+    StepData& P = c->steps[k];
+    StepData& S = c->sub[k];
+    Selection& L = c->sel[k];
+    if (join_side(c, P)) return -2;
+    if (L.gathered && L.gathered_version == P.data_version) return 0;
+    const StepTables& t = L.tables;
+    const int M = c->d.n_tasks, n = (int)L.lay.idx.size(), R = (int)t.row_t.size();
+    const size_t O = c->d.obs_dim, A = c->d.act_dim;
+    if (R > S.cap_rows) {
+        if (S.obs.alloc(R * O) || S.act.alloc(R * A) || S.adv32.alloc(R) || S.old_mean.alloc(R * A)) return -2;
+        // (log_std in either layout: one row per row of the slab, or one per task)
+        if (S.old_ls.alloc((size_t)std::max(R, M) * A) || S.hcache.release() != hipSuccess) return -2;
+        S.cap_rows = R;
+    }
+    if (n > L.cap_paths) {
+        if (L.idx.alloc(n) || S.path_row_offsets.alloc((size_t)n + 1)) return -2;
+        L.cap_paths = n;
+    }
+    if (!S.obs_absmax) {
+        if (S.obs_absmax.alloc((size_t)M) || S.task_row_offsets.alloc((size_t)M + 1) || S.task_wg_offsets[0].alloc((size_t)M + 1)) return -2;
+        if (S.chain_slot_offsets.alloc((size_t)M + 1) || S.work[0].alloc((size_t)c->max_work)) return -2;
+        if (S.chain_segs.alloc((size_t)c->max_work) || S.chain_wg_offsets.alloc((size_t)c->max_work + 1)) return -2;
+    }
+    hipStream_t st = c->stream;
+    if (!L.tables_sent) {
+        HIPCHECK(hipMemcpyAsync(L.idx, L.lay.idx.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(S.path_row_offsets, t.pro.data(), sizeof(int) * (n + 1), hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(S.task_row_offsets, t.tro.data(), sizeof(int) * (M + 1), hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(S.chain_segs, t.segs.data(), sizeof(ChainSeg) * t.segs.size(), hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(S.chain_wg_offsets, t.wg_off.data(), sizeof(int) * t.wg_off.size(), hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(S.chain_slot_offsets, t.slot_chain.data(), sizeof(int) * (M + 1), hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(S.task_wg_offsets[0], t.two[0].data(), sizeof(int) * (M + 1), hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(S.work[0], t.work[0].data(), sizeof(WorkItem) * t.work[0].size(), hipMemcpyHostToDevice, st));
+        HIPCHECK(hipStreamSynchronize(st));        // (the sources may be replaced by the next selection)
+        S.n_paths = n; S.n_rows = R; S.n_work[0] = (int)t.work[0].size(); S.n_work[1] = 0;
+        S.n_chain_wg = (int)t.wg_off.size() - 1;
+        L.tables_sent = true;
+    }
+    GatherSelectionArgs g;
+    g.obs_in = P.obs; g.act_in = P.act; g.adv_in = P.adv32; g.mean_in = P.old_mean; g.ls_in = P.ls_per_row ? P.old_ls.p : nullptr;
+    g.obs = S.obs; g.act = S.act; g.adv = S.adv32; g.mean = S.old_mean; g.ls = S.old_ls;
+    g.sel_path = L.idx; g.src_row_offsets = P.path_row_offsets; g.dst_row_offsets = S.path_row_offsets;
+    g.O = (int)O; g.A = (int)A;
+    PROMP_LAUNCH(k_gather_selection, dim3(n), 256, 0, st, g);
+    HIPCHECK(hipGetLastError());
+    if (!P.ls_per_row) HIPCHECK(hipMemcpyAsync(S.old_ls, P.old_ls, sizeof(float) * M * A, hipMemcpyDeviceToDevice, st));
+    S.ls_per_row = P.ls_per_row; S.has_policy = P.has_policy; S.has_adv = P.has_adv;
+    S.data_version = P.data_version;
+    S.obs_range_valid = false;         // (the FP16 split's scales are those of the selected rows)
+    P.dirty = true;
+    L.gathered = true; L.gathered_version = P.data_version;
+    return 0;
+}
+// The evaluation set of the selections, every compact slab current.  Refuses unless every step has a selection (a product over
+// some steps' subsamples and other steps' whole slabs is no function anybody asked for) and for the DiCE inner objective
+// (TRPO-MAML has none; its coupling rows are not among the copies).
+int selection_set(promp_ctx* c, int inner_kind, EvalSet* E) {
+    const int K = c->d.num_inner_steps, n = n_selected(c);
+    if (n != K + 1) return fail(-3, "%d of %d steps have a selection: set one on every step (promp_set_step_selection) or on none", n, K + 1);
+    if (inner_kind == PROMP_INNER_DICE) return fail(-3, "the DiCE inner objective is not evaluated on a selection (TRPO-MAML has no DiCE inner type)");
+    for (int k = 0; k <= K; ++k)
+        if (c->steps[k].n_rows == 0) return fail(-3, "step %d has no data", k);
+    for (int k = 0; k <= K; ++k)
+        if (ensure_sub(c, k)) return -2;
+    *E = EvalSet{&c->sub, c->sel_chain, c->sel_scal_inner, &c->chvp_sel, true};
     return 0;
 }
 
@@ -1149,6 +1280,7 @@ int promp_upload_step(promp_ctx* c, int step, int n_paths, const int32_t* tpo, c
     StepScope sc(c, step, /*writes=*/true, /*needs_data=*/false);
     if (sc.rc) return sc.rc;
     StepData& S = sc.S();
+    clear_selection(c, step);
     if (set_step_layout(c, S, c->stream, false, n_paths, tpo, pro)) return -2;
     return copy_step_data(c, S, c->stream, obs, act, rew, old_mean, old_ls, ls_per_row);
 }
@@ -1201,6 +1333,7 @@ int promp_commit_step(promp_ctx* c, int step) {
     if (c->back.empty() || !c->back[step].staged) return fail(-3, "step %d has nothing staged", step);
     // uses of the outgoing set that are still unmarked get their mark now, while "everything enqueued so far" is tight
     if (mark_use(c, c->steps[step])) return -2;
+    clear_selection(c, step);
     std::swap(c->steps[step], c->back[step]);
     c->steps[step].staged = false;
     c->steps[step].data_version = ++c->version_counter;
@@ -1430,6 +1563,53 @@ int promp_set_advantages(promp_ctx* c, int step, const float* adv) {
     HIPCHECK(hipMemcpyAsync(S.adv32, adv, sizeof(float) * S.n_rows, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipStreamSynchronize(c->stream));
     S.has_adv = true;
+    return 0;
+}
+
+int promp_set_step_selection(promp_ctx* c, int step, int n_sel, const int32_t* path_idx) {
+    StepScope sc(c, step);
+    if (sc.rc) return sc.rc;
+    if (n_sel < 0) return fail(-1, "n_sel %d is negative", n_sel);
+    if (n_sel == 0 || !path_idx) {
+        if ((size_t)step < c->sel.size() && c->sel[step].on) {
+            clear_selection(c, step);
+            ++c->version_counter;
+        }
+        return 0;
+    }
+    const StepData& P = sc.S();
+    const int M = c->d.n_tasks, K = c->d.num_inner_steps;
+    if (P.n_rows == 0 || (int)P.lay_tpo.size() != M + 1) return fail(-3, "step %d has no data", step);
+    // everything that can refuse comes first: the selection, the compact slab's tables, the buffers every selection shares
+    SelectionLayout lay;
+    StepTables tables;
+    std::string why;
+    if (const int rc = build_selection(M, P.n_paths, P.lay_tpo.data(), P.lay_pro.data(), n_sel, path_idx, &lay, &why)) return fail_plan(rc, why);
+    if (const int rc = build_step_tables(c->n_cus, c->max_work, lay.pro[n_sel], n_sel, M, n_sel, lay.tpo.data(), lay.pro.data(), &tables, &why))
+        return fail_plan(rc, why);
+    if (c->sel.empty()) {
+        const size_t MNP = (size_t)M * c->NP;
+        if (c->sel_chain.alloc((size_t)(K + 1) * MNP) || c->sel_scal_inner.alloc((size_t)K * M * 2)) return -2;
+        c->sub.resize(K + 1);
+        c->sel.resize(K + 1);
+    }
+    Selection& L = c->sel[step];
+    L.on = true; L.lay = std::move(lay); L.tables = std::move(tables);
+    L.tables_sent = false; L.gathered = false;
+    c->chvp_sel.valid = false;             // (its caches hold another selection's rows)
+    ++c->version_counter;
+    return 0;
+}
+
+int promp_step_selection(promp_ctx* c, int step) {
+    StepScope sc(c, step);
+    if (sc.rc) return sc.rc;
+    return ((size_t)step < c->sel.size() && c->sel[step].on) ? (int)c->sel[step].lay.idx.size() : 0;
+}
+
+int promp_use_selection(promp_ctx* c, int on) {
+    NEED_CTX(c);
+    c->use_sel = on != 0;
     return 0;
 }
 
@@ -1713,6 +1893,7 @@ static int begin_fixed_rollout(StepScope& sc, int B, int T) {
     for (int p = 0; p <= M * B; ++p) pro[p] = p * T;
     if (sc.open(/*writes=*/true, /*needs_data=*/false)) return sc.rc;
     StepData& S = sc.S();
+    clear_selection(c, sc.step);
     if (set_step_layout(c, S, c->stream, false, M * B, tpo.data(), pro.data())) return -2;
     S.has_policy = true;
     S.ls_per_row = 0;
@@ -1799,6 +1980,7 @@ int promp_end_collection(promp_ctx* c, int step, int n_paths, const int32_t* tas
     }
     if (pro[n_paths] > c->d.max_rows) return fail(-1, "%d collected rows exceed max_rows = %d", pro[n_paths], c->d.max_rows);
     if (sc.open(/*writes=*/true, /*needs_data=*/false)) return sc.rc;
+    clear_selection(c, step);
     if (set_step_layout(c, S, c->stream, false, n_paths, task_path_offsets, pro.data())) return -2;
     // the finished episodes: staging rows -> slab rows in path order
     if (c->rollout_buf.reserve(sizeof(int32_t) * 2 * (size_t)n_paths, 2)) return -2;
@@ -1910,8 +2092,13 @@ int promp_download_step(promp_ctx* c, int step, float* obs, float* act, float* r
 int promp_meta_grad(promp_ctx* c, float clip_eps, const float* eta, int inner_kind, int outer_kind, float* grad_out,
                     float* stats_out) {
     if (!c || !eta) return fail(-1, "NULL argument");
+    EvalSet E = full_set(c);
+    if (c->use_sel && outer_kind == PROMP_OUTER_KL) {        // the constraint on the selections (promp_use_selection)
+        const int rc = selection_set(c, inner_kind, &E);
+        if (rc) return rc;
+    }
     if (upload_eta(c, eta)) return -2;
-    if (enqueue_meta(c, clip_eps, eta, inner_kind, outer_kind, true, false, 0.f)) return -2;
+    if (enqueue_meta_on(c, E, clip_eps, eta, inner_kind, outer_kind, true, false, 0.f, true)) return -2;
     if (grad_out && params_out(c, grad_out, c->grad_mean, 1)) return -2;
     if (stats_out && copy_out(c, stats_out, c->stats, c->d.num_inner_steps + 2)) return -2;
     HIPCHECK(hipStreamSynchronize(c->stream));
@@ -1924,20 +2111,22 @@ int promp_meta_grad(promp_ctx* c, float clip_eps, const float* eta, int inner_ki
 // The terms that differentiate the J_k are contracted with grad_{theta_K} KL, which is zero where TRPO builds the
 // product: at the parameters the samples were drawn with (old distribution == adapted policy).  2K + 1 R-operator passes.
 // (the direction is in c->grad_mean, the sums over the tasks -- all-reduced -- are left in c->red)
-static int enqueue_constraint_hvp(promp_ctx* c, int inner_kind, int refresh_chain) {
+static int enqueue_constraint_hvp(promp_ctx* c, const EvalSet& E, int inner_kind, int refresh_chain) {
+    std::vector<StepData>& W = *E.steps;
+    ChvpRec& R = *E.chvp;
     if (sharded_without_comm(c))
         return fail(-3, "this context holds %d of %d tasks and has no communicator: the product would be this rank's share only "
                         "(promp_comm_init first)", c->d.n_tasks, c->d.n_tasks_global);
     const int K = c->d.num_inner_steps, M = c->d.n_tasks, NP = c->NP;
     const size_t MNP = (size_t)M * NP;
     for (int k = 0; k <= K; ++k) {
-        if (c->steps[k].n_rows == 0) return fail(-3, "step %d has no data", k);
-        if (join_side(c, c->steps[k])) return -2;
+        if (W[k].n_rows == 0) return fail(-3, "step %d has no data", k);
+        if (join_side(c, W[k])) return -2;
     }
     if (!c->wbuf && c->wbuf.alloc(MNP)) return -2;
     auto theta_of = [&](int k, long long* stride) -> const float* {
         *stride = (k == 0) ? 0 : NP;
-        return (k == 0) ? c->theta : c->chain + (size_t)k * MNP;
+        return (k == 0) ? c->theta : E.chain + (size_t)k * MNP;
     };
     const int lk = loss_kind_inner(inner_kind);
     long long st = 0;
@@ -1947,37 +2136,37 @@ static int enqueue_constraint_hvp(promp_ctx* c, int inner_kind, int refresh_chai
     // meta-objective's cache (enqueue_meta).
     const bool use_cache = primal_cache_on(c);
     if (refresh_chain) {
-        c->chvp.valid = false;
+        R.valid = false;
         for (int k = 0; k <= K && use_cache; ++k)
-            if (ensure_primal_cache(c, c->steps[k])) return -2;
+            if (ensure_primal_cache(c, W[k])) return -2;
         for (int k = 0; k < K; ++k) {
             const float* th = theta_of(k, &st);
-            if (k == 0 && adapt0_stands(c, inner_kind, use_cache)) {       // promp_inner_adapt has just run exactly this pass
+            if (k == 0 && !E.sub && adapt0_stands(c, inner_kind, use_cache)) {       // promp_inner_adapt has just run exactly this pass
                 c->adapt_passes_skipped += 1;
                 continue;
             }
             PassReq q;
             q.theta = th; q.theta_stride = st; q.loss_kind = lk; q.clip_ls = k == 0;
-            q.red_mode = RED_STEP; q.cur = th; q.cur_stride = st; q.next = c->chain + (size_t)(k + 1) * MNP; q.scal = c->scal_inner + (size_t)k * M * 2;
+            q.red_mode = RED_STEP; q.cur = th; q.cur_stride = st; q.next = E.chain + (size_t)(k + 1) * MNP; q.scal = E.scal_inner + (size_t)k * M * 2;
             q.cache = use_cache ? 1 : 0;
-            if (launch_pass(c, c->steps[k], q)) return -2;
+            if (launch_pass(c, W[k], q)) return -2;
         }
         if (use_cache) {
             PassReq q;
             q.theta = theta_of(K, &q.theta_stride); q.loss_kind = LOSS_KL; q.clip_ls = K == 0; q.cache = 1;
-            if (launch_pass(c, c->steps[K], q)) return -2;
-            c->chvp.valid = true; c->chvp.theta_version = c->theta_version; c->chvp.sizes_version = c->sizes_version;
-            c->chvp.inner_kind = inner_kind; c->chvp.min_log_std = c->min_log_std;
+            if (launch_pass(c, W[K], q)) return -2;
+            R.valid = true; R.theta_version = c->theta_version; R.sizes_version = c->sizes_version;
+            R.inner_kind = inner_kind; R.min_log_std = c->min_log_std;
             for (int k = 0; k <= K; ++k) {
-                c->chvp.data_version[k] = c->steps[k].data_version;
-                c->chvp.tag[k] = c->steps[k].cache_tag;
+                R.data_version[k] = W[k].data_version;
+                R.tag[k] = W[k].cache_tag;
             }
         }
     }
-    const bool rec_ok = use_cache && c->chvp.valid && c->chvp.theta_version == c->theta_version && c->chvp.sizes_version == c->sizes_version &&
-                        c->chvp.inner_kind == inner_kind && c->chvp.min_log_std == c->min_log_std;
+    const bool rec_ok = use_cache && R.valid && R.theta_version == c->theta_version && R.sizes_version == c->sizes_version &&
+                        R.inner_kind == inner_kind && R.min_log_std == c->min_log_std;
     auto cache_ok = [&](int k) {
-        return rec_ok && c->steps[k].hcache && c->chvp.data_version[k] == c->steps[k].data_version && c->chvp.tag[k] == c->steps[k].cache_tag;
+        return rec_ok && W[k].hcache && R.data_version[k] == W[k].data_version && R.tag[k] == W[k].cache_tag;
     };
     PROMP_LAUNCH(k_replicate, dim3((NP + 255) / 256), 256, 0, c->stream, c->vbuf, c->grad_mean, NP, M);
     const dim3 eg((NP + 255) / 256, M);
@@ -1986,7 +2175,7 @@ static int enqueue_constraint_hvp(promp_ctx* c, int inner_kind, int refresh_chai
         q.hvp = true; q.theta = theta_of(k, &q.theta_stride); q.loss_kind = kind; q.clip_ls = k == 0;
         q.cache = cache_ok(k) ? 2 : 0;
         c->chvp_cached_passes += q.cache ? 1 : 0;
-        return launch_pass(c, c->steps[k], q);
+        return launch_pass(c, W[k], q);
     };
     for (int k = 0; k < K; ++k) {                      // u = J_{K-1} ... J_0 v
         if (pass(k, lk)) return -2;
@@ -2001,19 +2190,24 @@ static int enqueue_constraint_hvp(promp_ctx* c, int inner_kind, int refresh_chai
     HIPCHECK(hipGetLastError());
     FinalArgs f;
     f.lam = c->wbuf; f.NP = NP; f.K = K; f.n_tasks = M;
-    f.scal_inner = c->scal_inner; f.scal_outer = c->scal_outer; f.red = c->red; f.want_grad = 1;
+    f.scal_inner = E.scal_inner; f.scal_outer = c->scal_outer; f.red = c->red; f.want_grad = 1;
     c->red_has_sizes = false;
     PROMP_LAUNCH(k_reduce_final, dim3((NP + K + 2 + 63) / 64), 256, 0, c->stream, f);
     HIPCHECK(hipGetLastError());
     if (exchange_sums(c, c->red, (size_t)NP)) return -4;
-    for (int k = 0; k <= K; ++k) c->steps[k].dirty = true;
+    for (int k = 0; k <= K; ++k) W[k].dirty = true;
     return 0;
 }
 
 int promp_constraint_hvp(promp_ctx* c, int inner_kind, const float* v, int refresh_chain, float* out) {
     if (!c || !v || !out) return fail(-1, "NULL argument");
+    EvalSet E = full_set(c);
+    if (c->use_sel) {
+        const int rc = selection_set(c, inner_kind, &E);
+        if (rc) return rc;
+    }
     if (params_in(c, c->grad_mean, v, 1)) return -2;
-    const int rc = enqueue_constraint_hvp(c, inner_kind, refresh_chain);
+    const int rc = enqueue_constraint_hvp(c, E, inner_kind, refresh_chain);
     if (rc) return rc;
     if (params_out(c, out, c->red, 1)) return -2;
     const float inv = 1.0f / (float)c->d.n_tasks_global;
@@ -2032,6 +2226,12 @@ int promp_cg_solve(promp_ctx* c, int inner_kind, const float* b, int cg_iters, f
     if (sharded_without_comm(c))
         return fail(-3, "this context holds %d of %d tasks and has no communicator: the products would be this rank's share only "
                         "(promp_comm_init first)", c->d.n_tasks, c->d.n_tasks_global);
+    // every step has a selection: the products run on the compact slabs; some have one: refused before anything is written
+    EvalSet E = full_set(c);
+    if (n_selected(c) > 0) {
+        const int rc = selection_set(c, inner_kind, &E);
+        if (rc) return rc;
+    }
     const int NP = c->NP;
     // (one guard each: a call whose second allocation failed must not leave the next one running k_cg_step without its scalars)
     if (!c->cg_buf && c->cg_buf.alloc((size_t)7 * NP)) return -2;
@@ -2051,12 +2251,12 @@ int promp_cg_solve(promp_ctx* c, int inner_kind, const float* b, int cg_iters, f
         PROMP_LAUNCH(k_cg_displace, dim3((NP + 255) / 256), 256, 0, c->stream, c->theta, th0, v, s, NP);
         c->theta_version = ++c->version_counter;
         c->ls_known = false;
-        return enqueue_meta(c, 0.f, eta, inner_kind, PROMP_OUTER_KL, true, false, 0.f, /*sizes_grad=*/false);
+        return enqueue_meta_on(c, E, 0.f, eta, inner_kind, PROMP_OUTER_KL, true, false, 0.f, /*sizes_grad=*/false);
     };
     if (!exact) {
         HIPCHECK(hipMemcpyAsync(th0, c->theta, sizeof(float) * NP, hipMemcpyDeviceToDevice, c->stream));
         if (hvp_mode == 1) {                                      // one-sided: the gradient at theta0 itself, once
-            if (enqueue_meta(c, 0.f, eta, inner_kind, PROMP_OUTER_KL, true, false, 0.f, /*sizes_grad=*/false)) return -2;
+            if (enqueue_meta_on(c, E, 0.f, eta, inner_kind, PROMP_OUTER_KL, true, false, 0.f, /*sizes_grad=*/false)) return -2;
             HIPCHECK(hipMemcpyAsync(th0 + NP, c->grad_mean, sizeof(float) * NP, hipMemcpyDeviceToDevice, c->stream));
         }
     }
@@ -2064,7 +2264,7 @@ int promp_cg_solve(promp_ctx* c, int inner_kind, const float* b, int cg_iters, f
     auto product = [&](const float* v, int mode) -> int {        // hd = (H + reg I) v and the vector updates of `mode`
         if (exact) {
             HIPCHECK(hipMemcpyAsync(c->grad_mean, v, sizeof(float) * NP, hipMemcpyDeviceToDevice, c->stream));
-            const int rc = enqueue_constraint_hvp(c, inner_kind, fresh ? 0 : 1);
+            const int rc = enqueue_constraint_hvp(c, E, inner_kind, fresh ? 0 : 1);
             if (rc) return rc;
             fresh = true;
             a.g_ahead = c->red; a.g_behind = nullptr; a.div_h = 1.f; a.mul_s = 1.0f / (float)c->d.n_tasks_global;

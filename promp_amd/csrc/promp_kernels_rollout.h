@@ -143,6 +143,32 @@ __global__ void __launch_bounds__(256) k_gather_paths(GatherPathsArgs a) {
     }
 }
 
+// A selection of a step's paths (promp_set_step_selection) copied into its compact slab, in path order: everything a policy pass
+// reads of a row.  Selected path p = paths[sel_path[p]] of the step; its rows go to [dst_row_offsets[p], dst_row_offsets[p + 1]).
+struct GatherSelectionArgs {
+    const float *obs_in, *act_in, *adv_in, *mean_in, *ls_in;   // the step's slabs (ls_in: NULL when log_std is one row per task)
+    float *obs, *act, *adv, *mean, *ls;                         // the compact slab
+    const int *sel_path, *src_row_offsets, *dst_row_offsets;
+    int O, A;
+};
+// grid = selected paths, block = 256
+__global__ void __launch_bounds__(256) k_gather_selection(GatherSelectionArgs a) {
+    const int p = blockIdx.x, s0 = a.src_row_offsets[a.sel_path[p]], r0 = a.dst_row_offsets[p], n = a.dst_row_offsets[p + 1] - r0;
+    const int W = a.O + 1 + (a.ls_in ? 3 : 2) * a.A;
+    for (int e = threadIdx.x; e < n * W; e += 256) {
+        const int t = e / W;
+        int k = e - t * W;
+        const long long src = s0 + t, dst = r0 + t;
+        if (k < a.O) { a.obs[dst * a.O + k] = a.obs_in[src * a.O + k]; continue; }
+        k -= a.O;
+        if (k == 0) { a.adv[dst] = a.adv_in[src]; continue; }
+        k -= 1;
+        if (k < a.A) a.act[dst * a.A + k] = a.act_in[src * a.A + k];
+        else if (k < 2 * a.A) a.mean[dst * a.A + (k - a.A)] = a.mean_in[src * a.A + (k - a.A)];
+        else a.ls[dst * a.A + (k - 2 * a.A)] = a.ls_in[src * a.A + (k - 2 * a.A)];
+    }
+}
+
 enum { POINT_REWARD_DENSE = 0, POINT_REWARD_DENSE_SQUARED = 1, POINT_REWARD_SPARSE = 2 };
 
 // |p - c|_2 the way a row-wise 2-norm rounds it (squares, sum, root; no fused multiply-add): the sparse reward compares the

@@ -4,6 +4,7 @@
 //                family of pass kernels serves a (padded) shape
 //   Stage A      which Gram and fit kernels promp_process_samples launches for a baseline kind and an observation width
 //   step tables  the work tables, the chain kernels' segment table, the time indices and the task row offsets of a sampling step
+//   selections   which paths of a step a subsampled constraint product keeps, and the layout of the compact slab that holds them
 //   switches     the PROMP_* environment switches the above depend on, read once
 //
 // HIP-free: the C ABI header and the standard library only, so plain `g++ -std=c++17` compiles it alone and
@@ -13,6 +14,7 @@
 #include "../../include/promp_hip.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -495,5 +497,49 @@ inline int build_step_tables(int n_cus, int max_work, int max_rows, int max_path
     out->wg_off = std::move(T.wg_off); out->slot_chain = std::move(T.slot_off);
     out->segs = std::move(T.segs);
     for (int t = 0; t < 2; ++t) { out->two[t] = std::move(two[t]); out->work[t] = std::move(work[t]); }
+    return 0;
+}
+
+// ---- selections (promp_set_step_selection) ---------------------------------------------------------------------------------
+// How many of a task's P paths a subsampling factor f in (0, 1] keeps: floor(f P), at least one.  The guard keeps products that
+// are whole numbers on paper from landing just below them (0.29 * 100 = 28.999999999999996).
+inline int selection_count(double f, int n_paths) {
+    const int n = (int)std::floor(f * (double)n_paths + 1e-6);
+    return n < 1 ? 1 : n > n_paths ? n_paths : n;
+}
+// A selection of a step's paths and the layout of the slab that holds copies of their rows in path order: what
+// promp_upload_step would be given for the selected paths alone.
+struct SelectionLayout {
+    std::vector<int> idx;          // [n_sel] the selected paths, strictly increasing
+    std::vector<int> tpo, pro;     // [tasks + 1] / [n_sel + 1] offsets of the compact slab
+};
+// Checks a selection against the step's layout (tpo [M + 1], pro [n_paths + 1], both well-formed) before anything is indexed by
+// it: indices inside the step, strictly increasing, at least one path left in every task.  Nothing is written on refusal.
+inline int build_selection(int M, int n_paths, const int32_t* tpo, const int32_t* pro, int n_sel, const int32_t* idx,
+                           SelectionLayout* out, std::string* why) {
+    if (n_sel < 0) return plan_fail(why, -1, "n_sel %d is negative", n_sel);
+    if (n_sel < 1 || !idx) return plan_fail(why, -1, "an empty selection (n_sel = 0 or NULL clears the step's selection)");
+    if (n_sel > n_paths) return plan_fail(why, -1, "selection of %d paths from a step of %d", n_sel, n_paths);
+    for (int j = 0; j < n_sel; ++j) {
+        if (idx[j] < 0 || idx[j] >= n_paths)
+            return plan_fail(why, -1, "selection entry %d: path index %d out of range [0, %d)", j, idx[j], n_paths);
+        if (j > 0 && idx[j] == idx[j - 1]) return plan_fail(why, -1, "selection entry %d repeats path %d", j, idx[j]);
+        if (j > 0 && idx[j] < idx[j - 1])
+            return plan_fail(why, -1, "selection is not sorted: entry %d (path %d) follows path %d", j, idx[j], idx[j - 1]);
+    }
+    SelectionLayout L;
+    L.idx.assign(idx, idx + n_sel);
+    L.tpo.assign(M + 1, 0);
+    L.pro.assign(n_sel + 1, 0);
+    int j = 0;
+    for (int i = 0; i < M; ++i) {
+        while (j < n_sel && idx[j] < tpo[i + 1]) {
+            L.pro[j + 1] = L.pro[j] + (pro[idx[j] + 1] - pro[idx[j]]);
+            ++j;
+        }
+        if (j == L.tpo[i]) return plan_fail(why, -1, "selection leaves task %d with no path", i);
+        L.tpo[i + 1] = j;
+    }
+    *out = std::move(L);
     return 0;
 }

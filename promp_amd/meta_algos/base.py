@@ -65,7 +65,8 @@ class MAMLAlgo(MetaAlgo):
         the first upload: a context that grows between two uploads would drop the slabs uploaded so far."""
         missing = [sd for k, sd in enumerate(all_samples_data) if self.session.resident_slot(sd) != k]
         if missing:
-            self.session.ensure(max(sum(len(d['advantages']) for d in sd) for sd in missing), self.meta_batch_size)
+            n_paths = lambda sd: sum(len(d['path_lengths']) if 'path_lengths' in d else 1 for d in sd)
+            self.session.ensure(max(sum(len(d['advantages']) for d in sd) for sd in missing), max(n_paths(sd) for sd in missing))
         for k, sd in enumerate(all_samples_data):
             if self.session.resident_slot(sd) != k:   # not resident, or resident in another slot (an extra process_samples call)
                 self._upload_into(k, sd)

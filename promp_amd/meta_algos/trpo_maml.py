@@ -15,10 +15,13 @@ class _DeviceEvaluator(object):
         self.algo = algo
         self._memo = None
         self._gmemo = None       # (key, loss gradient): gradient() twice at one state is one device evaluation
+        self._selected = False   # use_selection: the constraint's gradient and product run on the subsample
 
     def _key(self):
         ctx = self.ctx
-        return (id(ctx), ctx.state_version(), self.algo.inner_kind)
+        # (setting or clearing a selection moves state_version; the switch is named as well: nothing evaluated on a subsample is
+        #  ever served for the whole batch, or the reverse)
+        return (id(ctx), ctx.state_version(), self.algo.inner_kind, self._selected)
 
     def objectives_ride_on_gradient(self):
         """the loss gradient's pass computes the surrogate loss and the mean KL on its way (promp_meta_grad returns them): where that
@@ -63,10 +66,10 @@ class _DeviceEvaluator(object):
         after / KL after: conjugate_gradient_optimizer.py:227-236, trpo_maml.py:170-191); the second question is answered from
         the first one's pass as long as nothing the evaluation reads has been replaced (promp_state_version)."""
         ctx = self.ctx
-        key = (id(ctx), ctx.state_version(), self.algo.inner_kind)
+        key = self._key()
         if self._memo is None or self._memo[0] != key:
             r = self.algo.session.meta_eval(0.0, self._eta(), self.algo.inner_kind, _lib.OUTER_RATIO)
-            self._memo = ((id(ctx), ctx.state_version(), self.algo.inner_kind), r)
+            self._memo = (self._key(), r)
         return self._memo[1]
 
     def loss(self):          # -mean_i mean(ratio * adv) at theta'_i   (trpo_maml.py:135,150)
@@ -107,6 +110,30 @@ class _DeviceEvaluator(object):
             return None
         return self.ctx.cg_solve(np.asarray(b, dtype=np.float32), cg_iters, reg_coeff, eps, hvp_mode, residual_tol, self.algo.inner_kind)
 
+    # ---- subsampled constraint products (ConjugateGradientOptimizer's subsample_factor) ----
+    def select_paths(self, factor):
+        """draws this rank's subsample -- per sampling step and task max(1, floor(factor P)) of its P paths, without replacement,
+        sorted -- and sets it in the context: -> the counts, [step][task].  Not a prefix: the sampler files paths in completion
+        order, which goes with episode length.  (Samples handed in as plain dicts are one path per task unless they carry
+        'path_lengths', session.upload_samples: one path is all there is to keep.)"""
+        from ..optimizers.conjugate_gradient_optimizer import subsample_counts
+        ctx, kept = self.ctx, []
+        for k in range(ctx.K + 1):
+            tpo = ctx.step_tpo[k]
+            counts = subsample_counts(factor, np.diff(tpo))
+            ctx.set_step_selection(k, np.concatenate([tpo[i] + np.sort(np.random.choice(int(tpo[i + 1] - tpo[i]), n, replace=False))
+                                                      for i, n in enumerate(counts)]))
+            kept.append(counts)
+        return kept
+
+    def use_selection(self, on):
+        """the constraint's gradient and exact product (host loop, ranks under an external collective) on the subsample / the batch"""
+        self._selected = bool(on)
+        self.ctx.use_selection(on)
+
+    def clear_selection(self):
+        self.ctx.clear_selections()
+
     def get_theta(self):
         return self.ctx.get_theta()
 
@@ -118,7 +145,9 @@ class TRPOMAML(MAMLAlgo):
     """
     Args (trpo_maml.py:23-31): policy, name, step_size (trust region), inner_type in {'log_likelihood',
     'likelihood_ratio'}, exploration (E-MAML), inner_lr, meta_batch_size, num_inner_grad_steps,
-    trainable_inner_step_size; plus hvp_approach in {'finite_difference' (the reference's, default), 'exact'}
+    trainable_inner_step_size; plus hvp_approach in {'finite_difference' (the reference's, default), 'exact'} and
+    subsample_factor in (0, 1] (ConjugateGradientOptimizer: the products of the conjugate-gradient solve on a subsample of the
+    paths, redrawn in every optimize_policy; 1.: the whole batch)
 
     trainable_inner_step_size is accepted and, as in the reference, changes nothing here: the conjugate-gradient step is over
     theta, the step sizes stay np.full(Theta, inner_lr) and are constants of the objective, its gradient and the constraint.
@@ -126,7 +155,7 @@ class TRPOMAML(MAMLAlgo):
     trains_step_sizes = False
 
     def __init__(self, *args, name='trpo_maml', step_size=0.01, inner_type='likelihood_ratio', exploration=False,
-                 hvp_approach='finite_difference', **kwargs):
+                 hvp_approach='finite_difference', subsample_factor=1., **kwargs):
         super(TRPOMAML, self).__init__(*args, **kwargs)
         assert hvp_approach in ('finite_difference', 'exact')
         assert inner_type in ['log_likelihood', 'likelihood_ratio', 'dice']
@@ -141,6 +170,7 @@ class TRPOMAML(MAMLAlgo):
         if exploration:      # trpo_maml.py:41-42
             self._optimization_keys.append('adj_avg_rewards')
         self.optimizer = ConjugateGradientOptimizer(
+            subsample_factor=subsample_factor,
             hvp_approach=ExactDeviceHvp() if hvp_approach == 'exact' else FiniteDifferenceHvp())
         self.optimizer.build_graph(_DeviceEvaluator(self), step_size)
 

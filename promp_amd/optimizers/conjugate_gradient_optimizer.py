@@ -49,6 +49,12 @@ def conjugate_gradients(f_Ax, b, cg_iters=10, verbose=False, residual_tol=1e-10)
     return solution
 
 
+def subsample_counts(factor, paths_per_task):
+    """paths a subsampling factor keeps of each task: floor(factor * P), at least one.  (The 1e-6 keeps products that are whole
+    numbers on paper from landing below them: int(0.29 * 100) is 28.)"""
+    return [max(1, int(np.floor(factor * int(p) + 1e-6))) for p in paths_per_task]
+
+
 class FiniteDifferenceHvp(object):
     """Hessian-vector products of the constraint from gradients at displaced parameters:
         symmetric:  H x ~ (grad c(theta + eps x) - grad c(theta - eps x)) / (2 eps)
@@ -95,7 +101,9 @@ class ExactDeviceHvp(object):
     reference, which only has the finite-difference approach (SURVEY 8f row 2 asks for this one); FiniteDifferenceHvp stays
     the default and the parity mode.  Exact where the constraint is evaluated by TRPO: at the parameters the last step's
     samples were drawn with (there the constraint's gradient wrt the adapted parameters is zero, and with it every term
-    that differentiates the adaptation Jacobians)."""
+    that differentiates the adaptation Jacobians).  On a subsample (ConjugateGradientOptimizer's subsample_factor < 1) the
+    product is J_S^T H_KL J_S over the selected paths: positive semi-definite, but no longer the full Hessian -- the parameters
+    adapted on the subsample are not the ones the last step was sampled with, so the dropped third-order term is not zero."""
 
     def __init__(self, allow_fallback=True, fallback_eps=1e-5, fallback_symmetric=True):
         """allow_fallback: where the exact product does not exist (below) use a FiniteDifferenceHvp(fallback_eps,
@@ -140,15 +148,24 @@ class ExactDeviceHvp(object):
 
 class ConjugateGradientOptimizer(object):
     """
-    Args: cg_iters=10, reg_coeff=0 (Tikhonov term added to H), subsample_factor=1. (kept for signature compatibility:
-    the device evaluates the constraint on the whole batch), backtrack_ratio=0.8, max_backtracks=15, debug_nan=False,
-    accept_violation=False, hvp_approach=None (a FiniteDifferenceHvp by default)
+    Args: cg_iters=10, reg_coeff=0 (Tikhonov term added to H), subsample_factor=1., backtrack_ratio=0.8, max_backtracks=15,
+    debug_nan=False, accept_violation=False, hvp_approach=None (a FiniteDifferenceHvp by default)
 
-    After optimize(), `last` holds loss_before, descent_direction, initial_step_size, n_backtracks and rejected.
+    subsample_factor in (0, 1] (rllab's TRPO; the reference stores the argument and never reads it): the products x -> H x of
+    the solve and the closing d.H d see a subsample of the paths -- per task and sampling step max(1, floor(f P)) of its P paths,
+    drawn anew with np.random.choice(P, n, replace=False) in every optimize() -- while the loss, its gradient, the line search
+    and constraint_val() see the whole batch.  The constraint on a subsample is the same function on fewer paths: inner
+    adaptation on the selected paths of steps 0..K-1, KL mean over those of step K.  With ExactDeviceHvp the product is then
+    J_S^T H_KL J_S, not the full Hessian (see there).  1. (the default) selects nothing and changes nothing.
+
+    After optimize(), `last` holds loss_before, descent_direction, initial_step_size, n_backtracks, rejected and
+    subsample_paths (per sampling step the paths kept of each task; None without subsampling).
     """
 
     def __init__(self, cg_iters=10, reg_coeff=0, subsample_factor=1., backtrack_ratio=0.8, max_backtracks=15,
                  debug_nan=False, accept_violation=False, hvp_approach=None, device_solve=True):
+        if not 0 < subsample_factor <= 1:
+            raise ValueError('subsample_factor must be in (0, 1], got %r' % (subsample_factor,))
         self._device_solve = bool(device_solve)
         self._cg_iters = cg_iters
         self._reg_coeff = reg_coeff
@@ -164,7 +181,8 @@ class ConjugateGradientOptimizer(object):
         self.last = None
 
     def build_graph(self, evaluator, leq_constraint_value):
-        """evaluator: loss(), constraint_val(), gradient(), constraint_gradient(), get_theta(), set_theta(theta)"""
+        """evaluator: loss(), constraint_val(), gradient(), constraint_gradient(), get_theta(), set_theta(theta); with
+        subsample_factor < 1 also select_paths(factor) -> kept paths per step and task, use_selection(on), clear_selection()"""
         self._ev = evaluator
         self._max_constraint_val = leq_constraint_value
         self._hvp_approach.build_graph(evaluator, self._reg_coeff)
@@ -223,17 +241,26 @@ class ConjugateGradientOptimizer(object):
         logger.log('trust-region step: conjugate gradients')
         loss_before = self.loss()
         grad = self.gradient()
-        solved = self._solve_on_device(grad)
-        if solved is not None:
-            direction, curved = solved
-        else:
-            curvature = self._hvp_approach.build_eval()
-            direction = conjugate_gradients(curvature, grad, cg_iters=self._cg_iters)
-            curved = direction.dot(curvature(direction))
+        # the products of the solve and the closing one on a subsample of the paths; everything else on the whole batch
+        kept = ev.select_paths(self._subsample_factor) if self._subsample_factor < 1 else None
+        try:
+            solved = self._solve_on_device(grad)
+            if solved is not None:
+                direction, curved = solved
+            else:
+                if kept is not None:
+                    ev.use_selection(True)
+                curvature = self._hvp_approach.build_eval()
+                direction = conjugate_gradients(curvature, grad, cg_iters=self._cg_iters)
+                curved = direction.dot(curvature(direction))
+        finally:
+            if kept is not None:
+                ev.use_selection(False)
+                ev.clear_selection()
         with np.errstate(invalid='ignore'):       # negative curvature along the direction: NaN, rejected below (as the reference, :264-268)
             length = np.sqrt(2.0 * self._max_constraint_val * (1. / (curved + 1e-8)))
         self.last = dict(loss_before=loss_before, gradient=grad, descent_direction=direction, initial_step_size=float(length),
-                         n_backtracks=0, rejected=False)
+                         n_backtracks=0, rejected=False, subsample_paths=kept)
         if np.isnan(length):
             logger.log('trust-region step: step length is NaN, update rejected')
             self.last['rejected'] = True

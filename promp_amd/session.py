@@ -223,12 +223,17 @@ class DeviceSession:
         return self.upload_serial[slot]
 
     def upload_samples(self, slot, samples_data_meta_batch):
-        """Upload processed samples (list[M] of dicts) that did not come from this session's processor."""
+        """Upload processed samples (list[M] of dicts) that did not come from this session's processor.  A task's rows are one
+        path unless its dict says otherwise under 'path_lengths' (the rows of its paths, in order): what is selected per path --
+        TRPOMAML's subsample_factor -- needs to know them."""
         assert len(samples_data_meta_batch) == self.M
         n = [len(sd['advantages']) for sd in samples_data_meta_batch]
+        lens = [np.asarray(sd['path_lengths'], dtype=np.int64).reshape(-1) if 'path_lengths' in sd else np.array([k], dtype=np.int64)
+                for sd, k in zip(samples_data_meta_batch, n)]
+        assert all(int(l.sum()) == k and (l > 0).all() for l, k in zip(lens, n)), 'path_lengths must add up to the task\'s rows'
         cat = lambda f: np.concatenate([np.asarray(f(sd), dtype=np.float32) for sd in samples_data_meta_batch])
-        fl = dict(task_path_offsets=np.arange(self.M + 1, dtype=np.int32),
-                  path_row_offsets=np.concatenate([[0], np.cumsum(n)]).astype(np.int32),
+        fl = dict(task_path_offsets=np.concatenate([[0], np.cumsum([len(l) for l in lens])]).astype(np.int32),
+                  path_row_offsets=np.concatenate([[0], np.cumsum(np.concatenate(lens))]).astype(np.int32),
                   obs=cat(lambda sd: sd['observations']).reshape(sum(n), -1), rew=np.zeros(sum(n), np.float32),
                   act=cat(lambda sd: sd['actions']).reshape(sum(n), -1),
                   old_mean=cat(lambda sd: sd['agent_infos']['mean']).reshape(sum(n), -1),

@@ -38,6 +38,7 @@ DEFAULT = {
     'inner_type': 'log_likelihood',
     'exploration': False,          # True: E-MAML (e-maml_run_mujoco.py:60)
     'hvp_approach': 'finite_difference',   # the reference's; 'exact': the device's exact constraint product
+    'subsample_factor': 1.,        # < 1: the conjugate-gradient solve's products on that share of each task's paths
 }
 
 
@@ -55,7 +56,8 @@ def main(config):
                                            normalize_adv=config['normalize_adv'])
     algo = TRPOMAML(policy=policy, step_size=config['step_size'], inner_type=config['inner_type'], inner_lr=config['inner_lr'],
                     meta_batch_size=config['meta_batch_size'], num_inner_grad_steps=config['num_inner_grad_steps'],
-                    exploration=bool(config.get('exploration', False)), hvp_approach=config.get('hvp_approach', 'finite_difference'))
+                    exploration=bool(config.get('exploration', False)), hvp_approach=config.get('hvp_approach', 'finite_difference'),
+                    subsample_factor=float(config.get('subsample_factor', 1.)))
     trainer = Trainer(algo=algo, policy=policy, env=env, sampler=sampler, sample_processor=sample_processor,
                       n_itr=config['n_itr'], num_inner_grad_steps=config['num_inner_grad_steps'])
     trainer.train()
@@ -69,6 +71,8 @@ if __name__ == '__main__':
     ap.add_argument('--n_itr', type=int, default=None)
     ap.add_argument('--exploration', action='store_true', help='E-MAML (e-maml_run_mujoco.py)')
     ap.add_argument('--hvp', type=str, default=None, choices=['finite_difference', 'exact'])
+    ap.add_argument('--subsample_factor', type=float, default=None,
+                    help='share of each task\'s paths the conjugate-gradient products see, in (0, 1]')
     ap.add_argument('--quiet', action='store_true')
     args = ap.parse_args()
     cfg = dict(DEFAULT)
@@ -80,6 +84,8 @@ if __name__ == '__main__':
         cfg['exploration'] = True
     if args.hvp:
         cfg['hvp_approach'] = args.hvp
+    if args.subsample_factor is not None:
+        cfg['subsample_factor'] = args.subsample_factor
     logger.configure(dir=args.dump_path or None, snapshot_mode='last_gap', snapshot_gap=50, quiet=args.quiet)
     if args.dump_path:
         json.dump(cfg, open(os.path.join(args.dump_path, 'params.json'), 'w'), cls=ClassEncoder)
