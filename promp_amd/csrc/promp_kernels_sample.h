@@ -1,11 +1,35 @@
 // promp_kernels_sample.h -- sample processing on the device (reference rows a1-a7), FP64 like the
 // reference (SciPy lfilter / NumPy lstsq compute in float64).
 //
-//   k_returns   : per path  R[t] = r[t] + g R[t+1]             utils/utils.py:74-81, samplers/base.py:103-104
-//   k_gram      : per task  [Phi R]^T [Phi R] (normal equations) baselines/linear_baseline.py:66-67,101-106
-//   k_fit       : per task  (G + reg I) w = Phi^T R, NaN retry   baselines/linear_baseline.py:68-77
-//   k_gae       : per path  b = Phi w ; delta ; GAE scan          baselines/linear_baseline.py:17-33, samplers/base.py:151-162
-//   k_normalize : per task  (adv-mean)/(std+1e-8) [, shift >0]    utils/utils.py:59-71
+// The kernels, in launch order (sample_plan() in promp_plan.h decides which of the Gram / fit kernels a call launches; D + 1 =
+// the feature columns and the target, NBLK = its blocks of 16):
+//   k_returns        per path  R[t] = r[t] + g R[t+1], per-path sums          utils/utils.py:74-81, samplers/base.py:103-104
+//                    every call
+//   k_dice_scan      per path  DiCE's suffix / prefix sums of the row weights  meta_algos/dice_maml.py:39-45, 245-258
+//                    promp_set_dice_rewards (mode 0) and the DICE curvature pass (mode 1), not process_samples
+//   k_gram<NBLK>     per work item  partial [Phi R]^T [Phi R], wave-private tiles  baselines/linear_baseline.py:66-67, 101-106
+//                    LinearFeatureBaseline obs_dim <= 32 (NBLK <= 5), LinearTimeBaseline (NBLK = 1)
+//   k_gram_wide      the same, one shared tile, waves own runs of the block-pair list
+//                    obs_dim 33-93 (NBLK <= 12), and wider with PROMP_GRAM_UNTILED=1
+//   k_gram_tiled     the same, a wave owns a square of 3 x 3 blocks, operands reused in registers
+//                    obs_dim >= 94 (NBLK >= 13: Ant 15 blocks, Humanoid 48)
+//   k_fit_wave<DT>   per task  sum the partials, (G + reg I) w = Phi^T R in ONE wave, NaN retry  baselines/linear_baseline.py:68-77
+//                    D + 1 <= 64 (DT = 12, 45, 48, 64: obs_dim <= 29, LinearTimeBaseline)
+//   k_fit            the same solve, one workgroup, matrices in LDS
+//                    obs_dim 30-32 (D + 1 = 65..69)
+//   k_gram_sum_wide  per task  sum the partials into G and the work matrix in global memory
+//                    obs_dim >= 33, in front of
+//   k_fit_wide<NB>   the same solve, blocked right-looking Cholesky, panels of NB = 32 (16: D > ~580) columns through LDS
+//                    obs_dim >= 33; alone for D < 400 (PROMP_FIT_ONE_LAUNCH=1: always), else only the retries behind
+//   k_fitw_panel<NB>, k_fitw_update<NB>, k_fitw_back<NB>   the same factorisation, one launch per phase
+//                    D >= 400 (Humanoid)
+//   k_gae            per path  b = Phi w ; delta ; GAE scan ; moments    baselines/linear_baseline.py:17-33, samplers/base.py:151-162
+//                    every call (ZeroBaseline: b = 0)
+//   k_normalize      per work item  (adv - mean) / (std + 1e-8) [, shift > 0]  utils/utils.py:59-71
+//                    every call
+// What several of them share is written once, in front of its first user: suffix_scan_chunk; linfeat_obs / linfeat_row_tail (the
+// feature row); tri_pair_blocks / tri_pair_index / gram_store_block / gram_scatter_entry (the partial-block layout);
+// fit_any_nan; fitw_back_substitute and the chol_* panel steps (the blocked Cholesky).
 //
 // One wavefront owns one path in the scans: the linear recurrence y[t] = x[t] + c*y[t+1] is a
 // 6-step wave-level suffix scan over 64 time steps (weights c, c^2, c^4, ...), chained across
@@ -48,6 +72,21 @@ struct SampleArgs {
     double* bl64;           // optional [rows]: the baseline predictions Phi.w (LinearBaseline.predict), else NULL
 };
 
+// Suffix scan of one 64-step chunk, a step per lane: y[lane] = sum_{d >= 0, lane + d < 64} c^d x[lane + d] in six shuffle steps
+// (weights c, c^2, c^4, ...).  The unweighted instance (c = 1: DiCE's sums) multiplies by nothing.  The caller chains chunks from
+// the end of the path: + c^(64 - lane) * carry, carry = the next chunk's lane 0.
+template <bool WEIGHTED>
+PROMP_DEV double suffix_scan_chunk(double x, int lane, double c = 1.0) {
+    double y = x, cc = c;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const double up = shfl_down_f64(y, d);
+        if (lane + d < 64) y += WEIGHTED ? cc * up : up;
+        if (WEIGHTED) cc *= cc;
+    }
+    return y;
+}
+
 // grid = paths, block = 64
 __global__ void __launch_bounds__(64) k_returns(SampleArgs a) {
     const int p = blockIdx.x, lane = threadIdx.x;
@@ -59,13 +98,7 @@ __global__ void __launch_bounds__(64) k_returns(SampleArgs a) {
         const int t = end - 64 + lane;
         const int rr = row0 + (t >= 0 ? t : 0);
         const double x = (t >= 0) ? (a.rew64 ? a.rew64[rr] : (double)a.rew[rr]) : 0.0;
-        double y = x, gg = g;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const double up = shfl_down_f64(y, d);
-            if (lane + d < 64) y += gg * up;
-            gg *= gg;
-        }
+        double y = suffix_scan_chunk<true>(x, lane, g);
         y += f * carry;
         if (t >= 0) {
             a.ret64[row0 + t] = y;
@@ -89,7 +122,7 @@ __global__ void __launch_bounds__(64) k_returns(SampleArgs a) {
 // DiCE weights (meta_algos/dice_maml.py:39-45, 245-258: the magic box couples the time steps of a path).
 //   mode 0:  out[t] = sum_{t' >= t} rw[t']                                   (gradient weights w)
 //   mode 1:  out[t] = sum_{t' >= t} rw[t'] C[t'],  C[t'] = sum_{t'' <= t'} c[t'']   (Hessian-vector coupling weights u)
-// One wave per path, float64 suffix scans in 64-row chunks from the end (as k_returns with discount 1); the prefix sum
+// One wave per path, float64 suffix scans in 64-row chunks from the end (suffix_scan_chunk, unweighted); the prefix sum
 // is total - suffix + own.  grid = paths, block = 64.
 struct DiceScanArgs {
     const int* path_row_offsets;
@@ -99,15 +132,6 @@ struct DiceScanArgs {
     double* tmp;           // [rows] scratch (mode 1)
     int mode;
 };
-PROMP_DEV double dice_suffix_chunk(double x, int lane) {
-    double y = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const double up = shfl_down_f64(y, d);
-        if (lane + d < 64) y += up;
-    }
-    return y;
-}
 __global__ void __launch_bounds__(64) k_dice_scan(DiceScanArgs a) {
     const int p = blockIdx.x, lane = threadIdx.x;
     const int row0 = a.path_row_offsets[p], T = a.path_row_offsets[p + 1] - row0;
@@ -117,7 +141,7 @@ __global__ void __launch_bounds__(64) k_dice_scan(DiceScanArgs a) {
         for (int end = T; end > 0; end -= 64) {
             const int t = end - 64 + lane;
             const double x = (t >= 0) ? (double)a.c[row0 + t] : 0.0;
-            const double y = dice_suffix_chunk(x, lane) + carry;
+            const double y = suffix_scan_chunk<false>(x, lane) + carry;
             if (t >= 0) a.tmp[row0 + t] = y;
             carry = shfl_idx_f64(y, 0);
         }
@@ -131,9 +155,73 @@ __global__ void __launch_bounds__(64) k_dice_scan(DiceScanArgs a) {
             x = (double)a.rw[row0 + t];
             if (a.mode == 1) x *= total - a.tmp[row0 + t] + (double)a.c[row0 + t];     // C[t]
         }
-        const double y = dice_suffix_chunk(x, lane) + carry;
+        const double y = suffix_scan_chunk<false>(x, lane) + carry;
         if (t >= 0) a.out[row0 + t] = (float)y;
         carry = shfl_idx_f64(y, 0);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The LinearFeatureBaseline feature row (baselines/linear_baseline.py:101-106), one row of [Phi R]:
+//   columns 0 .. O-1 clip(obs, -10, 10) | O .. 2O-1 its square | qt .. qt+3 tau, tau^2, tau^3, 1 (tau = t / 100) | D the target
+// (qt = 2 O; LinearTimeBaseline: no observation columns, qt = 0).  The reference squares in the observations' own dtype
+// (float32), then promotes.  tau * tau * tau associates as (tau tau) tau.
+// ---------------------------------------------------------------------------------------------
+// one observation entry: the clipped value into row[c], its float32 square into row[c2] (live = false: a row past the chunk's
+// last, zeros)
+PROMP_DEV void linfeat_obs(float x, bool live, double* row, int c, int c2) {
+    const float oc = live ? fminf(fmaxf(x, -10.f), 10.f) : 0.f;
+    row[c] = (double)oc;
+    row[c2] = (double)(oc * oc);
+}
+PROMP_DEV double linfeat_tau(int t) { return (double)t / 100.0; }
+// a row's tail into the feature row pr (valid = false: a row past the chunk's last, zeros)
+PROMP_DEV void linfeat_row_tail(double* pr, int qt, int D, bool valid, int t, double target) {
+    const double tau = valid ? linfeat_tau(t) : 0.0;
+    pr[qt] = tau;
+    pr[qt + 1] = tau * tau;
+    pr[qt + 2] = tau * tau * tau;
+    pr[qt + 3] = valid ? 1.0 : 0.0;
+    pr[D] = valid ? target : 0.0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The partial Gram of a work item (gram_partials): [pair][256] doubles.  The D + 1 columns of [Phi R] are cut into n = NBLK
+// blocks of 16; pair = the row-major index of block (bi, bj >= bi) in the upper block triangle; entry (i, j) of a block sits at
+// 16 i + j.  An FP64 16x16x4 accumulator holds, in lane (kk = lane >> 4, i16 = lane & 15), the entries (kk + 4 r, i16), r = 0..3.
+// (k_gram_tiled numbers its squares of bands the same way, n = the number of bands.)
+// ---------------------------------------------------------------------------------------------
+PROMP_DEV void tri_pair_blocks(int p, int n, int& bi, int& bj) {
+    bi = 0;
+    int rem = p;
+    while (rem >= n - bi) {
+        rem -= n - bi;
+        ++bi;
+    }
+    bj = bi + rem;
+}
+PROMP_DEV int tri_pair_index(int bi, int bj, int n) { return bi * n - bi * (bi - 1) / 2 + (bj - bi); }
+// an accumulator into block p of out (global partials, or a wave's LDS slab)
+PROMP_DEV void gram_store_block(double* out, int p, const f64x4& acc, int kk, int i16) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) out[p * 256 + (kk + 4 * r) * 16 + i16] = acc[r];
+}
+// entry e of the partial layout, summed over the task's work items, into the symmetric (D + 1) x (D + 1) matrix G -- and, WORK,
+// into the work matrix Wm = G + reg I of a first factorisation attempt (the ridge term on the D feature rows, not on the target's)
+template <bool WORK = false>
+PROMP_DEV void gram_scatter_entry(double s, int e, int NBLK, int D, double* G, double* Wm = nullptr, double reg = 0.0) {
+    const int DA = D + 1;
+    int bi, bj;
+    tri_pair_blocks(e >> 8, NBLK, bi, bj);
+    const int row = 16 * bi + ((e & 255) >> 4), col = 16 * bj + (e & 15);
+    if (row < DA && col < DA) {
+        const double diag = (row == col && row < D) ? reg : 0.0;
+        G[(size_t)row * DA + col] = s;
+        if (WORK) Wm[(size_t)row * DA + col] = s + diag;
+        if (bi != bj) {
+            G[(size_t)col * DA + row] = s;
+            if (WORK) Wm[(size_t)col * DA + row] = s;
+        }
     }
 }
 
@@ -214,23 +302,9 @@ __global__ void __launch_bounds__(64 * GramCfg<NBLK>::NW) k_gram(SampleArgs a) {
         const int nrows = (wk.row_end - base) < 16 ? (wk.row_end - base) : 16;
 #pragma unroll
         for (int u = 0; u < 8; ++u)
-            if (poff[u] >= 0) {
-                // (rows past the chunk's last arrive as zeros.)  the reference squares in the observations' own dtype (float32),
-                // then promotes
-                const float oc = fminf(fmaxf(xr[u], -10.f), 10.f);
-                Phi[poff[u]] = (double)oc;
-                Phi[poff[u] + O] = (double)(oc * oc);
-            }
-        if (lane < 16) {
-            const bool rv = lane < nrows;
-            const double tau = rv ? (double)ttr / 100.0 : 0.0;
-            double* pr = Phi + lane * FS;
-            pr[qt] = tau;
-            pr[qt + 1] = tau * tau;
-            pr[qt + 2] = tau * tau * tau;
-            pr[qt + 3] = rv ? 1.0 : 0.0;
-            pr[D] = rv ? tr : 0.0;
-        }
+            if (poff[u] >= 0)
+                linfeat_obs(xr[u], true, Phi, poff[u], poff[u] + O);       // (rows past the chunk's last arrive as zeros)
+        if (lane < 16) linfeat_row_tail(Phi + lane * FS, qt, D, lane < nrows, ttr, tr);
         SA_PHASE(1);
         request(base + 16 * NW);
         wave_sync();
@@ -256,9 +330,7 @@ __global__ void __launch_bounds__(64 * GramCfg<NBLK>::NW) k_gram(SampleArgs a) {
     SA_PHASE(4);
     double* S = (double*)smem;   // [NW][NPAIR*256]
 #pragma unroll
-    for (int p = 0; p < NPAIR; ++p)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) S[(w * NPAIR + p) * 256 + (kk + 4 * r) * 16 + i16] = acc[p][r];
+    for (int p = 0; p < NPAIR; ++p) gram_store_block(S, w * NPAIR + p, acc[p], kk, i16);
     __syncthreads();
     double* out = a.gram_partials + (long long)blockIdx.x * (NPAIR * 256);
     for (int e = tid; e < NPAIR * 256; e += 64 * NW) {
@@ -273,6 +345,22 @@ __global__ void __launch_bounds__(64 * GramCfg<NBLK>::NW) k_gram(SampleArgs a) {
         printf("k_gram cycles (wave 0 of workgroup 0): entry %llu | features %llu | request + sync %llu | products %llu | barrier %llu | slab sums %llu\n",
                ph[0], ph[1], ph[2], ph[3], ph[4], ph[5]);
 #endif
+}
+
+// "NaN in the solution => reg *= 10" (linear_baseline.py:68-77), the workgroup's vote through an LDS flag: nonzero if any of
+// wv[0 .. D) is a NaN.  Every thread of the nt calls it.  The caller has zeroed *flag in front of a barrier that also covers
+// wv, and passes another barrier before it zeroes the flag again.  ONE_TRIP: D <= nt, a thread looks at one entry (k_fit: as a
+// loop of one trip the vote measured 2.6 us per launch slower at obs_dim 31).
+template <bool ONE_TRIP>
+PROMP_DEV int fit_any_nan(const double* wv, int D, int* flag, int tid, int nt) {
+    if (ONE_TRIP) {
+        if (tid < D && wv[tid] != wv[tid]) *flag = 1;
+    } else {
+        for (int e = tid; e < D; e += nt)
+            if (wv[e] != wv[e]) *flag = 1;
+    }
+    __syncthreads();
+    return *flag;
 }
 
 // grid = tasks, block = 256.  smem: G[(D+1)^2] + Wm[(D+1)^2] + yv[D+1] + wv[D+1] + dg[D+1]  (doubles)
@@ -296,17 +384,7 @@ __global__ void __launch_bounds__(256) k_fit(SampleArgs a, int NBLK) {
         double s = 0.0;
 #pragma unroll 4
         for (int wg = wg0; wg < wg1; ++wg) s += a.gram_partials[(long long)wg * (NPAIR * 256) + e];
-        int p = e >> 8, bi = 0, rem = p;
-        while (rem >= NBLK - bi) {
-            rem -= NBLK - bi;
-            ++bi;
-        }
-        const int bj = bi + rem;
-        const int row = 16 * bi + ((e & 255) >> 4), col = 16 * bj + (e & 15);
-        if (row < DA && col < DA) {
-            G[row * DA + col] = s;
-            if (bi != bj) G[col * DA + row] = s;
-        }
+        gram_scatter_entry(s, e, NBLK, D, G);
     }
     __syncthreads();
     // 2. Cholesky of (G[:D,:D] + reg I) carrying the right-hand-side row D along (forward solve for free),
@@ -343,9 +421,7 @@ __global__ void __launch_bounds__(256) k_fit(SampleArgs a, int NBLK) {
         }
         if (tid == 0) *flag = 0;
         __syncthreads();
-        if (tid < D && wv[tid] != wv[tid]) *flag = 1;
-        __syncthreads();
-        const int bad = *flag;
+        const int bad = fit_any_nan<true>(wv, D, flag, tid, 256);
         __syncthreads();
         if (!bad) break;
         reg *= 10.0;
@@ -463,19 +539,7 @@ __global__ void __launch_bounds__(FITWV_NT) k_fit_wave(SampleArgs a, int NBLK) {
 #pragma unroll
         for (int q = 0; q < NE; ++q) {
             const int e = threadIdx.x + q * FITWV_NT;
-            if (e < NPAIR * 256) {
-                int p = e >> 8, bi = 0, rem = p;
-                while (rem >= NBLK - bi) {
-                    rem -= NBLK - bi;
-                    ++bi;
-                }
-                const int bj = bi + rem;
-                const int row = 16 * bi + ((e & 255) >> 4), col = 16 * bj + (e & 15);
-                if (row < DA && col < DA) {
-                    G[row * DA + col] = sacc[q];
-                    if (bi != bj) G[col * DA + row] = sacc[q];
-                }
-            }
+            if (e < NPAIR * 256) gram_scatter_entry(sacc[q], e, NBLK, D, G);
         }
     }
     __syncthreads();
@@ -547,26 +611,20 @@ __global__ void __launch_bounds__(64) k_gae(SampleArgs a) {
             int q = 0;
             if (a.kind == BASE_LINFEAT) {
                 for (int c = 0; c < O; ++c) {
-                    const float o = a.obs[row * O + c];
-                    const float oc = fminf(fmaxf(o, -10.f), 10.f);
-                    b += wc[c] * (double)oc + wc[O + c] * (double)(oc * oc);
+                    double f[2];
+                    linfeat_obs(a.obs[row * O + c], true, f, 0, 1);
+                    b += wc[c] * f[0] + wc[O + c] * f[1];
                 }
                 q = 2 * O;
             }
-            const double tau = (double)t / 100.0;
+            const double tau = linfeat_tau(t);
             b += wc[q] * tau + wc[q + 1] * (tau * tau) + wc[q + 2] * (tau * tau * tau) + wc[q + 3];
         }
         double bn = shfl_down_f64(b, 1);
         if (lane == 63) bn = bcarry;
         const double rw = a.rew64 ? a.rew64[valid ? row : 0] : (double)a.rew[valid ? row : 0];
         const double x = valid ? (rw + g * bn - b) : 0.0;
-        double y = x, gg = gl;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const double up = shfl_down_f64(y, d);
-            if (lane + d < 64) y += gg * up;
-            gg *= gg;
-        }
+        double y = suffix_scan_chunk<true>(x, lane, gl);
         y += f * carry;
         if (valid) {
             if (a.bl64 != nullptr) a.bl64[row] = b;
@@ -628,7 +686,7 @@ __global__ void __launch_bounds__(256) k_normalize(SampleArgs a) {
 // k_gram_wide: the upper-triangular 16x16 block pairs of [Phi R]^T [Phi R] no longer fit one wave's registers
 // (120 pairs at D = 226), so the workgroup shares the feature tile: 8 waves, wave w owns a contiguous eighth of the pair list
 // (<= GRAMW_PPW of them) over ALL rows of the work item -- no cross-wave reduction, each partial block is written by
-// its owner.  Rounds of GRAMW_ROWS rows; same partial layout as k_gram ([NPAIR][256] doubles per work item).
+// its owner.  Rounds of GRAMW_ROWS rows; out: the partial layout above.
 // grid = work items (table 0) x pair slices, block = 512.  smem: the feature tile, ROWS * FS doubles.
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(512, 2) k_gram_wide(SampleArgs a, int NBLK, int GRAMW_ROWS) {
@@ -648,13 +706,10 @@ __global__ void __launch_bounds__(512, 2) k_gram_wide(SampleArgs a, int NBLK, in
 #pragma unroll
     for (int j = 0; j < GRAMW_PPW; ++j) {
         const int p = p0 + j;
-        int bi = 0, rem = (j < ppw && p < pend) ? p : 0;
-        while (rem >= NBLK - bi) {
-            rem -= NBLK - bi;
-            ++bi;
-        }
+        int bi, bj;
+        tri_pair_blocks((j < ppw && p < pend) ? p : 0, NBLK, bi, bj);
         ca[j] = 16 * bi;
-        cb[j] = 16 * (bi + rem);
+        cb[j] = 16 * bj;
     }
     f64x4 acc[GRAMW_PPW];
 #pragma unroll
@@ -683,10 +738,7 @@ __global__ void __launch_bounds__(512, 2) k_gram_wide(SampleArgs a, int NBLK, in
                     const int e = e0 + 512 * u;
                     if (e < tot) {
                         const int r = (int)(((float)e + 0.5f) * rO), c = e - r * O;
-                        // (rows past the chunk's last become zeros.)  the reference squares in the observations' own dtype, then promotes
-                        const float oc = e < lim ? fminf(fmaxf(x[u], -10.f), 10.f) : 0.f;
-                        Phi[r * FS + c] = (double)oc;
-                        Phi[r * FS + O + c] = (double)(oc * oc);
+                        linfeat_obs(x[u], e < lim, Phi, r * FS + c, r * FS + O + c);
                     }
                 }
             }
@@ -694,14 +746,7 @@ __global__ void __launch_bounds__(512, 2) k_gram_wide(SampleArgs a, int NBLK, in
         if (tid < GRAMW_ROWS) {
             const bool rv = tid < nrows;
             const int r = rv ? tid : 0;
-            const double t = a.ret64[base + r];
-            const double tau = rv ? (double)a.row_t[base + r] / 100.0 : 0.0;
-            double* pr = Phi + tid * FS;
-            pr[qt] = tau;
-            pr[qt + 1] = tau * tau;
-            pr[qt + 2] = tau * tau * tau;
-            pr[qt + 3] = rv ? 1.0 : 0.0;
-            pr[D] = rv ? t : 0.0;
+            linfeat_row_tail(Phi + tid * FS, qt, D, rv, a.row_t[base + r], a.ret64[base + r]);
         }
         __syncthreads();
         // The products, software-pipelined: the operands of the NEXT group of four pairs are requested before the current group's
@@ -751,9 +796,7 @@ __global__ void __launch_bounds__(512, 2) k_gram_wide(SampleArgs a, int NBLK, in
 #pragma unroll
     for (int j = 0; j < GRAMW_PPW; ++j) {
         const int p = p0 + j;
-        if (j < ppw && p < pend)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) out[p * 256 + (kk + 4 * r) * 16 + i16] = acc[j][r];
+        if (j < ppw && p < pend) gram_store_block(out, p, acc[j], kk, i16);
     }
 }
 
@@ -766,8 +809,8 @@ __global__ void __launch_bounds__(512, 2) k_gram_wide(SampleArgs a, int NBLK, in
 // immediate offsets from two lane addresses.  Squares on the diagonal issue their upper triangle (6 products from 3 reads).  The
 // two shapes are two instances of the step loop: products behind wave-uniform branches, or more loop shapes (short last bands),
 // made the register allocator spill accumulators -- the block count is padded to whole bands instead (the padding columns are
-// zero in the tile and are never written out).  out[] keeps k_gram_wide's layout ([pair][256] per work item, pair = row-major
-// index of the upper block triangle), so k_gram_sum_wide / the fits do not change.
+// zero in the tile and are never written out).  out[] is the partial layout above, whichever Gram kernel wrote
+// it: k_gram_sum_wide / the fits do not change.
 //   * Ant's 15 blocks are 5 bands = 15 squares = 15 waves of ONE workgroup (10 x 9 + 5 x 6 = 120 products per k-step, the
 //     unpadded count); the host shares them out over the SIMDs by cost (GramtMap; wave w runs on SIMD w mod 4).  More squares:
 //     slices of NWV along gridDim.y (Humanoid's 48 blocks: 136 squares, 9 slices).
@@ -826,7 +869,7 @@ PROMP_DEV void gramt_walk(const SampleArgs& a, int NBLK, int ROWS, int DB, doubl
 #pragma unroll
         for (int jj = 0; jj < TB; ++jj) acc[ii][jj] = zero4d();
 
-    // The tile build, as k_gram_wide's: element e of the round's [ROWS][O] chunk of observations is observation e mod O of row
+    // The tile build: element e of the round's [ROWS][O] chunk of observations is observation e mod O of row
     // e / O and goes to columns c and O + c; threads 0 .. ROWS - 1 add their row's time features, the constant and the target.
     // Split in two: the requests (into x[], tgt, rt) and, a round of products later, the writes.
     const float rO = 1.0f / (float)(O > 0 ? O : 1);
@@ -860,24 +903,12 @@ PROMP_DEV void gramt_walk(const SampleArgs& a, int NBLK, int ROWS, int DB, doubl
                 const int e = tid + NT * u + oz;
                 if (e < tot) {
                     const int r = (int)(((float)e + 0.5f) * rO), c = e - r * O;
-                    // (rows past the chunk's last become zeros.)  the reference squares in the observations' own dtype, then promotes
-                    const float oc = e < lim ? fminf(fmaxf(x[u], -10.f), 10.f) : 0.f;
-                    buf[r * FS + c] = (double)oc;
-                    buf[r * FS + O + c] = (double)(oc * oc);
+                    linfeat_obs(x[u], e < lim, buf, r * FS + c, r * FS + O + c);
                 }
                 sched_fence();      // one element at a time: interleaved, the NLD elements' temporaries push accumulators into scratch
             }
         }
-        if (tid < ROWS) {
-            const bool rv = tid < nrows;
-            const double tau = rv ? (double)rt / 100.0 : 0.0;
-            double* pr = buf + tid * FS;
-            pr[qt] = tau;
-            pr[qt + 1] = tau * tau;
-            pr[qt + 2] = tau * tau * tau;
-            pr[qt + 3] = rv ? 1.0 : 0.0;
-            pr[D] = rv ? tgt : 0.0;
-        }
+        if (tid < ROWS) linfeat_row_tail(buf + tid * FS, qt, D, tid < nrows, rt, tgt);
     };
 
     for (int e = tid; e < (DB ? 2 : 1) * ROWS * FS; e += NT) Phi[e] = 0.0;      // columns past D + 1 stay zero
@@ -920,11 +951,7 @@ PROMP_DEV void gramt_walk(const SampleArgs& a, int NBLK, int ROWS, int DB, doubl
 #pragma unroll
         for (int jj = 0; jj < TB; ++jj) {
             const int gi = TB * bi + ii, gj = TB * bj + jj;
-            if (active && gramt_has<SHAPE>(ii, jj) && gj < NBLK) {
-                const int p = gi * NBLK - gi * (gi - 1) / 2 + (gj - gi);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) out[p * 256 + (kk + 4 * r) * 16 + i16] = acc[ii][jj][r];
-            }
+            if (active && gramt_has<SHAPE>(ii, jj) && gj < NBLK) gram_store_block(out, tri_pair_index(gi, gj, NBLK), acc[ii][jj], kk, i16);
         }
 }
 
@@ -936,12 +963,8 @@ __global__ void __launch_bounds__(64 * NWV) k_gram_tiled(SampleArgs a, int NBLK,
     // this wave's square: band pair bi <= bj of the row-major list
     const int rect = wave_uniform(gridDim.y == 1 ? (int)map.rect[w] : (int)blockIdx.y * NWV + w);
     const bool active = rect < NR;
-    int bi = 0, rem = active ? rect : 0;
-    while (rem >= NB - bi) {
-        rem -= NB - bi;
-        ++bi;
-    }
-    const int bj = bi + rem;
+    int bi, bj;
+    tri_pair_blocks(active ? rect : 0, NB, bi, bj);
     const int part = wave_uniform(gridDim.y == 1 ? (int)map.part[w] : GRAMT_DIAG);
     double* Phi = (double*)PROMP_SMEM_PTR;
     if (bi != bj) gramt_walk<TB, NWV, NLD, GRAMT_FULL>(a, NBLK, ROWS, DB, Phi, active, bi, bj);
@@ -954,11 +977,8 @@ __global__ void __launch_bounds__(64 * NWV) k_gram_tiled(SampleArgs a, int NBLK,
 // k_fit_wide: the same solve as k_fit when the (D+1)^2 matrices do not fit in LDS (Ant: D = 226).  G and the work matrix live in
 // global memory (L2-resident, 0.4 MB per task).  Right-looking blocked Cholesky, 32-column panels through LDS, the right-hand
 // side carried along as row D (k_fit's forward solve for free):
-//   1. the panel's 32 x 32 diagonal block is factorised by ONE wave in registers (a row per lane, pivots and multipliers by
-//      v_readlane: k_fit_wave's column step -- 32 dependent steps with no barrier and no memory access on the chain);
-//   2. the rows below it (and the right-hand-side row) are solved against that block one row per thread (independent rows);
-//   3. the rank-32 update of the trailing matrix runs on the FP64 matrix cores: v_mfma_f64_16x16x4_f64 over the 16 x 16 tiles of
-//      the lower triangle, all waves, operands straight from the panel in LDS.
+// the panel's diagonal block in one wave's registers (chol_diag_block), the rows below it one per thread (chol_rows_below), the
+// rank-32 update of the trailing matrix on the FP64 matrix cores, all waves (chol_trailing_update).
 // The back substitution walks the factor in 32-row blocks: one wave solves the block's triangle in registers, all threads apply
 // its 32 solved entries to the rows above.  Round 3's version took two workgroup barriers per COLUMN (226 x 2, plus 226 in the
 // back substitution) and updated the trailing matrix with scalar FMAs: 676 us per launch at Ant's size; this one takes four
@@ -992,22 +1012,7 @@ __global__ void __launch_bounds__(256) k_gram_sum_wide(SampleArgs a, int NBLK, d
 #pragma unroll
             for (int u = 0; u < 8; ++u) s += (base + u < wg1) ? v[u] : 0.0;
         }
-        int p = e >> 8, bi = 0, rem = p;
-        while (rem >= NBLK - bi) {
-            rem -= NBLK - bi;
-            ++bi;
-        }
-        const int bj = bi + rem;
-        const int row = 16 * bi + ((e & 255) >> 4), col = 16 * bj + (e & 15);
-        if (row < DA && col < DA) {
-            const double diag = (row == col && row < D) ? a.reg : 0.0;
-            G[(size_t)row * DA + col] = s;
-            Wm[(size_t)row * DA + col] = s + diag;
-            if (bi != bj) {
-                G[(size_t)col * DA + row] = s;
-                Wm[(size_t)col * DA + row] = s;
-            }
-        }
+        gram_scatter_entry<true>(s, e, NBLK, D, G, Wm, a.reg);
     }
 }
 
@@ -1099,11 +1104,132 @@ PROMP_DEV void fitw_back_substitute(const double* Wm, int D, int DA, double* yv,
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The steps of one NB-column panel of the blocked right-looking Cholesky (k_fit_wide runs them in one workgroup per task,
+// k_fitw_panel / k_fitw_update one launch per phase: the same functions, so the two agree bit for bit).  The panel sits in LDS
+// as Pn[row][NB + 1]; Wm is the task's (D + 1) x (D + 1) work matrix in global memory, row D the right-hand side; nb <= NB the
+// panel's columns (a last panel may be narrower).  Barriers between the steps are the caller's.
+// ---------------------------------------------------------------------------------------------
+// rows row0 .. row0 + nrows - 1, columns col0 .. col0 + nb - 1 of Wm into Pn, the columns past nb and PAD more rows as zeros
+// (the trailing update reads whole 16-row tiles)
+template <int NB>
+PROMP_CX int chol_log_nb() { return NB == 32 ? 5 : 4; }       // (panels are 32 or 16 columns wide)
+template <int NB, int PAD>
+PROMP_DEV void chol_panel_load(double* Pn, const double* Wm, int DA, int row0, int col0, int nrows, int nb, int tid) {
+    constexpr int PS = NB + 1, LOG_NB = chol_log_nb<NB>();
+    for (int e = tid; e < (nrows + PAD) * NB; e += FITW_NT) {
+        const int i = e >> LOG_NB, c = e & (NB - 1);
+        Pn[i * PS + c] = (c < nb && (PAD == 0 || i < nrows)) ? Wm[(size_t)(row0 + i) * DA + col0 + c] : 0.0;
+    }
+}
+// The panel's NB x NB diagonal block, factorised by ONE wave in registers: a row per lane (lanes >= nb shadow the last row:
+// finite, never stored), pivots and multipliers by v_readlane -- nb dependent steps with no barrier and no memory access on the
+// chain.  Leaves L (diagonal included) in Pn, 1 / L[c][c] in rdp[c] and, KEEP_DIAG, L[c][c] in dg[c].
+template <int NB, bool KEEP_DIAG>
+PROMP_DEV void chol_diag_block(double* Pn, double* rdp, double* dg, int nb, int lane) {
+    constexpr int PS = NB + 1;
+    const int row = lane < nb ? lane : nb - 1;
+    double W[NB];
+    double rdg = 1.0, dgv = 0.0;
+#pragma unroll
+    for (int k = 0; k < NB; ++k) W[k] = Pn[row * PS + k];
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+        if (j < nb) {     // (wave-uniform)
+            const double dj = readlane_f64(W[j], j), rs = rsqrt(dj), piv = dj * rs;
+            W[j] = (lane == j) ? piv : W[j] * rs;
+            rdg = (lane == j) ? rs : rdg;
+            dgv = (lane == j) ? piv : dgv;       // (W[lane] read at the end would index the array by a runtime value: the
+                                                 //  whole row then lives in scratch memory, loop included)
+#pragma unroll
+            for (int k = j + 1; k < NB; ++k) W[k] -= W[j] * readlane_f64(W[j], k);     // lane k holds L[k][j] in W[j]
+        }
+    }
+    if (lane < nb) {
+#pragma unroll
+        for (int k = 0; k < NB; ++k)
+            if (k <= lane) Pn[lane * PS + k] = W[k];
+        if (KEEP_DIAG) dg[lane] = dgv;
+        rdp[lane] = rdg;
+    }
+}
+// The nbelow rows under the diagonal block (the right-hand side among them): x L^T = a, one row per thread, forward
+// substitution over the block's columns.
+template <int NB>
+PROMP_DEV void chol_rows_below(double* Pn, const double* rdp, int nb, int nbelow, int tid) {
+    constexpr int PS = NB + 1;
+    for (int rr = tid; rr < nbelow; rr += FITW_NT) {       // (one trip up to 512 rows below the block)
+        double* xr = Pn + (size_t)(nb + rr) * PS;
+        double x[NB];
+#pragma unroll
+        for (int c = 0; c < NB; ++c) x[c] = xr[c];
+        // column by column, right-looking: once x[c] is final the later entries take their x[c] L[c2][c] at once -- NB - 1 - c
+        // independent multiply-adds (the left-looking form is one dependent chain of c per entry).  L[c2][c] is the same
+        // address in every lane: a broadcast.  In a last panel narrower than NB the rows / columns >= nb of the block hold
+        // other rows' data: finite junk that only reaches entries >= nb, which are stored as 0.
+#pragma unroll
+        for (int c = 0; c < NB; ++c) {
+            if (c < nb) {
+                x[c] *= rdp[c];
+#pragma unroll
+                for (int c2 = c + 1; c2 < NB; ++c2) x[c2] -= x[c] * Pn[c2 * PS + c];
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < NB; ++c) xr[c] = (c < nb) ? x[c] : 0.0;
+    }
+}
+// the factored panel (nr rows from the diagonal block's first) back into Wm: the part below the diagonal and the right-hand-side
+// row; with_diag: the diagonal too
+template <int NB>
+PROMP_DEV void chol_panel_store(double* Wm, const double* Pn, int DA, int k0, int nr, int nb, bool with_diag, int tid) {
+    constexpr int PS = NB + 1, LOG_NB = chol_log_nb<NB>();
+    for (int e = tid; e < nr * NB; e += FITW_NT) {
+        const int i = e >> LOG_NB, c = e & (NB - 1);
+        if (c < nb && (with_diag ? i >= c : i > c)) Wm[(size_t)(k0 + i) * DA + k0 + c] = Pn[i * PS + c];
+    }
+}
+// Rank-nb update of the trailing matrix on the FP64 matrix cores: rows k1..D, columns k1..D-1 of Wm -= panel panel^T over the
+// 16 x 16 tiles of the lower triangle; this wave takes tiles first, first + stride, ...  The panel's rows below its diagonal
+// block start at row prow0 of Pn and are followed by 16 rows of zeros.  Every trailing entry takes one NB-term MFMA sum
+// whichever wave computes it.
+template <int NB>
+PROMP_DEV void chol_trailing_update(double* Wm, const double* Pn, int prow0, int D, int k1, int first, int stride, int lane) {
+    constexpr int PS = NB + 1;
+    const int DA = D + 1, i16 = lane & 15, kk = lane >> 4;
+    const int tr = DA - k1, tc = D - k1;
+    const int nti = (tr + 15) >> 4, ntj = (tc + 15) >> 4;
+    const int ntile = nti * ntj;                    // (tiles above the diagonal are skipped below)
+    for (int tix = first; tix < ntile; tix += stride) {
+        const int bi = tix / ntj, bj = tix - bi * ntj;
+        if (bj > bi) continue;                     // wave-uniform
+        const double* pa = Pn + (size_t)(prow0 + 16 * bi + i16) * PS + kk;
+        const double* pb = Pn + (size_t)(prow0 + 16 * bj + i16) * PS + kk;
+        // the entries this lane will update, requested before the products (clamped addresses, masked at the store)
+        double* dst[4];
+        double old[4];
+        bool ok[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int io = 16 * bi + kk + 4 * r, jo = 16 * bj + i16;
+            ok[r] = io < tr && jo < tc && jo <= io;
+            dst[r] = Wm + (size_t)(k1 + (ok[r] ? io : 0)) * DA + k1 + (ok[r] ? jo : 0);
+            old[r] = *dst[r];
+        }
+        f64x4 acc = zero4d();
+#pragma unroll
+        for (int sidx = 0; sidx < NB / 4; ++sidx) acc = mfma16d(pa[4 * sidx], pb[4 * sidx], acc);
+        // D: col = lane & 15, row = (lane >> 4) + 4 r
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (ok[r]) *dst[r] = old[r] - acc[r];
+    }
+}
 // only_bad != nullptr: the launch behind the one-launch-per-phase factorisation below -- tasks whose flag is 0 are done; the others
 // (a NaN in the solution: the ridge term was too small) start over at the second attempt, reg x 10, exactly as they would have here.
 template <int NB>
 __global__ void __launch_bounds__(FITW_NT) k_fit_wide(SampleArgs a, int NBLK, double* scratch, const int* only_bad) {
-    constexpr int PS = NB + 1, LOG_NB = NB == 32 ? 5 : 4;
+    constexpr int PS = NB + 1;
     PROMP_SMEM_DECL;
 #ifdef PROMP_DEV_STAMPS
     unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tph = promp_clock();
@@ -1113,7 +1239,6 @@ __global__ void __launch_bounds__(FITW_NT) k_fit_wide(SampleArgs a, int NBLK, do
 #endif
     const int D = a.D, DA = D + 1, NT = FITW_NT;
     const int tid = threadIdx.x, task = blockIdx.x, lane = tid & 63, w = wave_uniform(tid >> 6);
-    const int i16 = lane & 15, kk = lane >> 4;
     double* Pn = (double*)PROMP_SMEM_PTR;     // panel [DA - k0 (+ 16)][33]
     double* yv = Pn + (size_t)(DA + 16) * PS;
     double* wv = yv + DA;
@@ -1139,100 +1264,18 @@ __global__ void __launch_bounds__(FITW_NT) k_fit_wide(SampleArgs a, int NBLK, do
         for (int k0 = 0; k0 < D; k0 += NB) {
             const int nb = (D - k0) < NB ? (D - k0) : NB;   // columns of this panel
             const int nr = DA - k0;                                  // rows k0..D (the last one is the right-hand side)
-            for (int e = tid; e < (nr + 16) * NB; e += NT) {
-                const int i = e >> LOG_NB, c = e & (NB - 1);
-                Pn[i * PS + c] = (c < nb && i < nr) ? Wm[(size_t)(k0 + i) * DA + k0 + c] : 0.0;
-            }
+            chol_panel_load<NB, 16>(Pn, Wm, DA, k0, k0, nr, nb, tid);       // (16 rows of zeros behind the panel)
             __syncthreads();
             FITW_PHASE(2);
-            if (w == 0) {
-                // ---- the diagonal block, one wave, rows in registers (lanes >= nb shadow the last row: finite, never stored)
-                const int row = lane < nb ? lane : nb - 1;
-                double W[NB];
-                double rdg = 1.0, dgv = 0.0;
-#pragma unroll
-                for (int k = 0; k < NB; ++k) W[k] = Pn[row * PS + k];
-#pragma unroll
-                for (int j = 0; j < NB; ++j) {
-                    if (j < nb) {     // (wave-uniform)
-                        const double dj = readlane_f64(W[j], j), rs = rsqrt(dj), piv = dj * rs;
-                        W[j] = (lane == j) ? piv : W[j] * rs;
-                        rdg = (lane == j) ? rs : rdg;
-                        dgv = (lane == j) ? piv : dgv;       // (W[lane] read at the end would index the array by a runtime value: the
-                                                             //  whole row then lives in scratch memory, loop included)
-#pragma unroll
-                        for (int k = j + 1; k < NB; ++k) W[k] -= W[j] * readlane_f64(W[j], k);     // lane k holds L[k][j] in W[j]
-                    }
-                }
-                if (lane < nb) {
-#pragma unroll
-                    for (int k = 0; k < NB; ++k)
-                        if (k <= lane) Pn[lane * PS + k] = W[k];
-                    dg[k0 + lane] = dgv;
-                    rdp[lane] = rdg;
-                }
-            }
+            if (w == 0) chol_diag_block<NB, true>(Pn, rdp, dg + k0, nb, lane);
             __syncthreads();
             FITW_PHASE(3);
-            // ---- the rows below: x L^T = a, one row per thread (forward substitution over the block's columns)
-            for (int rr = tid; rr < nr - nb; rr += NT) {       // (one trip up to 512 rows below the block)
-                double* xr = Pn + (size_t)(nb + rr) * PS;
-                double x[NB];
-#pragma unroll
-                for (int c = 0; c < NB; ++c) x[c] = xr[c];
-                // column by column, right-looking: once x[c] is final the later entries take their x[c] L[c2][c] at once -- 31 - c
-                // independent multiply-adds (the left-looking form is one dependent chain of c per entry).  L[c2][c] is the same
-                // address in every lane: a broadcast.  In a last panel narrower than 32 the rows / columns >= nb of the block hold
-                // other rows' data: finite junk that only reaches entries >= nb, which are stored as 0.
-#pragma unroll
-                for (int c = 0; c < NB; ++c) {
-                    if (c < nb) {
-                        x[c] *= rdp[c];
-#pragma unroll
-                        for (int c2 = c + 1; c2 < NB; ++c2) x[c2] -= x[c] * Pn[c2 * PS + c];
-                    }
-                }
-#pragma unroll
-                for (int c = 0; c < NB; ++c) xr[c] = (c < nb) ? x[c] : 0.0;
-            }
+            chol_rows_below<NB>(Pn, rdp, nb, nr - nb, tid);
             __syncthreads();
             FITW_PHASE(4);
-            // write the factored panel back (strictly-lower part and the right-hand-side row)
-            for (int e = tid; e < nr * NB; e += NT) {
-                const int i = e >> LOG_NB, c = e & (NB - 1);
-                if (c < nb && i > c) Wm[(size_t)(k0 + i) * DA + k0 + c] = Pn[i * PS + c];
-            }
-            // ---- rank-nb update of the trailing matrix on the FP64 matrix cores: rows k1..D, columns k1..D-1, the tiles of the
-            //      lower triangle, wave w takes tiles w, w + 16, ...
-            const int k1 = k0 + nb, tr = DA - k1, tc = D - k1;
-            if (tc > 0) {
-                const int nti = (tr + 15) >> 4, ntj = (tc + 15) >> 4;
-                const int ntile = nti * ntj;                    // (tiles above the diagonal are skipped below)
-                for (int tix = w; tix < ntile; tix += FITW_NT / 64) {
-                    const int bi = tix / ntj, bj = tix - bi * ntj;
-                    if (bj > bi) continue;                     // wave-uniform
-                    const double* pa = Pn + (size_t)(nb + 16 * bi + i16) * PS + kk;
-                    const double* pb = Pn + (size_t)(nb + 16 * bj + i16) * PS + kk;
-                    // the entries this lane will update, requested before the products (clamped addresses, masked at the store)
-                    double* dst[4];
-                    double old[4];
-                    bool ok[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int io = 16 * bi + kk + 4 * r, jo = 16 * bj + i16;
-                        ok[r] = io < tr && jo < tc && jo <= io;
-                        dst[r] = Wm + (size_t)(k1 + (ok[r] ? io : 0)) * DA + k1 + (ok[r] ? jo : 0);
-                        old[r] = *dst[r];
-                    }
-                    f64x4 acc = zero4d();
-#pragma unroll
-                    for (int sidx = 0; sidx < NB / 4; ++sidx) acc = mfma16d(pa[4 * sidx], pb[4 * sidx], acc);
-                    // D: col = lane & 15, row = (lane >> 4) + 4 r
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (ok[r]) *dst[r] = old[r] - acc[r];
-                }
-            }
+            chol_panel_store<NB>(Wm, Pn, DA, k0, nr, nb, false, tid);       // (the diagonal stays in dg[])
+            // all waves of the workgroup: wave w takes tiles w, w + 8, ...
+            if (k0 + nb < D) chol_trailing_update<NB>(Wm, Pn, nb, D, k0 + nb, w, FITW_NT / 64, lane);
             __syncthreads();
             FITW_PHASE(5);
         }
@@ -1246,10 +1289,7 @@ __global__ void __launch_bounds__(FITW_NT) k_fit_wide(SampleArgs a, int NBLK, do
         FITW_PHASE(6);
         if (tid == 0) *flag = 0;
         __syncthreads();
-        for (int e = tid; e < D; e += NT)
-            if (wv[e] != wv[e]) *flag = 1;
-        __syncthreads();
-        const int bad = *flag;
+        const int bad = fit_any_nan<false>(wv, D, flag, tid, NT);
         __syncthreads();
         if (!bad) break;
         reg *= 10.0;
@@ -1279,111 +1319,37 @@ PROMP_HD size_t fitw_back_smem(int D, int nb) { return sizeof(double) * ((size_t
 
 template <int NB>
 __global__ void __launch_bounds__(FITW_NT) k_fitw_panel(SampleArgs a, double* scratch, int k0) {
-    constexpr int PS = NB + 1, LOG_NB = NB == 32 ? 5 : 4;
+    constexpr int PS = NB + 1;
     PROMP_SMEM_DECL;
-    const int D = a.D, DA = D + 1, NT = FITW_NT;
+    const int D = a.D, DA = D + 1;
     const int tid = threadIdx.x, task = blockIdx.x, lane = tid & 63, w = wave_uniform(tid >> 6);
     double* Pn = (double*)PROMP_SMEM_PTR;             // [DA - k0][PS]
     double* rdp = Pn + (size_t)(DA + 16) * PS;        // 1 / L[c][c] of the diagonal block
     double* Wm = scratch + (size_t)task * 2 * DA * DA + (size_t)DA * DA;
     const int nb = (D - k0) < NB ? (D - k0) : NB;     // columns of this panel
     const int nr = DA - k0;                           // rows k0..D (the last one is the right-hand side)
-    for (int e = tid; e < nr * NB; e += NT) {
-        const int i = e >> LOG_NB, c = e & (NB - 1);
-        Pn[i * PS + c] = c < nb ? Wm[(size_t)(k0 + i) * DA + k0 + c] : 0.0;
-    }
+    chol_panel_load<NB, 0>(Pn, Wm, DA, k0, k0, nr, nb, tid);
     __syncthreads();
-    if (w == 0) {
-        // ---- the diagonal block, one wave, rows in registers (k_fit_wide's step 1)
-        const int row = lane < nb ? lane : nb - 1;
-        double W[NB];
-        double rdg = 1.0;
-#pragma unroll
-        for (int k = 0; k < NB; ++k) W[k] = Pn[row * PS + k];
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            if (j < nb) {     // (wave-uniform)
-                const double dj = readlane_f64(W[j], j), rs = rsqrt(dj), piv = dj * rs;
-                W[j] = (lane == j) ? piv : W[j] * rs;
-                rdg = (lane == j) ? rs : rdg;
-#pragma unroll
-                for (int k = j + 1; k < NB; ++k) W[k] -= W[j] * readlane_f64(W[j], k);
-            }
-        }
-        if (lane < nb) {
-#pragma unroll
-            for (int k = 0; k < NB; ++k)
-                if (k <= lane) Pn[lane * PS + k] = W[k];
-            rdp[lane] = rdg;
-        }
-    }
+    if (w == 0) chol_diag_block<NB, false>(Pn, rdp, nullptr, nb, lane);
     __syncthreads();
-    // ---- the rows below: x L^T = a, one row per thread (k_fit_wide's step 2)
-    for (int rr = tid; rr < nr - nb; rr += NT) {
-        double* xr = Pn + (size_t)(nb + rr) * PS;
-        double x[NB];
-#pragma unroll
-        for (int c = 0; c < NB; ++c) x[c] = xr[c];
-#pragma unroll
-        for (int c = 0; c < NB; ++c) {
-            if (c < nb) {
-                x[c] *= rdp[c];
-#pragma unroll
-                for (int c2 = c + 1; c2 < NB; ++c2) x[c2] -= x[c] * Pn[c2 * PS + c];
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < NB; ++c) xr[c] = (c < nb) ? x[c] : 0.0;
-    }
+    chol_rows_below<NB>(Pn, rdp, nb, nr - nb, tid);
     __syncthreads();
-    // the factored panel back: lower part INCLUDING the diagonal, and the right-hand-side row
-    for (int e = tid; e < nr * NB; e += NT) {
-        const int i = e >> LOG_NB, c = e & (NB - 1);
-        if (c < nb && i >= c) Wm[(size_t)(k0 + i) * DA + k0 + c] = Pn[i * PS + c];
-    }
+    chol_panel_store<NB>(Wm, Pn, DA, k0, nr, nb, true, tid);                // (the diagonal with it: k_fitw_back reads it there)
 }
 
 template <int NB>
 __global__ void __launch_bounds__(FITW_NT) k_fitw_update(SampleArgs a, double* scratch, int k0) {
-    constexpr int PS = NB + 1, LOG_NB = NB == 32 ? 5 : 4;
     PROMP_SMEM_DECL;
-    const int D = a.D, DA = D + 1, NT = FITW_NT;
+    const int D = a.D, DA = D + 1;
     const int tid = threadIdx.x, task = blockIdx.x, lane = tid & 63, w = wave_uniform(tid >> 6);
-    const int i16 = lane & 15, kk = lane >> 4;
     double* Pn = (double*)PROMP_SMEM_PTR;             // [tr + 16][PS]: the factored panel's rows below its diagonal block
     double* Wm = scratch + (size_t)task * 2 * DA * DA + (size_t)DA * DA;
     const int nb = (D - k0) < NB ? (D - k0) : NB;
-    const int k1 = k0 + nb, tr = DA - k1, tc = D - k1;
-    for (int e = tid; e < (tr + 16) * NB; e += NT) {
-        const int i = e >> LOG_NB, c = e & (NB - 1);
-        Pn[i * PS + c] = (c < nb && i < tr) ? Wm[(size_t)(k1 + i) * DA + k0 + c] : 0.0;
-    }
+    const int k1 = k0 + nb;
+    chol_panel_load<NB, 16>(Pn, Wm, DA, k1, k0, DA - k1, nb, tid);
     __syncthreads();
-    // rows k1..D, columns k1..D-1, the 16 x 16 tiles of the lower triangle dealt to all waves of the task's workgroups
-    const int nti = (tr + 15) >> 4, ntj = (tc + 15) >> 4, ntile = nti * ntj;
-    const int nw = (FITW_NT / 64) * (int)gridDim.y;
-    for (int tix = w + (FITW_NT / 64) * (int)blockIdx.y; tix < ntile; tix += nw) {
-        const int bi = tix / ntj, bj = tix - bi * ntj;
-        if (bj > bi) continue;                     // wave-uniform
-        const double* pa = Pn + (size_t)(16 * bi + i16) * PS + kk;
-        const double* pb = Pn + (size_t)(16 * bj + i16) * PS + kk;
-        double* dst[4];
-        double old[4];
-        bool ok[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int io = 16 * bi + kk + 4 * r, jo = 16 * bj + i16;
-            ok[r] = io < tr && jo < tc && jo <= io;
-            dst[r] = Wm + (size_t)(k1 + (ok[r] ? io : 0)) * DA + k1 + (ok[r] ? jo : 0);
-            old[r] = *dst[r];
-        }
-        f64x4 acc = zero4d();
-#pragma unroll
-        for (int sidx = 0; sidx < NB / 4; ++sidx) acc = mfma16d(pa[4 * sidx], pb[4 * sidx], acc);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (ok[r]) *dst[r] = old[r] - acc[r];
-    }
+    // the tiles dealt to all waves of the task's workgroups
+    chol_trailing_update<NB>(Wm, Pn, 0, D, k1, w + (FITW_NT / 64) * (int)blockIdx.y, (FITW_NT / 64) * (int)gridDim.y, lane);
 }
 
 template <int NB>
@@ -1397,17 +1363,14 @@ __global__ void __launch_bounds__(FITW_NT) k_fitw_back(SampleArgs a, double* scr
     double* tri = rdv + DA;                   // two triangles of the factor's diagonal blocks
     int* flag = (int*)(tri + 2 * NB * (NB + 1));
     const double* Wm = scratch + (size_t)task * 2 * DA * DA + (size_t)DA * DA;
-    // ---- back substitution L^T w = z, z = row D of the factor, NB rows of L at a time (k_fit_wide's)
+    // ---- back substitution L^T w = z, z = row D of the factor, NB rows of L at a time
     for (int e = tid; e < D; e += NT) {
         yv[e] = Wm[(size_t)D * DA + e];
         rdv[e] = 1.0 / Wm[(size_t)e * DA + e];
     }
     if (tid == 0) *flag = 0;
-    fitw_back_substitute<NB>(Wm, D, DA, yv, wv, rdv, tri, tid, lane, w);
-    for (int e = tid; e < D; e += NT)
-        if (wv[e] != wv[e]) *flag = 1;
-    __syncthreads();
-    const int isbad = *flag;
+    fitw_back_substitute<NB>(Wm, D, DA, yv, wv, rdv, tri, tid, lane, w);       // (its barriers cover the flag)
+    const int isbad = fit_any_nan<false>(wv, D, flag, tid, NT);
     if (tid == 0) bad[task] = isbad;
     if (!isbad)
         for (int e = tid; e < D; e += NT) a.coeffs[(long long)task * a.coeff_stride + e] = wv[e];
