@@ -626,7 +626,7 @@ static void launch_coop_split(promp_ctx* c, StepData& S, PassArgs& a, const Pass
         // the direction's planes carry its scale: its largest entry per task first (one small launch)
         VecAbsmaxArgs va;
         va.src = c->vbuf; va.stride = c->NP; va.n = c->NP; va.out = c->vdir_absmax;
-        va.n_w1 = c->d.obs_dim * c->d.hidden1; va.obs_absmax = a.obs_absmax;
+        va.n_w1 = mlp2_layout(c->d.obs_dim, c->d.hidden1, c->d.hidden2, c->d.act_dim).b1; va.obs_absmax = a.obs_absmax;
         PROMP_LAUNCH(k_vec_absmax, dim3(c->d.n_tasks), 1024, 64, c->stream, va);
         a.vdir_absmax = (const float*)c->vdir_absmax.p;
         pa.src = c->vbuf; pa.src_stride = c->NP; pa.dst = c->wb_vplanes; pa.vec_absmax = a.vdir_absmax;

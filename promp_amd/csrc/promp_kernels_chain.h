@@ -379,7 +379,7 @@ PROMP_DEV float chain_stage_nets(float* sm, float* vmx, const float* src0, const
     // to memory: 9.4 k instead of 5.4 k cycles until the last load is issued, k_chain_hvp 100.2 -> 96.4 us per launch (measured).
     tid += opaque_zero();
     const int lane = tid & 63, i16 = lane & 15, kk = lane >> 4, w = wave_uniform(tid >> 6);
-    const int ob1 = O * H1, oW2 = ob1 + H1, ob2 = oW2 + H1 * H2, oW3 = ob2 + H2, ob3 = oW3 + H2 * A;
+    const Mlp2Layout lay = mlp2_layout(O, H1, H2, A);
     // output block: the action of row i16.  Fragment order by action SLOT (slot 4 ko + ro <-> action 2 ko + ro, ro < 2; the other
     // lanes hold zeros), or -- BWDP -- by action: lanes i16 and i16 + 8 both stage action i16 & 7 (same values, same addresses)
     const int mm = i16, ro3 = mm & 3, aa3 = BWDP ? (mm & 7) : 2 * (mm >> 2) + ro3;
@@ -426,32 +426,32 @@ PROMP_DEV float chain_stage_nets(float* sm, float* vmx, const float* src0, const
                 const int bj = w + it * NW, P = bj < NB3P ? bj : NB3P - 1;
 #pragma unroll
                 for (int e = 0; e < 8; ++e)
-                    x3p[n][it][e] = src[oW3 + (16 * (2 * P + (e >> 2)) + 4 * kk + (e & 3)) * A + (aok ? aact : 0)];
+                    x3p[n][it][e] = src[lay.W3 + (16 * (2 * P + (e >> 2)) + 4 * kk + (e & 3)) * A + (aok ? aact : 0)];
             }
         }
 #pragma unroll
         for (int it = 0; it < IT2; ++it) {
             const int bj = w + it * NW, b = bj < NB2 ? bj : NB2 - 1, c2 = b / (NC1 / 2), P = b - c2 * (NC1 / 2);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) x2[n][it][e] = src[oW2 + (16 * (2 * P + (e >> 2)) + 4 * kk + (e & 3)) * H2 + 16 * c2 + i16];
+            for (int e = 0; e < 8; ++e) x2[n][it][e] = src[lay.W2 + (16 * (2 * P + (e >> 2)) + 4 * kk + (e & 3)) * H2 + 16 * c2 + i16];
         }
 #pragma unroll
         for (int it = 0; it < IT4; ++it) {
             const int bj = w + it * NW, b = bj < NB4 ? bj : NB4 - 1, c1 = b / (NC2 / 2), P = b - c1 * (NC2 / 2);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) x4[n][it][e] = src[oW2 + (16 * c1 + i16) * H2 + 16 * (2 * P + (e >> 2)) + 4 * kk + (e & 3)];
+            for (int e = 0; e < 8; ++e) x4[n][it][e] = src[lay.W2 + (16 * c1 + i16) * H2 + 16 * (2 * P + (e >> 2)) + 4 * kk + (e & 3)];
         }
 #pragma unroll
         for (int it = 0; it < IT3; ++it) {
             const int bj = w + it * NW, c = bj < NB3 ? bj : NB3 - 1;
             if (!BWDP) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) x3[n][it][r] = src[oW3 + (16 * c + 4 * kk + r) * A + (ok3 ? aa3 : 0)];
+                for (int r = 0; r < 4; ++r) x3[n][it][r] = src[lay.W3 + (16 * c + 4 * kk + r) * A + (ok3 ? aa3 : 0)];
             }
 #pragma unroll
             for (int ro = 0; ro < 2; ++ro) {
                 const int aa = 2 * kk + ro;
-                y3[n][it][ro] = src[oW3 + (16 * c + i16) * A + (aa < A ? aa : 0)];
+                y3[n][it][ro] = src[lay.W3 + (16 * c + i16) * A + (aa < A ? aa : 0)];
             }
         }
     }
@@ -459,7 +459,7 @@ PROMP_DEV float chain_stage_nets(float* sm, float* vmx, const float* src0, const
     for (int it = 0; it < IS; ++it) {
         const int dj = tid + it * NT, d = dj < N5 ? dj : N5 - 1;
         const int aa = d - H1 - H2;
-        const int idx = d < H1 ? ob1 + d : d < H1 + H2 ? ob2 + d - H1 : ob3 + (aa < A ? aa : 0);
+        const int idx = d < H1 ? lay.b1 + d : d < H1 + H2 ? lay.b2 + d - H1 : lay.b3 + (aa < A ? aa : 0);
         z[0][it] = src0[idx];
         z[1][it] = src1[idx];
     }
@@ -498,8 +498,7 @@ PROMP_DEV float chain_stage_nets(float* sm, float* vmx, const float* src0, const
         float m = 0.f;
 #pragma unroll
         for (int ww = 0; ww < NW; ++ww) m = fmaxf(m, vmx[ww]);
-        int k = (m > 0.f && m < 3.0e38f) ? scale_exp(m, vt) : 0;
-        k = k < -100 ? -100 : k > 100 ? 100 : k;
+        const int k = (m > 0.f && m < 3.0e38f) ? scale_exp_clamped(m, vt) : 0;
         vs = pow2f(k);
     }
     sched_fence();
@@ -613,6 +612,8 @@ PROMP_DEV float chain_stage_nets(float* sm, float* vmx, const float* src0, const
 // distribution constants of the theta network: s (clipped), exp(-s), exp(2 s), gradient mask, R{s}, 1 / (2 exp(2 s) + 1e-8).
 // The two global reads are issued by chain_dist_load BEFORE the networks are staged (their round trip to L2 hides behind the
 // staging loads instead of following them).
+// (The clip rule is promp_objective.h's log_std_terms, spelled out here: through the helper k_pass's instruction stream moved by two
+// s_nop and its slot measured 0.3 us slower, 49.8 against 49.4 .. 49.6 us -- profiles/pass_dedup_timing.txt.)
 struct ChainDistRaw { float s, v; };
 PROMP_DEV ChainDistRaw chain_dist_load(const float* th, const float* v, int oS, int A, int tid) {
     ChainDistRaw r;
@@ -695,8 +696,8 @@ PROMP_DEV bool chain_reduce_to_partial(float* S, float* P, const f32x4 (&aw2)[NC
     //  this point are spilled across the tile loop, and each reload here is a round trip to scratch memory in the kernel's tail)
     tid += opaque_zero();
     const int lane = tid & 63, w = tid >> 6, i16 = lane & 15, kk = lane >> 4;
-    const int ob1 = O * H1, oW2 = ob1 + H1, ob2 = oW2 + H1 * H2, oW3 = ob2 + H2, ob3 = oW3 + H2 * A, oS = ob3 + A, NP = oS + A;
-    const int SL = (NP + 2 + 3) & ~3;
+    const Mlp2Layout lay = mlp2_layout(O, H1, H2, A);
+    const int SL = (lay.NP + 2 + 3) & ~3;
     if (lane == 0) ((int*)S)[w - 4] = bad;      // the four words in front of the slabs
     lds_barrier();                // every wave is done with the parameter / transpose regions
     {
@@ -709,14 +710,14 @@ PROMP_DEV bool chain_reduce_to_partial(float* S, float* P, const f32x4 (&aw2)[NC
                 for (int bj = 0; bj < NC2 / 2; ++bj)
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
-                        mine[oW2 + (32 * bi + (r & 3) + 8 * (r >> 2) + 4 * kh) * H2 + 32 * bj + j32] = aw2w[bi][bj][r] * us;
+                        mine[lay.W2 + (32 * bi + (r & 3) + 8 * (r >> 2) + 4 * kh) * H2 + 32 * bj + j32] = aw2w[bi][bj][r] * us;
         } else {
 #pragma unroll
             for (int i = 0; i < NC1; ++i)
 #pragma unroll
                 for (int j = 0; j < NC2; ++j)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) mine[oW2 + (16 * i + 4 * kk + r) * H2 + 16 * j + i16] = aw2[i][j][r] * us;
+                    for (int r = 0; r < 4; ++r) mine[lay.W2 + (16 * i + 4 * kk + r) * H2 + 16 * j + i16] = aw2[i][j][r] * us;
         }
         if (W32) {                // (round 6) the hidden_0 kernel gradient in the 32 x 32 result layout: rows = observation slots
             const int j32 = lane & 31, kh = lane >> 5;
@@ -742,40 +743,40 @@ PROMP_DEV bool chain_reduce_to_partial(float* S, float* P, const f32x4 (&aw2)[NC
         for (int j = 0; j < NC2; ++j)
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-                if (i16 < A) mine[oW3 + (16 * j + 4 * kk + r) * A + i16] = aw3[j][r] * us;
+                if (i16 < A) mine[lay.W3 + (16 * j + 4 * kk + r) * A + i16] = aw3[j][r] * us;
         if (kk == 0) {
             if (!W32) {
 #pragma unroll
-                for (int j = 0; j < NC1; ++j) mine[ob1 + 16 * j + i16] = gb1[j] * us;
+                for (int j = 0; j < NC1; ++j) mine[lay.b1 + 16 * j + i16] = gb1[j] * us;
             }
             if (!W32) {
 #pragma unroll
-                for (int j = 0; j < NC2; ++j) mine[ob2 + 16 * j + i16] = gb2[j] * us;
+                for (int j = 0; j < NC2; ++j) mine[lay.b2 + 16 * j + i16] = gb2[j] * us;
             }
         }
         if (W32 && i16 == 0) {
 #pragma unroll
             for (int j = 0; j < NC2; ++j)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) mine[ob2 + 16 * j + 4 * kk + r] = gb2v[j][r] * us;
+                for (int r = 0; r < 4; ++r) mine[lay.b2 + 16 * j + 4 * kk + r] = gb2v[j][r] * us;
 #pragma unroll
             for (int j = 0; j < NC1; ++j)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) mine[ob1 + 16 * j + 4 * kk + r] = gb1v[j][r] * us;
+                for (int r = 0; r < 4; ++r) mine[lay.b1 + 16 * j + 4 * kk + r] = gb1v[j][r] * us;
         }
         if (i16 == 0) {           // lane (0, kk) holds the sums of actions 2 kk, 2 kk + 1
             if (2 * kk < A) {
-                mine[ob3 + 2 * kk] = gb30;
-                mine[oS + 2 * kk] = gs0;
+                mine[lay.b3 + 2 * kk] = gb30;
+                mine[lay.ls + 2 * kk] = gs0;
             }
             if (2 * kk + 1 < A) {
-                mine[ob3 + 2 * kk + 1] = gb31;
-                mine[oS + 2 * kk + 1] = gs1;
+                mine[lay.b3 + 2 * kk + 1] = gb31;
+                mine[lay.ls + 2 * kk + 1] = gs1;
             }
         }
         if (lane == 0) {
-            mine[NP] = loss;
-            mine[NP + 1] = klsum;
+            mine[lay.NP] = loss;
+            mine[lay.NP + 1] = klsum;
         }
     }
     lds_barrier();
@@ -980,7 +981,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) k_chain_hvp(PassArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, w = wave_uniform(tid >> 6);
     const int i16 = lane & 15, kk = lane >> 4;
     const int O = a.O, A = a.A;
-    const int ob1 = O * H1, oW2 = ob1 + H1, ob2 = oW2 + H1 * H2, oW3 = ob2 + H2, ob3 = oW3 + H2 * A, oS = ob3 + A, NP = oS + A;
+    const Mlp2Layout lay = mlp2_layout(O, H1, H2, A);
     float* net = sm + 4;
     float* vnet = net + L.net_stride;
     constexpr int VO = L.net_stride;                  // the -v fragments sit at the same offsets, one block further
@@ -1034,11 +1035,11 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) k_chain_hvp(PassArgs a) {
         const int trow0 = a.task_row_offsets[task], tnrows = a.task_row_offsets[task + 1] - trow0;
         const float invN = 1.0f / (float)tnrows;
         const float* th = a.theta + (long long)task * a.theta_task_stride;
-        const float* v = a.vdir + (long long)task * NP;
+        const float* v = a.vdir + (long long)task * lay.NP;
         // The segment's requests, in the order their answers are needed: the distribution's raw parameters and the networks (from
         // L2), then -- inside the staging, behind its last load -- the first tile's observations and (CACHED) its cache block (from
         // memory); the workgroup joins (the previous segment is done with LDS) only after everything is on its way.
-        const ChainDistRaw draw = chain_dist_load(th, v, oS, A, tid);
+        const ChainDistRaw draw = chain_dist_load(th, v, lay.ls, A, tid);
         const int tend = seg.tile0 + seg.ntiles;
         float xT[KS];
         float xr[8];              // CACHED: the tile's observations as k_pass reads them (eight consecutive slots of the lane's sample)
@@ -1055,7 +1056,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) k_chain_hvp(PassArgs a) {
         //  them --, the third lowers it too)
         const int vt = CHAIN_V_TARGET - (attempt >= 2 ? CHAIN_V_RETRY : 0), ct = attempt ? CHAIN_CT_REDO - (attempt - 1) * CHAIN_CT_RETRY : CHAIN_CT_TARGET;
         // (L is the layout for a parameter count of 0: the slabs of the real one may end behind L.vmx; the host sized LDS for both)
-        const int slabs_end = 4 + NW * ((NP + 2 + 3) & ~3), vmx_off = slabs_end > L.vmx ? slabs_end : L.vmx;
+        const int slabs_end = 4 + NW * ((lay.NP + 2 + 3) & ~3), vmx_off = slabs_end > L.vmx ? slabs_end : L.vmx;
         const float vs = chain_stage_nets<NC1, NC2, NW, CACHED>(sm, sm + vmx_off, th, v, O, A, tid, vt, w1w, [&]() {
             {
                 const int t = seg.tile0 + w;
@@ -1130,8 +1131,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) k_chain_hvp(PassArgs a) {
         float cs = 1.f, qs = vs, ivs = 1.f / vs, amax = 0.f;
         int prov = 1;
         if (PROMP_NT == 2 && attempt > 0 && redo_amax > 0.f && redo_amax < 3.0e38f) {      // the segment again: the largest cotangent is known
-            int k = scale_exp(redo_amax, CHAIN_CT_REDO - (attempt - 1) * CHAIN_CT_RETRY);
-            k = k < -100 ? -100 : k > 100 ? 100 : k;
+            const int k = scale_exp_clamped(redo_amax, CHAIN_CT_REDO - (attempt - 1) * CHAIN_CT_RETRY);
             cs = pow2f(k);
             qs = cs * vs;
             prov = 0;
@@ -1750,7 +1750,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) k_chain_hvp(PassArgs a) {
         }
         attempt = 0;
         CH_STAMP(3);
-        if (a.fuse_reduce) chain_task_reduce<NT>(a, (int*)sm, task, NP, tid);
+        if (a.fuse_reduce) chain_task_reduce<NT>(a, (int*)sm, task, lay.NP, tid);
         CH_STAMP(4);
         CH_WGSTAMP(1 + (sg - sg0 < 2 ? sg - sg0 : 1));
     }

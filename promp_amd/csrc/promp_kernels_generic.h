@@ -401,14 +401,12 @@ __global__ void __launch_bounds__(256) k_gen_loss(GenArgs a, int pp) {
     const float* __restrict__ g_om = a.old_mean;
     float* __restrict__ g_dz = a.dz[pp]; float* __restrict__ g_qz = a.qz[pp];
     if (tid < A) {
-        const float sr = th[oS + tid];
-        const bool clipped = a.clip_log_std && sr < a.min_log_std;
-        const float s = clipped ? a.min_log_std : sr;
-        cst[tid] = s;
-        cst[GEN_MAX_A + tid] = expf(-s);
-        cst[2 * GEN_MAX_A + tid] = expf(2.f * s);
-        cst[3 * GEN_MAX_A + tid] = clipped ? 0.f : 1.f;
-        cst[4 * GEN_MAX_A + tid] = (HVP && !clipped) ? -a.vdir[(long long)wk.task * NP + oS + tid] : 0.f;
+        const LogStdTerms t = log_std_terms(th[oS + tid], a.clip_log_std, a.min_log_std);
+        cst[tid] = t.s;
+        cst[GEN_MAX_A + tid] = t.es;
+        cst[2 * GEN_MAX_A + tid] = t.sn2;
+        cst[3 * GEN_MAX_A + tid] = t.mask;
+        cst[4 * GEN_MAX_A + tid] = (HVP && !t.clipped) ? -a.vdir[(long long)wk.task * NP + oS + tid] : 0.f;
         if (!a.ls_per_row) {
             const float so = a.old_log_std[(long long)wk.task * A + tid];
             cst[5 * GEN_MAX_A + tid] = so;

@@ -117,7 +117,7 @@ PROMP_DEV void pass_stage_net(float* sm, const float* th, int O, int A, int tid,
     constexpr int B1 = L.f_w2f / 64, B2 = L.f_w2b / 64, B3 = L.f_w3f / 64, NBLK = L.n_frag / 64;
     constexpr int IS = (L.n_side + NT - 1) / NT;
     const int lane = tid & 63, i16 = lane & 15, kk = lane >> 4, w = wave_uniform(tid >> 6);
-    const int ob1 = O * H1, oW2 = ob1 + H1, ob2 = oW2 + H1 * H2, oW3 = ob2 + H2, ob3 = oW3 + H2 * A;
+    const Mlp2Layout lay = mlp2_layout(O, H1, H2, A);
     // output row m = i16 of the mean GEMM carries action 2 (m / 4) + m % 4 for m % 4 < 2 (a lane's D registers 0, 1 are then
     // actions 2 kk, 2 kk + 1: the distribution epilogue keeps all four lane groups busy), nothing otherwise
     const int aro = i16 & 3, aact = 2 * (i16 >> 2) + aro;
@@ -142,19 +142,19 @@ PROMP_DEV void pass_stage_net(float* sm, const float* th, int O, int A, int tid,
     for (int it = 0; it < IT2; ++it) {              // W2[u(P, kk, e)][16 c2 + i16]
         const int bj = w + it * NW, b = bj < NK2 ? bj : NK2 - 1, c2 = b / NP1, P = b - c2 * NP1;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) x2[it][e] = th[oW2 + pass_unit(0, kk, e) * H2 + (32 * P * H2 + 16 * c2) + i16];
+        for (int e = 0; e < 8; ++e) x2[it][e] = th[lay.W2 + pass_unit(0, kk, e) * H2 + (32 * P * H2 + 16 * c2) + i16];
     }
 #pragma unroll
     for (int it = 0; it < IT3; ++it) {              // W2[16 c1 + i16][u(P, kk, e)]
         const int bj = w + it * NW, b = bj < NK3 ? bj : NK3 - 1, c1 = b / NP2, P = b - c1 * NP2;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) x3[it][e] = th[oW2 + i16 * H2 + pass_unit(0, kk, e) + (16 * c1 * H2 + 32 * P)];
+        for (int e = 0; e < 8; ++e) x3[it][e] = th[lay.W2 + i16 * H2 + pass_unit(0, kk, e) + (16 * c1 * H2 + 32 * P)];
     }
 #pragma unroll
     for (int it = 0; it < IT4; ++it) {              // W3[u(P, kk, e)][action of row i16]
         const int bj = w + it * NW, P = bj < NK4 ? bj : NK4 - 1;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) x4[it][e] = th[oW3 + (pass_unit(0, kk, e) + 32 * P) * A + (aok ? aact : 0)];
+        for (int e = 0; e < 8; ++e) x4[it][e] = th[lay.W3 + (pass_unit(0, kk, e) + 32 * P) * A + (aok ? aact : 0)];
     }
     // float32 side tables: W3 for dH2 = W3 dmu^T ([c][lane][ro]: W3[16 c + i16][2 kk + ro]), biases (those that feed a tanh prescaled)
 #pragma unroll
@@ -164,17 +164,17 @@ PROMP_DEV void pass_stage_net(float* sm, const float* th, int O, int A, int tid,
         float m = 0.f;
         if (wd < L.b1) {
             const int c = e >> 7, l = (e >> 1) & 63, aa = 2 * (l >> 4) + (e & 1);
-            idx = oW3 + (16 * c + (l & 15)) * A + (aa < A ? aa : 0);
+            idx = lay.W3 + (16 * c + (l & 15)) * A + (aa < A ? aa : 0);
             m = aa < A ? 1.f : 0.f;
         } else if (wd < L.b2) {
-            idx = ob1 + (wd - L.b1);
+            idx = lay.b1 + (wd - L.b1);
             m = PROMP_TANH_PRESCALE;
         } else if (wd < L.b3) {
-            idx = ob2 + (wd - L.b2);
+            idx = lay.b2 + (wd - L.b2);
             m = PROMP_TANH_PRESCALE;
         } else {
             const int aa = wd - L.b3;
-            idx = ob3 + (aa < A ? aa : 0);
+            idx = lay.b3 + (aa < A ? aa : 0);
             m = aa < A ? 1.f : 0.f;
         }
         y[it] = th[idx] * m;
@@ -247,8 +247,8 @@ PROMP_DEV bool pass_reduce_to_partial(float* S, float* P, const f32x16 (&aw2)[NC
     constexpr int H1 = 16 * NC1, H2 = 16 * NC2, NT = 64 * NW;
     tid += opaque_zero();         // (as in chain_reduce_to_partial: no lane-constant index kept alive, and spilled, across the tile loop)
     const int lane = tid & 63, w = tid >> 6, i16 = lane & 15, kk = lane >> 4, j32 = lane & 31, kh = lane >> 5;
-    const int ob1 = O * H1, oW2 = ob1 + H1, ob2 = oW2 + H1 * H2, oW3 = ob2 + H2, ob3 = oW3 + H2 * A, oS = ob3 + A, NP = oS + A;
-    const int SL = (NP + 2 + 3) & ~3;
+    const Mlp2Layout lay = mlp2_layout(O, H1, H2, A);
+    const int SL = (lay.NP + 2 + 3) & ~3;
     if (lane == 0) ((int*)S)[w - 4] = bad;     // the spare words in front of the slabs: this wave's overflow vote
     lds_barrier();                // every wave is done with the parameter planes / transposed tiles
     {
@@ -259,7 +259,7 @@ PROMP_DEV bool pass_reduce_to_partial(float* S, float* P, const f32x16 (&aw2)[NC
             for (int bj = 0; bj < NC2 / 2; ++bj)
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    mine[oW2 + (32 * bi + (r & 3) + 8 * (r >> 2) + 4 * kh) * H2 + 32 * bj + j32] = aw2[bi][bj][r] * gsc;
+                    mine[lay.W2 + (32 * bi + (r & 3) + 8 * (r >> 2) + 4 * kh) * H2 + 32 * bj + j32] = aw2[bi][bj][r] * gsc;
 #pragma unroll
         for (int bj = 0; bj < NC1 / 2; ++bj)
 #pragma unroll
@@ -271,28 +271,28 @@ PROMP_DEV bool pass_reduce_to_partial(float* S, float* P, const f32x16 (&aw2)[NC
         for (int c = 0; c < NC2; ++c)
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-                if (i16 < A) mine[oW3 + (16 * c + 4 * kk + r) * A + i16] = aw3[c][r] * gsc;
+                if (i16 < A) mine[lay.W3 + (16 * c + 4 * kk + r) * A + i16] = aw3[c][r] * gsc;
         if (i16 == 0) {           // (bias sums already folded over the 16 sample lanes) units 16 c + 4 kk + r; actions 2 kk, 2 kk + 1
 #pragma unroll
             for (int c = 0; c < NC1; ++c)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) mine[ob1 + 16 * c + 4 * kk + r] = gb1[c][r] * gsc;
+                for (int r = 0; r < 4; ++r) mine[lay.b1 + 16 * c + 4 * kk + r] = gb1[c][r] * gsc;
 #pragma unroll
             for (int c = 0; c < NC2; ++c)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) mine[ob2 + 16 * c + 4 * kk + r] = gb2[c][r] * gsc;
+                for (int r = 0; r < 4; ++r) mine[lay.b2 + 16 * c + 4 * kk + r] = gb2[c][r] * gsc;
             if (2 * kk < A) {
-                mine[ob3 + 2 * kk] = gb30;
-                mine[oS + 2 * kk] = gs0;
+                mine[lay.b3 + 2 * kk] = gb30;
+                mine[lay.ls + 2 * kk] = gs0;
             }
             if (2 * kk + 1 < A) {
-                mine[ob3 + 2 * kk + 1] = gb31;
-                mine[oS + 2 * kk + 1] = gs1;
+                mine[lay.b3 + 2 * kk + 1] = gb31;
+                mine[lay.ls + 2 * kk + 1] = gs1;
             }
         }
         if (lane == 0) {
-            mine[NP] = loss;
-            mine[NP + 1] = klsum;
+            mine[lay.NP] = loss;
+            mine[lay.NP + 1] = klsum;
         }
     }
     lds_barrier();
@@ -748,7 +748,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) k_pass(PassArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, w = wave_uniform(tid >> 6);
     const int i16 = lane & 15, kk = lane >> 4;
     const int O = a.O, A = a.A;
-    const int ob1 = O * H1, oW2 = ob1 + H1, ob2 = oW2 + H1 * H2, oW3 = ob2 + H2, ob3 = oW3 + H2 * A, oS = ob3 + A, NP = oS + A;
+    const Mlp2Layout lay = mlp2_layout(O, H1, H2, A);
     const float* dist = sm + L.dist;
     float* wreg = sm + L.wave0 + w * L.wave_stride;
     const PassTileAddr T = pass_tile_addr(lane);
@@ -776,7 +776,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) k_pass(PassArgs a) {
         // observations (from memory) behind the staging's last load; the workgroup joins after everything is on its way
         float xr[8];
         int t = seg.tile0 + w;
-        const ChainDistRaw draw = chain_dist_load(th, nullptr, oS, A, tid);
+        const ChainDistRaw draw = chain_dist_load(th, nullptr, lay.ls, A, tid);
         CH_STAMP(0);
         // FP16 split: the task's observations times 2^-sx, the hidden_0 kernel times 2^sx (obs_shift, promp_kernels_chain.h)
         float w1s = 1.f;
@@ -877,8 +877,8 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) k_pass(PassArgs a) {
                     l += sm[4 + 2 * ww];
                     k += sm[4 + 2 * ww + 1];
                 }
-                P[NP] = l;
-                P[NP + 1] = k;
+                P[lay.NP] = l;
+                P[lay.NP + 1] = k;
             }
             continue;
         }

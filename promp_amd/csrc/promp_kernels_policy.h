@@ -350,24 +350,24 @@ struct ForwardArgs {
 __global__ void __launch_bounds__(256) k_policy_forward(ForwardArgs a) {
     const int task = blockIdx.x;
     const int O = a.O, A = a.A, H1 = a.H1, H2 = a.H2;
-    const int ob1 = O * H1, oW2 = ob1 + H1, ob2 = oW2 + H1 * H2, oW3 = ob2 + H2, ob3 = oW3 + H2 * A, NP = ob3 + 2 * A;
-    const float* th = a.theta_tasks + (long long)task * NP;
+    const Mlp2Layout lay = mlp2_layout(O, H1, H2, A);
+    const float* th = a.theta_tasks + (long long)task * lay.NP;
     for (int row = threadIdx.x; row < a.B; row += 256) {
         const float* x = a.obs + ((long long)task * a.B + row) * O;
         float h1[128], h2[128];   // hidden sizes up to 128
         for (int j = 0; j < H1; ++j) {
-            float z = th[ob1 + j];
+            float z = th[lay.b1 + j];
             for (int k = 0; k < O; ++k) z = fmaf(x[k], th[k * H1 + j], z);
             h1[j] = fast_tanh(z);
         }
         for (int j = 0; j < H2; ++j) {
-            float z = th[ob2 + j];
-            for (int k = 0; k < H1; ++k) z = fmaf(h1[k], th[oW2 + k * H2 + j], z);
+            float z = th[lay.b2 + j];
+            for (int k = 0; k < H1; ++k) z = fmaf(h1[k], th[lay.W2 + k * H2 + j], z);
             h2[j] = fast_tanh(z);
         }
         for (int j = 0; j < A; ++j) {
-            float z = th[ob3 + j];
-            for (int k = 0; k < H2; ++k) z = fmaf(h2[k], th[oW3 + k * A + j], z);
+            float z = th[lay.b3 + j];
+            for (int k = 0; k < H2; ++k) z = fmaf(h2[k], th[lay.W3 + k * A + j], z);
             a.mean[((long long)task * a.B + row) * A + j] = z;
         }
     }

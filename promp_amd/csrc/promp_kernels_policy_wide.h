@@ -17,6 +17,11 @@
 //     Only the tiny output kernel (128 x 8) sits in LDS.
 //   * k mapping of a step (the four k values lane groups kk = 0..3 contract) is chosen per GEMM so that the two
 //     lane groups of a 32-lane LDS access are 16 k (or 16 rows) apart: conflict-free with the odd tile strides.
+//
+// What k_wide_fwd_bwd and k_wide_hvp share is written once, in front of them: coop_item (work item, 1 / N, parameter base) and
+// coop_stage_log_std (the clipped log_std constants through promp_objective.h's log_std_terms) -- both also used by the k_wb_* pair
+// of promp_kernels_wide_bf16.h --, wide_action_sums_to_lds (the epilogue lanes' per-action sums) and wide_write_partial (log_std
+// and bias entries, the three kernel slices of the partial row).  The parameter offsets are promp_plan.h's Mlp2Layout.
 #pragma once
 #include "promp_kernels_policy.h"
 
@@ -118,20 +123,20 @@ template <int WIDE_H>
 PROMP_DEV void wide_stage_head(float* W3s, float* W3Ts, float* b1s, float* b2s, float* b3s, const float* src, int O, int A,
                                int tid, int nthreads) {
     constexpr int WIDE_HS = WIDE_H + 1;
-    const int ob1 = O * WIDE_H, oW2 = ob1 + WIDE_H, ob2 = oW2 + WIDE_H * WIDE_H, oW3 = ob2 + WIDE_H, ob3 = oW3 + WIDE_H * A;
+    const Mlp2Layout lay = mlp2_layout(O, WIDE_H, WIDE_H, A);
     for (int e = tid; e < WIDE_H * 16; e += nthreads) {
         const int k = e >> 4, j = e & 15;
-        W3s[k * WIDE_W3S + j] = (j < A) ? src[oW3 + k * A + j] : 0.f;
+        W3s[k * WIDE_W3S + j] = (j < A) ? src[lay.W3 + k * A + j] : 0.f;
     }
     for (int e = tid; e < 8 * WIDE_H; e += nthreads) {
         const int aa = e / WIDE_H, k = e - aa * WIDE_H;
-        W3Ts[aa * WIDE_HS + k] = (aa < A) ? src[oW3 + k * A + aa] : 0.f;
+        W3Ts[aa * WIDE_HS + k] = (aa < A) ? src[lay.W3 + k * A + aa] : 0.f;
     }
     for (int e = tid; e < WIDE_H; e += nthreads) {
-        b1s[e] = src[ob1 + e];
-        b2s[e] = src[ob2 + e];
+        b1s[e] = src[lay.b1 + e];
+        b2s[e] = src[lay.b2 + e];
     }
-    if (tid < 16) b3s[tid] = (tid < A) ? src[ob3 + tid] : 0.f;
+    if (tid < 16) b3s[tid] = (tid < A) ? src[lay.b3 + tid] : 0.f;
 }
 
 // one round's observations -> LDS tile (rows >= nrows zero, columns >= O stay zero from the initial fill)
@@ -143,6 +148,87 @@ PROMP_DEV void wide_load_x(float* Xs, int XS, const float* obs, long long row0, 
         const float x = obs[row0 * O + (e < lim ? e : 0)];
         Xs[r * XS + (e - r * O)] = (e < lim) ? x : 0.f;
     }
+}
+
+// ---- the pieces the cooperative twins share (k_wide_fwd_bwd / k_wide_hvp here, k_wb_fwd_bwd / k_wb_hvp in promp_kernels_wide_bf16.h) ----
+// The work item of this workgroup: its partial row wi, its rows wk, 1 / (rows of its task), its task's parameters
+struct CoopItem {
+    int wi;
+    WorkItem wk;
+    float invN;
+    const float* th;
+};
+PROMP_DEV CoopItem coop_item(const PassArgs& a) {
+    CoopItem it;
+    it.wi = xcd_item(blockIdx.x, gridDim.x);       // which work item (and partial row) this workgroup takes
+    it.wk = a.work[it.wi];
+    const int ntask = a.task_row_offsets[it.wk.task + 1] - a.task_row_offsets[it.wk.task];
+    it.invN = 1.0f / (float)ntask;
+    it.th = a.theta + (long long)it.wk.task * a.theta_task_stride;
+    return it;
+}
+// thread tid < 16 stages the log_std terms of action slot tid (promp_objective.h: log_std_terms); they are returned for the
+// R-operator kernels, which stage the direction's entry R{s} = mask * v_s from them
+PROMP_DEV LogStdTerms coop_stage_log_std(float* lss, float* lmask, float* ess, float* sn2s, const float* th, int oS, int A,
+                                         const PassArgs& a, int tid) {
+    const LogStdTerms t = log_std_terms((tid < A) ? th[oS + tid] : 0.f, a.clip_log_std, a.min_log_std);
+    lss[tid] = t.s;
+    lmask[tid] = t.mask;
+    ess[tid] = t.es;
+    sn2s[tid] = t.sn2;
+    return t;
+}
+
+// ---- the tail of k_wide_fwd_bwd / k_wide_hvp: the first NEW waves ran the epilogue, 4 lanes per row with actions {q, q + 4} ----
+// per-action sums (log_std: s0 / s1, output bias: b0 / b1) over a wave's rows -> red[16 w + ..]; behind a barrier of its own
+template <int NEW>
+PROMP_DEV void wide_action_sums_to_lds(float* red, float s0, float s1, float b0, float b1, int lane, int w) {
+#pragma unroll
+    for (int m = 4; m <= 32; m <<= 1) {
+        s0 += shfl_xor_f32(s0, m);  s1 += shfl_xor_f32(s1, m);  b0 += shfl_xor_f32(b0, m);  b1 += shfl_xor_f32(b1, m);
+    }
+    __syncthreads();
+    if (lane < 4 && w < NEW) {     // lane == q
+        float* rw = red + 16 * w;
+        rw[lane] = s0;  rw[4 + lane] = s1;  rw[8 + lane] = b0;  rw[12 + lane] = b1;
+    }
+}
+// the partial row but its two scalars: log_std and output-bias entries (the waves' sums in wave order), the hidden biases' (g1, g2:
+// this lane's share of column col), the three kernel slices straight from their owners
+template <int H, int NOB, int NEW>
+PROMP_DEV void wide_write_partial(float* P, const Mlp2Layout& lay, int O, int A, const float* red, const float* lmask, float g1, float g2,
+                                  const f32x4 (&aw1)[NOB], const f32x4 (&aw2)[H / 16], const f32x4& aw3, int tid) {
+    const int i16 = tid & 15, kk = (tid & 63) >> 4, w = tid >> 6, col = 16 * w + i16;
+    if (tid < 16) {
+        const int j = tid & 3, which = tid >> 2;     // which: 0 s0(q) 1 s1(q+4) 2 b0(q) 3 b1(q+4)
+        float t = red[4 * which + j];
+        for (int ww = 1; ww < NEW; ++ww) t += red[16 * ww + 4 * which + j];
+        const int aidx = j + ((which & 1) ? 4 : 0);
+        if (aidx < A) {
+            if (which < 2) P[lay.ls + aidx] = t * lmask[aidx];
+            else P[lay.b3 + aidx] = t;
+        }
+    }
+    g1 += shfl_xor_f32(g1, 16);  g1 += shfl_xor_f32(g1, 32);
+    g2 += shfl_xor_f32(g2, 16);  g2 += shfl_xor_f32(g2, 32);
+    if (kk == 0) {
+        P[lay.b1 + col] = g1;
+        P[lay.b2 + col] = g2;
+    }
+#pragma unroll
+    for (int ob = 0; ob < NOB; ++ob)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = 16 * ob + 4 * kk + r;
+            if (row < O) P[row * H + col] = aw1[ob][r];
+        }
+#pragma unroll
+    for (int i = 0; i < H / 16; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) P[lay.W2 + (16 * i + 4 * kk + r) * H + col] = aw2[i][r];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        if (i16 < A) P[lay.W3 + (16 * w + 4 * kk + r) * A + i16] = aw3[r];
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -157,36 +243,27 @@ __global__ void __launch_bounds__(4 * H, 2) k_wide_fwd_bwd(PassArgs a) {
     float* sm = (float*)PROMP_SMEM_PTR;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int i16_ = lane & 15, kk_ = lane >> 4;
-    const int wi = xcd_item(blockIdx.x, gridDim.x);       // which work item (and partial row) this workgroup takes
-    const WorkItem wk = a.work[wi];
-    const int task = wk.task;
+    const CoopItem item = coop_item(a);
+    const int wi = item.wi, task = item.wk.task;
+    const WorkItem wk = item.wk;
+    const float invN = item.invN;
     const int O = a.O, A = a.A;
-    const int ob1 = O * H, oW2 = ob1 + H, ob2 = oW2 + H * H, oW3 = ob2 + H, ob3 = oW3 + H * A, oS = ob3 + A, NP = oS + A;
+    const Mlp2Layout lay = mlp2_layout(O, H, H, A);
     const LdsWide L = make_layout_wide(H, RB, NOB, false);
     const int XS = L.XS;
     float *Xs = sm + L.x, *W3s = sm + L.w3, *W3Ts = sm + L.w3t, *b1s = sm + L.b1, *b2s = sm + L.b2, *b3s = sm + L.b3,
           *lss = sm + L.ls, *lmask = sm + L.lmask, *ess = sm + L.es, *sn2s = sm + L.sn2, *red = sm + L.red;
-    const int ntask = a.task_row_offsets[task + 1] - a.task_row_offsets[task];
-    const float invN = 1.0f / (float)ntask;
-    const float* th = a.theta + (long long)task * a.theta_task_stride;
+    const float* th = item.th;
     const int col_ = 16 * w + i16_;   // the hidden column this lane owns in every MFMA result
 
     for (int e = tid; e < R * XS; e += NT) Xs[e] = 0.f;
     wide_stage_head<H>(W3s, W3Ts, b1s, b2s, b3s, th, O, A, tid, NT);
-    if (tid < 16) {
-        const float sr = (tid < A) ? th[oS + tid] : 0.f;
-        const bool clipped = a.clip_log_std && (sr < a.min_log_std);   // tf.maximum: gradient iff var >= min
-        const float s = clipped ? a.min_log_std : sr;
-        lss[tid] = s;
-        lmask[tid] = clipped ? 0.f : 1.f;
-        ess[tid] = expf(-s);
-        sn2s[tid] = expf(2.f * s);
-    }
+    if (tid < 16) coop_stage_log_std(lss, lmask, ess, sn2s, th, lay.ls, A, a, tid);
     // weight slices of this lane, resident for the whole kernel
     float w1r[KO / 4], w2c[WIDE_NS], w2r[WIDE_NS];
     wide_load_cols<KO, H>(w1r, th, O, col_, kk_, 1.f);
-    wide_load_cols<H, H>(w2c, th + oW2, H, col_, kk_, 1.f);
-    if (BWD) wide_load_rows<H>(w2r, th + oW2, col_, kk_, 1.f);
+    wide_load_cols<H, H>(w2c, th + lay.W2, H, col_, kk_, 1.f);
+    if (BWD) wide_load_rows<H>(w2r, th + lay.W2, col_, kk_, 1.f);
 
     // gradient slices: hidden_0 kernel [16 ob + ..][col], hidden_1 kernel [16 i + ..][col], output kernel rows 16w..
     f32x4 aw1[NOB], aw2[WIDE_NC], aw3 = zero4();
@@ -384,18 +461,12 @@ __global__ void __launch_bounds__(4 * H, 2) k_wide_fwd_bwd(PassArgs a) {
 
     // ---- results: scalars through LDS in wave order, gradient slices straight from their owners ----
     const int tidt = tid + opaque_zero();          // (the tail's lane indices too: recomputed, not reloaded from a spill)
-    const int i16 = tidt & 15, kk = (tidt & 63) >> 4, col = 16 * (tidt >> 6) + i16;
     float* P = a.partials + (long long)wi * a.partial_stride;
 #pragma unroll
     for (int m = 4; m <= 32; m <<= 1) {
-        gs0 += shfl_xor_f32(gs0, m);  gs1 += shfl_xor_f32(gs1, m);  gb30 += shfl_xor_f32(gb30, m);
-        gb31 += shfl_xor_f32(gb31, m);  loss += shfl_xor_f32(loss, m);  klsum += shfl_xor_f32(klsum, m);
+        loss += shfl_xor_f32(loss, m);  klsum += shfl_xor_f32(klsum, m);
     }
-    __syncthreads();
-    if (lane < 4 && w < 4) {       // waves 0..3 ran the epilogue; lane == q
-        float* rw = red + 16 * w;
-        rw[lane] = gs0;  rw[4 + lane] = gs1;  rw[8 + lane] = gb30;  rw[12 + lane] = gb31;
-    }
+    wide_action_sums_to_lds<4>(red, gs0, gs1, gb30, gb31, lane, w);       // waves 0..3 ran the epilogue
     __syncthreads();
     float* sc = Xs;                // two scalars per wave
     if (lane == 0) {
@@ -409,40 +480,11 @@ __global__ void __launch_bounds__(4 * H, 2) k_wide_fwd_bwd(PassArgs a) {
             l += sc[2 * ww];
             k += sc[2 * ww + 1];
         }
-        P[NP] = l;
-        P[NP + 1] = k;
+        P[lay.NP] = l;
+        P[lay.NP + 1] = k;
     }
     if (!BWD) return;
-    if (tid < 16) {
-        const int j = tid & 3, which = tid >> 2;     // which: 0 gs(q) 1 gs(q+4) 2 gb3(q) 3 gb3(q+4)
-        float t = 0.f;
-        for (int ww = 0; ww < 4; ++ww) t += red[16 * ww + 4 * which + j];
-        const int aidx = j + ((which & 1) ? 4 : 0);
-        if (aidx < A) {
-            if (which < 2) P[oS + aidx] = t * lmask[aidx];
-            else P[ob3 + aidx] = t;
-        }
-    }
-    gb1 += shfl_xor_f32(gb1, 16);  gb1 += shfl_xor_f32(gb1, 32);
-    gb2 += shfl_xor_f32(gb2, 16);  gb2 += shfl_xor_f32(gb2, 32);
-    if (kk == 0) {
-        P[ob1 + col] = gb1;
-        P[ob2 + col] = gb2;
-    }
-#pragma unroll
-    for (int ob = 0; ob < NOB; ++ob)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = 16 * ob + 4 * kk + r;
-            if (row < O) P[row * H + col] = aw1[ob][r];
-        }
-#pragma unroll
-    for (int i = 0; i < WIDE_NC; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) P[oW2 + (16 * i + 4 * kk + r) * H + col] = aw2[i][r];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-        if (i16 < A) P[oW3 + (16 * w + 4 * kk + r) * A + i16] = aw3[r];
+    wide_write_partial<H, NOB, 4>(P, lay, O, A, red, lmask, gb1, gb2, aw1, aw2, aw3, tidt);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -458,36 +500,27 @@ __global__ void __launch_bounds__(4 * H, 2) k_wide_hvp(PassArgs a) {
     float* sm = (float*)PROMP_SMEM_PTR;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int i16_ = lane & 15, kk_ = lane >> 4;
-    const int wi = xcd_item(blockIdx.x, gridDim.x);       // which work item (and partial row) this workgroup takes
-    const WorkItem wk = a.work[wi];
-    const int task = wk.task;
+    const CoopItem item = coop_item(a);
+    const int wi = item.wi, task = item.wk.task;
+    const WorkItem wk = item.wk;
+    const float invN = item.invN;
     const int O = a.O, A = a.A;
-    const int ob1 = O * H, oW2 = ob1 + H, ob2 = oW2 + H * H, oW3 = ob2 + H, ob3 = oW3 + H * A, oS = ob3 + A, NP = oS + A;
+    const Mlp2Layout lay = mlp2_layout(O, H, H, A);
     const LdsWide L = make_layout_wide(H, RB, NOB, true);
     const int XS = L.XS;
     float *Xs = sm + L.x, *W3s = sm + L.w3, *W3Ts = sm + L.w3t, *vW3s = sm + L.vw3, *vW3Ts = sm + L.vw3t, *b1s = sm + L.b1,
           *b2s = sm + L.b2, *b3s = sm + L.b3, *vb1s = sm + L.vb1, *vb2s = sm + L.vb2, *vb3s = sm + L.vb3, *lss = sm + L.ls,
           *lmask = sm + L.lmask, *ess = sm + L.es, *sn2s = sm + L.sn2, *vls = sm + L.vls, *red = sm + L.red;
-    const int ntask = a.task_row_offsets[task + 1] - a.task_row_offsets[task];
-    const float invN = 1.0f / (float)ntask;
-    const float* th0 = a.theta + (long long)task * a.theta_task_stride;
-    const float* v0 = a.vdir + (long long)task * NP;
+    const float* th0 = item.th;
+    const float* v0 = a.vdir + (long long)task * lay.NP;
     const int col_ = 16 * w + i16_;
 
     for (int e = tid; e < R * XS; e += NT) Xs[e] = 0.f;
     wide_stage_head<H>(W3s, W3Ts, b1s, b2s, b3s, th0, O, A, tid, NT);
     wide_stage_head<H>(vW3s, vW3Ts, vb1s, vb2s, vb3s, v0, O, A, tid, NT);
     if (tid < 16) {
-        const float* th = th0;
-        const float* v = v0;
-        const float sr = (tid < A) ? th[oS + tid] : 0.f;
-        const bool clipped = a.clip_log_std && (sr < a.min_log_std);
-        const float s = clipped ? a.min_log_std : sr;
-        lss[tid] = s;
-        lmask[tid] = clipped ? 0.f : 1.f;
-        ess[tid] = expf(-s);
-        sn2s[tid] = expf(2.f * s);
-        vls[tid] = (tid < A && !clipped) ? v[oS + tid] : 0.f;   // R{s} = mask * v_s
+        const LogStdTerms t = coop_stage_log_std(lss, lmask, ess, sn2s, th0, lay.ls, A, a, tid);
+        vls[tid] = (tid < A && !t.clipped) ? v0[lay.ls + tid] : 0.f;   // R{s} = mask * v_s
     }
 
     f32x4 aw1[NOB], aw2[WIDE_NC], aw3 = zero4();
@@ -550,8 +583,8 @@ __global__ void __launch_bounds__(4 * H, 2) k_wide_hvp(PassArgs a) {
         {
             float wr[WIDE_NS], vr[WIDE_NS];
             sched_fence();
-            wide_load_cols<H, H>(wr, th + oW2, H, col, kk, 1.f);
-            wide_load_cols<H, H>(vr, v + oW2, H, col, kk, 1.f);
+            wide_load_cols<H, H>(wr, th + lay.W2, H, col, kk, 1.f);
+            wide_load_cols<H, H>(vr, v + lay.W2, H, col, kk, 1.f);
             __syncthreads();
             f32x4 az[RB], ar[RB];
 #pragma unroll
@@ -716,8 +749,8 @@ __global__ void __launch_bounds__(4 * H, 2) k_wide_hvp(PassArgs a) {
         {
             float wr[WIDE_NS], vr[WIDE_NS];
             sched_fence();
-            wide_load_rows<H>(wr, th + oW2, col, kk, 1.f);
-            wide_load_rows<H>(vr, v + oW2, col, kk, -1.f);
+            wide_load_rows<H>(wr, th + lay.W2, col, kk, 1.f);
+            wide_load_rows<H>(vr, v + lay.W2, col, kk, -1.f);
             __syncthreads();
 #pragma unroll
             for (int s = 0; s < 4 * RB; ++s) {
@@ -758,52 +791,16 @@ __global__ void __launch_bounds__(4 * H, 2) k_wide_hvp(PassArgs a) {
     }
 
     const int tidt = tid + opaque_zero();          // (the tail's lane indices too: recomputed, not reloaded from a spill)
-    const int i16 = tidt & 15, kk = (tidt & 63) >> 4, col = 16 * (tidt >> 6) + i16;
     float* P = a.partials + (long long)wi * a.partial_stride;
 #pragma unroll
-    for (int m = 4; m <= 32; m <<= 1) {
-        outs0 += shfl_xor_f32(outs0, m);  outs1 += shfl_xor_f32(outs1, m);  outb30 += shfl_xor_f32(outb30, m);
-        outb31 += shfl_xor_f32(outb31, m);  klsum += shfl_xor_f32(klsum, m);
-    }
-    __syncthreads();
-    if (lane < 4 && w < 2) {       // waves 0..1 ran the epilogue (4 lanes x 32 rows); lane == q
-        float* rw = red + 16 * w;
-        rw[lane] = outs0;  rw[4 + lane] = outs1;  rw[8 + lane] = outb30;  rw[12 + lane] = outb31;
-    }
+    for (int m = 4; m <= 32; m <<= 1) klsum += shfl_xor_f32(klsum, m);
+    wide_action_sums_to_lds<2>(red, outs0, outs1, outb30, outb31, lane, w);      // waves 0..1 ran the epilogue (4 lanes x 32 rows)
     float* sc = Xs;
     if (lane == 0 && w < 2) sc[w] = klsum;
     __syncthreads();
     if (tid == 0) {
-        P[NP] = 0.f;
-        P[NP + 1] = sc[0] + sc[1];
+        P[lay.NP] = 0.f;
+        P[lay.NP + 1] = sc[0] + sc[1];
     }
-    if (tid < 16) {
-        const int j = tid & 3, which = tid >> 2;
-        const float t = red[4 * which + j] + red[16 + 4 * which + j];
-        const int aidx = j + ((which & 1) ? 4 : 0);
-        if (aidx < A) {
-            if (which < 2) P[oS + aidx] = t * lmask[aidx];
-            else P[ob3 + aidx] = t;
-        }
-    }
-    ob1acc += shfl_xor_f32(ob1acc, 16);  ob1acc += shfl_xor_f32(ob1acc, 32);
-    ob2acc += shfl_xor_f32(ob2acc, 16);  ob2acc += shfl_xor_f32(ob2acc, 32);
-    if (kk == 0) {
-        P[ob1 + col] = ob1acc;
-        P[ob2 + col] = ob2acc;
-    }
-#pragma unroll
-    for (int ob = 0; ob < NOB; ++ob)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = 16 * ob + 4 * kk + r;
-            if (row < O) P[row * H + col] = aw1[ob][r];
-        }
-#pragma unroll
-    for (int i = 0; i < WIDE_NC; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) P[oW2 + (16 * i + 4 * kk + r) * H + col] = aw2[i][r];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-        if (i16 < A) P[oW3 + (16 * w + 4 * kk + r) * A + i16] = aw3[r];
+    wide_write_partial<H, NOB, 2>(P, lay, O, A, red, lmask, ob1acc, ob2acc, aw1, aw2, aw3, tidt);
 }

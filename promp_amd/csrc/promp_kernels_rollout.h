@@ -57,21 +57,21 @@ PROMP_HD void action_noise(unsigned long long seed, unsigned long long row, unsi
 
 // mean network of one observation row under flat parameters th (hidden widths <= 128, act_dim <= 8)
 PROMP_DEV void mlp_mean(const float* th, const float* x, int O, int A, int H1, int H2, float* mean) {
-    const int ob1 = O * H1, oW2 = ob1 + H1, ob2 = oW2 + H1 * H2, oW3 = ob2 + H2, ob3 = oW3 + H2 * A;
+    const Mlp2Layout lay = mlp2_layout(O, H1, H2, A);
     float h1[128], h2[128];
     for (int j = 0; j < H1; ++j) {
-        float z = th[ob1 + j];
+        float z = th[lay.b1 + j];
         for (int k = 0; k < O; ++k) z = fmaf(x[k], th[k * H1 + j], z);
         h1[j] = fast_tanh(z);
     }
     for (int j = 0; j < H2; ++j) {
-        float z = th[ob2 + j];
-        for (int k = 0; k < H1; ++k) z = fmaf(h1[k], th[oW2 + k * H2 + j], z);
+        float z = th[lay.b2 + j];
+        for (int k = 0; k < H1; ++k) z = fmaf(h1[k], th[lay.W2 + k * H2 + j], z);
         h2[j] = fast_tanh(z);
     }
     for (int j = 0; j < A; ++j) {
-        float z = th[ob3 + j];
-        for (int k = 0; k < H2; ++k) z = fmaf(h2[k], th[oW3 + k * A + j], z);
+        float z = th[lay.b3 + j];
+        for (int k = 0; k < H2; ++k) z = fmaf(h2[k], th[lay.W3 + k * A + j], z);
         mean[j] = z;
     }
 }

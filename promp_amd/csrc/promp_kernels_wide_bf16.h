@@ -36,6 +36,13 @@
 //   * Nothing a round needs from memory is requested inside the round that uses it: the observations of round r + 1 are requested
 //     during round r - 1 and split into the second observation tile during round r; the row data of the distribution epilogue
 //     (actions, old means / log-stds, advantage: one (row, action) pair per thread) at the top of its round.
+//
+// What k_wb_fwd_bwd and k_wb_hvp share is written once, in front of them: the work item and the log_std staging (coop_item,
+// coop_stage_log_std of promp_kernels_policy_wide.h), wb_row_request (the loss level's row data), wb_xt_z_half (the hidden_0 kernel
+// gradient block, the cotangent tile its parameter), wb_split_vote (the FP16 split's end-of-walk vote; the bound's factor and the
+// event slot its parameters), wb_action_sums_to_lds / wb_write_action_sums (the per-action sums of the tail) and wb_write_slices
+// (the partial row's kernel slices, the scale its parameter).  The scalars of the tails stay with the kernels: `loss` exists in one
+// of them only.  The redo exponent is promp_objective.h's scale_exp_clamped, the parameter offsets promp_plan.h's Mlp2Layout.
 #pragma once
 #include "promp_kernels_policy_wide.h"
 
@@ -85,9 +92,7 @@ PROMP_DEV int wb_obs_shift(const float* obs_absmax, int task) { return obs_shift
 PROMP_DEV float wb_vec_scale(const float* vec_absmax, int task, int t) {
     if (PROMP_NT != 2 || vec_absmax == nullptr) return 1.f;
     const float mx = vec_absmax[task];
-    int k = (mx > 0.f && mx < 3.0e38f) ? scale_exp(mx, t) : 0;
-    k = k < -100 ? -100 : k > 100 ? 100 : k;
-    return pow2f(k);
+    return pow2f((mx > 0.f && mx < 3.0e38f) ? scale_exp_clamped(mx, t) : 0);
 }
 
 struct LdsWB {
@@ -428,13 +433,13 @@ __global__ void __launch_bounds__(256) k_wb_planes(WbPlaneArgs a) {
     if (r >= n1 + 2 * n2 + 256) return;
     const float* src = a.src + (long long)task * a.src_stride;
     unsigned* dst = a.dst + (long long)task * wb_planes_words(a.NKO);
-    const int oW2a = a.O * 128 + 128;
+    const Mlp2Layout lay = mlp2_layout(a.O, 128, 128, a.A);
     int region = 0;
     const float vsc = wb_vec_scale(a.vec_absmax, task, WB_V_TARGET), w1sc = pow2f(wb_obs_shift(a.obs_absmax, task)) * vsc;
     if (r >= n1 + 2 * n2) {               // the output kernel's fragments (wb_load_w3)
         r -= n1 + 2 * n2;
         u32x4 pl[PROMP_NT];
-        wb_load_w3(pl, src + oW2a + 128 * 128 + 128, a.A, r & 63, r >> 6, vsc);
+        wb_load_w3(pl, src + lay.W3, a.A, r & 63, r >> 6, vsc);
 #pragma unroll
         for (int t = 0; t < PROMP_NT; ++t) *(u32x4*)(dst + wb_planes_w3(a.NKO) + ((r >> 6) * PROMP_NT + t) * 256 + 4 * (r & 63)) = pl[t];
         return;
@@ -444,15 +449,14 @@ __global__ void __launch_bounds__(256) k_wb_planes(WbPlaneArgs a) {
     const int NK = region == 0 ? a.NKO : 8;
     const int lane = r & 63, wq = r >> 6, w = wq / NK, q = wq - w * NK;
     const int i = lane & 31, h = lane >> 5;
-    const int oW2 = a.O * 128 + 128;
     f32x4 lo, hi;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const int k = 16 * q + 8 * h + e;
         float x;
         if (region == 0) x = k < a.O ? w1sc * src[k * 128 + 32 * w + i] : 0.f;
-        else if (region == 1) x = vsc * src[oW2 + k * 128 + 32 * w + i];
-        else x = (a.row_sign * vsc) * src[oW2 + (32 * w + i) * 128 + k];
+        else if (region == 1) x = vsc * src[lay.W2 + k * 128 + 32 * w + i];
+        else x = (a.row_sign * vsc) * src[lay.W2 + (32 * w + i) * 128 + k];
         if (e < 4) lo[e] = x;
         else hi[e - 4] = x;
     }
@@ -498,6 +502,124 @@ __global__ void __launch_bounds__(1024) k_vec_absmax(VecAbsmaxArgs a) {
     }
 }
 
+// ---- the pieces k_wb_fwd_bwd and k_wb_hvp share (the work item and the log_std staging: coop_item, coop_stage_log_std of
+//      promp_kernels_policy_wide.h) ----
+// The loss level's row data of one (row, action) pair per thread: row n, action qq (the callers give a thread whose action slot is
+// unowned or whose row is past the round a valid pair whose data is never used)
+struct WbRowData { float advn, ac, mo, so; };
+PROMP_DEV WbRowData wb_row_request(const PassArgs& a, int task, long long n, int qq, int A) {
+    const float* olsp = a.old_log_std + (a.ls_per_row ? n * A : (long long)task * A);
+    WbRowData d;
+    d.advn = a.adv[n];
+    d.ac = a.act[n * A + qq];
+    d.mo = a.old_mean[n * A + qq];
+    d.so = olsp[qq];
+    return d;
+}
+// hidden_0 kernel gradient columns 32 w .. += X^T Z over sample half t of the round's cotangent tile Z (row OC of X: the hidden_0
+// bias gradient); needs only this wave's own columns of Z.  (One half per call, the two-trip loop with the kernels: as one call for
+// both halves k_wb_fwd_bwd<8, 4, true> spilled a register to scratch.)
+template <int NXB>
+PROMP_DEV void wb_xt_z_half(f32x16 (&aw1)[NXB], const float* Xs, const float* Zs, int lane, int w, int t) {
+    u32x4 fz[PROMP_NT];
+    wb_read_tr(fz, Zs, lane, w, t);
+    if (NXB == 1) {
+        u32x4 fa[PROMP_NT];
+        wb_read_tr(fa, Xs, lane, 0, t);
+        wb_mma6(aw1[0], fa, fz);
+    } else {
+#pragma unroll
+        for (int m = 0; m + 1 < NXB; m += 2) {
+            u32x4 fa0[PROMP_NT], fa1[PROMP_NT];
+            wb_read_tr(fa0, Xs, lane, m, t);
+            wb_read_tr(fa1, Xs, lane, m + 1, t);
+            wb_mma6_two(aw1[m], aw1[m + 1], fa0, fa1, fz);
+        }
+    }
+}
+// FP16 split, the vote at the end of a walk: did every split stay inside the format?  The mean cotangents' planes feed the output
+// kernel's sums only: their largest value amax (per thread) at the scale cs, times `over` (k_wb_hvp: amax holds the larger of |d| and
+// 1 / over of |q|), against the format's largest; everything else ends in the hidden_0 kernel sums (x * 0 is 0 for finite x only).
+// bad: the work item is walked again, sized by redo_amax, and counted in *events.
+struct WbVote { bool bad; float redo_amax; };
+template <int NXB>
+PROMP_DEV WbVote wb_split_vote(const f32x16 (&aw1)[NXB], float amax, float cs, float over, float* red, int w, int* events) {
+    float chk = 0.f;
+#pragma unroll
+    for (int m = 0; m < NXB; ++m)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) chk = __builtin_fmaf(aw1[m][r], 0.f, chk);
+    const float wm = wave_absmax_f32(amax), wbad = wave_any(chk != chk) ? 1.f : 0.f;
+    const int lane = threadIdx.x & 63;
+    __syncthreads();
+    if (lane == 0) {
+        red[w] = wm;
+        red[4 + w] = wbad;
+    }
+    __syncthreads();
+    WbVote v;
+    v.redo_amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    v.bad = (red[4] + red[5] + red[6] + red[7]) > 0.f || !(v.redo_amax * cs * over <= 65504.f);
+    if (v.bad && threadIdx.x == 0) atomic_add_agent(events, 1);
+    return v;
+}
+// ---- the tail: the per-action sums of the epilogue lanes (action = lane & 7; s: log_std, b: output bias) over the wave's 8 rows
+// -> red[16 w + ..], behind a barrier of its own; then over the waves in wave order into the partial row
+PROMP_DEV void wb_action_sums_to_lds(float* red, float s, float b, int lane, int w) {
+#pragma unroll
+    for (int m = 8; m <= 32; m <<= 1) {
+        s += shfl_xor_f32(s, m);
+        b += shfl_xor_f32(b, m);
+    }
+    __syncthreads();
+    if (lane < 8) {
+        float* rw = red + 16 * w;
+        rw[lane] = s;
+        rw[8 + lane] = b;
+    }
+}
+PROMP_DEV void wb_write_action_sums(float* P, const Mlp2Layout& lay, int A, const float* red, const float* lmask, int tid) {
+    if (tid < 16) {
+        const int aidx = tid & 7, which = tid >> 3;     // which: 0 log-std entries, 1 output bias entries
+        const float t = (red[8 * which + aidx] + red[16 + 8 * which + aidx]) + (red[32 + 8 * which + aidx] + red[48 + 8 * which + aidx]);
+        if (aidx < A) {
+            if (which == 0) P[lay.ls + aidx] = t * lmask[aidx];
+            else P[lay.b3 + aidx] = t;
+        }
+    }
+}
+// the kernel slices of the partial row straight from their owners, times sc (what the cotangents' scales leave on the sums)
+template <int NXB, int OC>
+PROMP_DEV void wb_write_slices(float* P, const Mlp2Layout& lay, int O, int A, const f32x16 (&aw1)[NXB], const f32x16 (&aw2)[4],
+                               const f32x4 (&aw3)[2], float sc, float w1u, int lane, int w) {
+    constexpr int H = 128;
+    const int j = lane & 31, h = lane >> 5;
+    // hidden_1 kernel: block m, register 4 g + i <-> row 32 m + 8 g + 4 h + i, column 32 w + j
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) P[lay.W2 + (32 * m + 8 * (r >> 2) + 4 * h + (r & 3)) * H + 32 * w + j] = aw2[m][r] * sc;
+    // hidden_0 kernel; row OC = the hidden_0 bias
+#pragma unroll
+    for (int m = 0; m < NXB; ++m)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = 32 * m + 8 * (r >> 2) + 4 * h + (r & 3);
+            if (row < O) P[row * H + 32 * w + j] = aw1[m][r] * (sc * w1u);     // (the observations' scale comes off here)
+            else if (row == OC) P[lay.b1 + 32 * w + j] = aw1[m][r] * sc;
+        }
+    // output kernel rows 32 w + 16 ub + (lane & 15): D rows 4 g4 + r = actions; action slot 15 = the hidden_1 bias
+    const int j16 = lane & 15, g4 = lane >> 4;
+#pragma unroll
+    for (int ub = 0; ub < 2; ++ub)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int aa = 4 * g4 + r, unit = 32 * w + 16 * ub + j16;
+            if (aa < A) P[lay.W3 + unit * A + aa] = aw3[ub][r] * sc;
+            else if (aa == 15) P[lay.b2 + unit] = aw3[ub][r] * sc;
+        }
+}
+
 // ---------------------------------------------------------------------------------------------
 // k_wb_fwd_bwd: objective (+ gradient) of one policy pass; PassArgs / partial layout of k_wide_fwd_bwd.
 // grid = work items (table 0), block = 256 (4 waves, one per SIMD), one workgroup per CU.
@@ -510,16 +632,15 @@ __global__ void __launch_bounds__(256, 1) k_wb_fwd_bwd(PassArgs a) {
     PROMP_SMEM_DECL;
     float* sm = (float*)PROMP_SMEM_PTR;
     const int w = wave_uniform(threadIdx.x >> 6);
-    const int wi = xcd_item(blockIdx.x, gridDim.x);
-    const WorkItem wk = a.work[wi];
-    const int task = wk.task;
+    const CoopItem item = coop_item(a);
+    const int wi = item.wi, task = item.wk.task;
+    const WorkItem wk = item.wk;
+    const float invN = item.invN;
+    const float* th = item.th;
     const int O = a.O, A = a.A;
-    const int ob1 = O * H, oW2 = ob1 + H, ob2 = oW2 + H * H, oW3 = ob2 + H, ob3 = oW3 + H * A, oS = ob3 + A, NP = oS + A;
+    const Mlp2Layout lay = mlp2_layout(O, H, H, A);
     const LdsWB L = wb_layout(false);
     float *Mp = sm + L.mp, *lmask = sm + L.lmask, *red = sm + L.red;
-    const int ntask = a.task_row_offsets[task + 1] - a.task_row_offsets[task];
-    const float invN = 1.0f / (float)ntask;
-    const float* th = a.theta + (long long)task * a.theta_task_stride;
     const unsigned* PL = a.wb_theta_planes + (long long)task * a.wb_plane_stride;
     const unsigned* PR2 = PL + wb_planes_r2(NKO);
     // FP16 split: the task's observations times 2^-sx (k_wb_planes multiplied the hidden_0 kernel by 2^sx)
@@ -539,20 +660,14 @@ __global__ void __launch_bounds__(256, 1) k_wb_fwd_bwd(PassArgs a) {
         for (int q = 0; q < NKO; ++q) wb_gload(w1p[q], PL, NKO, w, q, lane);
 #pragma unroll
         for (int q = 0; q < 8; ++q) wb_gload(w2c[q], PL + wb_planes_c2(NKO), 8, w, q, lane);
-        if (BWD) wb_load_w3f(w3f, th + oW3, A, lane, w, 1.f);
+        if (BWD) wb_load_w3f(w3f, th + lay.W3, A, lane, w, 1.f);
         for (int e = tid; e < H; e += 256) {
-            b1s[e] = th[ob1 + e];
-            b2s[e] = th[ob2 + e];
+            b1s[e] = th[lay.b1 + e];
+            b2s[e] = th[lay.b2 + e];
         }
         if (tid < 16) {
-            const float sr = (tid < A) ? th[oS + tid] : 0.f;
-            const bool clipped = a.clip_log_std && (sr < a.min_log_std);   // tf.maximum: gradient iff var >= min
-            const float s = clipped ? a.min_log_std : sr;
-            lss[tid] = s;
-            lmask[tid] = clipped ? 0.f : 1.f;
-            ess[tid] = expf(-s);
-            sn2s[tid] = expf(2.f * s);
-            b3s[tid] = (tid < A) ? th[ob3 + tid] : 0.f;
+            coop_stage_log_std(lss, lmask, ess, sn2s, th, lay.ls, A, a, tid);
+            b3s[tid] = (tid < A) ? th[lay.b3 + tid] : 0.f;
         }
         for (int e = tid; e < R * MS; e += 256) Mss[e] = 0.f;
         for (int e = tid; e < PROMP_NT * WB_DMPL; e += 256) ((unsigned*)Dm)[e] = 0u;
@@ -590,8 +705,7 @@ __global__ void __launch_bounds__(256, 1) k_wb_fwd_bwd(PassArgs a) {
     amax = 0.f;
     prov = 1;
     if (PROMP_NT == 2 && attempt > 0 && redo_amax > 0.f && redo_amax < 3.0e38f) {
-        int k = scale_exp(redo_amax, PASS_CT_REDO - (attempt - 1) * PASS_CT_RETRY);
-        k = k < -100 ? -100 : k > 100 ? 100 : k;
+        const int k = scale_exp_clamped(redo_amax, PASS_CT_REDO - (attempt - 1) * PASS_CT_RETRY);
         cs = pow2f(k);
         ics = pow2f(-k);
         prov = 0;
@@ -614,16 +728,8 @@ __global__ void __launch_bounds__(256, 1) k_wb_fwd_bwd(PassArgs a) {
         // ---- the distribution epilogue's row data, requested now: one (row, action) pair per thread
         const int erow = tid >> 3, eq = tid & 7;
         const bool eown = eq < A, rvalid = erow < nrows;
-        float advn, eac, emo, eso;
-        {
-            const long long n = (long long)base + (rvalid ? erow : 0);
-            const int qq = eown ? eq : 0;
-            const float* olsp = a.old_log_std + (a.ls_per_row ? n * A : (long long)task * A);
-            advn = a.adv[n];
-            eac = a.act[n * A + qq];
-            emo = a.old_mean[n * A + qq];
-            eso = olsp[qq];
-        }
+        const WbRowData rd = wb_row_request(a, task, (long long)base + (rvalid ? erow : 0), eown ? eq : 0, A);
+        const float advn = rd.advn, eac = rd.ac, emo = rd.mo, eso = rd.so;
         // ---- layer 1: H1 = tanh(W1^T X^T + b1), own units.  The NEXT round's observations (requested a round ago, in registers) are
         //      split into the other observation tile chunk by chunk among the chain's products: vector work in the matrix
         //      instructions' shadow (it used to run behind the layer: 2.2 k of a round's 21.7 k cycles)
@@ -844,70 +950,27 @@ __global__ void __launch_bounds__(256, 1) k_wb_fwd_bwd(PassArgs a) {
         WB_STAMP(12);
         WB_STAMP(13);
         // ---- hidden_0 kernel gradient columns 32 w .. (+=): needs only this wave's own dZ1 columns
-        {
 #pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                u32x4 fz[PROMP_NT];
-                wb_read_tr(fz, DZ1, lane, w, t);
-                if (NXB == 1) {
-                    u32x4 fa[PROMP_NT];
-                    wb_read_tr(fa, Xs, lane, 0, t);
-                    wb_mma6(aw1[0], fa, fz);
-                } else {
-#pragma unroll
-                    for (int m = 0; m + 1 < NXB; m += 2) {
-                        u32x4 fa0[PROMP_NT], fa1[PROMP_NT];
-                        wb_read_tr(fa0, Xs, lane, m, t);
-                        wb_read_tr(fa1, Xs, lane, m + 1, t);
-                        wb_mma6_two(aw1[m], aw1[m + 1], fa0, fa1, fz);
-                    }
-                }
-            }
-        }
+        for (int t = 0; t < 2; ++t) wb_xt_z_half<NXB>(aw1, Xs, DZ1, lane, w, t);
         WB_STAMP(14);
         ++rix;
     }
-    // FP16 split: did every split stay inside the format?  The mean cotangents' planes (they feed the output kernel's sums only): their
-    // largest value at the scale; everything else ends in the hidden_0 kernel sums (x * 0 is 0 for finite x only).
+    // FP16 split: did every split stay inside the format (wb_split_vote)?
     if (!BWD || PROMP_NT != 2 || attempt + 1 >= PASS_CT_ATTEMPTS) break;
-    {
-        float chk = 0.f;
-#pragma unroll
-        for (int m = 0; m < NXB; ++m)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) chk = __builtin_fmaf(aw1[m][r], 0.f, chk);
-        const float wm = wave_absmax_f32(amax), wbad = wave_any(chk != chk) ? 1.f : 0.f;
-        const int lane = threadIdx.x & 63;
-        __syncthreads();
-        if (lane == 0) {
-            red[w] = wm;
-            red[4 + w] = wbad;
-        }
-        __syncthreads();
-        redo_amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-        const bool bad = (red[4] + red[5] + red[6] + red[7]) > 0.f || !(redo_amax * cs <= 65504.f);
-        if (!bad) break;
-        if (threadIdx.x == 0) atomic_add_agent(a.split_events + 0, 1);
-    }
+    const WbVote vote = wb_split_vote<NXB>(aw1, amax, cs, 1.f, red, w, a.split_events + 0);
+    redo_amax = vote.redo_amax;
+    if (!vote.bad) break;
     }
 
     // ---- results: scalars through LDS in wave order, gradient slices straight from their owners ----
     float* P = a.partials + (long long)wi * a.partial_stride;
-    const int tidt = threadIdx.x + opaque_zero(), lane = tidt & 63, j = lane & 31, h = lane >> 5, tid = tidt;
-    // per-action sums of the epilogue lanes (action = lane & 7): over the wave's 8 rows, then over the waves in wave order
+    const int tid = threadIdx.x + opaque_zero(), lane = tid & 63;
 #pragma unroll
     for (int m = 8; m <= 32; m <<= 1) {
-        gs += shfl_xor_f32(gs, m);
-        gb3 += shfl_xor_f32(gb3, m);
         loss += shfl_xor_f32(loss, m);
         klsum += shfl_xor_f32(klsum, m);
     }
-    __syncthreads();
-    if (lane < 8) {
-        float* rw = red + 16 * w;
-        rw[lane] = gs;
-        rw[8 + lane] = gb3;
-    }
+    wb_action_sums_to_lds(red, gs, gb3, lane, w);
     float* sc = Mp;                // two scalars per wave
     if (lane == 0) {
         sc[2 * w] = loss;
@@ -915,44 +978,12 @@ __global__ void __launch_bounds__(256, 1) k_wb_fwd_bwd(PassArgs a) {
     }
     __syncthreads();
     if (tid == 0) {
-        P[NP] = (sc[0] + sc[2]) + (sc[4] + sc[6]);
-        P[NP + 1] = (sc[1] + sc[3]) + (sc[5] + sc[7]);
+        P[lay.NP] = (sc[0] + sc[2]) + (sc[4] + sc[6]);
+        P[lay.NP + 1] = (sc[1] + sc[3]) + (sc[5] + sc[7]);
     }
     if (!BWD) return;
-    if (tid < 16) {
-        const int aidx = tid & 7, which = tid >> 3;     // which: 0 log-std gradient, 1 output bias gradient
-        const float t = (red[8 * which + aidx] + red[16 + 8 * which + aidx]) + (red[32 + 8 * which + aidx] + red[48 + 8 * which + aidx]);
-        if (aidx < A) {
-            if (which == 0) P[oS + aidx] = t * lmask[aidx];
-            else P[ob3 + aidx] = t;
-        }
-    }
-    // hidden_1 kernel gradient: block m, register 4 g + i <-> row 32 m + 8 g + 4 h + i, column 32 w + j
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) P[oW2 + (32 * m + 8 * (r >> 2) + 4 * h + (r & 3)) * H + 32 * w + j] = aw2[m][r] * ics;
-    // hidden_0 kernel gradient; row OC = the hidden_0 bias gradient
-#pragma unroll
-    for (int m = 0; m < NXB; ++m)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = 32 * m + 8 * (r >> 2) + 4 * h + (r & 3);
-            if (row < O) P[row * H + 32 * w + j] = aw1[m][r] * (ics * w1u);     // (the observations' scale comes off here)
-            else if (row == OC) P[ob1 + 32 * w + j] = aw1[m][r] * ics;
-        }
-    // output kernel rows 32 w + 16 ub + (lane & 15): D rows 4 g4 + r = actions; action slot 15 = hidden_1 bias gradient
-    {
-        const int j16 = lane & 15, g4 = lane >> 4;
-#pragma unroll
-        for (int ub = 0; ub < 2; ++ub)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int aa = 4 * g4 + r, unit = 32 * w + 16 * ub + j16;
-                if (aa < A) P[oW3 + unit * A + aa] = aw3[ub][r] * ics;
-                else if (aa == 15) P[ob2 + unit] = aw3[ub][r] * ics;
-            }
-    }
+    wb_write_action_sums(P, lay, A, red, lmask, tid);
+    wb_write_slices<NXB, OC>(P, lay, O, A, aw1, aw2, aw3, ics, w1u, lane, w);
 }
 
 // ca += a x ba ;  cb += a x bb   (one weight slice against two activation tensors), products interleaved
@@ -987,17 +1018,16 @@ __global__ void __launch_bounds__(256, 1) k_wb_hvp(PassArgs a) {
     PROMP_SMEM_DECL;
     float* sm = (float*)PROMP_SMEM_PTR;
     const int w = wave_uniform(threadIdx.x >> 6);
-    const int wi = xcd_item(blockIdx.x, gridDim.x);
-    const WorkItem wk = a.work[wi];
-    const int task = wk.task;
+    const CoopItem item = coop_item(a);
+    const int wi = item.wi, task = item.wk.task;
+    const WorkItem wk = item.wk;
+    const float invN = item.invN;
+    const float* th = item.th;
     const int O = a.O, A = a.A;
-    const int ob1 = O * H, oW2 = ob1 + H, ob2 = oW2 + H * H, oW3 = ob2 + H, ob3 = oW3 + H * A, oS = ob3 + A, NP = oS + A;
+    const Mlp2Layout lay = mlp2_layout(O, H, H, A);
     const LdsWB L = wb_layout(true);
     float *Mp = sm + L.mp, *lmask = sm + L.lmask, *red = sm + L.red;
-    const int ntask = a.task_row_offsets[task + 1] - a.task_row_offsets[task];
-    const float invN = 1.0f / (float)ntask;
-    const float* th = a.theta + (long long)task * a.theta_task_stride;
-    const float* vv = a.vdir + (long long)task * NP;
+    const float* vv = a.vdir + (long long)task * lay.NP;
     const unsigned* PT = a.wb_theta_planes + (long long)task * a.wb_plane_stride;
     const unsigned* PV = a.wb_v_planes + (long long)task * wb_planes_words(NKO);
     const int oC2 = wb_planes_c2(NKO), oR2 = wb_planes_r2(NKO), oW3P = wb_planes_w3(NKO);
@@ -1019,25 +1049,19 @@ __global__ void __launch_bounds__(256, 1) k_wb_hvp(PassArgs a) {
         wb_xreq<NKO>(X, a.obs, wk.row_begin, wk.row_end - wk.row_begin, O, tid);
         wb_stream_begin(GT, PT, NKO, w, lane);
         wb_stream_begin(GV, PV, NKO, w, lane);
-        wb_load_w3f(w3f, th + oW3, A, lane, w, 1.f);
-        wb_load_w3f(v3f, vv + oW3, A, lane, w, vs);
+        wb_load_w3f(w3f, th + lay.W3, A, lane, w, 1.f);
+        wb_load_w3f(v3f, vv + lay.W3, A, lane, w, vs);
         for (int e = tid; e < H; e += 256) {
-            b1s[e] = th[ob1 + e];
-            b2s[e] = th[ob2 + e];
-            vb1s[e] = vs * vv[ob1 + e];
-            vb2s[e] = vs * vv[ob2 + e];
+            b1s[e] = th[lay.b1 + e];
+            b2s[e] = th[lay.b2 + e];
+            vb1s[e] = vs * vv[lay.b1 + e];
+            vb2s[e] = vs * vv[lay.b2 + e];
         }
         if (tid < 16) {
-            const float sr = (tid < A) ? th[oS + tid] : 0.f;
-            const bool clipped = a.clip_log_std && (sr < a.min_log_std);
-            const float s = clipped ? a.min_log_std : sr;
-            lss[tid] = s;
-            lmask[tid] = clipped ? 0.f : 1.f;
-            ess[tid] = expf(-s);
-            sn2s[tid] = expf(2.f * s);
-            vls[tid] = (tid < A && !clipped) ? vs * vv[oS + tid] : 0.f;   // R{s} = mask * v_s
-            b3s[tid] = (tid < A) ? th[ob3 + tid] : 0.f;
-            vb3s[tid] = (tid < A) ? vs * vv[ob3 + tid] : 0.f;
+            const LogStdTerms t = coop_stage_log_std(lss, lmask, ess, sn2s, th, lay.ls, A, a, tid);
+            vls[tid] = (tid < A && !t.clipped) ? vs * vv[lay.ls + tid] : 0.f;   // R{s} = mask * v_s
+            b3s[tid] = (tid < A) ? th[lay.b3 + tid] : 0.f;
+            vb3s[tid] = (tid < A) ? vs * vv[lay.b3 + tid] : 0.f;
         }
         for (int e = tid; e < R * MS; e += 256) Mss[e] = Ms2s[e] = 0.f;
         for (int e = tid; e < PROMP_NT * WB_DMPL; e += 256) ((unsigned*)Dm)[e] = ((unsigned*)Dm2)[e] = 0u;
@@ -1064,16 +1088,15 @@ __global__ void __launch_bounds__(256, 1) k_wb_hvp(PassArgs a) {
         ivs = 1.f / vs;
         klv = a.kl_weight * vs;
         __syncthreads();
-        wb_load_w3f(v3f, vv + oW3, A, lane, w, vs);
+        wb_load_w3f(v3f, vv + lay.W3, A, lane, w, vs);
         for (int e = tid; e < H; e += 256) {
-            vb1s[e] = vs * vv[ob1 + e];
-            vb2s[e] = vs * vv[ob2 + e];
+            vb1s[e] = vs * vv[lay.b1 + e];
+            vb2s[e] = vs * vv[lay.b2 + e];
         }
         if (tid < 16) {
-            const float sr = (tid < A) ? th[oS + tid] : 0.f;
-            const bool clipped = a.clip_log_std && (sr < a.min_log_std);
-            vls[tid] = (tid < A && !clipped) ? vs * vv[oS + tid] : 0.f;
-            vb3s[tid] = (tid < A) ? vs * vv[ob3 + tid] : 0.f;
+            const LogStdTerms t = log_std_terms((tid < A) ? th[lay.ls + tid] : 0.f, a.clip_log_std, a.min_log_std);
+            vls[tid] = (tid < A && !t.clipped) ? vs * vv[lay.ls + tid] : 0.f;
+            vb3s[tid] = (tid < A) ? vs * vv[lay.b3 + tid] : 0.f;
         }
         wb_xreq<NKO>(X, a.obs, wk.row_begin, wk.row_end - wk.row_begin, O, tid);
         wb_stream_begin(GT, PT, NKO, w, lane);
@@ -1089,8 +1112,7 @@ __global__ void __launch_bounds__(256, 1) k_wb_hvp(PassArgs a) {
     amax = 0.f;
     prov = 1;
     if (PROMP_NT == 2 && attempt > 0 && redo_amax > 0.f && redo_amax < 3.0e38f) {
-        int k = scale_exp(redo_amax, CHAIN_CT_REDO - (attempt - 1) * CHAIN_CT_RETRY);
-        k = k < -100 ? -100 : k > 100 ? 100 : k;
+        const int k = scale_exp_clamped(redo_amax, CHAIN_CT_REDO - (attempt - 1) * CHAIN_CT_RETRY);
         cs = pow2f(k);
         prov = 0;
     }
@@ -1117,16 +1139,8 @@ __global__ void __launch_bounds__(256, 1) k_wb_hvp(PassArgs a) {
         // ---- the loss level's row data: one (row, action) pair per thread
         const int erow = tid >> 3, eq = tid & 7;
         const bool eown = eq < A, rvalid = erow < nrows;
-        float advn, eac, emo, eso;
-        {
-            const long long n = (long long)base + (rvalid ? erow : 0);
-            const int qq = eown ? eq : 0;
-            const float* olsp = a.old_log_std + (a.ls_per_row ? n * A : (long long)task * A);
-            advn = a.adv[n];
-            eac = a.act[n * A + qq];
-            emo = a.old_mean[n * A + qq];
-            eso = olsp[qq];
-        }
+        const WbRowData rd = wb_row_request(a, task, (long long)base + (rvalid ? erow : 0), eown ? eq : 0, A);
+        const float advn = rd.advn, eac = rd.ac, emo = rd.mo, eso = rd.so;
         WB_STAMP(1);
         __syncthreads();
         WB_STAMP(2);
@@ -1449,107 +1463,33 @@ __global__ void __launch_bounds__(256, 1) k_wb_hvp(PassArgs a) {
         wb_store_own(H2s, qz1, j, h, w);
         wave_sync();
         // ---- out_W1 columns 32 w .. += x^T qZ1 (row OC: out_b1)
-        {
 #pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                u32x4 fz[PROMP_NT];
-                wb_read_tr(fz, H2s, lane, w, t);
-                if (NXB == 1) {
-                    u32x4 fa[PROMP_NT];
-                    wb_read_tr(fa, Xs, lane, 0, t);
-                    wb_mma6(aw1[0], fa, fz);
-                } else {
-#pragma unroll
-                    for (int m = 0; m + 1 < NXB; m += 2) {
-                        u32x4 fa0[PROMP_NT], fa1[PROMP_NT];
-                        wb_read_tr(fa0, Xs, lane, m, t);
-                        wb_read_tr(fa1, Xs, lane, m + 1, t);
-                        wb_mma6_two(aw1[m], aw1[m + 1], fa0, fa1, fz);
-                    }
-                }
-            }
-        }
+        for (int t = 0; t < 2; ++t) wb_xt_z_half<NXB>(aw1, Xs, H2s, lane, w, t);
         WB_STAMP(14);
         ++rix;
     }
-    // FP16 split: every split of this kernel ends in the hidden_0 kernel sums (x * 0 is 0 for finite x only)
+    // FP16 split: did every split stay inside the format (wb_split_vote; amax holds the larger of |d| and 2^-CHAIN_Q_OVER_D |q|)?
     if (PROMP_NT != 2 || attempt + 1 >= CHAIN_ATTEMPTS) break;
-    {
-        float chk = 0.f;
-#pragma unroll
-        for (int m = 0; m < NXB; ++m)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) chk = __builtin_fmaf(aw1[m][r], 0.f, chk);
-        const float wm = wave_absmax_f32(amax), wbad = wave_any(chk != chk) ? 1.f : 0.f;
-        const int lane = threadIdx.x & 63;
-        __syncthreads();
-        if (lane == 0) {
-            red[w] = wm;
-            red[4 + w] = wbad;
-        }
-        __syncthreads();
-        redo_amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-        // (the mean cotangents' planes feed the output kernel's sums only: their largest values at the scale -- amax holds the larger of
-        //  |d| and 2^-CHAIN_Q_OVER_D |q|)
-        const bool bad = (red[4] + red[5] + red[6] + red[7]) > 0.f || !(redo_amax * cs * (float)(1 << CHAIN_Q_OVER_D) <= 65504.f);
-        if (!bad) break;
-        if (threadIdx.x == 0) atomic_add_agent(a.split_events + 1, 1);
-    }
+    const WbVote vote = wb_split_vote<NXB>(aw1, amax, cs, (float)(1 << CHAIN_Q_OVER_D), red, w, a.split_events + 1);
+    redo_amax = vote.redo_amax;
+    if (!vote.bad) break;
     }
     const float us = PROMP_NT == 2 ? 1.f / (cs * vs) : 1.f;      // what the tangent cotangents' sums carry
     outs *= ivs;
     outb3 *= ivs;
 
     float* P = a.partials + (long long)wi * a.partial_stride;
-    const int tidt = threadIdx.x + opaque_zero(), lane = tidt & 63, j = lane & 31, h = lane >> 5, tid = tidt;
+    const int tid = threadIdx.x + opaque_zero(), lane = tid & 63;
 #pragma unroll
-    for (int m = 8; m <= 32; m <<= 1) {
-        outs += shfl_xor_f32(outs, m);
-        outb3 += shfl_xor_f32(outb3, m);
-        klsum += shfl_xor_f32(klsum, m);
-    }
-    __syncthreads();
-    if (lane < 8) {
-        float* rw = red + 16 * w;
-        rw[lane] = outs;
-        rw[8 + lane] = outb3;
-    }
+    for (int m = 8; m <= 32; m <<= 1) klsum += shfl_xor_f32(klsum, m);
+    wb_action_sums_to_lds(red, outs, outb3, lane, w);
     float* sc = Mp;
     if (lane == 0) sc[w] = klsum;
     __syncthreads();
     if (tid == 0) {
-        P[NP] = 0.f;
-        P[NP + 1] = (sc[0] + sc[1]) + (sc[2] + sc[3]);
+        P[lay.NP] = 0.f;
+        P[lay.NP + 1] = (sc[0] + sc[1]) + (sc[2] + sc[3]);
     }
-    if (tid < 16) {
-        const int aidx = tid & 7, which = tid >> 3;
-        const float t = (red[8 * which + aidx] + red[16 + 8 * which + aidx]) + (red[32 + 8 * which + aidx] + red[48 + 8 * which + aidx]);
-        if (aidx < A) {
-            if (which == 0) P[oS + aidx] = t * lmask[aidx];
-            else P[ob3 + aidx] = t;
-        }
-    }
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) P[oW2 + (32 * m + 8 * (r >> 2) + 4 * h + (r & 3)) * H + 32 * w + j] = aw2[m][r] * us;
-#pragma unroll
-    for (int m = 0; m < NXB; ++m)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = 32 * m + 8 * (r >> 2) + 4 * h + (r & 3);
-            if (row < O) P[row * H + 32 * w + j] = aw1[m][r] * (us * w1u);
-            else if (row == OC) P[ob1 + 32 * w + j] = aw1[m][r] * us;
-        }
-    {
-        const int j16 = lane & 15, g4 = lane >> 4;
-#pragma unroll
-        for (int ub = 0; ub < 2; ++ub)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int aa = 4 * g4 + r, unit = 32 * w + 16 * ub + j16;
-                if (aa < A) P[oW3 + unit * A + aa] = aw3[ub][r] * us;
-                else if (aa == 15) P[ob2 + unit] = aw3[ub][r] * us;
-            }
-    }
+    wb_write_action_sums(P, lay, A, red, lmask, tid);
+    wb_write_slices<NXB, OC>(P, lay, O, A, aw1, aw2, aw3, us, w1u, lane, w);
 }

@@ -130,14 +130,37 @@ PROMP_DEV RowObjective row_objective_invn_last(int loss_kind, float rho, float k
     return r;
 }
 
+// ---- log_std of one action as the policy uses it.  sr: the parameter (0 for an action slot past act_dim); with `clip` set the policy
+// takes max(sr, min_s) (tf.maximum: the gradient passes where the parameter is at or above min_s, mask = 0 below it).
+// Where the four terms go (LDS arrays, registers) and the direction's entry R's = mask v_s are the caller's business.  Users: k_wide_*,
+// k_wb_* (coop_stage_log_std), k_gen_loss; chain_stage_dist (k_pass, k_chain_hvp) keeps the same lines in place, see there.
+struct LogStdTerms {
+    float s, es, sn2, mask;      // s, e^{-s}, e^{2s}, d s / d sr
+    bool clipped;                // mask == 0, for the callers that select by it
+};
+PROMP_DEV LogStdTerms log_std_terms(float sr, int clip, float min_s) {
+    LogStdTerms t;
+    t.clipped = clip && (sr < min_s);
+    t.s = t.clipped ? min_s : sr;
+    t.es = expf(-t.s);
+    t.sn2 = expf(2.f * t.s);
+    t.mask = t.clipped ? 0.f : 1.f;
+    return t;
+}
+
 // ---- FP16 split: the power of two 2^k a walk's cotangents are multiplied by (cs), its inverse (ics).  A largest |cotangent| of mx
 // goes to [2^target, 2^(target + 1)); mx = 0 / not finite: 2^-4 N, for adv / N, and `prov` (no cotangent yet, the scale is still
 // free).  The reasoning: promp_kernels_pass.h (PassSums).  Who reduces mx, over a wave or a workgroup, is the caller's business.
+// scale_exp_clamped: the exponent k that takes |m| to [2^t, 2^(t + 1)), kept to +-100 so that 2^k and 2^-k are both normal floats; every
+// scale of the split (the direction's, a walk's first and its redo's) is pow2f of it.
+PROMP_DEV int scale_exp_clamped(float m, int t) {
+    const int k = scale_exp(m, t);
+    return k < -100 ? -100 : k > 100 ? 100 : k;
+}
 struct CotangentScale { float cs, ics; int prov; };
 PROMP_DEV CotangentScale cotangent_scale(float mx, float invN, int target) {
     const bool okm = mx > 0.f && mx < 3.0e38f;
-    int k = scale_exp(okm ? mx : invN, okm ? target : -4);
-    k = k < -100 ? -100 : k > 100 ? 100 : k;
+    const int k = scale_exp_clamped(okm ? mx : invN, okm ? target : -4);
     CotangentScale r;
     r.cs = pow2f(k);
     r.ics = pow2f(-k);

@@ -116,8 +116,29 @@ inline int check_dims(const promp_dims* d, std::string* why) {
     return 0;
 }
 
+// The flattened parameter vector of a two-hidden-layer policy, in the order policies/base.py:271-277 fixes: hidden_0 kernel [O][H1]
+// at 0, then hidden_0 bias, hidden_1 kernel [H1][H2], hidden_1 bias, output kernel [H2][A], output bias, log_std; NP entries.
+// Every kernel that indexes a parameter vector, a direction or a partial row of such a policy takes its offsets from here, and so
+// do param_count, remap_params and the hidden_0 block of k_vec_absmax (tests/host/plan_check.cpp ties them to each other).
+struct Mlp2Layout {
+    int b1, W2, b2, W3, b3, ls, NP;
+};
+// (always inlined: the kernels' force-inlined helpers call it, and they are inlined before the optimiser looks at an ordinary call)
+PROMP_PLAN_HD __attribute__((always_inline)) Mlp2Layout mlp2_layout(int O, int H1, int H2, int A) {
+    Mlp2Layout l;
+    l.b1 = O * H1;
+    l.W2 = l.b1 + H1;
+    l.b2 = l.W2 + H1 * H2;
+    l.W3 = l.b2 + H2;
+    l.b3 = l.W3 + H2 * A;
+    l.ls = l.b3 + A;
+    l.NP = l.ls + A;
+    return l;
+}
+
 inline int param_count(const promp_dims* d) {
     const HiddenList L = hidden_list(d);
+    if (L.n == 2) return mlp2_layout(d->obs_dim, L.h[0], L.h[1], d->act_dim).NP;
     int n = 0, in = d->obs_dim;
     for (int l = 0; l < L.n; ++l) {
         n += in * L.h[l] + L.h[l];
@@ -150,23 +171,22 @@ inline void pad_dims(const promp_dims* u, promp_dims* p) {
 // one parameter vector between the caller's layout (du) and the padded one (dp); to_padded: dst must arrive zeroed
 inline void remap_params(const promp_dims& du, const promp_dims& dp, const float* src, float* dst, bool to_padded) {
     const int O = du.obs_dim, A = du.act_dim, h1 = du.hidden1, h2 = du.hidden2, H1 = dp.hidden1, H2 = dp.hidden2;
-    size_t ou = 0, op = 0;
-    auto rows = [&](int nrows_u, int nrows_p, int cols_u, int cols_p) {
+    const Mlp2Layout lu = mlp2_layout(O, h1, h2, A), lp = mlp2_layout(O, H1, H2, A);
+    // one block: nrows_u x cols_u entries of the caller's vector at ou, embedded in rows of cols_p entries at op
+    auto rows = [&](int ou, int op, int nrows_u, int cols_u, int cols_p) {
         for (int r = 0; r < nrows_u; ++r)
             for (int cc = 0; cc < cols_u; ++cc) {
                 if (to_padded) dst[op + (size_t)r * cols_p + cc] = src[ou + (size_t)r * cols_u + cc];
                 else dst[ou + (size_t)r * cols_u + cc] = src[op + (size_t)r * cols_p + cc];
             }
-        ou += (size_t)nrows_u * cols_u;
-        op += (size_t)nrows_p * cols_p;
     };
-    rows(O, O, h1, H1);      // hidden_0/kernel
-    rows(1, 1, h1, H1);      // hidden_0/bias
-    rows(h1, H1, h2, H2);    // hidden_1/kernel
-    rows(1, 1, h2, H2);      // hidden_1/bias
-    rows(h2, H2, A, A);      // output/kernel
-    rows(1, 1, A, A);        // output/bias
-    rows(1, 1, A, A);        // log_std
+    rows(0, 0, O, h1, H1);             // hidden_0/kernel
+    rows(lu.b1, lp.b1, 1, h1, H1);     // hidden_0/bias
+    rows(lu.W2, lp.W2, h1, h2, H2);    // hidden_1/kernel
+    rows(lu.b2, lp.b2, 1, h2, H2);     // hidden_1/bias
+    rows(lu.W3, lp.W3, h2, A, A);      // output/kernel
+    rows(lu.b3, lp.b3, 1, A, A);       // output/bias
+    rows(lu.ls, lp.ls, 1, A, A);       // log_std
 }
 
 // which kernels run the policy passes of a context (promp_ctx_create chooses once, from the padded dims)

@@ -5,7 +5,8 @@
 // and runs it once.  One line per failed expectation, exit status 1 if there was any.
 //
 //   dispatch     every row of the kernel table in tests/test_gpu_parity.py's docstring gives exactly the kernels the table names
-//   shapes       padded widths, remap_params round trip and where the zeros sit; pass family and observation class
+//   shapes       padded widths, remap_params round trip and where the zeros sit, Mlp2Layout against both; pass family and
+//                observation class
 //   step tables  the invariants the kernels rely on, for small, ragged, large and many-task layouts at 2, 8 and 256 CUs;
 //                malformed offsets are refused with their message (and, under the sanitizer, without a stray access)
 //   gramt        the wave -> square map of k_gram_tiled
@@ -175,6 +176,22 @@ static void check_padding(int O, int A, const std::vector<int>& hidden, const st
         EXPECT(ok, "obs %d hidden %d,%d: parameter block %zu is not the caller's block padded with zeros", O, hidden[0], hidden[1], b);
         ou += (size_t)ru * cu;
         op += (size_t)rp * cp;
+    }
+    // Mlp2Layout, the offsets every kernel indexes by: NP is param_count, the seven blocks follow each other without a gap in
+    // remap_params' order, and a padded vector holds each caller entry at the offset the layout gives for the padded widths
+    const Mlp2Layout lu = mlp2_layout(O, hidden[0], hidden[1], A), lp = mlp2_layout(O, padded[0], padded[1], A);
+    const int offu[8] = {0, lu.b1, lu.W2, lu.b2, lu.W3, lu.b3, lu.ls, lu.NP}, offp[8] = {0, lp.b1, lp.W2, lp.b2, lp.W3, lp.b3, lp.ls, lp.NP};
+    EXPECT(lu.NP == param_count(&du) && lp.NP == param_count(&dp), "obs %d hidden %d,%d: layout NP %d / %d, param_count %d / %d", O, hidden[0],
+           hidden[1], lu.NP, lp.NP, param_count(&du), param_count(&dp));
+    for (size_t b = 0; b < bu.size(); ++b) {
+        EXPECT(offu[b + 1] - offu[b] == bu[b].first * bu[b].second && offp[b + 1] - offp[b] == bp[b].first * bp[b].second,
+               "obs %d hidden %d,%d: layout block %zu spans %d / %d entries, the reference's order says %d / %d", O, hidden[0], hidden[1], b,
+               offu[b + 1] - offu[b], offp[b + 1] - offp[b], bu[b].first * bu[b].second, bp[b].first * bp[b].second);
+        bool ok = true;
+        for (int r = 0; r < bu[b].first && ok; ++r)
+            for (int c = 0; c < bu[b].second && ok; ++c)
+                ok = w[offp[b] + (size_t)r * bp[b].second + c] == v[offu[b] + (size_t)r * bu[b].second + c];
+        EXPECT(ok, "obs %d hidden %d,%d: block %zu of the padded vector is not at the layout's offset", O, hidden[0], hidden[1], b);
     }
 }
 static void check_family(int O, int A, const std::vector<int>& hidden, int act, PassFamily want, int cls, PassFamily want_fp32) {
