@@ -8,7 +8,8 @@
 //   shapes       padded widths, remap_params round trip and where the zeros sit, Mlp2Layout against both; pass family and
 //                observation class
 //   step tables  the invariants the kernels rely on, for small, ragged, large and many-task layouts at 2, 8 and 256 CUs;
-//                malformed offsets are refused with their message (and, under the sanitizer, without a stray access)
+//                malformed offsets are refused with their message (and, under the sanitizer, without a stray access);
+//                one item per task at 1 CU and the 256-row cut of 513 rows at 2 CUs (what tests/layered_checks.py builds on)
 //   gramt        the wave -> square map of k_gram_tiled
 #include "../../promp_amd/csrc/promp_plan.h"
 
@@ -240,6 +241,15 @@ static void check_shapes() {
     check_family(20, 9, {64, 64}, PROMP_ACT_TANH, Layered, 0, Layered);
     check_family(20, 6, {64, 64}, PROMP_ACT_RELU, Layered, 0, Layered);
     check_family(129, 6, {64, 64}, PROMP_ACT_TANH, Layered, 0, Layered);
+    // the shapes of tests/layered_checks.py: two tanh layers of up to 128 units with few actions are padded onto a fused family, the
+    // same widths with nine actions (or a third layer) stay layer by layer -- which of its cases reach k_gb_* / k_gen_* hangs on this
+    check_family(9, 3, {72, 40}, PROMP_ACT_TANH, Split, 1, Fp32);
+    check_family(9, 9, {72, 40}, PROMP_ACT_TANH, Layered, 0, Layered);
+    check_family(9, 3, {72, 40, 24}, PROMP_ACT_TANH, Layered, 0, Layered);
+    check_family(33, 5, {33, 65}, PROMP_ACT_TANH, Split, 1, Fp32);
+    check_family(33, 9, {33, 65}, PROMP_ACT_TANH, Layered, 0, Layered);
+    check_family(5, 2, {33, 20}, PROMP_ACT_TANH, Chain, 0, Chain);
+    check_family(5, 9, {33, 20}, PROMP_ACT_TANH, Layered, 0, Layered);
     // instances the launches are written for
     EXPECT(chain_ksteps(8) == 2 && chain_ksteps(9) == 5 && chain_ksteps(20) == 5 && chain_ksteps(21) == 8 && chain_ksteps(32) == 8, "chain_ksteps");
     EXPECT(wide_nob(32) == 2 && wide_nob(33) == 4 && wide_nob(64) == 4 && wide_nob(65) == 8 && wide_nob(128) == 8, "wide_nob");
@@ -346,7 +356,32 @@ static void check_malformed(const char* name, int M, int n_paths, int max_rows, 
     EXPECT(rc == -1 && why == want, "%s: returned %d '%s', expected -1 '%s'", name, rc, why.c_str(), want);
     EXPECT(T.row_t.empty() && T.segs.empty() && T.work[0].empty(), "%s: tables written on refusal", name);
 }
+// Table 0 of a layout at n_cus compute units must be exactly the row ranges `want` (pairs of begin, end), in order.
+// tests/layered_checks.py relies on it: PROMP_MAX_CUS=1 makes every task ONE work item (so that the layer-by-layer kernels walk
+// several rounds, chunks and loss blocks per item), PROMP_MAX_CUS=2 cuts a one-task batch of 513 rows at row 256.
+static void check_long_items(const char* name, const std::vector<std::vector<int>>& lengths, int n_cus, const std::vector<std::pair<int, int>>& want) {
+    const Offsets o = offsets_of(lengths);
+    const int M = o.M, R = o.pro[o.n_paths];
+    StepTables T;
+    std::string why;
+    const int rc = build_step_tables(n_cus, 2 * n_cus + M, R, o.n_paths, M, o.n_paths, o.tpo.get(), o.pro.get(), &T, &why);
+    EXPECT(rc == 0, "%s at %d CUs: refused (%d): %s", name, n_cus, rc, why.c_str());
+    if (rc) return;
+    const auto& W = T.work[0];
+    EXPECT(W.size() == want.size(), "%s at %d CUs: table 0 has %zu items, expected %zu", name, n_cus, W.size(), want.size());
+    if (W.size() != want.size()) return;
+    for (size_t k = 0; k < W.size(); ++k)
+        EXPECT(W[k].row_begin == want[k].first && W[k].row_end == want[k].second, "%s at %d CUs: item %zu is rows [%d, %d), expected [%d, %d)", name, n_cus,
+               k, W[k].row_begin, W[k].row_end, want[k].first, want[k].second);
+}
 static void check_step_tables() {
+    // one compute unit: one item per task, whatever the row counts (the work-item lengths of tests/layered_checks.py)
+    check_long_items("one task, one item", {{300, 21}}, 1, {{0, 321}});
+    check_long_items("three ragged tasks, one item each", {{300, 21}, {256, 256, 1}, {1}}, 1, {{0, 321}, {321, 834}, {834, 835}});
+    check_long_items("three ragged tasks, one item each", {{16}, {17}, {32, 1}}, 1, {{0, 16}, {16, 33}, {33, 66}});
+    check_long_items("three ragged tasks, one item each", {{200, 55}, {256}, {256, 1}}, 1, {{0, 255}, {255, 511}, {511, 768}});
+    // two compute units, one task of 513 rows (33 tiles): two items that meet at row 256
+    check_long_items("513 rows on two units", {{513}}, 2, {{0, 256}, {256, 513}});
     const std::vector<int> edge{1, 2, 63, 64, 65, 127, 128, 129};        // around the scans' 64-row chunks (EDGE_LENGTHS)
     for (int n_cus : {2, 8, 256}) {
         check_tables("one row", {{1}}, n_cus);

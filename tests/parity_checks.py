@@ -308,12 +308,27 @@ def make_ctx(lib, M, O, A, hidden, K, all_paths, n_tasks_global=None, hidden_act
                         output_act=output_act)
 
 
+def note_worst(worst, key, value):
+    """keep the largest figure seen under `key` (worst: a dict the caller prints, or None)"""
+    if worst is not None:
+        worst[key] = max(worst.get(key, 0.0), float(value))
+
+
+def of_tolerance(got, want, rtol, atol):
+    """the largest |got - want| as a fraction of what assert_allclose(rtol, atol) admits"""
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    return float(np.max(np.abs(got - want) / (atol + rtol * np.abs(want))))
+
+
 def check_loss_grad(lib, seed, M, P, T, O, A, hidden, ragged=False, compact_log_std=False, low_log_std=False, min_std=1e-6,
-                    hidden_act='tanh', output_act=None):
+                    hidden_act='tanh', output_act=None, lengths_per_task=None, worst=None):
     """low_log_std: some log_std entries below log(min_std), i.e. the tf.maximum clip is active.  At the default min_std = 1e-6
-    values are not comparable in float32 (see below); with a benign min_std (0.5) they are, and are compared."""
+    values are not comparable in float32 (see below); with a benign min_std (0.5) they are, and are compared.
+    lengths_per_task: explicit path lengths (helpers.make_promp_case) instead of P paths of T rows.
+    worst: a dict that collects the largest errors ('loss' and 'kl' as fractions of their tolerance, 'grad' of the max-norm),
+    noted BEFORE each assertion."""
     theta, all_slabs, all_paths = helpers.make_promp_case(seed, M, P, T, O, A, hidden, 1, ragged=ragged,
-                                                          low_log_std=low_log_std, min_std=min_std)
+                                                          low_log_std=low_log_std, min_std=min_std, lengths_per_task=lengths_per_task)
     spec = op.PolicySpec(O, A, hidden, min_std=min_std, hidden_act=hidden_act, output_act=output_act or 'identity')
     comparable = not low_log_std or min_std > 1e-3
     ctx = make_ctx(lib, M, O, A, hidden, 1, all_paths, hidden_act=hidden_act, output_act=output_act)
@@ -328,9 +343,12 @@ def check_loss_grad(lib, seed, M, P, T, O, A, hidden, ragged=False, compact_log_
             for i in range(M):
                 r = pm.loss_and_grad(spec, th[i].astype(np.float64), all_slabs[1][i], name, clip_ls, clip_eps=0.3)
                 if comparable:
+                    note_worst(worst, 'loss', of_tolerance(l[i], r['loss'], 1e-4, 1e-6))
+                    note_worst(worst, 'kl', of_tolerance(k[i], r['kl'], 1e-4, 1e-6))
+                    note_worst(worst, 'grad', rel_max(g[i], r['grad']))
                     np.testing.assert_allclose(l[i], r['loss'], rtol=1e-4, atol=1e-6)
                     np.testing.assert_allclose(k[i], r['kl'], rtol=1e-4, atol=1e-6)
-                    assert rel_max(g[i], r['grad']) < 1e-4, (name, i)
+                    assert rel_max(g[i], r['grad']) < 1e-4, (name, i, rel_max(g[i], r['grad']))
                 else:
                     # sigma = 1e-6 makes z = (a-mu)/sigma amplify the float32 rounding of mu by 1e6, so values
                     # are not comparable in float32 (the oracle's mask arithmetic is pinned in float64 by
@@ -342,8 +360,9 @@ def check_loss_grad(lib, seed, M, P, T, O, A, hidden, ragged=False, compact_log_
     ctx.close()
 
 
-def check_hvp(lib, seed, M, P, T, O, A, hidden, ragged=False, hidden_act='tanh', output_act=None):
-    theta, all_slabs, all_paths = helpers.make_promp_case(seed, M, P, T, O, A, hidden, 1, ragged=ragged)
+def check_hvp(lib, seed, M, P, T, O, A, hidden, ragged=False, hidden_act='tanh', output_act=None, lengths_per_task=None, worst=None):
+    """lengths_per_task, worst ('hvp': of the product's max-norm): as check_loss_grad's"""
+    theta, all_slabs, all_paths = helpers.make_promp_case(seed, M, P, T, O, A, hidden, 1, ragged=ragged, lengths_per_task=lengths_per_task)
     spec = op.PolicySpec(O, A, hidden, hidden_act=hidden_act, output_act=output_act or 'identity')
     ctx = make_ctx(lib, M, O, A, hidden, 1, all_paths, hidden_act=hidden_act, output_act=output_act)
     helpers.upload_slabs(ctx, all_paths, all_slabs)
@@ -357,7 +376,8 @@ def check_hvp(lib, seed, M, P, T, O, A, hidden, ragged=False, hidden_act='tanh',
             t64 = th[i].astype(np.float64)
             ref = -pm.hvp(spec, t64, all_slabs[0][i], v[i].astype(np.float64), name, True) + \
                 0.37 * pm.loss_and_grad(spec, t64, all_slabs[0][i], name, True)['grad_kl']
-            assert rel_max(out[i], ref) < 1e-4, (name, i)
+            note_worst(worst, 'hvp', rel_max(out[i], ref))
+            assert rel_max(out[i], ref) < 1e-4, (name, i, rel_max(out[i], ref))
     ctx.close()
 
 
@@ -530,9 +550,12 @@ def check_adam_golden(lib, name):
     return worst, excluded
 
 
-def check_meta(lib, seed, M, P, T, O, A, hidden, K, ragged=False, epochs=2, compact_log_std=False, hidden_act='tanh', output_act=None):
-    """meta-objective + exact gradient, _adapt, and E Adam epochs + compute_stats."""
-    theta, all_slabs, all_paths = helpers.make_promp_case(seed, M, P, T, O, A, hidden, K, ragged=ragged)
+def check_meta(lib, seed, M, P, T, O, A, hidden, K, ragged=False, epochs=2, compact_log_std=False, hidden_act='tanh', output_act=None,
+               lengths_per_task=None, worst=None):
+    """meta-objective + exact gradient, _adapt, and E Adam epochs + compute_stats.
+    lengths_per_task, worst ('meta_loss', 'meta_kl' as fractions of their tolerance, 'meta_grad' and 'adapt' of the max-norm):
+    as check_loss_grad's"""
+    theta, all_slabs, all_paths = helpers.make_promp_case(seed, M, P, T, O, A, hidden, K, ragged=ragged, lengths_per_task=lengths_per_task)
     spec = op.PolicySpec(O, A, hidden, hidden_act=hidden_act, output_act=output_act or 'identity')
     ctx = make_ctx(lib, M, O, A, hidden, K, all_paths, hidden_act=hidden_act, output_act=output_act)
     helpers.upload_slabs(ctx, all_paths, all_slabs, compact_log_std=compact_log_std)
@@ -543,14 +566,18 @@ def check_meta(lib, seed, M, P, T, O, A, hidden, K, ragged=False, epochs=2, comp
     ctx.set_step_sizes(alpha)
     g, st = ctx.meta_grad(0.3, eta)
     r = pm.meta_objective_and_grad(spec, t64, all_slabs, a64, e64, 0.3)
+    note_worst(worst, 'meta_loss', of_tolerance(st['loss'], r['loss'], 1e-4, 1e-6))
+    note_worst(worst, 'meta_kl', max(of_tolerance(st['inner_kl'], r['inner_kl'], 1e-4, 0.0), of_tolerance(st['outer_kl'], r['outer_kl'], 1e-4, 0.0)))
+    note_worst(worst, 'meta_grad', rel_max(g, r['grad']))
     np.testing.assert_allclose(st['loss'], r['loss'], rtol=1e-4, atol=1e-6)
     np.testing.assert_allclose(st['inner_kl'], r['inner_kl'], rtol=1e-4)
     np.testing.assert_allclose(st['outer_kl'], r['outer_kl'], rtol=1e-4)
-    assert rel_max(g, r['grad']) < 1e-4
+    assert rel_max(g, r['grad']) < 1e-4, rel_max(g, r['grad'])
     # MAMLAlgo._adapt
     ctx.switch_to_pre_update()
     ctx.inner_adapt(0)
     ad = pm.adapt(spec, [t64] * M, all_slabs[0], a64)
+    note_worst(worst, 'adapt', rel_max(ctx.get_task_thetas() - theta, np.stack(ad) - t64))
     assert rel_max(ctx.get_task_thetas() - theta, np.stack(ad) - t64) < 1e-4
     # ProMP.optimize_policy core
     res = ctx.optimize(epochs, 1e-3, 0.3, eta)
@@ -1297,7 +1324,7 @@ def check_dice(lib, name, tol=1e-4):
     return check_dice_case(lib, c, t64, all_slabs, tol, golden_grad=g['grad'])
 
 
-def check_dice_case(lib, c, t64, all_slabs, tol=1e-4, golden_grad=None):
+def check_dice_case(lib, c, t64, all_slabs, tol=1e-4, golden_grad=None, worst=None):
     """check_dice's comparison on a case in hand: c (M, K, O, A, hidden, alpha), theta float64, slabs of steps 0..K in
     oracle/dice.py:to_slab form.  golden_grad: torch.autograd's gradient where a fixture holds one.
     -> the meta-gradient's error against the oracle (of its max-norm)."""
@@ -1316,11 +1343,13 @@ def check_dice_case(lib, c, t64, all_slabs, tol=1e-4, golden_grad=None):
     ctx.switch_to_pre_update()
     ctx.inner_adapt(0, _lib.INNER_DICE)
     ad = dice.adapt(spec, [t64] * M, all_slabs[0], alpha.astype(np.float64))
+    note_worst(worst, 'dice_adapt', rel_max(ctx.get_task_thetas() - theta, np.stack(ad) - t64))
     assert rel_max(ctx.get_task_thetas() - theta, np.stack(ad) - t64) < tol
     # exact meta-gradient through the adaptation, incl. the path-coupled second-order term
     grad, _ = ctx.meta_grad(0.0, np.zeros(K, np.float32), _lib.INNER_DICE, _lib.OUTER_LOGLIK)
     r = dice.meta_objective_and_grad(spec, t64, all_slabs, alpha.astype(np.float64))
     err = rel_max(grad, r['grad'])
+    note_worst(worst, 'dice_meta_grad', err)
     assert err < tol, err
     if golden_grad is not None:
         assert rel_max(grad, golden_grad) < tol                # torch.autograd on the padded magic-box graph
@@ -1331,7 +1360,7 @@ def check_dice_case(lib, c, t64, all_slabs, tol=1e-4, golden_grad=None):
     return err
 
 
-def check_dice_path_lengths(lib, seed, lengths_per_task, O=5, A=3, hidden=(32, 32), K=1, alpha=0.1, tol=1e-4):
+def check_dice_path_lengths(lib, seed, lengths_per_task, O=5, A=3, hidden=(32, 32), K=1, alpha=0.1, tol=1e-4, worst=None):
     """DICE-MAML's inner step and meta-gradient on paths of the given lengths (k_dice_scan's 64-row chunks: lengths on both sides
     of one and two chunks), against the float64 oracle (oracle/dice.py) alone.  The inputs follow oracle/gen_golden.py's
     make_dice_inputs: seeded paths per step, N(0,1) adjusted rewards, padded to the longest path."""
@@ -1360,7 +1389,7 @@ def check_dice_path_lengths(lib, seed, lengths_per_task, O=5, A=3, hidden=(32, 3
     for step in all_slabs:
         assert [list(np.diff(sl['path_row_offsets'])) for sl in step] == [list(lens) for lens in lengths_per_task]
     c = dict(M=len(lengths_per_task), K=K, O=O, A=A, hidden=tuple(hidden), alpha=alpha)
-    err = check_dice_case(lib, c, theta.astype(np.float64), all_slabs, tol)
+    err = check_dice_case(lib, c, theta.astype(np.float64), all_slabs, tol, worst=worst)
     print('sample_edges dice O=%d hidden=%s K=%d lengths=%s: meta-gradient %.2e of its max-norm against the oracle (tolerance %.0e)'
           % (O, 'x'.join(map(str, hidden)), K, lengths_per_task, err, tol))
     return err

@@ -3,7 +3,8 @@
   * torch.autograd goldens of the TF graph's arithmetic (tests/golden/promp_autograd_*.npz),
   * the float64 oracle on seeded inputs (sizes the oracle finishes in seconds),
   * size-independent properties at BASELINE.json's full config-3 size.
-Tolerances are stated in tests/parity_checks.py.
+Tolerances are stated in tests/parity_checks.py.  The layer-by-layer kernels (test_generic_policy_shapes and its neighbours) run
+one-tile work items here; tests/test_gpu_layered.py runs them on long items and at their width limits.
 
 Sample processing picks its Gram and fit kernels from LinearFeatureBaseline's column count (promp_plan.h: sample_plan): D = 2 obs_dim + 4
 features, D + 1 columns with the target, nblk = ceil((D + 1) / 16) blocks of 16.  The test_sample_processing_edges_* tests below run
@@ -138,7 +139,8 @@ def test_generic_policy_shapes(lib, hidden, O, A):
     """mlp.py:5-62 builds any number of hidden layers of any width, and the reference's Humanoid environments have 376
     observations and 17 actions (envs/mujoco_envs/humanoid_rand_direc.py): shapes outside the fused kernels run on the
     layer-by-layer kernels (promp_kernels_generic.h) -- objective, gradient, Hessian-vector product, _adapt, the Adam epochs
-    against the float64 oracle"""
+    against the float64 oracle.  (Here every work item is one 16-row tile; items of several rounds / chunks / loss blocks and the
+    width limits of these kernels: tests/test_gpu_layered.py)"""
     pc.check_loss_grad(lib, 71, M=2, P=2, T=45, O=O, A=A, hidden=hidden, ragged=True)
     pc.check_loss_grad(lib, 74, M=2, P=2, T=45, O=O, A=A, hidden=hidden, compact_log_std=True, low_log_std=True, min_std=0.5)
     pc.check_hvp(lib, 72, M=2, P=2, T=45, O=O, A=A, hidden=hidden, ragged=True)
