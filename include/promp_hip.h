@@ -387,6 +387,30 @@ int promp_optimize(promp_ctx* ctx, int num_epochs, float learning_rate, float cl
 int promp_optimize_begin(promp_ctx* ctx, int num_epochs, float learning_rate, float clip_eps,
                          const float* inner_kl_coeff, int inner_kind, int outer_kind);
 int promp_optimize_end(promp_ctx* ctx, float* loss_before, float* stats_after);
+/* Minibatched Adam epochs: what the reference's `num_minibatches` promises and never implements ("number of mini-batches for
+ * performing the gradient step. The mini-batch size is batch size//num_minibatches": optimizers/maml_first_order_optimizer.py:
+ * 16-17; stored at :41 as "# Unused"; ":97-99  # Todo: reimplement minibatches").  An epoch is num_minibatches Adam steps instead
+ * of one.  assign [num_epochs][sum_k n_paths_k] (int32, steps 0..K one behind the other) names, for every epoch and sampling
+ * step, the minibatch in [0, num_minibatches) of each path; every task must keep at least one path of every step in every
+ * minibatch.  Minibatch j of an epoch is the meta-objective on share j of every task at every step -- the inner adaptation on
+ * share j of steps 0..K-1, the outer objective, the outer KL and the inner-KL penalty on share j, the means over the share's
+ * rows, the mean over all tasks: the same function on fewer paths, as a selection (promp_set_step_selection) is.  Advantages, old
+ * means and old log_std are the stored ones; nothing is renormalised per minibatch.  Per (epoch, step) ONE launch deals the
+ * step's paths to the minibatches' compact slabs, each laid out exactly as promp_upload_step would lay out an upload of those
+ * paths alone; the Adam steps of an epoch follow in the order j = 0 .. num_minibatches - 1 (adam_t advances by num_minibatches
+ * per epoch; trained step sizes step along).  loss_before is the WHOLE batch's objective before the first step (one extra
+ * forward-only evaluation), stats_after the whole batch's behind the last: the statistics never see a minibatch quantity.
+ * num_minibatches = 1 is promp_optimize_begin itself (assign is not read).  Everything is validated before anything is
+ * enqueued, and nothing waits for the device between the first enqueue and the return; promp_optimize_end collects.  What the
+ * call leaves behind (the chain of adapted parameters, the constraint products' caches, the selections) is what promp_optimize
+ * leaves: the minibatch evaluations keep a chain, inner scalars and caches of their own.  Refused: PROMP_INNER_DICE and steps
+ * that carry DiCE rewards (the coupling rows are not among the copies), a sharded context without a communicator, a pending
+ * optimisation.  With a communicator every Adam step has its one exchange, as an epoch of promp_optimize has. */
+int promp_optimize_minibatch_begin(promp_ctx* ctx, int num_epochs, int num_minibatches, const int32_t* assign, float learning_rate,
+                                   float clip_eps, const float* inner_kl_coeff, int inner_kind, int outer_kind);
+int promp_optimize_minibatch(promp_ctx* ctx, int num_epochs, int num_minibatches, const int32_t* assign, float learning_rate,
+                             float clip_eps, const float* inner_kl_coeff, int inner_kind, int outer_kind, float* loss_before,
+                             float* stats_after);
 
 /* ---- multi-GPU: task-sharded data parallelism, one process per GPU, RCCL over xGMI.
  * The only exchange on the path is the task-mean of the meta-objective / its gradient
@@ -435,7 +459,8 @@ int promp_eval_hvp(promp_ctx* ctx, int step, int inner_kind, int clip_log_std, f
 /* ---- measurement: HIP-event timing of the pass kernels on the context's stream ------------- */
 enum { PROMP_KERNEL_FWD_BWD = 0, PROMP_KERNEL_HVP = 1, PROMP_KERNEL_GRAM = 2, PROMP_KERNEL_FWD = 3 /* forward-only k_pass */,
        PROMP_KERNEL_EXCHANGE = 4 /* the ranks' exchange of [Theta+K+2] floats (all-reduce, or all-gather + ordered sum) */,
-       PROMP_KERNEL_COUNT = 5 };
+       PROMP_KERNEL_SCATTER = 5 /* k_scatter_partition: a step's paths dealt to its minibatches' slabs (promp_optimize_minibatch) */,
+       PROMP_KERNEL_COUNT = 6 };
 int promp_prof_enable(promp_ctx* ctx, int on);
 int promp_prof_read(promp_ctx* ctx, int kernel_id, double* total_ms, int64_t* launches, int64_t* rows);
 /* The fused pass kernels run their float32-equivalent products as a two-term FP16 split (promp_amd/csrc/promp_device.h); FP16 has a

@@ -21,7 +21,7 @@ BASELINE_ZERO, BASELINE_LINEAR_FEATURE, BASELINE_LINEAR_TIME = 0, 1, 2
 INNER_RATIO, INNER_LOGLIK, INNER_DICE = 0, 1, 2
 OUTER_CLIP, OUTER_RATIO, OUTER_KL, OUTER_LOGLIK = 0, 1, 2, 3
 LOSS_RATIO, LOSS_CLIP, LOSS_LOGLIK, LOSS_KL = 0, 1, 2, 3
-KERNEL_FWD_BWD, KERNEL_HVP, KERNEL_GRAM, KERNEL_FWD, KERNEL_EXCHANGE = 0, 1, 2, 3, 4
+KERNEL_FWD_BWD, KERNEL_HVP, KERNEL_GRAM, KERNEL_FWD, KERNEL_EXCHANGE, KERNEL_SCATTER = 0, 1, 2, 3, 4, 5
 
 
 class PrompError(RuntimeError):
@@ -116,6 +116,8 @@ SIGNATURES = {
     'promp_set_dice_rewards': (C.c_int, [_P, C.c_int, _F]),
     'promp_optimize_begin': (C.c_int, [_P, C.c_int, C.c_float, C.c_float, _F, C.c_int, C.c_int]),
     'promp_optimize_end': (C.c_int, [_P, _F, _F]),
+    'promp_optimize_minibatch': (C.c_int, [_P, C.c_int, C.c_int, _I, C.c_float, C.c_float, _F, C.c_int, C.c_int, _F, _F]),
+    'promp_optimize_minibatch_begin': (C.c_int, [_P, C.c_int, C.c_int, _I, C.c_float, C.c_float, _F, C.c_int, C.c_int]),
     'promp_comm_unique_id': (C.c_int, [_P, C.c_size_t]),
     'promp_comm_init': (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t]),
     'promp_comm_move': (C.c_int, [_P, _P]),
@@ -876,6 +878,42 @@ class Context:
         self._call('promp_optimize_end', C.byref(lb), _ptr(stats, C.c_float))
         return dict(loss_before=float(lb.value), loss_after=float(stats[0]), inner_kl=stats[1:1 + self.K].copy(),
                     outer_kl=float(stats[1 + self.K]))
+
+    def _assignment(self, num_epochs, assign):
+        """[num_epochs][sum_k n_paths_k] int32 from a flat array or from per-epoch lists of per-step arrays"""
+        if isinstance(assign, (list, tuple)) and len(assign) and isinstance(assign[0], (list, tuple)):
+            assign = np.concatenate([np.concatenate([np.asarray(a, dtype=np.int32).reshape(-1) for a in epoch]) for epoch in assign])
+        assign = np.ascontiguousarray(assign, dtype=np.int32).reshape(-1)
+        if any(k not in self.step_tpo for k in range(self.K + 1)):
+            raise PrompError('optimize_minibatch: a step has no data')
+        n = sum(int(self.step_tpo[k][-1]) for k in range(self.K + 1))
+        if assign.size != int(num_epochs) * n:
+            raise PrompError('optimize_minibatch: the assignment holds %d entries, %d epochs x %d paths of steps 0..%d need %d'
+                             % (assign.size, int(num_epochs), n, self.K, int(num_epochs) * n))
+        return assign
+
+    def optimize_minibatch(self, num_epochs, num_minibatches, assign, lr, clip_eps, inner_kl_coeff, inner_kind=INNER_RATIO,
+                           outer_kind=OUTER_CLIP):
+        """promp_optimize_minibatch: num_epochs x num_minibatches Adam steps; `assign` names the minibatch of every path, per epoch
+        and sampling step ([num_epochs][sum_k n_paths_k], or per epoch a list of K + 1 arrays).  num_minibatches = 1 is optimize()."""
+        eta = _f32(inner_kl_coeff)
+        assert eta.shape == (self.K,)
+        a = None if int(num_minibatches) == 1 else self._assignment(num_epochs, assign)
+        lb, stats = C.c_float(0), np.empty(self.K + 2, np.float32)
+        self._call('promp_optimize_minibatch', int(num_epochs), int(num_minibatches), None if a is None or not a.size else _ptr(a, C.c_int32),
+                   float(lr), float(clip_eps), _ptr(eta, C.c_float), int(inner_kind), int(outer_kind), C.byref(lb), _ptr(stats, C.c_float))
+        return dict(loss_before=float(lb.value), loss_after=float(stats[0]), inner_kl=stats[1:1 + self.K].copy(),
+                    outer_kl=float(stats[1 + self.K]))
+
+    def optimize_minibatch_begin(self, num_epochs, num_minibatches, assign, lr, clip_eps, inner_kl_coeff, inner_kind=INNER_RATIO,
+                                 outer_kind=OUTER_CLIP):
+        """promp_optimize_minibatch_begin: enqueue and return at once; optimize_end() collects"""
+        eta = _f32(inner_kl_coeff)
+        assert eta.shape == (self.K,)
+        a = None if int(num_minibatches) == 1 else self._assignment(num_epochs, assign)
+        self._call('promp_optimize_minibatch_begin', int(num_epochs), int(num_minibatches),
+                   None if a is None or not a.size else _ptr(a, C.c_int32), float(lr), float(clip_eps), _ptr(eta, C.c_float),
+                   int(inner_kind), int(outer_kind))
 
     def eval_loss_grad(self, step, kind, clip_eps=0.0, clip_log_std=False):
         g = np.empty((self.n_tasks, self.n_params), np.float32)

@@ -54,16 +54,20 @@ template <class T, bool PINNED>
 struct Buf {
     T* p = nullptr;
     size_t cap = 0;                    // reserve(): elements held
+    bool own = true;                   // false: a view into another owner's block (borrow()), never released here
     Buf() = default;
-    Buf(Buf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
-    Buf& operator=(Buf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    Buf(Buf&& o) noexcept : p(o.p), cap(o.cap), own(o.own) { o.p = nullptr; o.cap = 0; o.own = true; }
+    Buf& operator=(Buf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); std::swap(own, o.own); return *this; }
     ~Buf() { (void)release(); }
     operator T*() const { return p; }
     hipError_t release() {
         T* q = p;
-        p = nullptr; cap = 0;
-        return !q ? hipSuccess : PINNED ? hipHostFree(q) : hipFree(q);
+        const bool mine = own;
+        p = nullptr; cap = 0; own = true;
+        return (!q || !mine) ? hipSuccess : PINNED ? hipHostFree(q) : hipFree(q);
     }
+    // a view of q in place of what it held (the block's owner outlives every use of the view)
+    void borrow(T* q) { (void)release(); p = q; own = false; }
     // n elements (at least one) in place of what it held; device memory arrives zero-filled
     int alloc(size_t n) {
         const size_t bytes = (n ? n : 1) * sizeof(T);
@@ -210,6 +214,33 @@ struct EvalSet {
     bool sub;
 };
 
+// promp_optimize_minibatch: one sampling step's paths dealt to the B compact slabs of its minibatches.  One pooled allocation per
+// array, rows ordered [minibatch][task][path] (every slab starts on a multiple of 64 rows); one block of tables -- the copy
+// launch's and the B slabs' pass tables -- that a single asynchronous copy fills per (epoch, step).  The slabs themselves are
+// StepData whose buffers are views into these (promp_ctx::mb).
+struct MbPool {
+    DevBuf<float> obs, act, adv, mean, ls;
+    DevBuf<unsigned> absmax;           // [B][tasks]
+    DevBuf<int> tables;
+    size_t cap_rows = 0, cap_tables = 0, cap_absmax = 0;
+    bool ls_rows = false;
+};
+// where the pieces of a step's table block lie (in ints; every piece starts on a multiple of 64)
+struct MbBlock {
+    size_t shift = 0, slab0 = 0, slab_stride = 0, tro = 0, two = 0, slot = 0, wg_off = 0, work = 0, segs = 0, total = 0;
+    // (copy table at 0: [paths][2])
+    MbBlock(int n_paths, int B, int M, int max_work) {
+        auto r64 = [](size_t n) { return (n + 63) & ~(size_t)63; };
+        shift = r64(2 * (size_t)n_paths);
+        slab0 = shift + r64(B);
+        tro = 0; two = r64(M + 1); slot = 2 * r64(M + 1); wg_off = 3 * r64(M + 1);
+        work = wg_off + r64((size_t)max_work + 1);
+        segs = work + r64(4 * (size_t)max_work);
+        slab_stride = segs + r64(4 * (size_t)max_work);
+        total = slab0 + (size_t)B * slab_stride;
+    }
+};
+
 struct ProfSlot {
     std::vector<Event> ev;       // start/stop pairs
     size_t used = 0;
@@ -302,6 +333,14 @@ struct promp_ctx {
     DevBuf<float> sel_chain, sel_scal_inner;
     ChvpRec chvp_sel;
     bool use_sel = false;                // promp_use_selection: promp_meta_grad (outer kind KL) and promp_constraint_hvp run on the selections
+    // minibatched Adam epochs (promp_optimize_minibatch): per step the pooled copies, per minibatch the slab views [B][steps]; the
+    // evaluations on them keep a chain, inner scalars and a cache record of their own, like the selections'
+    std::vector<MbPool> mb_pool;
+    std::vector<std::vector<StepData>> mb;
+    DevBuf<float> mb_chain, mb_scal_inner;
+    ChvpRec chvp_mb;
+    PinBuf<int> mb_stage;                // page-locked sources of every (epoch, step) table copy of the pending optimisation
+    bool mb_enqueued = false;            // copies out of mb_stage may still be on the stream (until promp_optimize_end)
     long long chvp_cached_passes = 0;          // R-operator passes of promp_constraint_hvp that read a primal cache (tests, tools)
     long long adapt_passes_skipped = 0;
     bool force_split = false;            // take the multi-rank launch sequence (reduce / all-reduce / Adam) on one rank too
@@ -1003,6 +1042,131 @@ int selection_set(promp_ctx* c, int inner_kind, EvalSet* E) {
     for (int k = 0; k <= K; ++k)
         if (ensure_sub(c, k)) return -2;
     *E = EvalSet{&c->sub, c->sel_chain, c->sel_scal_inner, &c->chvp_sel, true};
+    return 0;
+}
+
+// promp_optimize_begin / promp_optimize_minibatch_begin on a context that holds a shard and no communicator
+int refuse_sharded_optimize(const promp_ctx* c) {
+    return fail(-3, "this context holds %d of %d tasks and has no communicator: promp_optimize would apply this rank's sums as if they "
+                    "were the meta-batch's.  Attach one (promp_comm_init), or run the exchange yourself: promp_meta_grad -> "
+                    "promp_reduced_get -> all-reduce -> promp_reduced_set -> promp_adam_step", c->d.n_tasks, c->d.n_tasks_global);
+}
+
+// ---- minibatched Adam epochs ------------------------------------------------------------------------------------------------
+// the first row of every slab in the pool: multiples of 64 rows (a slab's arrays start aligned like an upload's), at least 16
+// rows between two slabs
+std::vector<size_t> mb_places(const PartitionLayout& part) {
+    const int B = (int)part.lay.size();
+    std::vector<size_t> at(B + 1, 0);
+    for (int j = 0; j < B; ++j) at[j + 1] = (at[j] + (size_t)(part.row_base[j + 1] - part.row_base[j]) + 16 + 63) & ~(size_t)63;
+    return at;
+}
+// Everything promp_optimize_minibatch_begin allocates, before its first enqueue: the pools and table blocks of every step sized
+// for the largest epoch, the B x (K + 1) slab records, the primal caches of the slabs the gradient passes store into, the
+// evaluation set's own chain and scalars, the page-locked staging of all table copies.
+int mb_reserve(promp_ctx* c, int E, int B, const std::vector<PartitionLayout>& parts, size_t* stage_ints) {
+    const int K = c->d.num_inner_steps, M = c->d.n_tasks;
+    const size_t O = c->d.obs_dim, A = c->d.act_dim, MNP = (size_t)M * c->NP;
+    if (c->mb_pool.empty()) {
+        if (c->mb_chain.alloc((size_t)(K + 1) * MNP) || c->mb_scal_inner.alloc((size_t)K * M * 2)) return -2;
+        c->mb_pool.resize(K + 1);
+    }
+    while ((int)c->mb.size() < B) {
+        c->mb.emplace_back();
+        c->mb.back().resize(K + 1);
+    }
+    *stage_ints = 0;
+    for (int k = 0; k <= K; ++k) {
+        const StepData& P = c->steps[k];
+        MbPool& pool = c->mb_pool[k];
+        const size_t rows = (size_t)P.n_rows + 80 * (size_t)B;
+        const bool ls_rows = P.ls_per_row != 0;
+        if (rows > pool.cap_rows || (ls_rows && !pool.ls_rows)) {
+            if (pool.obs.alloc(rows * O) || pool.act.alloc(rows * A) || pool.adv.alloc(rows) || pool.mean.alloc(rows * A)) return -2;
+            if (ls_rows && pool.ls.alloc(rows * A)) return -2;
+            if (!ls_rows) HIPCHECK(pool.ls.release());
+            pool.cap_rows = rows; pool.ls_rows = ls_rows;
+        }
+        const MbBlock blk(P.n_paths, B, M, c->max_work);
+        if (blk.total > pool.cap_tables) {
+            if (pool.tables.alloc(blk.total)) return -2;
+            pool.cap_tables = blk.total;
+        }
+        if ((size_t)B * M > pool.cap_absmax) {
+            if (pool.absmax.alloc((size_t)B * M)) return -2;
+            pool.cap_absmax = (size_t)B * M;
+        }
+        *stage_ints += (size_t)E * blk.total;
+        for (int j = 0; j < B; ++j) {
+            StepData& S = c->mb[j][k];
+            int most = 0;
+            for (int e = 0; e < E; ++e) most = std::max(most, (int)parts[(size_t)e * (K + 1) + k].tables[j].row_t.size());
+            if (most > S.cap_rows) {
+                HIPCHECK(S.hcache.release());
+                S.cap_rows = most;
+            }
+            if (k < K && primal_cache_on(c) && ensure_primal_cache(c, S)) return -2;
+        }
+    }
+    if (c->mb_stage.reserve(*stage_ints, 1)) return -2;
+    return 0;
+}
+// One (epoch, step): the table block's image in `stage` (page-locked, untouched until the optimisation is collected), its copy,
+// the copy launch, and the B slab records as the passes enqueued next are to see them.
+int mb_enqueue_step(promp_ctx* c, int k, int B, const PartitionLayout& part, int* stage) {
+    const int M = c->d.n_tasks;
+    const size_t O = c->d.obs_dim, A = c->d.act_dim;
+    StepData& P = c->steps[k];
+    MbPool& pool = c->mb_pool[k];
+    const MbBlock blk(P.n_paths, B, M, c->max_work);
+    const std::vector<size_t> at = mb_places(part);
+    memset(stage, 0, sizeof(int) * blk.total);
+    memcpy(stage, part.copy.data(), sizeof(int) * part.copy.size());
+    for (int j = 0; j < B; ++j) {
+        const StepTables& t = part.tables[j];
+        stage[blk.shift + j] = (int)at[j] - part.row_base[j];
+        int* s = stage + blk.slab0 + (size_t)j * blk.slab_stride;
+        memcpy(s + blk.tro, t.tro.data(), sizeof(int) * (M + 1));
+        memcpy(s + blk.two, t.two[0].data(), sizeof(int) * (M + 1));
+        memcpy(s + blk.slot, t.slot_chain.data(), sizeof(int) * (M + 1));
+        memcpy(s + blk.wg_off, t.wg_off.data(), sizeof(int) * t.wg_off.size());
+        memcpy(s + blk.work, t.work[0].data(), sizeof(WorkItem) * t.work[0].size());
+        memcpy(s + blk.segs, t.segs.data(), sizeof(ChainSeg) * t.segs.size());
+    }
+    hipStream_t st = c->stream;
+    if (join_side(c, P)) return -2;
+    HIPCHECK(hipMemcpyAsync(pool.tables, stage, sizeof(int) * blk.total, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemsetAsync(pool.absmax, 0, sizeof(unsigned) * B * M, st));
+    ScatterPartitionArgs g;
+    g.obs_in = P.obs; g.act_in = P.act; g.adv_in = P.adv32; g.mean_in = P.old_mean; g.ls_in = P.ls_per_row ? P.old_ls.p : nullptr;
+    g.obs = pool.obs; g.act = pool.act; g.adv = pool.adv; g.mean = pool.mean; g.ls = pool.ls;
+    g.src_row_offsets = P.path_row_offsets; g.path_task = P.path_task;
+    g.copy = pool.tables; g.shift = pool.tables + blk.shift; g.absmax = pool.absmax;
+    g.O = (int)O; g.A = (int)A; g.n_tasks = M;
+    if (prof_begin(c, PROMP_KERNEL_SCATTER, P.n_rows)) return -2;
+    PROMP_LAUNCH(k_scatter_partition, dim3(P.n_paths), 256, 0, st, g);
+    HIPCHECK(hipGetLastError());
+    if (prof_end(c, PROMP_KERNEL_SCATTER)) return -2;
+    P.dirty = true;
+    c->wbp.valid = false;              // (the hidden_0 planes carry the observation scales this launch rewrites)
+    for (int j = 0; j < B; ++j) {
+        StepData& S = c->mb[j][k];
+        const StepTables& t = part.tables[j];
+        int* s = pool.tables + blk.slab0 + (size_t)j * blk.slab_stride;
+        S.obs.borrow(pool.obs + at[j] * O); S.act.borrow(pool.act + at[j] * A); S.adv32.borrow(pool.adv + at[j]);
+        S.old_mean.borrow(pool.mean + at[j] * A);
+        // (log_std of one row per task: every minibatch reads the step's own table)
+        S.old_ls.borrow(P.ls_per_row ? pool.ls + at[j] * A : P.old_ls.p);
+        S.obs_absmax.borrow(pool.absmax + (size_t)j * M);
+        S.task_row_offsets.borrow(s + blk.tro); S.task_wg_offsets[0].borrow(s + blk.two); S.chain_slot_offsets.borrow(s + blk.slot);
+        S.chain_wg_offsets.borrow(s + blk.wg_off);
+        S.work[0].borrow(reinterpret_cast<WorkItem*>(s + blk.work)); S.chain_segs.borrow(reinterpret_cast<ChainSeg*>(s + blk.segs));
+        S.n_paths = (int)part.lay[j].idx.size(); S.n_rows = (int)t.row_t.size();
+        S.n_work[0] = (int)t.work[0].size(); S.n_work[1] = 0; S.n_chain_wg = (int)t.wg_off.size() - 1;
+        S.ls_per_row = P.ls_per_row; S.has_policy = P.has_policy; S.has_adv = P.has_adv;
+        S.data_version = P.data_version;
+        S.obs_range_valid = true;      // (k_scatter_partition has left the slab's ranges)
+    }
     return 0;
 }
 
@@ -2332,10 +2496,7 @@ int promp_optimize_begin(promp_ctx* c, int num_epochs, float lr, float clip_eps,
     if (!c || !eta) return fail(-1, "NULL argument");
     if (num_epochs < 0) return fail(-1, "num_epochs must be >= 0");
     if (c->opt_pending) return fail(-1, "promp_optimize_begin: the previous optimisation has not been collected (promp_optimize_end)");
-    if (sharded_without_comm(c))
-        return fail(-3, "this context holds %d of %d tasks and has no communicator: promp_optimize would apply this rank's sums as if they "
-                        "were the meta-batch's.  Attach one (promp_comm_init), or run the exchange yourself: promp_meta_grad -> "
-                        "promp_reduced_get -> all-reduce -> promp_reduced_set -> promp_adam_step", c->d.n_tasks, c->d.n_tasks_global);
+    if (sharded_without_comm(c)) return refuse_sharded_optimize(c);
     if (upload_eta(c, eta)) return -2;
     const int K = c->d.num_inner_steps;
     for (int e = 0; e < num_epochs; ++e) {
@@ -2365,6 +2526,7 @@ int promp_optimize_end(promp_ctx* c, float* loss_before, float* stats_after) {
     NEED_CTX(c);
     if (!c->opt_pending) return fail(-1, "promp_optimize_end without promp_optimize_begin");
     c->opt_pending = false;
+    c->mb_enqueued = false;            // (returns behind the last launch or with the stream's error: nothing reads the staging any more)
     // poll the sequence number (the stream is queried now and then: a failed launch must not turn into an endless wait)
     for (unsigned long long spins = 0;; ++spins) {
         if (__atomic_load_n(c->stats_seq_host.p, __ATOMIC_ACQUIRE) == c->stats_seq) break;
@@ -2392,6 +2554,82 @@ int promp_optimize_end(promp_ctx* c, float* loss_before, float* stats_after) {
 int promp_optimize(promp_ctx* c, int num_epochs, float lr, float clip_eps, const float* eta, int inner_kind, int outer_kind,
                    float* loss_before, float* stats_after) {
     if (promp_optimize_begin(c, num_epochs, lr, clip_eps, eta, inner_kind, outer_kind)) return -2;
+    return promp_optimize_end(c, loss_before, stats_after);
+}
+
+int promp_optimize_minibatch_begin(promp_ctx* c, int num_epochs, int num_minibatches, const int32_t* assign, float lr, float clip_eps,
+                                   const float* eta, int inner_kind, int outer_kind) {
+    if (!c || !eta) return fail(-1, "NULL argument");
+    const int E = num_epochs, B = num_minibatches;
+    if (B < 1) return fail(-1, "num_minibatches %d is below 1", B);
+    // one minibatch is the whole batch: today's call on today's path (and so is an optimisation of no epochs)
+    if (B == 1 || E <= 0) return promp_optimize_begin(c, E, lr, clip_eps, eta, inner_kind, outer_kind);
+    if (!assign) return fail(-1, "NULL argument");
+    if (c->opt_pending) return fail(-1, "promp_optimize_minibatch_begin: the previous optimisation has not been collected (promp_optimize_end)");
+    if (sharded_without_comm(c)) return refuse_sharded_optimize(c);
+    if (inner_kind == PROMP_INNER_DICE)
+        return fail(-3, "the DiCE inner objective is not evaluated on minibatches: the coupling rows of a path are not among the copies");
+    const int K = c->d.num_inner_steps, M = c->d.n_tasks;
+    for (int k = 0; k <= K; ++k) {
+        const StepData& P = c->steps[k];
+        if (P.n_rows == 0 || (int)P.lay_tpo.size() != M + 1) return fail(-3, "step %d has no data", k);
+        if (P.has_dice) return fail(-3, "step %d carries DiCE rewards: minibatches are not formed of such steps (the coupling rows are not among the copies)", k);
+        if (!P.has_policy) return fail(-3, "step has no actions / agent_infos uploaded");
+        if (!P.has_adv) return fail(-3, "step has no advantages: call promp_process_samples or promp_set_advantages first");
+    }
+    // every epoch's partition of every step, before anything is allocated or enqueued
+    std::vector<PartitionLayout> parts((size_t)E * (K + 1));
+    {
+        std::string why;
+        const int32_t* a = assign;
+        for (int e = 0; e < E; ++e)
+            for (int k = 0; k <= K; ++k) {
+                const StepData& P = c->steps[k];
+                if (const int rc = build_partition(c->n_cus, c->max_work, M, P.n_paths, P.lay_tpo.data(), P.lay_pro.data(), B, a,
+                                                   &parts[(size_t)e * (K + 1) + k], &why))
+                    return fail(rc, "epoch %d, step %d: %s", e, k, why.c_str());
+                a += P.n_paths;
+            }
+    }
+    if (c->mb_enqueued) {              // (an earlier call gave up half-way: its copies may still read the staging)
+        HIPCHECK(hipStreamSynchronize(c->stream));
+        c->mb_enqueued = false;
+    }
+    size_t stage_ints = 0;
+    if (mb_reserve(c, E, B, parts, &stage_ints)) return -2;
+    if (upload_eta(c, eta)) return -2;
+    c->mb_enqueued = true;
+    // loss_before: the whole batch's objective at the parameters the first step starts from, parked in the second slot
+    c->stats_slot = 1;
+    const int rc_before = enqueue_meta(c, clip_eps, eta, inner_kind, outer_kind, false, false, 0.f);
+    c->stats_slot = 0;
+    if (rc_before) return -2;
+    int* stage = c->mb_stage;
+    for (int e = 0; e < E; ++e) {
+        for (int k = 0; k <= K; ++k) {
+            if (mb_enqueue_step(c, k, B, parts[(size_t)e * (K + 1) + k], stage)) return -2;
+            stage += MbBlock(c->steps[k].n_paths, B, M, c->max_work).total;
+        }
+        for (int j = 0; j < B; ++j) {
+            const EvalSet S{&c->mb[j], c->mb_chain, c->mb_scal_inner, &c->chvp_mb, true};
+            if (enqueue_meta_on(c, S, clip_eps, eta, inner_kind, outer_kind, true, true, lr, true)) return -2;
+        }
+    }
+    // compute_stats on the whole batch, publishing both slots (promp_optimize_begin)
+    c->stats_seq += 1;
+    c->publish_next = true;
+    const int rc_stats = enqueue_meta(c, clip_eps, eta, inner_kind, outer_kind, false, false, 0.f);
+    c->publish_next = false;
+    if (rc_stats) return -2;
+    c->opt_pending = true;
+    c->opt_epochs = E;
+    c->opt_theta_version = c->theta_version;
+    return 0;
+}
+
+int promp_optimize_minibatch(promp_ctx* c, int num_epochs, int num_minibatches, const int32_t* assign, float lr, float clip_eps,
+                             const float* eta, int inner_kind, int outer_kind, float* loss_before, float* stats_after) {
+    if (promp_optimize_minibatch_begin(c, num_epochs, num_minibatches, assign, lr, clip_eps, eta, inner_kind, outer_kind)) return -2;
     return promp_optimize_end(c, loss_before, stats_after);
 }
 

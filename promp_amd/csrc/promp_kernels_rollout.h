@@ -169,6 +169,67 @@ __global__ void __launch_bounds__(256) k_gather_selection(GatherSelectionArgs a)
     }
 }
 
+// A step's paths dealt to the B compact slabs of its minibatches (promp_optimize_minibatch; build_partition, promp_plan.h) in ONE
+// launch: source path p goes to minibatch copy[2p], rows [copy[2p + 1] + shift[minibatch], ...) of the pooled slabs -- everything
+// a policy pass reads of a row.  The walk over the observations also leaves, per (minibatch, task), the bits of the largest
+// |observation| that k_obs_range would find on that compact slab (promp_kernels_pass.h; a maximum of bit patterns does not depend
+// on the order it is taken in): one atomic per wave, into a table zeroed in front of the launch.
+struct ScatterPartitionArgs {
+    const float *obs_in, *act_in, *adv_in, *mean_in, *ls_in;   // the step's slabs (ls_in: NULL when log_std is one row per task)
+    float *obs, *act, *adv, *mean, *ls;                         // the pooled slabs
+    const int *src_row_offsets, *path_task;                     // the step's [paths + 1] / [paths]
+    const int *copy, *shift;                                    // [paths][2] / [minibatches]: rows between a slab's place and its offset
+    unsigned* absmax;                                           // [minibatches][tasks]
+    int O, A, n_tasks;
+};
+// n consecutive floats: consecutive lanes on consecutive addresses, four loads in flight per lane
+PROMP_DEV void scatter_span(float* dst, const float* src, long long n, int tid) {
+    long long i = tid;
+    for (; i + 768 < n; i += 1024) {
+        const float v0 = src[i], v1 = src[i + 256], v2 = src[i + 512], v3 = src[i + 768];
+        dst[i] = v0; dst[i + 256] = v1; dst[i + 512] = v2; dst[i + 768] = v3;
+    }
+    for (; i < n; i += 256) dst[i] = src[i];
+}
+// grid = the step's paths, block = 256
+__global__ void __launch_bounds__(256) k_scatter_partition(ScatterPartitionArgs a) {
+    const int p = blockIdx.x, tid = threadIdx.x, mb = a.copy[2 * p];
+    const long long s0 = a.src_row_offsets[p], n = a.src_row_offsets[p + 1] - s0, r0 = (long long)a.copy[2 * p + 1] + a.shift[mb];
+    {
+        const float* src = a.obs_in + s0 * a.O;
+        float* dst = a.obs + r0 * a.O;
+        const long long nf = n * a.O;
+        unsigned m = 0;
+        long long i = tid;
+        for (; i + 768 < nf; i += 1024) {
+            const float v0 = src[i], v1 = src[i + 256], v2 = src[i + 512], v3 = src[i + 768];
+            dst[i] = v0; dst[i + 256] = v1; dst[i + 512] = v2; dst[i + 768] = v3;
+            const unsigned u0 = __builtin_bit_cast(unsigned, v0) & 0x7FFFFFFFu, u1 = __builtin_bit_cast(unsigned, v1) & 0x7FFFFFFFu;
+            const unsigned u2 = __builtin_bit_cast(unsigned, v2) & 0x7FFFFFFFu, u3 = __builtin_bit_cast(unsigned, v3) & 0x7FFFFFFFu;
+            const unsigned x = u0 > u1 ? u0 : u1, y = u2 > u3 ? u2 : u3, z = x > y ? x : y;
+            m = z > m ? z : m;
+        }
+        for (; i < nf; i += 256) {
+            const float v = src[i];
+            dst[i] = v;
+            const unsigned u = __builtin_bit_cast(unsigned, v) & 0x7FFFFFFFu;
+            m = u > m ? u : m;
+        }
+        float mf = __builtin_bit_cast(float, m);      // (compared as integers: the bit patterns of non-negative floats are ordered)
+#pragma unroll
+        for (int x = 32; x >= 1; x >>= 1) {
+            const unsigned o = __builtin_bit_cast(unsigned, shfl_xor_f32(mf, x));
+            m = o > m ? o : m;
+            mf = __builtin_bit_cast(float, m);
+        }
+        if ((tid & 63) == 0 && m != 0) atomic_max_agent(a.absmax + (long long)mb * a.n_tasks + a.path_task[p], m);
+    }
+    scatter_span(a.adv + r0, a.adv_in + s0, n, tid);
+    scatter_span(a.act + r0 * a.A, a.act_in + s0 * a.A, n * a.A, tid);
+    scatter_span(a.mean + r0 * a.A, a.mean_in + s0 * a.A, n * a.A, tid);
+    if (a.ls_in) scatter_span(a.ls + r0 * a.A, a.ls_in + s0 * a.A, n * a.A, tid);
+}
+
 enum { POINT_REWARD_DENSE = 0, POINT_REWARD_DENSE_SQUARED = 1, POINT_REWARD_SPARSE = 2 };
 
 // |p - c|_2 the way a row-wise 2-norm rounds it (squares, sum, root; no fused multiply-add): the sparse reward compares the

@@ -563,3 +563,54 @@ inline int build_selection(int M, int n_paths, const int32_t* tpo, const int32_t
     *out = std::move(L);
     return 0;
 }
+
+// ---- partitions (promp_optimize_minibatch) -----------------------------------------------------------------------------------
+// A step's paths dealt to B minibatches: per minibatch the selection of its paths and the tables of the compact slab that holds
+// them -- what build_selection + build_step_tables give for {p : assign[p] = j} --, and the table of the one copy launch that
+// fills all B slabs (k_scatter_partition).  The slabs lie one behind the other, [minibatch][task][path]: minibatch j's rows are
+// [row_base[j], row_base[j + 1]) of the step's R rows.
+struct PartitionLayout {
+    std::vector<SelectionLayout> lay;      // [B]
+    std::vector<StepTables> tables;        // [B]
+    std::vector<int> row_base;             // [B + 1]
+    std::vector<int> copy;                 // [n_paths][2]: the minibatch of a source path, the first of its destination rows
+};
+// tpo [M + 1], pro [n_paths + 1]: the step's offsets, well-formed; assign [n_paths] in [0, B).  Refuses B < 1, B above a task's
+// path count, an entry outside [0, B) and a (minibatch, task) left without a path; nothing is written on refusal.
+inline int build_partition(int n_cus, int max_work, int M, int n_paths, const int32_t* tpo, const int32_t* pro, int B,
+                           const int32_t* assign, PartitionLayout* out, std::string* why) {
+    if (B < 1) return plan_fail(why, -1, "num_minibatches %d is below 1", B);
+    if (!assign) return plan_fail(why, -1, "the assignment is NULL");
+    for (int i = 0; i < M; ++i)
+        if (B > tpo[i + 1] - tpo[i])
+            return plan_fail(why, -1, "num_minibatches %d exceeds the %d paths of task %d", B, tpo[i + 1] - tpo[i], i);
+    for (int p = 0; p < n_paths; ++p)
+        if (assign[p] < 0 || assign[p] >= B)
+            return plan_fail(why, -1, "assignment entry %d: minibatch %d out of range [0, %d)", p, assign[p], B);
+    std::vector<std::vector<int32_t>> idx(B);
+    for (int i = 0; i < M; ++i) {
+        std::vector<int> have(B, 0);
+        for (int p = tpo[i]; p < tpo[i + 1]; ++p) have[assign[p]] += 1;
+        for (int j = 0; j < B; ++j)
+            if (!have[j]) return plan_fail(why, -1, "the assignment leaves minibatch %d without a path of task %d", j, i);
+    }
+    for (int p = 0; p < n_paths; ++p) idx[assign[p]].push_back(p);
+    PartitionLayout L;
+    L.lay.resize(B);
+    L.tables.resize(B);
+    L.row_base.assign(B + 1, 0);
+    L.copy.assign(2 * (size_t)n_paths, 0);
+    for (int j = 0; j < B; ++j) {
+        const int n = (int)idx[j].size();
+        if (const int rc = build_selection(M, n_paths, tpo, pro, n, idx[j].data(), &L.lay[j], why)) return rc;
+        const SelectionLayout& s = L.lay[j];
+        if (const int rc = build_step_tables(n_cus, max_work, s.pro[n], n, M, n, s.tpo.data(), s.pro.data(), &L.tables[j], why)) return rc;
+        L.row_base[j + 1] = L.row_base[j] + s.pro[n];
+        for (int q = 0; q < n; ++q) {
+            L.copy[2 * (size_t)s.idx[q]] = j;
+            L.copy[2 * (size_t)s.idx[q] + 1] = L.row_base[j] + s.pro[q];
+        }
+    }
+    *out = std::move(L);
+    return 0;
+}

@@ -9,8 +9,10 @@ from .base import MAMLAlgo
 
 class ProMP(MAMLAlgo):
     """
-    Args (pro_mp.py:30-57): policy, name, learning_rate, num_ppo_steps, num_minibatches (unused, as in the
-    reference: maml_first_order_optimizer.py:41,97-99), clip_eps, target_inner_step, init_inner_kl_penalty,
+    Args (pro_mp.py:30-57): policy, name, learning_rate, num_ppo_steps, num_minibatches (Adam steps per epoch: every task's
+    paths of every sampling step are dealt to that many minibatches, drawn anew per epoch from np.random -- documented and left
+    unimplemented in the reference, maml_first_order_optimizer.py:16-17,41,97-99; 1: full-batch epochs; LossBefore, LossAfter,
+    KLInner and the KL-coefficient rule stay whole-batch quantities), clip_eps, target_inner_step, init_inner_kl_penalty,
     adaptive_inner_kl_penalty, anneal_factor (unused in the reference too: clip_eps is fed un-annealed,
     pro_mp.py:182), inner_lr, meta_batch_size, num_inner_grad_steps, trainable_inner_step_size
     """

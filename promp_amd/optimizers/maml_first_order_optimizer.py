@@ -4,7 +4,10 @@ Behaviour contract (reference: meta_policy_search/optimizers/maml_first_order_op
 through `self.optimizer`):
 
   * `optimize(inputs)` takes `max_epochs` full-batch steps of tf.train.AdamOptimizer(learning_rate) on the meta-objective and returns
-    the loss BEFORE the first step (:82-115; `num_minibatches` and `tolerance` are accepted and unused, as there, :41, :97-113);
+    the loss BEFORE the first step (:82-115; `tolerance` is accepted and unused, as there, :97-113).  `num_minibatches` = B > 1 --
+    documented there (:16-17) and left unimplemented (:41, :97-99) -- makes an epoch B Adam steps, one per minibatch: every task's
+    paths of every sampling step are dealt to B shares (minibatch_assignment, drawn anew per epoch), minibatch j is the
+    meta-objective on share j; the loss before and the statistics after stay whole-batch quantities (promp_optimize_minibatch);
   * `loss(inputs)` evaluates the meta-objective at the current parameters (:66-80);
   * MAMLPPOOptimizer.compute_stats(inputs) returns (loss, inner_kl [per inner step], outer_kl) at the current parameters (:146-163).
 
@@ -17,6 +20,24 @@ there instead of walking the batch again (ProMP.optimize_policy asks exactly in 
 import numpy as np
 
 from .. import _lib
+
+
+def minibatch_assignment(path_counts, num_minibatches, rng=np.random):
+    """The minibatch of every path of one sampling step: per task (path_counts: its number of paths, in task order) a permutation
+    of its paths is drawn from `rng` (NumPy's global generator unless told otherwise: reproducible from np.random.seed, like the
+    samplers), and the path of rank r among P goes to minibatch floor(r B / P) -- share sizes differ by at most one.
+    -> int32 [sum(path_counts)], task after task.  A task with fewer paths than minibatches is refused."""
+    B = int(num_minibatches)
+    if B < 1:
+        raise ValueError('num_minibatches must be >= 1, got %r' % (num_minibatches,))
+    out = []
+    for i, P in enumerate(int(p) for p in path_counts):
+        if P < B:
+            raise ValueError('num_minibatches = %d exceeds the %d paths of task %d' % (B, P, i))
+        a = np.empty(P, dtype=np.int32)
+        a[rng.permutation(P)] = (np.arange(P, dtype=np.int64) * B) // P
+        out.append(a)
+    return np.concatenate(out) if out else np.zeros(0, np.int32)
 
 
 class Optimizer(object):
@@ -36,7 +57,7 @@ class MAMLFirstOrderOptimizer(Optimizer):
     """
     Args (maml_first_order_optimizer.py:22-46): tf_optimizer_cls / tf_optimizer_args -- only Adam exists on the device; the class
     argument is accepted for call compatibility and `tf_optimizer_args['learning_rate']` is honoured --, learning_rate, max_epochs,
-    tolerance (unused), num_minibatches (unused), verbose.
+    tolerance (unused), num_minibatches (Adam steps per epoch, see above), verbose.
     """
 
     def __init__(self, tf_optimizer_cls=None, tf_optimizer_args=None, learning_rate=1e-3, max_epochs=1, tolerance=1e-6,
@@ -45,7 +66,9 @@ class MAMLFirstOrderOptimizer(Optimizer):
         self._learning_rate = float(args.get('learning_rate', learning_rate))
         self._max_epochs = int(max_epochs)
         self._tolerance = tolerance
-        self._num_minibatches = num_minibatches      # unused, as in the reference
+        self._num_minibatches = int(num_minibatches)
+        if self._num_minibatches < 1:
+            raise ValueError('num_minibatches must be >= 1, got %r' % (num_minibatches,))
         self._verbose = verbose
         self._algo = None
         self._memo = None                            # (key, result of the last promp_optimize)
@@ -83,10 +106,26 @@ class MAMLFirstOrderOptimizer(Optimizer):
         self._place(input_val_dict)
         clip_eps, eta = self._settings(input_val_dict)
         a = self._algo
-        res = a.session.optimize(self._max_epochs, self._learning_rate, clip_eps, eta, a.inner_kind, a.outer_kind)
+        if self._num_minibatches > 1:
+            res = self._optimize_minibatched(clip_eps, eta)
+        else:
+            res = a.session.optimize(self._max_epochs, self._learning_rate, clip_eps, eta, a.inner_kind, a.outer_kind)
         a.session.param_version += 1
         self._memo = (self._key(clip_eps, eta), res)
         return res['loss_before']
+
+    def _optimize_minibatched(self, clip_eps, eta):
+        """E epochs of B Adam steps: E x (K + 1) assignments, epoch after epoch and step after step, from np.random"""
+        a = self._algo
+        s = a.session
+        if s.external():               # (refused there, with the reason, before anything is drawn)
+            return s.optimize(self._max_epochs, self._learning_rate, clip_eps, eta, a.inner_kind, a.outer_kind,
+                              num_minibatches=self._num_minibatches)
+        ctx = s.ensure()
+        counts = [np.diff(ctx.step_tpo[k]) for k in range(s.K + 1)]
+        assign = [[minibatch_assignment(c, self._num_minibatches) for c in counts] for _ in range(self._max_epochs)]
+        return s.optimize(self._max_epochs, self._learning_rate, clip_eps, eta, a.inner_kind, a.outer_kind,
+                          num_minibatches=self._num_minibatches, assign=assign)
 
     def _evaluate(self, input_val_dict):
         assert self._algo is not None, 'build_graph first'
@@ -121,5 +160,5 @@ class MAMLPPOOptimizer(MAMLFirstOrderOptimizer):
         return r['loss'], r['inner_kl'], r['outer_kl']
 
 
-__all__ = ['Optimizer', 'MAMLFirstOrderOptimizer', 'MAMLPPOOptimizer']
+__all__ = ['Optimizer', 'MAMLFirstOrderOptimizer', 'MAMLPPOOptimizer', 'minibatch_assignment']
 _ = _lib      # (the kinds the plugins carry are _lib's INNER_* / OUTER_* constants)

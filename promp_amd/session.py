@@ -87,13 +87,22 @@ class DeviceSession:
         J, kls, okl = sc[0] / n, sc[1:-1].astype(np.float64) / n, sc[-1] / n
         return dict(loss=float(J + np.mean(eta * kls)), inner_kl=kls.astype(np.float32), outer_kl=float(okl))
 
-    def optimize(self, num_epochs, lr, clip_eps, inner_kl_coeff, inner_kind=_lib.INNER_RATIO, outer_kind=_lib.OUTER_CLIP):
+    def optimize(self, num_epochs, lr, clip_eps, inner_kl_coeff, inner_kind=_lib.INNER_RATIO, outer_kind=_lib.OUTER_CLIP,
+                 num_minibatches=1, assign=None):
         """ProMP.optimize_policy's numerical core on this session: promp_optimize, or -- ranks that exchange through
         `collective` -- the same epochs with the [Theta + K + 2] buffer crossing the ranks on the host
-        (promp_meta_grad -> promp_reduced_get -> collective -> promp_reduced_set -> promp_adam_step)."""
+        (promp_meta_grad -> promp_reduced_get -> collective -> promp_reduced_set -> promp_adam_step).
+        num_minibatches > 1: promp_optimize_minibatch with `assign`, the minibatch of every path per epoch and step
+        (optimizers.maml_first_order_optimizer.minibatch_assignment draws one)."""
+        if int(num_minibatches) > 1 and self.external():
+            raise _lib.PrompError('num_minibatches = %d with an external collective: the minibatched epochs run inside one library '
+                                  'call, which has no place for the host-side exchange between two Adam steps (attach a communicator '
+                                  'instead, or keep num_minibatches = 1)' % int(num_minibatches))
         ctx = self.ensure()
         if self.train_step_sizes and int(num_epochs) > 0:
             self.param_version += 1       # the step sizes move with theta: what the tasks adapt with is no longer what it was
+        if int(num_minibatches) > 1:
+            return ctx.optimize_minibatch(num_epochs, num_minibatches, assign, lr, clip_eps, inner_kl_coeff, inner_kind, outer_kind)
         if not self.external():
             return ctx.optimize(num_epochs, lr, clip_eps, inner_kl_coeff, inner_kind, outer_kind)
         eta = np.asarray(inner_kl_coeff, dtype=np.float32)

@@ -29,7 +29,7 @@ DEFAULT = {
     'rollouts_per_meta_task': 20, 'max_path_length': 100, 'parallel': False,
     'discount': 0.99, 'gae_lambda': 1, 'normalize_adv': True,
     'hidden_sizes': (32, 32),
-    'inner_lr': 0.1, 'learning_rate': 1e-3, 'num_promp_steps': 5, 'clip_eps': 0.3, 'target_inner_step': 0.01,
+    'inner_lr': 0.1, 'learning_rate': 1e-3, 'num_promp_steps': 5, 'num_minibatches': 1, 'clip_eps': 0.3, 'target_inner_step': 0.01,
     'init_inner_kl_penalty': 5e-4, 'adaptive_inner_kl_penalty': False,
     'n_itr': 100, 'meta_batch_size': 4, 'num_inner_grad_steps': 1,
     'device_rollouts': False,      # True: the environment itself runs on the GPU (samplers/device_point_sampler.py)
@@ -56,7 +56,7 @@ def main(config):
                                            normalize_adv=config['normalize_adv'])
     algo = ProMP(policy=policy, inner_lr=config['inner_lr'], meta_batch_size=config['meta_batch_size'],
                  num_inner_grad_steps=config['num_inner_grad_steps'], learning_rate=config['learning_rate'],
-                 num_ppo_steps=config['num_promp_steps'], clip_eps=config['clip_eps'],
+                 num_ppo_steps=config['num_promp_steps'], num_minibatches=config.get('num_minibatches', 1), clip_eps=config['clip_eps'],
                  target_inner_step=config['target_inner_step'], init_inner_kl_penalty=config['init_inner_kl_penalty'],
                  adaptive_inner_kl_penalty=config['adaptive_inner_kl_penalty'])
     trainer = Trainer(algo=algo, policy=policy, env=env, sampler=sampler, sample_processor=sample_processor,
@@ -70,6 +70,8 @@ if __name__ == '__main__':
     ap.add_argument('--config_file', type=str, default='')
     ap.add_argument('--dump_path', type=str, default='')
     ap.add_argument('--n_itr', type=int, default=None)
+    ap.add_argument('--num_minibatches', type=int, default=None,
+                    help='Adam steps per epoch of the outer step: every task\'s paths are dealt to this many minibatches (default 1)')
     ap.add_argument('--quiet', action='store_true')
     args = ap.parse_args()
     cfg = dict(DEFAULT)
@@ -77,6 +79,8 @@ if __name__ == '__main__':
         cfg.update(json.load(open(args.config_file)))
     if args.n_itr is not None:
         cfg['n_itr'] = args.n_itr
+    if args.num_minibatches is not None:
+        cfg['num_minibatches'] = args.num_minibatches
     logger.configure(dir=args.dump_path or None, snapshot_mode='last_gap', snapshot_gap=50, quiet=args.quiet)
     if args.dump_path:
         json.dump({k: (list(v) if isinstance(v, tuple) else v) for k, v in cfg.items()}, open(os.path.join(args.dump_path, 'params.json'), 'w'))
