@@ -459,7 +459,8 @@ int promp_eval_hvp(promp_ctx* ctx, int step, int inner_kind, int clip_log_std, f
 /* ---- measurement: HIP-event timing of the pass kernels on the context's stream ------------- */
 enum { PROMP_KERNEL_FWD_BWD = 0, PROMP_KERNEL_HVP = 1, PROMP_KERNEL_GRAM = 2, PROMP_KERNEL_FWD = 3 /* forward-only k_pass */,
        PROMP_KERNEL_EXCHANGE = 4 /* the ranks' exchange of [Theta+K+2] floats (all-reduce, or all-gather + ordered sum) */,
-       PROMP_KERNEL_SCATTER = 5 /* k_scatter_partition: a step's paths dealt to its minibatches' slabs (promp_optimize_minibatch) */,
+       PROMP_KERNEL_SCATTER = 5 /* k_scatter_partition's launches that deal a step's paths to its minibatches' slabs
+                                   (promp_optimize_minibatch); the same kernel filling a selection's slab is not counted */,
        PROMP_KERNEL_COUNT = 6 };
 int promp_prof_enable(promp_ctx* ctx, int on);
 int promp_prof_read(promp_ctx* ctx, int kernel_id, double* total_ms, int64_t* launches, int64_t* rows);

@@ -54,20 +54,16 @@ template <class T, bool PINNED>
 struct Buf {
     T* p = nullptr;
     size_t cap = 0;                    // reserve(): elements held
-    bool own = true;                   // false: a view into another owner's block (borrow()), never released here
     Buf() = default;
-    Buf(Buf&& o) noexcept : p(o.p), cap(o.cap), own(o.own) { o.p = nullptr; o.cap = 0; o.own = true; }
-    Buf& operator=(Buf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); std::swap(own, o.own); return *this; }
+    Buf(Buf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    Buf& operator=(Buf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
     ~Buf() { (void)release(); }
     operator T*() const { return p; }
     hipError_t release() {
         T* q = p;
-        const bool mine = own;
-        p = nullptr; cap = 0; own = true;
-        return (!q || !mine) ? hipSuccess : PINNED ? hipHostFree(q) : hipFree(q);
+        p = nullptr; cap = 0;
+        return !q ? hipSuccess : PINNED ? hipHostFree(q) : hipFree(q);
     }
-    // a view of q in place of what it held (the block's owner outlives every use of the view)
-    void borrow(T* q) { (void)release(); p = q; own = false; }
     // n elements (at least one) in place of what it held; device memory arrives zero-filled
     int alloc(size_t n) {
         const size_t bytes = (n ? n : 1) * sizeof(T);
@@ -107,6 +103,27 @@ using Stream = Handle<hipStream_t, hipStreamDestroy>;
 #define NEED_CTX(c) \
     if (!(c)) return fail(-1, "ctx is NULL")
 
+// What a policy pass (launch_pass, PassReq) reads of the rows it walks, stated once: a sampling step's own arrays (StepData::ps,
+// bound by alloc_step) or a compact slab that holds copies of some of a step's paths (a selection's, a minibatch's: bound by
+// scatter_slabs).  The arrays and tables are views -- their owner outlives every use of the slab --; the primal cache is the
+// slab's own.  Its address is its identity (promp_ctx::wbp).
+struct PassSlab {
+    const float *obs = nullptr, *act = nullptr, *adv = nullptr, *old_mean = nullptr, *old_ls = nullptr;
+    unsigned* obs_absmax = nullptr;    // [tasks]: bits of the largest |observation| of each task's rows (the FP16 split's scale)
+    const int *task_row_offsets = nullptr, *task_wg_offsets = nullptr;   // [tasks + 1] each; the work items of a task
+    const int *chain_slot_offsets = nullptr, *chain_wg_offsets = nullptr;
+    const WorkItem* work = nullptr;    // one workgroup per CU (cooperative and layer-by-layer passes)
+    const ChainSeg* chain_segs = nullptr;
+    int n_rows = 0, n_work = 0, n_chain_wg = 0;
+    int ls_per_row = 0;
+    bool has_policy = false, has_adv = false;
+    bool obs_range_valid = false;      // false from whatever writes obs until obs_absmax holds its range (enqueue_obs_range, the copy launch)
+    unsigned long long data_version = 0;
+    DevBuf<float> hcache;              // primal cache (promp_kernels_chain.h: chain_cache_row), allocated on first use ...
+    size_t cache_rows = 0;             // ... for this many rows (a compact slab that outgrows it releases the cache)
+    unsigned long long cache_tag = 0;  // identity of the primal cache's contents (every storing pass draws a new one)
+};
+
 struct StepData {
     int n_paths = 0, n_rows = 0;
     int n_work[2] = {0, 0};            // [0]: one workgroup per CU (wide passes, gram, fit), [1]: two per CU (k_normalize)
@@ -115,13 +132,11 @@ struct StepData {
     int n_chain_wg = 0;                // workgroups of the register-chained kernels k_pass / k_chain_hvp (segment table)
     bool has_policy = false, processed = false, has_adv = false;
     unsigned long long data_version = 0;   // bumped by every entry point that may change what the policy passes read from this step
-    unsigned long long cache_tag = 0;      // identity of the primal cache's contents (every storing pass draws a new one)
     int ls_per_row = 0;
     int feat_dim = 0;
-    int cap_rows = 0;                  // a selection's compact slab: the rows its buffers hold (0: the context's max_rows)
+    PassSlab ps;                       // the step as the policy passes see it: reach it through pass_slab()
     DevBuf<float> obs, act, rew, old_mean, old_ls;
-    DevBuf<unsigned> obs_absmax;       // [tasks]: bits of the largest |observation| of each task's rows (k_obs_range; the FP16 split's scale)
-    bool obs_range_valid = false;      // false from every entry point that writes S.obs until k_obs_range has been enqueued behind it
+    DevBuf<unsigned> obs_absmax;       // [tasks]: ps.obs_absmax (k_obs_range)
     DevBuf<double> rew64;              // promp_set_rewards_f64 (allocated on first use); valid while has_rew64
     // DiCE (promp_set_dice_rewards; allocated on first use): per-row adjusted rewards, row tangents of the R-operator pass,
     // coupling weights, scan scratch
@@ -131,7 +146,6 @@ struct StepData {
     bool has_rew64 = false;
     DevBuf<float> ret32, adv32;
     DevBuf<double> ret64, adv64;
-    DevBuf<float> hcache;              // primal cache (promp_kernels_chain.h: chain_cache_row), allocated on first use
     DevBuf<int> path_row_offsets, path_task, row_t;
     DevBuf<int> task_row_offsets, task_path_offsets;
     DevBuf<int> task_wg_offsets[2];
@@ -191,54 +205,38 @@ struct ChvpRec {
     float min_log_std = 0.f;
 };
 
+// The device side of a step's compact slabs: one pooled allocation per row array (every slab starts on a multiple of 64 rows),
+// the observation ranges [slabs][tasks], and the table block (promp_plan.h: TableBlock) that one copy fills.  The slabs
+// themselves are PassSlabs whose pointers lead into these (scatter_slabs).
+struct SlabPool {
+    DevBuf<float> obs, act, adv, mean, ls;
+    DevBuf<unsigned> absmax;
+    DevBuf<int> tables;
+    size_t cap_rows = 0, cap_tables = 0, cap_absmax = 0;
+    bool ls_rows = false;
+};
+
 // promp_set_step_selection: the paths of a step that the subsampled constraint products keep.  The compact slab that holds copies
 // of their rows (promp_ctx::sub) is filled by the first evaluation that needs it and again whenever the step's data has moved.
 struct Selection {
     bool on = false;
     SelectionLayout lay;
     StepTables tables;                 // the compact slab's tables, as build_step_tables lays out an upload of the selected paths
-    DevBuf<int> idx;                   // lay.idx on the device
-    int cap_paths = 0;
-    bool tables_sent = false, gathered = false;
+    std::vector<int> image;            // the table block (one slab; the copy table sends the other paths nowhere)
+    SlabPool pool;
+    bool gathered = false;
     unsigned long long gathered_version = 0;   // the step's data_version the copies were taken at
 };
 
 // What an evaluation of the meta-objective or of the constraint product walks and leaves behind: the whole batch with the
-// context's chain of adapted parameters, or the selections' compact slabs with a chain, inner scalars and cache record of their
-// own (what promp_inner_adapt and the last full-batch product left behind stays valid under a subsampled solve)
+// context's chain of adapted parameters, or compact slabs (the selections', a minibatch's) with a chain, inner scalars and cache
+// record of their own (what promp_inner_adapt and the last full-batch product left behind stays valid under a subsampled solve)
 struct EvalSet {
-    std::vector<StepData>* steps;
+    PassSlab* slab[PROMP_ETA_MAX + 1];
+    StepData* full;                    // the steps that own the slabs (stream joins, use marks, DiCE rows); nullptr: compact slabs
     float* chain;
     float* scal_inner;
     ChvpRec* chvp;
-    bool sub;
-};
-
-// promp_optimize_minibatch: one sampling step's paths dealt to the B compact slabs of its minibatches.  One pooled allocation per
-// array, rows ordered [minibatch][task][path] (every slab starts on a multiple of 64 rows); one block of tables -- the copy
-// launch's and the B slabs' pass tables -- that a single asynchronous copy fills per (epoch, step).  The slabs themselves are
-// StepData whose buffers are views into these (promp_ctx::mb).
-struct MbPool {
-    DevBuf<float> obs, act, adv, mean, ls;
-    DevBuf<unsigned> absmax;           // [B][tasks]
-    DevBuf<int> tables;
-    size_t cap_rows = 0, cap_tables = 0, cap_absmax = 0;
-    bool ls_rows = false;
-};
-// where the pieces of a step's table block lie (in ints; every piece starts on a multiple of 64)
-struct MbBlock {
-    size_t shift = 0, slab0 = 0, slab_stride = 0, tro = 0, two = 0, slot = 0, wg_off = 0, work = 0, segs = 0, total = 0;
-    // (copy table at 0: [paths][2])
-    MbBlock(int n_paths, int B, int M, int max_work) {
-        auto r64 = [](size_t n) { return (n + 63) & ~(size_t)63; };
-        shift = r64(2 * (size_t)n_paths);
-        slab0 = shift + r64(B);
-        tro = 0; two = r64(M + 1); slot = 2 * r64(M + 1); wg_off = 3 * r64(M + 1);
-        work = wg_off + r64((size_t)max_work + 1);
-        segs = work + r64(4 * (size_t)max_work);
-        slab_stride = segs + r64(4 * (size_t)max_work);
-        total = slab0 + (size_t)B * slab_stride;
-    }
 };
 
 struct ProfSlot {
@@ -329,14 +327,14 @@ struct promp_ctx {
     // subsampled constraint products (promp_set_step_selection): per step the selection and its compact slab; the evaluations on
     // them keep their own chain, inner scalars and cache record (EvalSet), all allocated with the first selection
     std::vector<Selection> sel;
-    std::vector<StepData> sub;
+    std::vector<PassSlab> sub;
     DevBuf<float> sel_chain, sel_scal_inner;
     ChvpRec chvp_sel;
     bool use_sel = false;                // promp_use_selection: promp_meta_grad (outer kind KL) and promp_constraint_hvp run on the selections
-    // minibatched Adam epochs (promp_optimize_minibatch): per step the pooled copies, per minibatch the slab views [B][steps]; the
+    // minibatched Adam epochs (promp_optimize_minibatch): per step the pooled copies and the B slabs [steps][B]; the
     // evaluations on them keep a chain, inner scalars and a cache record of their own, like the selections'
-    std::vector<MbPool> mb_pool;
-    std::vector<std::vector<StepData>> mb;
+    std::vector<SlabPool> mb_pool;
+    std::vector<std::vector<PassSlab>> mb;
     DevBuf<float> mb_chain, mb_scal_inner;
     ChvpRec chvp_mb;
     PinBuf<int> mb_stage;                // page-locked sources of every (epoch, step) table copy of the pending optimisation
@@ -491,13 +489,13 @@ void gen_linear(promp_ctx* c, dim3 grid, const GenArgs& g, int li, int pp) {
     else { auto k = k_gen_linear<MODE, NBW>; PROMP_LAUNCH(k, grid, 256, gen_linear_smem(MODE, NBW), c->stream, g, li, pp); }
 }
 template <int NT, int NBW>
-void gen_wgrad(promp_ctx* c, const StepData& S, const GenArgs& g, int li, int pp) {
+void gen_wgrad(promp_ctx* c, const PassSlab& S, const GenArgs& g, int li, int pp) {
     if (c->gen_bf16) {
         auto k = k_gb_wgrad<NT, NBW>;
-        PROMP_LAUNCH(k, dim3(S.n_work[0] * Ly_K_slabs(c->lin[li].K)), 256, gb_smem(NT, NBW), c->stream, g, li, pp);
+        PROMP_LAUNCH(k, dim3(S.n_work * Ly_K_slabs(c->lin[li].K)), 256, gb_smem(NT, NBW), c->stream, g, li, pp);
     } else {      // one slab of 64 input units per workgroup
         auto k = k_gen_wgrad<NT, NBW>;
-        PROMP_LAUNCH(k, dim3(S.n_work[0], (c->lin[li].K + GEN_KC - 1) / GEN_KC), 256, gen_wgrad_smem(NT, c->lin[li].N), c->stream, g, li, pp);
+        PROMP_LAUNCH(k, dim3(S.n_work, (c->lin[li].K + GEN_KC - 1) / GEN_KC), 256, gen_wgrad_smem(NT, c->lin[li].N), c->stream, g, li, pp);
     }
 }
 // A pass on the layer-by-layer kernels (promp_kernels_generic.h): forward chain, loss level, then per layer (output first) the
@@ -512,7 +510,7 @@ void copy_layers(Args& dst, const promp_ctx* c) {
     dst.n_lin = c->n_lin;
     for (int l = 0; l < c->n_lin; ++l) dst.lin[l] = c->lin[l];
 }
-int launch_pass_generic(promp_ctx* c, StepData& S, const PassArgs& a, bool hvp, bool fwd_only) {
+int launch_pass_generic(promp_ctx* c, PassSlab& S, const PassArgs& a, bool hvp, bool fwd_only) {
     GenArgs g;
     memset(&g, 0, sizeof g);
     g.work = a.work; g.task_row_offsets = a.task_row_offsets;
@@ -527,9 +525,9 @@ int launch_pass_generic(promp_ctx* c, StepData& S, const PassArgs& a, bool hvp, 
     g.partials = a.partials; g.partial_stride = a.partial_stride;
     g.loss_kind = a.loss_kind; g.clip_eps = a.clip_eps; g.clip_log_std = a.clip_log_std; g.min_log_std = a.min_log_std;
     g.kl_weight = a.kl_weight; g.row_tan = a.row_tan;
-    const dim3 grid(S.n_work[0]);
+    const dim3 grid(S.n_work);
     // k_gen_linear / k_gb_linear: the 64-row rounds of a work item (about one CU's share of the rows) dealt to GEN_SPLIT workgroups
-    const dim3 lgrid(S.n_work[0], GEN_SPLIT);
+    const dim3 lgrid(S.n_work, GEN_SPLIT);
     hipStream_t st = c->stream;
     if (c->gen_bf16) {
         // the parameters' (and minus the direction's) kernels as BF16 planes, both orientations, in the GEMMs' chunk order
@@ -574,10 +572,10 @@ int launch_pass_generic(promp_ctx* c, StepData& S, const PassArgs& a, bool hvp, 
     return 0;
 }
 
-// The per-task range of a step's observations (the FP16 split's scale, promp_kernels_pass.h: k_obs_range), enqueued on `st` behind
+// The per-task range of a slab's observations (the FP16 split's scale, promp_kernels_pass.h: k_obs_range), enqueued on `st` behind
 // whatever wrote the slab there.  The uploads call it on their own stream (its cost is the upload's); the device-side writers only
 // mark the table stale and the first policy pass recomputes it.
-int enqueue_obs_range(promp_ctx* c, StepData& S, hipStream_t st) {
+int enqueue_obs_range(promp_ctx* c, PassSlab& S, hipStream_t st) {
     if (S.n_rows <= 0) return 0;
     HIPCHECK(hipMemsetAsync(S.obs_absmax, 0, sizeof(unsigned) * c->d.n_tasks, st));
     ObsRangeArgs r;
@@ -597,15 +595,14 @@ int enqueue_obs_range(promp_ctx* c, StepData& S, hipStream_t st) {
 // FP16 pipe (round 6: 12.2 k cycles per tile against 26.3 k for the recomputing one) the cache pays on small shards too: 0.516 vs
 // 0.545 ms at 5 tasks, 0.475 vs 0.485 at 3 (two A/B pairs, one box).
 static bool primal_cache_on(const promp_ctx* c) { return c->family == PassFamily::Chain && c->primal_cache != 0; }
-// the step's primal cache (promp_kernels_chain.h: chain_cache_row), allocated on first use
-static int ensure_primal_cache(promp_ctx* c, StepData& S) {
+// the slab's primal cache (promp_kernels_chain.h: chain_cache_row), allocated on first use
+static int ensure_primal_cache(promp_ctx* c, PassSlab& S) {
     if (S.hcache) return 0;
-    const size_t rows = S.cap_rows ? S.cap_rows : c->d.max_rows;
-    return S.hcache.alloc((rows + 16 * (size_t)c->d.n_tasks) * chain_cache_row(c->d.hidden1, c->d.hidden2));
+    return S.hcache.alloc((S.cache_rows + 16 * (size_t)c->d.n_tasks) * chain_cache_row(c->d.hidden1, c->d.hidden2));
 }
 
 // Chain: k_chain_hvp reduces in-launch when a.fuse_reduce says so; k_pass is followed by k_reduce_task
-static void launch_chain(promp_ctx* c, StepData& S, const PassArgs& a, const PassReq& q, int cache) {
+static void launch_chain(promp_ctx* c, PassSlab& S, const PassArgs& a, const PassReq& q, int cache) {
     const int n1 = c->d.hidden1 / 16, n2 = c->d.hidden2 / 16, ks = chain_ksteps(c->d.obs_dim);
     const dim3 grid(S.n_chain_wg);
     if (q.hvp) {
@@ -629,14 +626,14 @@ static void launch_chain(promp_ctx* c, StepData& S, const PassArgs& a, const Pas
 }
 
 // CoopFp32: hidden 128, or hidden 64 with obs_dim > 32 (promp_kernels_policy_wide.h)
-static void launch_coop_fp32(promp_ctx* c, StepData& S, const PassArgs& a, const PassReq& q) {
+static void launch_coop_fp32(promp_ctx* c, PassSlab& S, const PassArgs& a, const PassReq& q) {
     const int nob = wide_nob(c->d.obs_dim);
     const size_t sm = q.hvp ? c->smem_hvp : c->smem_fwd;
 #define PROMP_WIDE_CASE(HH, NOB)                                                                                                \
-    if (c->d.hidden1 == HH && nob == NOB) {                                                                                      \
-        if (q.hvp) { auto k = k_wide_hvp<HH, NOB>; PROMP_LAUNCH(k, dim3(S.n_work[0]), 4 * HH, sm, c->stream, a); }               \
-        else if (q.fwd_only) { auto k = k_wide_fwd_bwd<HH, NOB, false>; PROMP_LAUNCH(k, dim3(S.n_work[0]), 4 * HH, sm, c->stream, a); } \
-        else { auto k = k_wide_fwd_bwd<HH, NOB, true>; PROMP_LAUNCH(k, dim3(S.n_work[0]), 4 * HH, sm, c->stream, a); }            \
+    if (c->d.hidden1 == HH && nob == NOB) {                                                                                     \
+        if (q.hvp) { auto k = k_wide_hvp<HH, NOB>; PROMP_LAUNCH(k, dim3(S.n_work), 4 * HH, sm, c->stream, a); }                 \
+        else if (q.fwd_only) { auto k = k_wide_fwd_bwd<HH, NOB, false>; PROMP_LAUNCH(k, dim3(S.n_work), 4 * HH, sm, c->stream, a); } \
+        else { auto k = k_wide_fwd_bwd<HH, NOB, true>; PROMP_LAUNCH(k, dim3(S.n_work), 4 * HH, sm, c->stream, a); }             \
     }
     PROMP_WIDE_ALL(PROMP_WIDE_CASE)
 #undef PROMP_WIDE_CASE
@@ -644,7 +641,7 @@ static void launch_coop_fp32(promp_ctx* c, StepData& S, const PassArgs& a, const
 
 // CoopSplit: two layers of 128 units on the BF16 matrix pipe (promp_kernels_wide_bf16.h), behind the small launches that lay the
 // parameters' (and the direction's) hidden kernels out as BF16 planes in fragment order (276 KB per task)
-static void launch_coop_split(promp_ctx* c, StepData& S, PassArgs& a, const PassReq& q) {
+static void launch_coop_split(promp_ctx* c, PassSlab& S, PassArgs& a, const PassReq& q) {
     const int nko = wb_nko(c->wb_cls);
     WbPlaneArgs pa;
     const bool at_meta = q.theta == c->theta && q.theta_stride == 0 && c->wb_planes_meta;
@@ -674,32 +671,32 @@ static void launch_coop_split(promp_ctx* c, StepData& S, PassArgs& a, const Pass
     }
 #define PROMP_WB_CASE(CLS, NKO, NXB)                                                                                              \
     if (c->wb_cls == CLS) {                                                                                                       \
-        if (q.hvp) { auto k = k_wb_hvp<NKO, NXB>; PROMP_LAUNCH(k, dim3(S.n_work[0]), 256, c->smem_wb_hvp, c->stream, a); }          \
-        else if (q.fwd_only) { auto k = k_wb_fwd_bwd<NKO, NXB, false>; PROMP_LAUNCH(k, dim3(S.n_work[0]), 256, c->smem_wb_fwd, c->stream, a); } \
-        else { auto k = k_wb_fwd_bwd<NKO, NXB, true>; PROMP_LAUNCH(k, dim3(S.n_work[0]), 256, c->smem_wb_bwd, c->stream, a); }       \
+        if (q.hvp) { auto k = k_wb_hvp<NKO, NXB>; PROMP_LAUNCH(k, dim3(S.n_work), 256, c->smem_wb_hvp, c->stream, a); }           \
+        else if (q.fwd_only) { auto k = k_wb_fwd_bwd<NKO, NXB, false>; PROMP_LAUNCH(k, dim3(S.n_work), 256, c->smem_wb_fwd, c->stream, a); } \
+        else { auto k = k_wb_fwd_bwd<NKO, NXB, true>; PROMP_LAUNCH(k, dim3(S.n_work), 256, c->smem_wb_bwd, c->stream, a); }       \
     }
     PROMP_WB_ALL(PROMP_WB_CASE)
 #undef PROMP_WB_CASE
 }
 
-// One policy pass over a step's slabs plus the per-task reduction that consumes it (q.red_mode, promp_kernels_chain.h).
+// One policy pass over a slab plus the per-task reduction that consumes it (q.red_mode, promp_kernels_chain.h).
 // k_chain_hvp can do both in one launch; every other pass kernel is followed by k_reduce_task.
-int launch_pass(promp_ctx* c, StepData& S, const PassReq& q) {
+int launch_pass(promp_ctx* c, PassSlab& S, const PassReq& q) {
     if (!S.has_policy) return fail(-3, "step has no actions / agent_infos uploaded");
     if (!S.has_adv) return fail(-3, "step has no advantages: call promp_process_samples or promp_set_advantages first");
     if (!S.obs_range_valid && enqueue_obs_range(c, S, c->stream)) return -2;
     const bool chain = c->family == PassFamily::Chain;
     PassArgs a;
     memset(&a, 0, sizeof a);
-    a.obs_absmax = (const float*)S.obs_absmax.p;
-    a.obs = S.obs; a.act = S.act; a.adv = q.adv ? q.adv : S.adv32; a.old_mean = S.old_mean; a.old_log_std = S.old_ls;
+    a.obs_absmax = (const float*)S.obs_absmax;
+    a.obs = S.obs; a.act = S.act; a.adv = q.adv ? q.adv : S.adv; a.old_mean = S.old_mean; a.old_log_std = S.old_ls;
     a.row_tan = q.hvp ? q.row_tan : nullptr;
     const int cache = (!chain || q.fwd_only || !S.hcache) ? 0 : q.cache;
     a.hcache = cache ? S.hcache.p : nullptr;
     if (cache == 1) S.cache_tag = ++c->cache_counter;
     a.ls_per_row = S.ls_per_row;
     a.task_row_offsets = S.task_row_offsets;
-    a.work = S.work[0];
+    a.work = S.work;
     a.segs = S.chain_segs; a.wg_seg_offsets = S.chain_wg_offsets;
     a.theta = q.theta; a.theta_task_stride = q.theta_stride;
     a.vdir = c->vbuf;
@@ -735,7 +732,7 @@ int launch_pass(promp_ctx* c, StepData& S, const PassReq& q) {
     ReduceArgs r;
     r.partials = c->partials; r.partial_stride = c->partial_stride;
     // the register-chained kernels write one row per segment
-    r.task_wg_offsets = chain ? S.chain_slot_offsets : S.task_wg_offsets[0];
+    r.task_wg_offsets = chain ? S.chain_slot_offsets : S.task_wg_offsets;
     r.NP = c->NP;
     r.step_sizes = c->step_sizes; r.mode = q.red_mode;
     r.cur = q.cur; r.cur_task_stride = q.cur_stride; r.next = q.next;
@@ -809,33 +806,45 @@ static StepSizeArgs step_size_args(const promp_ctx* c) {
     return s;
 }
 
-static EvalSet full_set(promp_ctx* c) { return EvalSet{&c->steps, c->chain, c->scal_inner, &c->chvp, false}; }
+// The step as a policy pass is to see it.  The counts, flags and version that the step's entry points keep in StepData reach
+// the slab HERE and nowhere else; what the passes themselves write (obs_range_valid, the primal cache) lives in the slab alone.
+static PassSlab& pass_slab(StepData& S) {
+    PassSlab& ps = S.ps;
+    ps.n_rows = S.n_rows; ps.n_work = S.n_work[0]; ps.n_chain_wg = S.n_chain_wg;
+    ps.ls_per_row = S.ls_per_row; ps.has_policy = S.has_policy; ps.has_adv = S.has_adv; ps.data_version = S.data_version;
+    return ps;
+}
+static EvalSet full_set(promp_ctx* c) {
+    EvalSet E{{}, c->steps.data(), c->chain, c->scal_inner, &c->chvp};
+    for (size_t k = 0; k < c->steps.size(); ++k) E.slab[k] = &pass_slab(c->steps[k]);
+    return E;
+}
 
 // One evaluation of the meta-objective (+ gradient, + Adam) enqueued on the stream.  sizes_grad: with trainable step sizes the
 // gradient evaluation also leaves the step sizes' gradient (and Adam steps them); promp_cg_solve's evaluations say no.
 int enqueue_meta_on(promp_ctx* c, const EvalSet& E, float clip_eps, const float* eta_host, int inner_kind, int outer_kind,
                     bool want_grad, bool do_adam, float lr, bool sizes_grad) {
-    std::vector<StepData>& W = *E.steps;
+    PassSlab* const* W = E.slab;
     const int K = c->d.num_inner_steps, M = c->d.n_tasks, NP = c->NP;
     const size_t MNP = (size_t)M * NP;
     const bool ag = c->train_sizes && want_grad && sizes_grad;
     for (int k = 0; k <= K; ++k)
-        if (W[k].n_rows == 0) return fail(-3, "step %d has no data", k);
+        if (W[k]->n_rows == 0) return fail(-3, "step %d has no data", k);
     // a step's second-stream sample processing is waited for right in front of the first pass that reads its advantages:
     // the passes on earlier steps run while it finishes
-    if (E.sub && ag) c->adapt0.valid = false;      // (ginner[0] is about to hold the selection's gradient)
+    if (!E.full && ag) c->adapt0.valid = false;      // (ginner[0] is about to hold the selection's gradient)
     bool filled[PROMP_ETA_MAX] = {};      // steps whose primal cache this evaluation has written
     for (int k = 0; k < K; ++k) {
         const float* th = (k == 0) ? c->theta : E.chain + (size_t)k * MNP;
         const long long st = (k == 0) ? 0 : NP;
-        if (join_side(c, W[k])) return -2;
+        if (E.full && join_side(c, E.full[k])) return -2;
         // the R-operator pass of this step (below) runs at these parameters on this slab: it reads the activations and means
         // back instead of recomputing them (primal cache, promp_kernels_chain.h)
         const bool cached = want_grad && primal_cache_on(c);
-        if (cached && ensure_primal_cache(c, W[k])) return -2;
+        if (cached && ensure_primal_cache(c, *W[k])) return -2;
         // promp_inner_adapt has left exactly this pass's results behind (see there) if nothing it read has changed since and
         // the clip of log_std at log(min_std) -- the one difference between the two -- is not active
-        const bool reuse = k == 0 && !E.sub && adapt0_stands(c, inner_kind, cached);
+        const bool reuse = k == 0 && E.full && adapt0_stands(c, inner_kind, cached);
         if (reuse) {                               // (with trainable step sizes it left its gradient in ginner[0] as well)
             c->adapt_passes_skipped += 1;
             filled[k] = cached;
@@ -846,23 +855,23 @@ int enqueue_meta_on(promp_ctx* c, const EvalSet& E, float clip_eps, const float*
         q.red_mode = RED_STEP; q.cur = th; q.cur_stride = st; q.next = E.chain + (size_t)(k + 1) * MNP; q.scal = E.scal_inner + (size_t)k * M * 2;
         q.cache = cached ? 1 : 0;
         q.ginner = ag ? c->ginner + (size_t)k * MNP : nullptr;
-        if (launch_pass(c, W[k], q)) return -2;
+        if (launch_pass(c, *W[k], q)) return -2;
         filled[k] = cached;
     }
-    if (join_side(c, W[K])) return -2;
+    if (E.full && join_side(c, E.full[K])) return -2;
     {
         PassReq q;
         q.theta = E.chain + (size_t)K * MNP; q.theta_stride = NP; q.loss_kind = loss_kind_outer(outer_kind); q.clip_eps = clip_eps;
         q.fwd_only = !want_grad; q.red_mode = want_grad ? RED_OUTER : RED_SCAL; q.scal = c->scal_outer;
-        if (launch_pass(c, W[K], q)) return -2;
+        if (launch_pass(c, *W[K], q)) return -2;
     }
     if (want_grad) {
         for (int k = K - 1; k >= 0; --k) {
             const float* th = (k == 0) ? c->theta : E.chain + (size_t)k * MNP;
             const long long st = (k == 0) ? 0 : NP;
-            StepData& Sk = W[k];
-            const bool dice = inner_kind == PROMP_INNER_DICE;
-            if (dice && !Sk.has_dice) return fail(-3, "step %d has no DiCE rewards: call promp_set_dice_rewards first", k);
+            PassSlab& Sk = *W[k];
+            const bool dice = inner_kind == PROMP_INNER_DICE;     // (the step's coupling rows: compact sets are refused before)
+            if (dice && !(E.full && E.full[k].has_dice)) return fail(-3, "step %d has no DiCE rewards: call promp_set_dice_rewards first", k);
             if (ag) {
                 // lam is the complete multiplier of theta_{k+1} here, both pieces of a DiCE step included
                 PROMP_LAUNCH(k_step_size_grad, dim3((NP + 255) / 256, M), 256, 0, c->stream, c->galpha.p, (const float*)c->lam,
@@ -872,19 +881,20 @@ int enqueue_meta_on(promp_ctx* c, const EvalSet& E, float clip_eps, const float*
             PassReq q;
             q.hvp = true; q.theta = th; q.theta_stride = st; q.loss_kind = loss_kind_inner(inner_kind); q.clip_eps = clip_eps; q.clip_ls = k == 0;
             q.klw = dice ? 0.f : eta_host[k] / (float)K; q.red_mode = RED_HVP;
-            q.cache = filled[k] ? 2 : 0; q.row_tan = dice ? Sk.dice_c.p : nullptr;
+            q.cache = filled[k] ? 2 : 0; q.row_tan = dice ? E.full[k].dice_c.p : nullptr;
             if (launch_pass(c, Sk, q)) return -2;
             if (dice) {
                 // The magic box couples the time steps of a path: H v = H_loglik(w) v + grad_loglik(u(v)), u from the row tangents
                 // c_t = dlogpi_t . v of the pass above (meta_algos/dice_maml.py:245-258).  The pass ran on the direction -v, so its
                 // tangents and with them u carry the sign that makes the second piece ANOTHER "lam += g" reduction.
+                const StepData& D = E.full[k];
                 DiceScanArgs ds;
-                ds.path_row_offsets = Sk.path_row_offsets; ds.rw = Sk.dice_rw; ds.c = Sk.dice_c; ds.out = Sk.dice_u; ds.tmp = Sk.dice_tmp;
+                ds.path_row_offsets = D.path_row_offsets; ds.rw = D.dice_rw; ds.c = D.dice_c; ds.out = D.dice_u; ds.tmp = D.dice_tmp;
                 ds.mode = 1;
-                PROMP_LAUNCH(k_dice_scan, dim3(Sk.n_paths), 64, 0, c->stream, ds);
+                PROMP_LAUNCH(k_dice_scan, dim3(D.n_paths), 64, 0, c->stream, ds);
                 HIPCHECK(hipGetLastError());
                 PassReq qc;
-                qc.theta = th; qc.theta_stride = st; qc.loss_kind = LOSS_LOGLIK; qc.clip_ls = k == 0; qc.red_mode = RED_HVP; qc.adv = Sk.dice_u;
+                qc.theta = th; qc.theta_stride = st; qc.loss_kind = LOSS_LOGLIK; qc.clip_ls = k == 0; qc.red_mode = RED_HVP; qc.adv = D.dice_u;
                 if (launch_pass(c, Sk, qc)) return -2;
             }
         }
@@ -926,7 +936,7 @@ int enqueue_meta_on(promp_ctx* c, const EvalSet& E, float clip_eps, const float*
     } else if (split) PROMP_LAUNCH(k_mean_adam, dim3((NP + 1 + 255) / 256), 256, 0, c->stream, ad);
     else PROMP_LAUNCH(k_final_adam, dim3(final_blocks + 1), 256, 0, c->stream, f, ad);   // one rank: nothing in between
     HIPCHECK(hipGetLastError());
-    for (int k = 0; k <= K; ++k) W[k].dirty = true;
+    for (int k = 0; k <= K && E.full; ++k) E.full[k].dirty = true;
     return 0;
 }
 int enqueue_meta(promp_ctx* c, float clip_eps, const float* eta_host, int inner_kind, int outer_kind, bool want_grad,
@@ -957,6 +967,83 @@ int alloc_step(promp_ctx* c, StepData& S) {
     if (S.path_mom.alloc(3 * P) || S.coeffs.alloc((size_t)M * c->coeff_stride)) return -2;
     if (S.work[0].alloc((size_t)c->max_work) || S.work[1].alloc((size_t)c->max_work)) return -2;
     for (Event* ev : {&S.ev_use, &S.ev_done, &S.ev_ready}) HIPCHECK(hipEventCreateWithFlags(&ev->h, hipEventDisableTiming));
+    // what a policy pass reads of the step (the buffers stay where they are for the step's life, and travel with it in a swap)
+    PassSlab& ps = S.ps;
+    ps.obs = S.obs; ps.act = S.act; ps.adv = S.adv32; ps.old_mean = S.old_mean; ps.old_ls = S.old_ls; ps.obs_absmax = S.obs_absmax;
+    ps.task_row_offsets = S.task_row_offsets; ps.task_wg_offsets = S.task_wg_offsets[0]; ps.chain_slot_offsets = S.chain_slot_offsets;
+    ps.chain_wg_offsets = S.chain_wg_offsets; ps.work = S.work[0]; ps.chain_segs = S.chain_segs;
+    ps.cache_rows = R;
+    return 0;
+}
+
+// ---- compact slabs: copies of some of a step's paths, laid out as an upload of those paths alone would be -------------------
+// Two producers -- a step's selection (one slab; the other paths go nowhere) and its partition into minibatches (B slabs) -- and
+// one mechanism: a SlabPool, a table block (promp_plan.h: TableBlock) that one copy sends, one k_scatter_partition launch.
+// Room in `pool` for `rows` rows of every array (log_std among them if the step keeps one row per row), the block and B range rows.
+int pool_reserve(promp_ctx* c, SlabPool& pool, size_t rows, bool ls_rows, const TableBlock& blk, int B) {
+    const size_t O = c->d.obs_dim, A = c->d.act_dim, n_absmax = (size_t)B * c->d.n_tasks;
+    if (rows > pool.cap_rows || (ls_rows && !pool.ls_rows)) {
+        if (pool.obs.alloc(rows * O) || pool.act.alloc(rows * A) || pool.adv.alloc(rows) || pool.mean.alloc(rows * A)) return -2;
+        if (ls_rows && pool.ls.alloc(rows * A)) return -2;
+        if (!ls_rows) HIPCHECK(pool.ls.release());
+        pool.cap_rows = rows; pool.ls_rows = ls_rows;
+    }
+    if (blk.total > pool.cap_tables) {
+        if (pool.tables.alloc(blk.total)) return -2;
+        pool.cap_tables = blk.total;
+    }
+    if (n_absmax > pool.cap_absmax) {
+        if (pool.absmax.alloc(n_absmax)) return -2;
+        pool.cap_absmax = n_absmax;
+    }
+    return 0;
+}
+// a primal cache sized for fewer rows than the slab is about to hold goes; the next storing pass allocates one that fits
+int grow_cache_rows(PassSlab& S, size_t rows) {
+    if (rows <= S.cache_rows) return 0;
+    HIPCHECK(S.hcache.release());
+    S.cache_rows = rows;
+    return 0;
+}
+// a slab's pass tables and counts: its part `s` of a table block on the device, packed from t (pack_slab_tables)
+void bind_tables(PassSlab& S, const int* s, const TableBlock& blk, const StepTables& t) {
+    S.task_row_offsets = s + blk.tro; S.task_wg_offsets = s + blk.two; S.chain_slot_offsets = s + blk.slot;
+    S.chain_wg_offsets = s + blk.wg_off;
+    S.work = reinterpret_cast<const WorkItem*>(s + blk.work); S.chain_segs = reinterpret_cast<const ChainSeg*>(s + blk.segs);
+    S.n_rows = (int)t.row_t.size(); S.n_work = (int)t.work[0].size(); S.n_chain_wg = (int)t.wg_off.size() - 1;
+}
+// Behind the copy of step P's table block into pool.tables: the copy launch, and the B slabs as the passes enqueued next are to
+// see them -- slab j at row at[j] of the pool, with the tables of tables[j], the step's flags and version, its ranges in place.
+// timed: the launch counts in PROMP_KERNEL_SCATTER's profiling slot.
+int scatter_slabs(promp_ctx* c, StepData& P, SlabPool& pool, const TableBlock& blk, int B, const size_t* at, const StepTables* tables,
+                  PassSlab* slabs, bool timed) {
+    const int M = c->d.n_tasks;
+    const size_t O = c->d.obs_dim, A = c->d.act_dim;
+    hipStream_t st = c->stream;
+    HIPCHECK(hipMemsetAsync(pool.absmax, 0, sizeof(unsigned) * B * M, st));
+    ScatterPartitionArgs g;
+    g.obs_in = P.obs; g.act_in = P.act; g.adv_in = P.adv32; g.mean_in = P.old_mean; g.ls_in = P.ls_per_row ? P.old_ls.p : nullptr;
+    g.obs = pool.obs; g.act = pool.act; g.adv = pool.adv; g.mean = pool.mean; g.ls = pool.ls;
+    g.src_row_offsets = P.path_row_offsets; g.path_task = P.path_task;
+    g.copy = pool.tables; g.shift = pool.tables + blk.shift; g.absmax = pool.absmax;
+    g.O = (int)O; g.A = (int)A; g.n_tasks = M;
+    if (timed && prof_begin(c, PROMP_KERNEL_SCATTER, P.n_rows)) return -2;
+    PROMP_LAUNCH(k_scatter_partition, dim3(P.n_paths), 256, 0, st, g);
+    HIPCHECK(hipGetLastError());
+    if (timed && prof_end(c, PROMP_KERNEL_SCATTER)) return -2;
+    P.dirty = true;
+    c->wbp.valid = false;              // (the hidden_0 planes carry the observation scales this launch rewrites)
+    for (int j = 0; j < B; ++j) {
+        PassSlab& S = slabs[j];
+        S.obs = pool.obs + at[j] * O; S.act = pool.act + at[j] * A; S.adv = pool.adv + at[j]; S.old_mean = pool.mean + at[j] * A;
+        // (log_std of one row per task: every slab reads the step's own table)
+        S.old_ls = P.ls_per_row ? pool.ls + at[j] * A : P.old_ls.p;
+        S.obs_absmax = pool.absmax + (size_t)j * M;
+        bind_tables(S, pool.tables + blk.slab(j), blk, tables[j]);
+        S.ls_per_row = P.ls_per_row; S.has_policy = P.has_policy; S.has_adv = P.has_adv;
+        S.data_version = P.data_version;
+        S.obs_range_valid = true;      // (k_scatter_partition has left the slab's ranges)
+    }
     return 0;
 }
 
@@ -973,60 +1060,20 @@ int n_selected(const promp_ctx* c) {
     for (const Selection& L : c->sel) n += L.on ? 1 : 0;
     return n;
 }
-// The compact slab of step k's selection, current: buffers sized by the selection, its tables on the device, and copies of the
-// selected paths' rows taken at the step's present data_version (promp_process_samples / promp_set_advantages after the
+// The compact slab of step k's selection, current: a pool sized by the selection, its table block on the device, and copies of
+// the selected paths' rows taken at the step's present data_version (promp_process_samples / promp_set_advantages after the
 // selection are seen).  On the main stream, behind the step's pending side-stream / copy-stream work.
 int ensure_sub(promp_ctx* c, int k) {
     StepData& P = c->steps[k];
-    StepData& S = c->sub[k];
     Selection& L = c->sel[k];
     if (join_side(c, P)) return -2;
     if (L.gathered && L.gathered_version == P.data_version) return 0;
-    const StepTables& t = L.tables;
-    const int M = c->d.n_tasks, n = (int)L.lay.idx.size(), R = (int)t.row_t.size();
-    const size_t O = c->d.obs_dim, A = c->d.act_dim;
-    if (R > S.cap_rows) {
-        if (S.obs.alloc(R * O) || S.act.alloc(R * A) || S.adv32.alloc(R) || S.old_mean.alloc(R * A)) return -2;
-        // (log_std in either layout: one row per row of the slab, or one per task)
-        if (S.old_ls.alloc((size_t)std::max(R, M) * A) || S.hcache.release() != hipSuccess) return -2;
-        S.cap_rows = R;
-    }
-    if (n > L.cap_paths) {
-        if (L.idx.alloc(n) || S.path_row_offsets.alloc((size_t)n + 1)) return -2;
-        L.cap_paths = n;
-    }
-    if (!S.obs_absmax) {
-        if (S.obs_absmax.alloc((size_t)M) || S.task_row_offsets.alloc((size_t)M + 1) || S.task_wg_offsets[0].alloc((size_t)M + 1)) return -2;
-        if (S.chain_slot_offsets.alloc((size_t)M + 1) || S.work[0].alloc((size_t)c->max_work)) return -2;
-        if (S.chain_segs.alloc((size_t)c->max_work) || S.chain_wg_offsets.alloc((size_t)c->max_work + 1)) return -2;
-    }
-    hipStream_t st = c->stream;
-    if (!L.tables_sent) {
-        HIPCHECK(hipMemcpyAsync(L.idx, L.lay.idx.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(S.path_row_offsets, t.pro.data(), sizeof(int) * (n + 1), hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(S.task_row_offsets, t.tro.data(), sizeof(int) * (M + 1), hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(S.chain_segs, t.segs.data(), sizeof(ChainSeg) * t.segs.size(), hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(S.chain_wg_offsets, t.wg_off.data(), sizeof(int) * t.wg_off.size(), hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(S.chain_slot_offsets, t.slot_chain.data(), sizeof(int) * (M + 1), hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(S.task_wg_offsets[0], t.two[0].data(), sizeof(int) * (M + 1), hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(S.work[0], t.work[0].data(), sizeof(WorkItem) * t.work[0].size(), hipMemcpyHostToDevice, st));
-        HIPCHECK(hipStreamSynchronize(st));        // (the sources may be replaced by the next selection)
-        S.n_paths = n; S.n_rows = R; S.n_work[0] = (int)t.work[0].size(); S.n_work[1] = 0;
-        S.n_chain_wg = (int)t.wg_off.size() - 1;
-        L.tables_sent = true;
-    }
-    GatherSelectionArgs g;
-    g.obs_in = P.obs; g.act_in = P.act; g.adv_in = P.adv32; g.mean_in = P.old_mean; g.ls_in = P.ls_per_row ? P.old_ls.p : nullptr;
-    g.obs = S.obs; g.act = S.act; g.adv = S.adv32; g.mean = S.old_mean; g.ls = S.old_ls;
-    g.sel_path = L.idx; g.src_row_offsets = P.path_row_offsets; g.dst_row_offsets = S.path_row_offsets;
-    g.O = (int)O; g.A = (int)A;
-    PROMP_LAUNCH(k_gather_selection, dim3(n), 256, 0, st, g);
-    HIPCHECK(hipGetLastError());
-    if (!P.ls_per_row) HIPCHECK(hipMemcpyAsync(S.old_ls, P.old_ls, sizeof(float) * M * A, hipMemcpyDeviceToDevice, st));
-    S.ls_per_row = P.ls_per_row; S.has_policy = P.has_policy; S.has_adv = P.has_adv;
-    S.data_version = P.data_version;
-    S.obs_range_valid = false;         // (the FP16 split's scales are those of the selected rows)
-    P.dirty = true;
+    const TableBlock blk(P.n_paths, 1, c->d.n_tasks, c->max_work);
+    const size_t R = L.tables.row_t.size(), at = 0;
+    if (pool_reserve(c, L.pool, R, P.ls_per_row != 0, blk, 1) || grow_cache_rows(c->sub[k], R)) return -2;
+    HIPCHECK(hipMemcpyAsync(L.pool.tables, L.image.data(), sizeof(int) * blk.total, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(hipStreamSynchronize(c->stream));     // (the image may be replaced by the next selection)
+    if (scatter_slabs(c, P, L.pool, blk, 1, &at, &L.tables, &c->sub[k], /*timed=*/false)) return -2;
     L.gathered = true; L.gathered_version = P.data_version;
     return 0;
 }
@@ -1041,7 +1088,8 @@ int selection_set(promp_ctx* c, int inner_kind, EvalSet* E) {
         if (c->steps[k].n_rows == 0) return fail(-3, "step %d has no data", k);
     for (int k = 0; k <= K; ++k)
         if (ensure_sub(c, k)) return -2;
-    *E = EvalSet{&c->sub, c->sel_chain, c->sel_scal_inner, &c->chvp_sel, true};
+    *E = EvalSet{{}, nullptr, c->sel_chain, c->sel_scal_inner, &c->chvp_sel};
+    for (int k = 0; k <= K; ++k) E->slab[k] = &c->sub[k];
     return 0;
 }
 
@@ -1062,49 +1110,28 @@ std::vector<size_t> mb_places(const PartitionLayout& part) {
     return at;
 }
 // Everything promp_optimize_minibatch_begin allocates, before its first enqueue: the pools and table blocks of every step sized
-// for the largest epoch, the B x (K + 1) slab records, the primal caches of the slabs the gradient passes store into, the
-// evaluation set's own chain and scalars, the page-locked staging of all table copies.
+// for the largest epoch, the (K + 1) x B slabs, the primal caches of the slabs the gradient passes store into, the evaluation
+// set's own chain and scalars, the page-locked staging of all table copies.
 int mb_reserve(promp_ctx* c, int E, int B, const std::vector<PartitionLayout>& parts, size_t* stage_ints) {
     const int K = c->d.num_inner_steps, M = c->d.n_tasks;
-    const size_t O = c->d.obs_dim, A = c->d.act_dim, MNP = (size_t)M * c->NP;
+    const size_t MNP = (size_t)M * c->NP;
     if (c->mb_pool.empty()) {
         if (c->mb_chain.alloc((size_t)(K + 1) * MNP) || c->mb_scal_inner.alloc((size_t)K * M * 2)) return -2;
         c->mb_pool.resize(K + 1);
-    }
-    while ((int)c->mb.size() < B) {
-        c->mb.emplace_back();
-        c->mb.back().resize(K + 1);
+        c->mb.resize(K + 1);
     }
     *stage_ints = 0;
     for (int k = 0; k <= K; ++k) {
         const StepData& P = c->steps[k];
-        MbPool& pool = c->mb_pool[k];
-        const size_t rows = (size_t)P.n_rows + 80 * (size_t)B;
-        const bool ls_rows = P.ls_per_row != 0;
-        if (rows > pool.cap_rows || (ls_rows && !pool.ls_rows)) {
-            if (pool.obs.alloc(rows * O) || pool.act.alloc(rows * A) || pool.adv.alloc(rows) || pool.mean.alloc(rows * A)) return -2;
-            if (ls_rows && pool.ls.alloc(rows * A)) return -2;
-            if (!ls_rows) HIPCHECK(pool.ls.release());
-            pool.cap_rows = rows; pool.ls_rows = ls_rows;
-        }
-        const MbBlock blk(P.n_paths, B, M, c->max_work);
-        if (blk.total > pool.cap_tables) {
-            if (pool.tables.alloc(blk.total)) return -2;
-            pool.cap_tables = blk.total;
-        }
-        if ((size_t)B * M > pool.cap_absmax) {
-            if (pool.absmax.alloc((size_t)B * M)) return -2;
-            pool.cap_absmax = (size_t)B * M;
-        }
+        const TableBlock blk(P.n_paths, B, M, c->max_work);
+        if (pool_reserve(c, c->mb_pool[k], (size_t)P.n_rows + 80 * (size_t)B, P.ls_per_row != 0, blk, B)) return -2;
         *stage_ints += (size_t)E * blk.total;
+        if ((int)c->mb[k].size() < B) c->mb[k].resize(B);
         for (int j = 0; j < B; ++j) {
-            StepData& S = c->mb[j][k];
-            int most = 0;
-            for (int e = 0; e < E; ++e) most = std::max(most, (int)parts[(size_t)e * (K + 1) + k].tables[j].row_t.size());
-            if (most > S.cap_rows) {
-                HIPCHECK(S.hcache.release());
-                S.cap_rows = most;
-            }
+            PassSlab& S = c->mb[k][j];
+            size_t most = 0;
+            for (int e = 0; e < E; ++e) most = std::max(most, parts[(size_t)e * (K + 1) + k].tables[j].row_t.size());
+            if (grow_cache_rows(S, most)) return -2;
             if (k < K && primal_cache_on(c) && ensure_primal_cache(c, S)) return -2;
         }
     }
@@ -1112,62 +1139,18 @@ int mb_reserve(promp_ctx* c, int E, int B, const std::vector<PartitionLayout>& p
     return 0;
 }
 // One (epoch, step): the table block's image in `stage` (page-locked, untouched until the optimisation is collected), its copy,
-// the copy launch, and the B slab records as the passes enqueued next are to see them.
+// the copy launch and the B slabs bound to what it fills.
 int mb_enqueue_step(promp_ctx* c, int k, int B, const PartitionLayout& part, int* stage) {
-    const int M = c->d.n_tasks;
-    const size_t O = c->d.obs_dim, A = c->d.act_dim;
     StepData& P = c->steps[k];
-    MbPool& pool = c->mb_pool[k];
-    const MbBlock blk(P.n_paths, B, M, c->max_work);
+    SlabPool& pool = c->mb_pool[k];
+    const TableBlock blk(P.n_paths, B, c->d.n_tasks, c->max_work);
     const std::vector<size_t> at = mb_places(part);
-    memset(stage, 0, sizeof(int) * blk.total);
-    memcpy(stage, part.copy.data(), sizeof(int) * part.copy.size());
-    for (int j = 0; j < B; ++j) {
-        const StepTables& t = part.tables[j];
-        stage[blk.shift + j] = (int)at[j] - part.row_base[j];
-        int* s = stage + blk.slab0 + (size_t)j * blk.slab_stride;
-        memcpy(s + blk.tro, t.tro.data(), sizeof(int) * (M + 1));
-        memcpy(s + blk.two, t.two[0].data(), sizeof(int) * (M + 1));
-        memcpy(s + blk.slot, t.slot_chain.data(), sizeof(int) * (M + 1));
-        memcpy(s + blk.wg_off, t.wg_off.data(), sizeof(int) * t.wg_off.size());
-        memcpy(s + blk.work, t.work[0].data(), sizeof(WorkItem) * t.work[0].size());
-        memcpy(s + blk.segs, t.segs.data(), sizeof(ChainSeg) * t.segs.size());
-    }
-    hipStream_t st = c->stream;
+    std::vector<int> shifts(B);
+    for (int j = 0; j < B; ++j) shifts[j] = (int)at[j] - part.row_base[j];
+    pack_table_block(blk, part.copy, shifts, part.tables.data(), stage);
     if (join_side(c, P)) return -2;
-    HIPCHECK(hipMemcpyAsync(pool.tables, stage, sizeof(int) * blk.total, hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemsetAsync(pool.absmax, 0, sizeof(unsigned) * B * M, st));
-    ScatterPartitionArgs g;
-    g.obs_in = P.obs; g.act_in = P.act; g.adv_in = P.adv32; g.mean_in = P.old_mean; g.ls_in = P.ls_per_row ? P.old_ls.p : nullptr;
-    g.obs = pool.obs; g.act = pool.act; g.adv = pool.adv; g.mean = pool.mean; g.ls = pool.ls;
-    g.src_row_offsets = P.path_row_offsets; g.path_task = P.path_task;
-    g.copy = pool.tables; g.shift = pool.tables + blk.shift; g.absmax = pool.absmax;
-    g.O = (int)O; g.A = (int)A; g.n_tasks = M;
-    if (prof_begin(c, PROMP_KERNEL_SCATTER, P.n_rows)) return -2;
-    PROMP_LAUNCH(k_scatter_partition, dim3(P.n_paths), 256, 0, st, g);
-    HIPCHECK(hipGetLastError());
-    if (prof_end(c, PROMP_KERNEL_SCATTER)) return -2;
-    P.dirty = true;
-    c->wbp.valid = false;              // (the hidden_0 planes carry the observation scales this launch rewrites)
-    for (int j = 0; j < B; ++j) {
-        StepData& S = c->mb[j][k];
-        const StepTables& t = part.tables[j];
-        int* s = pool.tables + blk.slab0 + (size_t)j * blk.slab_stride;
-        S.obs.borrow(pool.obs + at[j] * O); S.act.borrow(pool.act + at[j] * A); S.adv32.borrow(pool.adv + at[j]);
-        S.old_mean.borrow(pool.mean + at[j] * A);
-        // (log_std of one row per task: every minibatch reads the step's own table)
-        S.old_ls.borrow(P.ls_per_row ? pool.ls + at[j] * A : P.old_ls.p);
-        S.obs_absmax.borrow(pool.absmax + (size_t)j * M);
-        S.task_row_offsets.borrow(s + blk.tro); S.task_wg_offsets[0].borrow(s + blk.two); S.chain_slot_offsets.borrow(s + blk.slot);
-        S.chain_wg_offsets.borrow(s + blk.wg_off);
-        S.work[0].borrow(reinterpret_cast<WorkItem*>(s + blk.work)); S.chain_segs.borrow(reinterpret_cast<ChainSeg*>(s + blk.segs));
-        S.n_paths = (int)part.lay[j].idx.size(); S.n_rows = (int)t.row_t.size();
-        S.n_work[0] = (int)t.work[0].size(); S.n_work[1] = 0; S.n_chain_wg = (int)t.wg_off.size() - 1;
-        S.ls_per_row = P.ls_per_row; S.has_policy = P.has_policy; S.has_adv = P.has_adv;
-        S.data_version = P.data_version;
-        S.obs_range_valid = true;      // (k_scatter_partition has left the slab's ranges)
-    }
-    return 0;
+    HIPCHECK(hipMemcpyAsync(pool.tables, stage, sizeof(int) * blk.total, hipMemcpyHostToDevice, c->stream));
+    return scatter_slabs(c, P, pool, blk, B, at.data(), part.tables.data(), c->mb[k].data(), /*timed=*/true);
 }
 
 }  // namespace
@@ -1380,7 +1363,7 @@ int promp_sync(promp_ctx* c) {
 static int set_step_layout(promp_ctx* c, StepData& S, hipStream_t st, bool async, int n_paths, const int32_t* tpo, const int32_t* pro) {
     if (!tpo || !pro) return fail(-1, "offsets are required");
     const int M = c->d.n_tasks;
-    S.obs_range_valid = false;         // (whoever describes a slab anew is about to fill it)
+    S.ps.obs_range_valid = false;         // (whoever describes a slab anew is about to fill it)
     // Same offsets as the batch this set held before (fixed-horizon environments: every batch): the time indices and the
     // work tables on the device are already the right ones -- nothing to rebuild on the host (0.3 ms at 160 000 rows), no
     // table copies to enqueue.  (A set is only ever re-described after its previous table copies have completed.)
@@ -1426,7 +1409,7 @@ static int copy_step_data(promp_ctx* c, StepData& S, hipStream_t st, const float
     const size_t R = (size_t)S.n_rows;
     const size_t O = c->d.obs_dim, A = c->d.act_dim;
     HIPCHECK(hipMemcpyAsync(S.obs, obs, sizeof(float) * R * O, hipMemcpyHostToDevice, st));
-    if (enqueue_obs_range(c, S, st)) return -2;
+    if (enqueue_obs_range(c, pass_slab(S), st)) return -2;
     HIPCHECK(hipMemcpyAsync(S.rew, rew, sizeof(float) * R, hipMemcpyHostToDevice, st));
     S.has_policy = act && old_mean && old_ls;
     if (S.has_policy) {
@@ -1751,6 +1734,10 @@ int promp_set_step_selection(promp_ctx* c, int step, int n_sel, const int32_t* p
     if (const int rc = build_selection(M, P.n_paths, P.lay_tpo.data(), P.lay_pro.data(), n_sel, path_idx, &lay, &why)) return fail_plan(rc, why);
     if (const int rc = build_step_tables(c->n_cus, c->max_work, lay.pro[n_sel], n_sel, M, n_sel, lay.tpo.data(), lay.pro.data(), &tables, &why))
         return fail_plan(rc, why);
+    // the table block of the one copy launch that fills the compact slab: the selection as a partition with B = 1
+    const TableBlock blk(P.n_paths, 1, M, c->max_work);
+    std::vector<int> image(blk.total);
+    pack_table_block(blk, selection_copy_table(P.n_paths, lay), {0}, &tables, image.data());
     if (c->sel.empty()) {
         const size_t MNP = (size_t)M * c->NP;
         if (c->sel_chain.alloc((size_t)(K + 1) * MNP) || c->sel_scal_inner.alloc((size_t)K * M * 2)) return -2;
@@ -1758,8 +1745,8 @@ int promp_set_step_selection(promp_ctx* c, int step, int n_sel, const int32_t* p
         c->sel.resize(K + 1);
     }
     Selection& L = c->sel[step];
-    L.on = true; L.lay = std::move(lay); L.tables = std::move(tables);
-    L.tables_sent = false; L.gathered = false;
+    L.on = true; L.lay = std::move(lay); L.tables = std::move(tables); L.image = std::move(image);
+    L.gathered = false;
     c->chvp_sel.valid = false;             // (its caches hold another selection's rows)
     ++c->version_counter;
     return 0;
@@ -1997,7 +1984,7 @@ int promp_inner_adapt(promp_ctx* c, int step, int inner_kind) {
     q.theta = cur; q.theta_stride = st; q.loss_kind = loss_kind_inner(inner_kind);
     q.red_mode = RED_STEP; q.cur = cur; q.cur_stride = st; q.next = c->theta_tasks;
     const bool cached = leave && primal_cache_on(c);
-    if (cached && ensure_primal_cache(c, S)) return -2;
+    if (cached && ensure_primal_cache(c, pass_slab(S))) return -2;
     q.cache = cached ? 1 : 0;
     if (leave) {
         q.next2 = c->chain + (size_t)c->d.n_tasks * c->NP;
@@ -2005,7 +1992,7 @@ int promp_inner_adapt(promp_ctx* c, int step, int inner_kind) {
         q.ginner = c->train_sizes ? c->ginner.p : nullptr;     // ... and the gradient itself, the step sizes' first factor
     }
     c->tasks_shared = false;
-    const int rc = launch_pass(c, S, q);
+    const int rc = launch_pass(c, pass_slab(S), q);
     if (rc) return rc;
     if (leave) {
         c->adapt0.valid = true; c->adapt0.theta_version = c->theta_version; c->adapt0.data_version = S.data_version;
@@ -2102,7 +2089,7 @@ int promp_rollout_point_env(promp_ctx* c, int step, int envs_per_task, int path_
     } else
     PROMP_LAUNCH(k_point_rollout, dim3(M), 64, 0, st, a);
     HIPCHECK(hipGetLastError());
-    S.obs_range_valid = false;
+    S.ps.obs_range_valid = false;
     return 0;
 }
 
@@ -2164,7 +2151,7 @@ int promp_end_collection(promp_ctx* c, int step, int n_paths, const int32_t* tas
     HIPCHECK(hipStreamSynchronize(c->stream));
     S.has_policy = true; S.ls_per_row = 0; S.has_rew64 = false; S.processed = false; S.has_adv = false;
     S.rollout_ragged = false; S.rollout_B = 0;
-    S.obs_range_valid = false;
+    S.ps.obs_range_valid = false;
     return 0;
 }
 
@@ -2205,7 +2192,7 @@ int promp_policy_step(promp_ctx* c, int step, int t, const float* obs, uint64_t 
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipMemcpyAsync(actions_out, d_act, sizeof(float) * n_act, hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
-    S.obs_range_valid = false;
+    S.ps.obs_range_valid = false;
     return 0;
 }
 
@@ -2276,7 +2263,7 @@ int promp_meta_grad(promp_ctx* c, float clip_eps, const float* eta, int inner_ki
 // product: at the parameters the samples were drawn with (old distribution == adapted policy).  2K + 1 R-operator passes.
 // (the direction is in c->grad_mean, the sums over the tasks -- all-reduced -- are left in c->red)
 static int enqueue_constraint_hvp(promp_ctx* c, const EvalSet& E, int inner_kind, int refresh_chain) {
-    std::vector<StepData>& W = *E.steps;
+    PassSlab* const* W = E.slab;
     ChvpRec& R = *E.chvp;
     if (sharded_without_comm(c))
         return fail(-3, "this context holds %d of %d tasks and has no communicator: the product would be this rank's share only "
@@ -2284,8 +2271,8 @@ static int enqueue_constraint_hvp(promp_ctx* c, const EvalSet& E, int inner_kind
     const int K = c->d.num_inner_steps, M = c->d.n_tasks, NP = c->NP;
     const size_t MNP = (size_t)M * NP;
     for (int k = 0; k <= K; ++k) {
-        if (W[k].n_rows == 0) return fail(-3, "step %d has no data", k);
-        if (join_side(c, W[k])) return -2;
+        if (W[k]->n_rows == 0) return fail(-3, "step %d has no data", k);
+        if (E.full && join_side(c, E.full[k])) return -2;
     }
     if (!c->wbuf && c->wbuf.alloc(MNP)) return -2;
     auto theta_of = [&](int k, long long* stride) -> const float* {
@@ -2302,10 +2289,10 @@ static int enqueue_constraint_hvp(promp_ctx* c, const EvalSet& E, int inner_kind
     if (refresh_chain) {
         R.valid = false;
         for (int k = 0; k <= K && use_cache; ++k)
-            if (ensure_primal_cache(c, W[k])) return -2;
+            if (ensure_primal_cache(c, *W[k])) return -2;
         for (int k = 0; k < K; ++k) {
             const float* th = theta_of(k, &st);
-            if (k == 0 && !E.sub && adapt0_stands(c, inner_kind, use_cache)) {       // promp_inner_adapt has just run exactly this pass
+            if (k == 0 && E.full && adapt0_stands(c, inner_kind, use_cache)) {       // promp_inner_adapt has just run exactly this pass
                 c->adapt_passes_skipped += 1;
                 continue;
             }
@@ -2313,24 +2300,24 @@ static int enqueue_constraint_hvp(promp_ctx* c, const EvalSet& E, int inner_kind
             q.theta = th; q.theta_stride = st; q.loss_kind = lk; q.clip_ls = k == 0;
             q.red_mode = RED_STEP; q.cur = th; q.cur_stride = st; q.next = E.chain + (size_t)(k + 1) * MNP; q.scal = E.scal_inner + (size_t)k * M * 2;
             q.cache = use_cache ? 1 : 0;
-            if (launch_pass(c, W[k], q)) return -2;
+            if (launch_pass(c, *W[k], q)) return -2;
         }
         if (use_cache) {
             PassReq q;
             q.theta = theta_of(K, &q.theta_stride); q.loss_kind = LOSS_KL; q.clip_ls = K == 0; q.cache = 1;
-            if (launch_pass(c, W[K], q)) return -2;
+            if (launch_pass(c, *W[K], q)) return -2;
             R.valid = true; R.theta_version = c->theta_version; R.sizes_version = c->sizes_version;
             R.inner_kind = inner_kind; R.min_log_std = c->min_log_std;
             for (int k = 0; k <= K; ++k) {
-                R.data_version[k] = W[k].data_version;
-                R.tag[k] = W[k].cache_tag;
+                R.data_version[k] = W[k]->data_version;
+                R.tag[k] = W[k]->cache_tag;
             }
         }
     }
     const bool rec_ok = use_cache && R.valid && R.theta_version == c->theta_version && R.sizes_version == c->sizes_version &&
                         R.inner_kind == inner_kind && R.min_log_std == c->min_log_std;
     auto cache_ok = [&](int k) {
-        return rec_ok && W[k].hcache && R.data_version[k] == W[k].data_version && R.tag[k] == W[k].cache_tag;
+        return rec_ok && W[k]->hcache && R.data_version[k] == W[k]->data_version && R.tag[k] == W[k]->cache_tag;
     };
     PROMP_LAUNCH(k_replicate, dim3((NP + 255) / 256), 256, 0, c->stream, c->vbuf, c->grad_mean, NP, M);
     const dim3 eg((NP + 255) / 256, M);
@@ -2339,7 +2326,7 @@ static int enqueue_constraint_hvp(promp_ctx* c, const EvalSet& E, int inner_kind
         q.hvp = true; q.theta = theta_of(k, &q.theta_stride); q.loss_kind = kind; q.clip_ls = k == 0;
         q.cache = cache_ok(k) ? 2 : 0;
         c->chvp_cached_passes += q.cache ? 1 : 0;
-        return launch_pass(c, W[k], q);
+        return launch_pass(c, *W[k], q);
     };
     for (int k = 0; k < K; ++k) {                      // u = J_{K-1} ... J_0 v
         if (pass(k, lk)) return -2;
@@ -2359,7 +2346,7 @@ static int enqueue_constraint_hvp(promp_ctx* c, const EvalSet& E, int inner_kind
     PROMP_LAUNCH(k_reduce_final, dim3((NP + K + 2 + 63) / 64), 256, 0, c->stream, f);
     HIPCHECK(hipGetLastError());
     if (exchange_sums(c, c->red, (size_t)NP)) return -4;
-    for (int k = 0; k <= K; ++k) W[k].dirty = true;
+    for (int k = 0; k <= K && E.full; ++k) E.full[k].dirty = true;
     return 0;
 }
 
@@ -2608,10 +2595,11 @@ int promp_optimize_minibatch_begin(promp_ctx* c, int num_epochs, int num_minibat
     for (int e = 0; e < E; ++e) {
         for (int k = 0; k <= K; ++k) {
             if (mb_enqueue_step(c, k, B, parts[(size_t)e * (K + 1) + k], stage)) return -2;
-            stage += MbBlock(c->steps[k].n_paths, B, M, c->max_work).total;
+            stage += TableBlock(c->steps[k].n_paths, B, M, c->max_work).total;
         }
         for (int j = 0; j < B; ++j) {
-            const EvalSet S{&c->mb[j], c->mb_chain, c->mb_scal_inner, &c->chvp_mb, true};
+            EvalSet S{{}, nullptr, c->mb_chain, c->mb_scal_inner, &c->chvp_mb};
+            for (int k = 0; k <= K; ++k) S.slab[k] = &c->mb[k][j];
             if (enqueue_meta_on(c, S, clip_eps, eta, inner_kind, outer_kind, true, true, lr, true)) return -2;
         }
     }
@@ -2644,7 +2632,7 @@ int promp_eval_loss_grad(promp_ctx* c, int step, int kind, float clip_eps, int c
     if (tasks_materialize(c)) return -2;
     PassReq q;
     q.theta = c->theta_tasks; q.theta_stride = c->NP; q.loss_kind = kind; q.clip_eps = clip_eps; q.clip_ls = clip_ls;
-    if (launch_pass(c, S, q)) return -2;
+    if (launch_pass(c, pass_slab(S), q)) return -2;
     if (grads_out && params_out(c, grads_out, c->lam, (size_t)M)) return -2;
     std::vector<float> scal((size_t)M * 2);
     if (copy_out(c, scal.data(), c->scal_tmp, scal.size())) return -2;
@@ -2666,7 +2654,7 @@ int promp_eval_hvp(promp_ctx* c, int step, int inner_kind, int clip_ls, float kl
     if (tasks_materialize(c)) return -2;
     PassReq q;
     q.hvp = true; q.theta = c->theta_tasks; q.theta_stride = NP; q.loss_kind = loss_kind_inner(inner_kind); q.clip_ls = clip_ls; q.klw = klw;
-    if (launch_pass(c, S, q)) return -2;
+    if (launch_pass(c, pass_slab(S), q)) return -2;
     return params_out(c, out, c->lam, (size_t)M);
 }
 
@@ -2787,16 +2775,16 @@ int promp_debug_phase_stamps(promp_ctx* c, int step, int hvp, unsigned long long
     q.theta = c->theta_tasks; q.theta_stride = c->NP; q.clip_eps = 0.3f;
     if (hvp == 2) {               // the cache-reading R-operator pass: fill the step's primal cache first (unstamped)
         if (c->family != PassFamily::Chain) return fail(-1, "no primal cache for this shape");
-        if (ensure_primal_cache(c, S)) return -2;
+        if (ensure_primal_cache(c, pass_slab(S))) return -2;
         q.cache = 1;
-        const int rc0 = launch_pass(c, S, q);
+        const int rc0 = launch_pass(c, pass_slab(S), q);
         if (rc0) return rc0;
     }
     HIPCHECK(hipMemsetAsync(c->dbg, 0, sizeof(unsigned long long) * (256 + 4 * 1024), c->stream));
     c->dbg_enabled = true;
     q.hvp = hvp != 0;
     q.cache = hvp == 2 ? 2 : 0;
-    const int rc = launch_pass(c, S, q);
+    const int rc = launch_pass(c, pass_slab(S), q);
     c->dbg_enabled = false;
     if (rc) return rc;
     HIPCHECK(hipMemcpyAsync(out, c->dbg, sizeof(unsigned long long) * (256 + 4 * 1024), hipMemcpyDeviceToHost, c->stream));

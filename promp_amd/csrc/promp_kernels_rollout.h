@@ -143,43 +143,18 @@ __global__ void __launch_bounds__(256) k_gather_paths(GatherPathsArgs a) {
     }
 }
 
-// A selection of a step's paths (promp_set_step_selection) copied into its compact slab, in path order: everything a policy pass
-// reads of a row.  Selected path p = paths[sel_path[p]] of the step; its rows go to [dst_row_offsets[p], dst_row_offsets[p + 1]).
-struct GatherSelectionArgs {
-    const float *obs_in, *act_in, *adv_in, *mean_in, *ls_in;   // the step's slabs (ls_in: NULL when log_std is one row per task)
-    float *obs, *act, *adv, *mean, *ls;                         // the compact slab
-    const int *sel_path, *src_row_offsets, *dst_row_offsets;
-    int O, A;
-};
-// grid = selected paths, block = 256
-__global__ void __launch_bounds__(256) k_gather_selection(GatherSelectionArgs a) {
-    const int p = blockIdx.x, s0 = a.src_row_offsets[a.sel_path[p]], r0 = a.dst_row_offsets[p], n = a.dst_row_offsets[p + 1] - r0;
-    const int W = a.O + 1 + (a.ls_in ? 3 : 2) * a.A;
-    for (int e = threadIdx.x; e < n * W; e += 256) {
-        const int t = e / W;
-        int k = e - t * W;
-        const long long src = s0 + t, dst = r0 + t;
-        if (k < a.O) { a.obs[dst * a.O + k] = a.obs_in[src * a.O + k]; continue; }
-        k -= a.O;
-        if (k == 0) { a.adv[dst] = a.adv_in[src]; continue; }
-        k -= 1;
-        if (k < a.A) a.act[dst * a.A + k] = a.act_in[src * a.A + k];
-        else if (k < 2 * a.A) a.mean[dst * a.A + (k - a.A)] = a.mean_in[src * a.A + (k - a.A)];
-        else a.ls[dst * a.A + (k - 2 * a.A)] = a.ls_in[src * a.A + (k - 2 * a.A)];
-    }
-}
-
-// A step's paths dealt to the B compact slabs of its minibatches (promp_optimize_minibatch; build_partition, promp_plan.h) in ONE
-// launch: source path p goes to minibatch copy[2p], rows [copy[2p + 1] + shift[minibatch], ...) of the pooled slabs -- everything
-// a policy pass reads of a row.  The walk over the observations also leaves, per (minibatch, task), the bits of the largest
-// |observation| that k_obs_range would find on that compact slab (promp_kernels_pass.h; a maximum of bit patterns does not depend
-// on the order it is taken in): one atomic per wave, into a table zeroed in front of the launch.
+// Some or all of a step's paths copied into B compact slabs in ONE launch -- the slabs of its minibatches (promp_optimize_minibatch;
+// build_partition, promp_plan.h), or the one slab of its selection (promp_set_step_selection; selection_copy_table): source path p
+// goes to slab copy[2p], rows [copy[2p + 1] + shift[slab], ...) of the pooled slabs -- everything a policy pass reads of a row --,
+// or nowhere if copy[2p] < 0.  The walk over the observations also leaves, per (slab, task), the bits of the largest |observation|
+// that k_obs_range would find on that compact slab (promp_kernels_pass.h; a maximum of bit patterns does not depend on the order
+// it is taken in): one atomic per wave, into a table zeroed in front of the launch.
 struct ScatterPartitionArgs {
     const float *obs_in, *act_in, *adv_in, *mean_in, *ls_in;   // the step's slabs (ls_in: NULL when log_std is one row per task)
     float *obs, *act, *adv, *mean, *ls;                         // the pooled slabs
     const int *src_row_offsets, *path_task;                     // the step's [paths + 1] / [paths]
-    const int *copy, *shift;                                    // [paths][2] / [minibatches]: rows between a slab's place and its offset
-    unsigned* absmax;                                           // [minibatches][tasks]
+    const int *copy, *shift;                                    // [paths][2] / [slabs]: rows between a slab's place and its offset
+    unsigned* absmax;                                           // [slabs][tasks]
     int O, A, n_tasks;
 };
 // n consecutive floats: consecutive lanes on consecutive addresses, four loads in flight per lane
@@ -194,6 +169,7 @@ PROMP_DEV void scatter_span(float* dst, const float* src, long long n, int tid) 
 // grid = the step's paths, block = 256
 __global__ void __launch_bounds__(256) k_scatter_partition(ScatterPartitionArgs a) {
     const int p = blockIdx.x, tid = threadIdx.x, mb = a.copy[2 * p];
+    if (mb < 0) return;
     const long long s0 = a.src_row_offsets[p], n = a.src_row_offsets[p + 1] - s0, r0 = (long long)a.copy[2 * p + 1] + a.shift[mb];
     {
         const float* src = a.obs_in + s0 * a.O;

@@ -5,6 +5,8 @@
 //   Stage A      which Gram and fit kernels promp_process_samples launches for a baseline kind and an observation width
 //   step tables  the work tables, the chain kernels' segment table, the time indices and the task row offsets of a sampling step
 //   selections   which paths of a step a subsampled constraint product keeps, and the layout of the compact slab that holds them
+//   partitions   a step's paths dealt to the compact slabs of its minibatches
+//   table blocks the one block of ints that holds a copy launch's table and the pass tables of the compact slabs it fills
 //   switches     the PROMP_* environment switches the above depend on, read once
 //
 // HIP-free: the C ABI header and the standard library only, so plain `g++ -std=c++17` compiles it alone and
@@ -563,6 +565,17 @@ inline int build_selection(int M, int n_paths, const int32_t* tpo, const int32_t
     *out = std::move(L);
     return 0;
 }
+// A selection as the table of the copy launch (k_scatter_partition): [n_paths][2], selected path q to slab 0 at the row lay.pro[q]
+// of its compact slab, every other path to slab -1: nowhere.  The partition into one minibatch in which some paths are dropped.
+inline std::vector<int> selection_copy_table(int n_paths, const SelectionLayout& lay) {
+    std::vector<int> copy(2 * (size_t)n_paths, 0);
+    for (int p = 0; p < n_paths; ++p) copy[2 * (size_t)p] = -1;
+    for (size_t q = 0; q < lay.idx.size(); ++q) {
+        copy[2 * (size_t)lay.idx[q]] = 0;
+        copy[2 * (size_t)lay.idx[q] + 1] = lay.pro[q];
+    }
+    return copy;
+}
 
 // ---- partitions (promp_optimize_minibatch) -----------------------------------------------------------------------------------
 // A step's paths dealt to B minibatches: per minibatch the selection of its paths and the tables of the compact slab that holds
@@ -613,4 +626,43 @@ inline int build_partition(int n_cus, int max_work, int M, int n_paths, const in
     }
     *out = std::move(L);
     return 0;
+}
+
+// ---- table blocks ------------------------------------------------------------------------------------------------------------
+// Everything one copy launch and the passes on the B compact slabs it fills read of the layout, in ONE block of ints that a single
+// copy sends: the copy table [paths][2] at 0, the slabs' shifts [B] (rows between a slab's place in its pool and its offset in the
+// copy table), then per slab its pass tables tro | two | slot | wg_off | work | segs.  Every piece starts on a multiple of 64
+// ints.  A selection's block is the same shape with B = 1.
+struct TableBlock {
+    size_t shift = 0, slab0 = 0, slab_stride = 0, total = 0;
+    size_t tro = 0, two = 0, slot = 0, wg_off = 0, work = 0, segs = 0;      // inside a slab's part
+    static size_t r64(size_t n) { return (n + 63) & ~(size_t)63; }
+    TableBlock(int n_paths, int B, int M, int max_work) {
+        static_assert(sizeof(WorkItem) == 4 * sizeof(int) && sizeof(ChainSeg) == 4 * sizeof(int), "tables are packed as ints");
+        shift = r64(2 * (size_t)n_paths);
+        slab0 = shift + r64(B);
+        two = r64(M + 1); slot = 2 * r64(M + 1); wg_off = 3 * r64(M + 1);
+        work = wg_off + r64((size_t)max_work + 1);
+        segs = work + r64(4 * (size_t)max_work);
+        slab_stride = segs + r64(4 * (size_t)max_work);
+        total = slab0 + (size_t)B * slab_stride;
+    }
+    size_t slab(int j) const { return slab0 + (size_t)j * slab_stride; }
+};
+// one slab's pass tables into its part s [blk.slab_stride] of a block's image (t built for at most the block's max_work and M)
+inline void pack_slab_tables(const TableBlock& blk, const StepTables& t, int* s) {
+    memcpy(s + blk.tro, t.tro.data(), sizeof(int) * t.tro.size());
+    memcpy(s + blk.two, t.two[0].data(), sizeof(int) * t.two[0].size());
+    memcpy(s + blk.slot, t.slot_chain.data(), sizeof(int) * t.slot_chain.size());
+    memcpy(s + blk.wg_off, t.wg_off.data(), sizeof(int) * t.wg_off.size());
+    memcpy(s + blk.work, t.work[0].data(), sizeof(WorkItem) * t.work[0].size());
+    memcpy(s + blk.segs, t.segs.data(), sizeof(ChainSeg) * t.segs.size());
+}
+// the block's image in dst [blk.total]: copy [paths][2], shifts [B], the pass tables of tables [B]
+inline void pack_table_block(const TableBlock& blk, const std::vector<int>& copy, const std::vector<int>& shifts,
+                             const StepTables* tables, int* dst) {
+    memset(dst, 0, sizeof(int) * blk.total);
+    memcpy(dst, copy.data(), sizeof(int) * copy.size());
+    memcpy(dst + blk.shift, shifts.data(), sizeof(int) * shifts.size());
+    for (size_t j = 0; j < shifts.size(); ++j) pack_slab_tables(blk, tables[j], dst + blk.slab((int)j));
 }

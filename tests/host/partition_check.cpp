@@ -7,6 +7,7 @@
 //   layout       for ragged offsets and several assignments: every minibatch's selection and tables are what build_selection +
 //                build_step_tables give for the same index set; the copy table sends every path behind its predecessors of the
 //                same minibatch and task, and the destination rows tile [0, R) without gap or overlap
+//   table block  pieces on multiples of 64 ints, `total` their sum, and the image reads back as the tables it was packed from
 //   refusals     B < 1, an entry outside [0, B), a (minibatch, task) left without a path, B above a task's path count: each with
 //                its message, and nothing written (under the sanitizer: without a stray access either)
 #include "../../promp_amd/csrc/promp_plan.h"
@@ -42,6 +43,44 @@ static bool same_segs(const std::vector<ChainSeg>& a, const std::vector<ChainSeg
     for (size_t i = 0; i < a.size(); ++i)
         if (a[i].task != b[i].task || a[i].tile0 != b[i].tile0 || a[i].ntiles != b[i].ntiles) return false;
     return true;
+}
+
+// The table block of a partition: pieces on multiples of 64 ints, one behind the other without overlap, `total` their sum; and
+// every table read back from the image at the layout's offsets is the StepTables it was packed from.
+static void check_block(const PartitionLayout& part, int B, int max_work) {
+    const TableBlock blk(NP, B, M, max_work);
+    auto r64 = [](size_t n) { return (n + 63) / 64 * 64; };
+    // copy table | shifts | B x (tro | two | slot | wg_off | work | segs), each piece rounded up to 64 ints
+    const size_t slab_pieces[6] = {(size_t)M + 1, (size_t)M + 1, (size_t)M + 1, (size_t)max_work + 1, 4 * (size_t)max_work, 4 * (size_t)max_work};
+    const size_t slab_at[6] = {blk.tro, blk.two, blk.slot, blk.wg_off, blk.work, blk.segs};
+    size_t at = 0;
+    for (int i = 0; i < 6; ++i) {
+        EXPECT(slab_at[i] == at && slab_at[i] % 64 == 0, "piece %d of a slab's part starts at %zu, expected %zu", i, slab_at[i], at);
+        at += r64(slab_pieces[i]);
+    }
+    EXPECT(blk.slab_stride == at, "a slab's part holds %zu ints, its pieces %zu", blk.slab_stride, at);
+    EXPECT(blk.shift == r64(2 * NP) && blk.slab0 == blk.shift + r64(B), "copy table and shifts in front of the slabs");
+    EXPECT(blk.total == r64(2 * NP) + r64(B) + B * at, "total %zu, the pieces sum to %zu", blk.total, r64(2 * NP) + r64(B) + B * at);
+    for (int j = 0; j < B; ++j) EXPECT(blk.slab(j) % 64 == 0 && blk.slab(j) == blk.slab0 + j * blk.slab_stride, "slab %d at %zu", j, blk.slab(j));
+    std::vector<int> shifts(B), image(blk.total + 1, -1);
+    for (int j = 0; j < B; ++j) shifts[j] = 1000 + 64 * j;
+    pack_table_block(blk, part.copy, shifts, part.tables.data(), image.data());
+    EXPECT(image[blk.total] == -1, "the image was written past its end");
+    EXPECT(std::equal(part.copy.begin(), part.copy.end(), image.begin()), "copy table of the image");
+    EXPECT(std::equal(shifts.begin(), shifts.end(), image.begin() + blk.shift), "shifts of the image");
+    for (int j = 0; j < B; ++j) {
+        const StepTables& t = part.tables[j];
+        const int* s = image.data() + blk.slab(j);
+        EXPECT(t.tro == std::vector<int>(s + blk.tro, s + blk.tro + M + 1), "slab %d: task row offsets", j);
+        EXPECT(t.two[0] == std::vector<int>(s + blk.two, s + blk.two + M + 1), "slab %d: work item offsets", j);
+        EXPECT(t.slot_chain == std::vector<int>(s + blk.slot, s + blk.slot + M + 1), "slab %d: chain slot offsets", j);
+        EXPECT(t.wg_off == std::vector<int>(s + blk.wg_off, s + blk.wg_off + t.wg_off.size()), "slab %d: workgroup segment offsets", j);
+        const WorkItem* w = reinterpret_cast<const WorkItem*>(s + blk.work);
+        const ChainSeg* g = reinterpret_cast<const ChainSeg*>(s + blk.segs);
+        EXPECT(same_items(t.work[0], std::vector<WorkItem>(w, w + t.work[0].size())), "slab %d: work items", j);
+        EXPECT(same_segs(t.segs, std::vector<ChainSeg>(g, g + t.segs.size())), "slab %d: chain segments", j);
+        EXPECT((int)t.work[0].size() <= max_work && (int)t.segs.size() <= max_work && (int)t.wg_off.size() <= max_work + 1, "slab %d: tables outgrow their pieces", j);
+    }
 }
 
 static void check_layout(const std::vector<int32_t>& pro) {
@@ -110,6 +149,7 @@ static void check_layout(const std::vector<int32_t>& pro) {
             int gaps = 0;
             for (int r = 0; r < R; ++r) gaps += owner[r] < 0;
             EXPECT(gaps == 0, "%d of %d destination rows are written by no path (B = %d)", gaps, R, B);
+            check_block(part, B, max_work);
         }
     }
 }

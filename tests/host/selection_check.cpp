@@ -9,6 +9,8 @@
 //   refusals     unsorted, repeated, out of range, a task left with no path, negative n_sel: each with its message, and nothing
 //                written (under the sanitizer: without a stray access either)
 //   layout       the compact slab's offsets for a ragged three-task batch, and the step tables built on them
+//   copy table   -1 exactly at the paths not selected, the slab's offsets at the others; a full selection's is the partition's
+//                with B = 1; the table block of one slab reads back as the tables it was packed from
 #include "../../promp_amd/csrc/promp_plan.h"
 
 #include <cstdio>
@@ -91,6 +93,25 @@ static void check_layout() {
             EXPECT(lay.tpo[i + 1] - lay.tpo[i] == want, "task %d keeps %d paths, selected %d", i, lay.tpo[i + 1] - lay.tpo[i], want);
             for (int j = lay.tpo[i]; j < lay.tpo[i + 1]; ++j) EXPECT(sel[j] >= TPO[i] && sel[j] < TPO[i + 1], "selected path %d filed under task %d", sel[j], i);
         }
+        // the copy table of the launch that fills the slab: -1 exactly at the paths not selected, the slab's own offsets at the others
+        const std::vector<int> copy = selection_copy_table(12, lay);
+        EXPECT((int)copy.size() == 24, "copy table of %d ints", (int)copy.size());
+        if (copy.size() == 24) {
+            for (int p = 0, q = 0; p < 12; ++p) {
+                const bool in = q < n && sel[q] == p;
+                EXPECT(copy[2 * p] == (in ? 0 : -1), "path %d (%s): slab %d", p, in ? "selected" : "not selected", copy[2 * p]);
+                if (in) {
+                    EXPECT(copy[2 * p + 1] == lay.pro[q], "path %d goes to row %d, the slab's offset is %d", p, copy[2 * p + 1], lay.pro[q]);
+                    ++q;
+                }
+            }
+            if (n == 12) {      // every path selected: the partition into one minibatch
+                PartitionLayout part;
+                const std::vector<int32_t> assign(12, 0);
+                const int prc = build_partition(2, 7, 3, 12, TPO, pro.data(), 1, assign.data(), &part, &why);
+                EXPECT(prc == 0 && part.copy == copy, "a full selection's copy table is not the identity partition's (%s)", why.c_str());
+            }
+        }
         // the tables of the compact slab are those of an upload of the selected paths alone, sized by the selection
         for (int n_cus : {2, 256}) {
             StepTables t;
@@ -109,6 +130,18 @@ static void check_layout() {
             for (const ChainSeg& s : t.segs) tiles += s.ntiles;
             for (int i = 0; i < 3; ++i) want_tiles += (t.tro[i + 1] - t.tro[i] + 15) / 16;
             EXPECT(tiles == want_tiles, "segments cover %d of %d tiles", tiles, want_tiles);
+            // the selection's table block: the partition's shape with one slab, read back whole
+            const TableBlock blk(12, 1, 3, 2 * n_cus + 3);
+            std::vector<int> image(blk.total, -1);
+            pack_table_block(blk, copy, {0}, &t, image.data());
+            EXPECT(std::equal(copy.begin(), copy.end(), image.begin()) && image[blk.shift] == 0, "copy table / shift of the image");
+            const int* s = image.data() + blk.slab(0);
+            EXPECT(blk.slab(0) % 64 == 0 && blk.total == blk.slab(0) + blk.slab_stride, "one slab behind the copy table and the shifts");
+            EXPECT(std::equal(t.tro.begin(), t.tro.end(), s + blk.tro) && std::equal(t.two[0].begin(), t.two[0].end(), s + blk.two) &&
+                   std::equal(t.slot_chain.begin(), t.slot_chain.end(), s + blk.slot) && std::equal(t.wg_off.begin(), t.wg_off.end(), s + blk.wg_off),
+                   "offset tables of the image");
+            EXPECT(memcmp(s + blk.work, t.work[0].data(), sizeof(WorkItem) * t.work[0].size()) == 0 &&
+                   memcmp(s + blk.segs, t.segs.data(), sizeof(ChainSeg) * t.segs.size()) == 0, "work / segment tables of the image");
         }
     }
 }

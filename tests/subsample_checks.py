@@ -189,8 +189,43 @@ def check_oracle(lib, seed, O, A, hidden, K, lengths=LENGTHS, selections=SELECTI
     A_.close()
 
 
-def check_staleness(lib, seed, O=5, A=3, hidden=(32, 32), K=1, lengths=LENGTHS, selections=SELECTIONS):
-    """item 4"""
+def _check_resizing(lib, seed, O, A, hidden, K, lengths, selections, solves):
+    """one context, three selections in turn -- one, a larger one (the compact slab's buffers and its primal cache grow), a smaller
+    one (rows of the larger one stay behind the slab's end): each solve is, bit for bit, the solve of a fresh context that holds
+    the selected paths alone"""
+    theta, all_slabs, all_paths = make_case(seed, lengths, O, A, hidden, K)
+    spec = op.PolicySpec(O, A, hidden)
+    alpha = np.full(spec.n_params, 0.05, np.float32)
+    b = np.random.RandomState(seed + 9).randn(spec.n_params).astype(np.float32)
+    M = len(lengths)
+    last = np.cumsum([len(l) for l in lengths]) - 1
+    first, larger, smaller = list(selections[0]), sorted(set(selections[0]) | set(selections[1])), [int(p) for p in last]
+    assert len(smaller) < len(first) < len(larger)
+
+    def ctx_of(paths, slabs):
+        ctx = make_ctx(lib, M, O, A, hidden, K, paths)
+        helpers.upload_slabs(ctx, paths, slabs)
+        ctx.set_theta(theta)
+        ctx.set_step_sizes(alpha)
+        return ctx
+
+    A_ = ctx_of(all_paths, all_slabs)
+    for sel in (first, larger, smaller):
+        sels = [sel] * (K + 1)
+        B_ = ctx_of(*truncate(all_paths, all_slabs, sels))
+        _select(A_, sels)
+        for mode, iters in solves:
+            xa, qa = A_.cg_solve(b, cg_iters=iters, hvp_mode=mode, inner_kind=_lib.INNER_LOGLIK)
+            xb, qb = B_.cg_solve(b, cg_iters=iters, hvp_mode=mode, inner_kind=_lib.INNER_LOGLIK)
+            assert np.array_equal(xa, xb) and qa == qb, (len(sel), mode, rel_max(xa, xb.astype(np.float64)), qa, qb)
+            assert np.isfinite(xa).all() and np.isfinite(qa)
+        B_.close()
+    A_.close()
+
+
+def check_staleness(lib, seed, O=5, A=3, hidden=(32, 32), K=1, lengths=LENGTHS, selections=SELECTIONS, resize_solves=((2, 2), (0, 1))):
+    """item 4; and a selection replaced by a larger, then by a smaller one"""
+    _check_resizing(lib, seed + 20, O, A, hidden, K, lengths, selections, resize_solves)
     A_, B_, sels, c = _pair(lib, seed, lengths, selections, O, A, hidden, K)
     kind, eta = _lib.INNER_LOGLIK, np.zeros(K, np.float32)
     v = np.random.RandomState(seed + 5).randn(c['spec'].n_params).astype(np.float32)

@@ -367,7 +367,8 @@ def test_destroy_releases_every_allocation(lib, two_cus):
     """Live device allocations / page-locked host blocks / events of the emulated runtime (hip_emu.h: emu_live_counts) are back at
     their starting values once the contexts are destroyed, after every buffer that is allocated on first use has been: float64
     rewards, DiCE rows, the fit's buffers of both streams, primal caches, promp_constraint_hvp's and promp_cg_solve's vectors, the
-    staged slab sets, the all-gather buffer, profiling events, the forward / rollout / collection staging areas (the rollout's
+    compact slabs of a selection on every step (one promp_cg_solve on them) and of one promp_optimize_minibatch with two
+    minibatches -- pools, table blocks, the slabs' own primal caches, the page-locked table staging --, the staged slab sets, the all-gather buffer, profiling events, the forward / rollout / collection staging areas (the rollout's
     grown twice) and the pinned download area -- on a fused (32,32) point-environment shape and on a layer-by-layer one."""
     import gc
 
@@ -393,6 +394,13 @@ def test_destroy_releases_every_allocation(lib, two_cus):
     ctx.set_step_sizes(np.full(ctx.n_params, 0.1, np.float32))
     for k in range(2):
         ctx.upload_step(k, *flat(all_paths[k], f64=True))                   # float64 rewards: promp_set_rewards_f64
+    # the minibatches' pools, table blocks, slabs and their primal caches (before step 0 carries DiCE rewards: refused from then on)
+    ctx.set_primal_cache(True)
+    for k in range(2):
+        ctx.set_advantages(k, rng.randn(ctx.step_rows[k]).astype(np.float32))
+    res = ctx.optimize_minibatch(1, 2, [[0, 1, 0, 1] * 2], 1e-3, 0.3, eta)
+    assert np.isfinite(res['loss_before']) and np.isfinite(res['loss_after'])
+    ctx.set_theta(theta)
     ctx.set_dice_rewards(0, rng.randn(ctx.step_rows[0]).astype(np.float32))
     for k in range(2):                                                       # step 1: the side stream's fit buffers
         ctx.process_samples(k, baseline_kind=pc.KIND['linear_feature'], **kw)
@@ -409,6 +417,12 @@ def test_destroy_releases_every_allocation(lib, two_cus):
     assert np.all(np.isfinite(ctx.constraint_hvp(v)))
     x, xhx = ctx.cg_solve(v, cg_iters=1)
     assert np.all(np.isfinite(x)) and np.isfinite(xhx)
+    # a selection on every step (one path of each task): its pool, table block, compact slab and that slab's primal cache
+    for k in range(2):
+        ctx.set_step_selection(k, [0, 2])
+    x, xhx = ctx.cg_solve(v, cg_iters=1, hvp_mode=2)
+    assert np.all(np.isfinite(x)) and np.isfinite(xhx)
+    ctx.clear_selections()
     ctx.comm_init(0, 1, _lib.comm_unique_id(lib))
     ctx.comm_fixed_order(True)
     ctx.comm_split_path(True)

@@ -33,7 +33,7 @@ def test_selection_against_oracle(lib):
 
 
 def test_selection_staleness_and_refusals(lib):
-    sc.check_staleness(lib, 14, **EMU)
+    sc.check_staleness(lib, 14, resize_solves=((2, 1),), **EMU)
 
 
 def test_malformed_selections_are_refused(lib):
