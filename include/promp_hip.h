@@ -96,7 +96,8 @@ const char* promp_last_error(void);
  * new fields, so bindings must be rebuilt).  Entry points added since the first v2 header -- round 3: promp_set_reuse_adapt,
  * promp_begin_collection / promp_end_collection, promp_state_version, the two pass counters; round 4: promp_comm_fixed_order;
  * later: promp_set_train_step_sizes with promp_get_step_sizes / promp_get_step_size_grad / promp_{set,get}_step_size_adam_state
- * and promp_reduced_count -- were additions and did not move it. */
+ * and promp_reduced_count; promp_set_outer_optimizer / promp_get_outer_optimizer / promp_get_grad_norm -- were additions and did
+ * not move it. */
 int promp_abi_version(void);
 /* Theta = O*H1+H1 + H1*H2+H2 + H2*A+A + A */
 int promp_param_count(const promp_dims* dims);
@@ -369,9 +370,39 @@ int promp_cg_solve(promp_ctx* ctx, int inner_kind, const float* b, int cg_iters,
 int promp_set_step_selection(promp_ctx* ctx, int step, int n_sel, const int32_t* path_idx);
 int promp_step_selection(promp_ctx* ctx, int step);
 int promp_use_selection(promp_ctx* ctx, int on);
-/* tf.train.AdamOptimizer step on theta with the gradient left by promp_meta_grad
- * (optimizers/maml_first_order_optimizer.py:24,64; b1=.9 b2=.999 eps=1e-8, bias-corrected lr). */
+/* The outer optimiser's step on theta with the gradient left by promp_meta_grad: tf.train.AdamOptimizer
+ * (optimizers/maml_first_order_optimizer.py:24,64; b1=.9 b2=.999 eps=1e-8, bias-corrected lr) unless promp_set_outer_optimizer
+ * asked for another rule or other arguments. */
 int promp_adam_step(promp_ctx* ctx, float learning_rate);
+/* The update rule of every stepping entry point (promp_adam_step, promp_optimize[_begin], promp_optimize_minibatch[_begin]):
+ * MAMLFirstOrderOptimizer's tf_optimizer_cls(**tf_optimizer_args) (optimizers/maml_first_order_optimizer.py:22-38), TF1 semantics.
+ * g is the task-mean gradient (clipped when clipping is on), lr the call's learning rate, t the step count, which advances
+ * under every rule:
+ *   PROMP_OUTER_ADAM      args = {beta1, beta2, epsilon, -}   slots m, v
+ *       lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t) (host, double);  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2;
+ *       theta -= lr_t m / (sqrt(v) + epsilon).  Default {0.9, 0.999, 1e-8}; an argument equal to a default's float32 value IS the
+ *       default (lr_t then uses the double constants 0.9 / 0.999 it always has).
+ *   PROMP_OUTER_SGD       args unused, no slots                theta -= lr g
+ *   PROMP_OUTER_MOMENTUM  args = {momentum, use_nesterov (0 / 1), -, -}   slot a, kept where Adam keeps m
+ *       a = momentum a + g;  theta -= lr a;  with use_nesterov:  theta -= lr (g + momentum a), a the new one.
+ * args = NULL: the rule's defaults (momentum 0, no Nesterov step).  Refused with a message, nothing changed: an unknown rule,
+ * beta or momentum outside [0, 1), epsilon <= 0, a negative or non-finite max_grad_norm.  Entries that are not trained
+ * (learn_std = False) are masked under every rule; trained step sizes take the same rule and arguments with slots of their own.
+ * Setting a DIFFERENT rule zeroes m, v, the step count and the step sizes' slots; the same rule with new arguments keeps them.
+ * promp_set_adam_state / promp_get_adam_state work under every rule (a slot a rule does not use is carried along).
+ *
+ * max_grad_norm = c > 0: the task-mean gradient is scaled by the global norm before the rule sees it, n = sqrt(sum_j g_j^2)
+ * over the trained entries of theta and, when they are trained, of the step sizes; scale = n > c ? c / n : 1 -- exactly 1 when
+ * the clip is not active, which tf.clip_by_global_norm's c * min(1 / n, 1 / c) equals up to the last bit only; a non-finite n
+ * gives non-finite updates, as there.  The norm is the GLOBAL meta-batch's (taken behind the exchange), summed in float64 in one
+ * fixed order by every workgroup of the stepping launch; what promp_meta_grad hands out stays the unclipped gradient.  With
+ * clipping on, a step is always sums -> [exchange] -> mean + step (one dependent launch more per epoch on a single rank).
+ * 0 (default): off.  With nothing set, every launch and argument is that of a library without this entry point. */
+enum { PROMP_OUTER_ADAM = 0, PROMP_OUTER_SGD = 1, PROMP_OUTER_MOMENTUM = 2 };
+int promp_set_outer_optimizer(promp_ctx* ctx, int rule, const float args[4], float max_grad_norm);
+int promp_get_outer_optimizer(promp_ctx* ctx, int* rule, float args[4], float* max_grad_norm);
+/* the unclipped global norm n of the last gradient a step was taken on; refused while clipping is off or before the first step */
+int promp_get_grad_norm(promp_ctx* ctx, float* out);
 /* ProMP.optimize_policy's numerical core (meta_algos/pro_mp.py:165-199 +
  * optimizers/maml_first_order_optimizer.py:82-115,146-163): num_epochs x (meta_grad, Adam), then
  * compute_stats.  loss_before = loss of the first epoch; stats_after [K+2] as in promp_meta_grad.

@@ -112,6 +112,9 @@ SIGNATURES = {
     'promp_download_step': (C.c_int, [_P, C.c_int, _F, _F, _F, _F, _F]),
     'promp_meta_grad': (C.c_int, [_P, C.c_float, _F, C.c_int, C.c_int, _F, _F]),
     'promp_adam_step': (C.c_int, [_P, C.c_float]),
+    'promp_set_outer_optimizer': (C.c_int, [_P, C.c_int, _F, C.c_float]),
+    'promp_get_outer_optimizer': (C.c_int, [_P, C.POINTER(C.c_int), _F, _F]),
+    'promp_get_grad_norm': (C.c_int, [_P, _F]),
     'promp_optimize': (C.c_int, [_P, C.c_int, C.c_float, C.c_float, _F, C.c_int, C.c_int, _F, _F]),
     'promp_set_dice_rewards': (C.c_int, [_P, C.c_int, _F]),
     'promp_optimize_begin': (C.c_int, [_P, C.c_int, C.c_float, C.c_float, _F, C.c_int, C.c_int]),
@@ -450,6 +453,61 @@ def output_act_id(act):
     if name not in OUTPUT_ACTS:
         raise PrompError('output nonlinearity %r unsupported: None (linear), tanh or relu' % (act,))
     return OUTPUT_ACTS[name]
+
+
+OUTER_RULES = dict(adam=0, sgd=1, momentum=2)      # PROMP_OUTER_ADAM / _SGD / _MOMENTUM
+_OUTER_NAMES = dict(adam='adam', sgd='sgd', gradient_descent='sgd', momentum='momentum')
+_OUTER_CLASSES = dict(AdamOptimizer='adam', GradientDescentOptimizer='sgd', MomentumOptimizer='momentum')
+# tf_optimizer_args a rule takes beside learning_rate, with TF1's defaults (momentum has none there: 0 here)
+OUTER_RULE_ARGS = dict(adam=dict(beta1=0.9, beta2=0.999, epsilon=1e-8), sgd=dict(), momentum=dict(momentum=0.0, use_nesterov=False))
+
+
+def outer_rule_id(cls_or_name):
+    """the reference's tf_optimizer_cls argument (optimizers/maml_first_order_optimizer.py:22-38: a TF optimizer class) ->
+    PROMP_OUTER_*: None / 'adam' -> 0, 'sgd' / 'gradient_descent' -> 1, 'momentum' -> 2, or any class or callable named
+    AdamOptimizer / GradientDescentOptimizer / MomentumOptimizer; anything else (RMSProp, ...) is refused by name -- never
+    silently replaced by Adam"""
+    if cls_or_name is None:
+        return OUTER_RULES['adam']
+    if isinstance(cls_or_name, str):
+        name = _OUTER_NAMES.get(cls_or_name)
+    else:
+        name = _OUTER_CLASSES.get(getattr(cls_or_name, '__name__', ''))
+    if name is None:
+        raise PrompError('outer optimiser %r unsupported: adam, sgd (gradient_descent), momentum, or a class named AdamOptimizer, '
+                         'GradientDescentOptimizer or MomentumOptimizer' % (cls_or_name,))
+    return OUTER_RULES[name]
+
+
+def outer_rule_name(rule):
+    names = {v: k for k, v in OUTER_RULES.items()}
+    if int(rule) not in names:
+        raise PrompError('outer optimiser rule %r unknown (0 adam, 1 sgd, 2 momentum)' % (rule,))
+    return names[int(rule)]
+
+
+def outer_rule_args(rule, tf_optimizer_args=None):
+    """tf_optimizer_args for rule `rule` -> (the float[4] of promp_set_outer_optimizer, learning_rate or None).  Keys: beta1, beta2,
+    epsilon (adam), momentum, use_nesterov (momentum), learning_rate (every rule); any other key is refused, as the TF class
+    would refuse it"""
+    name = outer_rule_name(rule)
+    given = dict(tf_optimizer_args or {})
+    lr = given.pop('learning_rate', None)
+    known = OUTER_RULE_ARGS[name]
+    for k in given:
+        if k not in known:
+            raise PrompError('tf_optimizer_args key %r is not an argument of the %s rule (it takes %s)'
+                             % (k, name, ', '.join(sorted(known) + ['learning_rate'])))
+    a = dict(known, **given)
+    # (the ranges promp_plan.h's outer_opt_plan holds: refused here too, so that a session without a context refuses at once)
+    for k in ('beta1', 'beta2', 'momentum'):
+        if k in a and not 0.0 <= float(a[k]) < 1.0:
+            raise PrompError('tf_optimizer_args: %s %r outside [0, 1)' % (k, a[k]))
+    if 'epsilon' in a and not (float(a['epsilon']) > 0.0 and np.isfinite(float(a['epsilon']))):
+        raise PrompError('tf_optimizer_args: epsilon %r must be positive and finite' % (a['epsilon'],))
+    vec = dict(adam=lambda: [a['beta1'], a['beta2'], a['epsilon'], 0.0], sgd=lambda: [0.0] * 4,
+               momentum=lambda: [a['momentum'], 1.0 if a['use_nesterov'] else 0.0, 0.0, 0.0])[name]()
+    return np.asarray(vec, dtype=np.float32), (None if lr is None else float(lr))
 
 
 class Context:
@@ -854,7 +912,33 @@ class Context:
         self._call('promp_set_learn_std', int(bool(on)))
 
     def adam_step(self, lr):
+        """one step of the outer optimiser's rule (Adam unless set_outer_optimizer said otherwise) on the sums in the exchange buffer"""
         self._call('promp_adam_step', float(lr))
+
+    def set_outer_optimizer(self, rule='adam', args=None, max_grad_norm=None):
+        """promp_set_outer_optimizer: `rule` as outer_rule_id takes it; `args` a dict (tf_optimizer_args' keys), the float[4] of the C
+        entry point, or None (the rule's defaults); max_grad_norm None / 0: no clipping"""
+        rid = outer_rule_id(rule) if not isinstance(rule, (int, np.integer)) else int(rule)
+        if isinstance(args, dict) or (args is None and rid in OUTER_RULES.values()):
+            args = outer_rule_args(rid, args)[0]
+        a = None if args is None else _f32(args)          # (None: an unknown rule number, refused by the library)
+        assert a is None or a.shape == (4,)
+        self._call('promp_set_outer_optimizer', rid, _ptr(a, C.c_float), float(0.0 if max_grad_norm is None else max_grad_norm))
+
+    def get_outer_optimizer(self):
+        """-> dict(rule=name, args=dict, max_grad_norm=float or None)"""
+        rule, a, c = C.c_int(0), np.zeros(4, np.float32), C.c_float(0)
+        self._call('promp_get_outer_optimizer', C.byref(rule), _ptr(a, C.c_float), C.byref(c))
+        name = outer_rule_name(rule.value)
+        args = dict(adam=lambda: dict(beta1=float(a[0]), beta2=float(a[1]), epsilon=float(a[2])), sgd=dict,
+                    momentum=lambda: dict(momentum=float(a[0]), use_nesterov=bool(a[1])))[name]()
+        return dict(rule=name, args=args, max_grad_norm=float(c.value) if c.value > 0 else None)
+
+    def grad_norm(self):
+        """promp_get_grad_norm: the unclipped global norm of the last gradient a clipped step was taken on"""
+        out = np.zeros(1, np.float32)
+        self._call('promp_get_grad_norm', _ptr(out, C.c_float))
+        return float(out[0])
 
     def optimize(self, num_epochs, lr, clip_eps, inner_kl_coeff, inner_kind=INNER_RATIO, outer_kind=OUTER_CLIP):
         eta = _f32(inner_kl_coeff)

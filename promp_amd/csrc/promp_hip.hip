@@ -266,6 +266,9 @@ struct promp_ctx {
     std::vector<StepData> steps;
     DevBuf<float> theta, step_sizes, adam_m, adam_v;
     long long adam_t = 0;
+    OuterOptPlan outer;                  // promp_set_outer_optimizer: the rule of every step, its arguments, the clip
+    DevBuf<float> grad_norm;             // [1] the unclipped global norm k_mean_outer left (promp_get_grad_norm); allocated with the first clip
+    bool norm_valid = false;             // a clipped step has been enqueued since clipping was switched on
     DevBuf<float> theta_tasks, chain, lam, vbuf;
     bool tasks_shared = false;           // switch_to_pre_update: every task's parameters ARE theta; theta_tasks is written when somebody reads it
     DevBuf<float> wbuf;                  // promp_constraint_hvp: [tasks][Theta], allocated on first use
@@ -904,8 +907,11 @@ int enqueue_meta_on(promp_ctx* c, const EvalSet& E, float clip_eps, const float*
     f.scal_inner = E.scal_inner; f.scal_outer = c->scal_outer; f.red = c->red; f.want_grad = want_grad ? 1 : 0;
     c->red_has_sizes = ag;
     const unsigned final_blocks = (unsigned)((red_count(c, ag) + 63) / 64);
-    // several ranks (or an external collective: more global than local tasks): sums first, mean + Adam after the exchange
-    const bool split = c->nranks > 1 || c->force_split || c->d.n_tasks_global != c->d.n_tasks;
+    // several ranks (or an external collective: more global than local tasks): sums first, mean + Adam after the exchange;
+    // a clipped step as well (the norm of ALL entries comes first), and settings that are not the default ones step in the
+    // general kernels (final_stage_plan)
+    const FinalPlan fp = final_stage_plan(c->outer, c->sw, do_adam, c->nranks > 1 || c->force_split || c->d.n_tasks_global != c->d.n_tasks);
+    const bool split = fp.split;
     if (split) {
         if (ag) PROMP_LAUNCH(k_reduce_final_ss, dim3(final_blocks), 256, 0, c->stream, f, (const float*)c->galpha);
         else PROMP_LAUNCH(k_reduce_final, dim3(final_blocks), 256, 0, c->stream, f);
@@ -926,10 +932,18 @@ int enqueue_meta_on(promp_ctx* c, const EvalSet& E, float clip_eps, const float*
         if (ag) c->sizes_version = ++c->version_counter;
         c->ls_known = false;
         c->adam_t += 1;
-        const double t = (double)c->adam_t;
-        ad.lr_t = (float)((double)lr * std::sqrt(1.0 - std::pow(0.999, t)) / (1.0 - std::pow(0.9, t)));
+        ad.lr_t = outer_lr_t(c->outer, lr, c->adam_t);
     }
-    if (ag) {
+    if (fp.general) {
+        const OuterOptArgs oo = outer_opt_args(c->outer);
+        if (ag) {
+            const StepSizeArgs ss = step_size_args(c);
+            if (split) PROMP_LAUNCH(k_mean_outer_ss, dim3((2 * NP + 1 + 255) / 256), 256, 0, c->stream, ad, ss, oo, c->grad_norm.p);
+            else PROMP_LAUNCH(k_final_outer_ss, dim3(final_blocks + 1), 256, 0, c->stream, f, ad, ss, oo);
+        } else if (split) PROMP_LAUNCH(k_mean_outer, dim3((NP + 1 + 255) / 256), 256, 0, c->stream, ad, oo, c->grad_norm.p);
+        else PROMP_LAUNCH(k_final_outer, dim3(final_blocks + 1), 256, 0, c->stream, f, ad, oo);
+        if (oo.max_norm > 0.f) c->norm_valid = true;
+    } else if (ag) {
         const StepSizeArgs ss = step_size_args(c);
         if (split) PROMP_LAUNCH(k_mean_adam_ss, dim3((2 * NP + 1 + 255) / 256), 256, 0, c->stream, ad, ss);
         else PROMP_LAUNCH(k_final_adam_ss, dim3(final_blocks + 1), 256, 0, c->stream, f, ad, ss);
@@ -2471,12 +2485,50 @@ int promp_adam_step(promp_ctx* c, float lr) {
     if (c->train_sizes) c->sizes_version = ++c->version_counter;
     c->ls_known = false;
     c->adam_t += 1;
-    const double t = (double)c->adam_t;
-    ad.lr_t = (float)((double)lr * std::sqrt(1.0 - std::pow(0.999, t)) / (1.0 - std::pow(0.9, t)));
-    if (c->train_sizes) PROMP_LAUNCH(k_mean_adam_ss, dim3((2 * c->NP + 1 + 255) / 256), 256, 0, c->stream, ad, step_size_args(c));
+    ad.lr_t = outer_lr_t(c->outer, lr, c->adam_t);
+    if (final_stage_plan(c->outer, c->sw, true, true).general) {
+        const OuterOptArgs oo = outer_opt_args(c->outer);
+        if (c->train_sizes) PROMP_LAUNCH(k_mean_outer_ss, dim3((2 * c->NP + 1 + 255) / 256), 256, 0, c->stream, ad, step_size_args(c), oo, c->grad_norm.p);
+        else PROMP_LAUNCH(k_mean_outer, dim3((c->NP + 1 + 255) / 256), 256, 0, c->stream, ad, oo, c->grad_norm.p);
+        if (oo.max_norm > 0.f) c->norm_valid = true;
+    } else if (c->train_sizes) PROMP_LAUNCH(k_mean_adam_ss, dim3((2 * c->NP + 1 + 255) / 256), 256, 0, c->stream, ad, step_size_args(c));
     else PROMP_LAUNCH(k_mean_adam, dim3((c->NP + 1 + 255) / 256), 256, 0, c->stream, ad);
     HIPCHECK(hipGetLastError());
     return 0;
+}
+
+// MAMLFirstOrderOptimizer's tf_optimizer_cls(**tf_optimizer_args) and max_grad_norm (include/promp_hip.h).  Validated in the plan
+// (outer_opt_plan) before anything is touched; a new rule starts from zeroed slots and step count, new arguments keep them.
+int promp_set_outer_optimizer(promp_ctx* c, int rule, const float* args, float max_grad_norm) {
+    NEED_CTX(c);
+    OuterOptPlan p;
+    std::string why;
+    if (const int rc = outer_opt_plan(rule, args, max_grad_norm, &p, &why)) return fail(rc, "promp_set_outer_optimizer: %s", why.c_str());
+    if (p.max_norm > 0.f && !c->grad_norm && c->grad_norm.alloc(1)) return -2;      // (a context that never clips allocates what it always did)
+    if (p.rule != c->outer.rule) {
+        const size_t bytes = sizeof(float) * (size_t)c->NP;
+        HIPCHECK(hipMemsetAsync(c->adam_m, 0, bytes, c->stream));
+        HIPCHECK(hipMemsetAsync(c->adam_v, 0, bytes, c->stream));
+        if (c->ss_m) {
+            HIPCHECK(hipMemsetAsync(c->ss_m, 0, bytes, c->stream));
+            HIPCHECK(hipMemsetAsync(c->ss_v, 0, bytes, c->stream));
+        }
+        c->adam_t = 0;
+    }
+    if (!(p.max_norm > 0.f)) c->norm_valid = false;
+    c->outer = p;
+    return 0;
+}
+int promp_get_outer_optimizer(promp_ctx* c, int* rule, float* args, float* max_grad_norm) {
+    NEED_CTX(c);
+    outer_opt_unplan(c->outer, rule, args, max_grad_norm);
+    return 0;
+}
+int promp_get_grad_norm(promp_ctx* c, float* out) {
+    if (!c || !out) return fail(-1, "NULL argument");
+    if (!(c->outer.max_norm > 0.f)) return fail(-3, "promp_get_grad_norm: gradient clipping is off (promp_set_outer_optimizer with max_grad_norm > 0)");
+    if (!c->norm_valid) return fail(-3, "promp_get_grad_norm: no clipped step has been taken yet");
+    return copy_out(c, out, c->grad_norm, 1);
 }
 
 int promp_optimize_begin(promp_ctx* c, int num_epochs, float lr, float clip_eps, const float* eta, int inner_kind, int outer_kind) {

@@ -5,6 +5,9 @@
 //   k_reduce_final : task sum of the per-task gradients and scalars                          (K14)
 //   k_mean_adam    : mean over the global meta-batch + tf.train.AdamOptimizer step            (K14)
 //   k_final_adam   : the two above in one launch (single rank)
+//   k_mean_outer / k_final_outer : the general twins of k_mean_adam / k_final_adam -- any rule and arguments of
+//                    promp_set_outer_optimizer, and in k_mean_outer the clip by the global norm; launched only when the settings
+//                    are not the default ones (final_stage_plan, promp_plan.h)
 //                    (their *_ss instances carry Theta more columns: trainable step sizes, promp_kernels_step_sizes.h;
 //                    the plain ones are the launches and arguments of a library without the feature)
 //   k_policy_forward : mean network under each task's current parameters (get_actions)
@@ -306,6 +309,153 @@ __global__ void __launch_bounds__(256) k_final_adam_ss(FinalArgs a, AdamArgs ad,
     __shared__ float part[4][64];
     __shared__ float sums[64];
     final_adam_body<true>(a, ad, ss, part, sums);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The general final stage (promp_set_outer_optimizer): the kernels above with the rule, its arguments and the clip as launch
+// arguments.  The plain kernels stay as they are -- a run-time branch in them is paid by every default step
+// (profiles/step_size_timing.txt) --, and final_stage_plan launches these only for settings that are not the default ones.
+// ---------------------------------------------------------------------------------------------
+// Sum of squares of the task-mean gradient over the trained entries -- theta's [0, n_trainable) and, SS, alpha's --, by EVERY
+// workgroup of k_mean_outer for itself: red is Theta or 2 Theta floats (24 KB at 5 900 parameters) that sit in L2 behind
+// k_reduce_final or the exchange, so no workgroup waits for another and no launch is added.  float64, one fixed order: thread t
+// adds the entries t, t + 256, ... (theta's, then alpha's), then a binary tree over the 256 partial sums in LDS -- the same bits
+// in every workgroup.  buf: 256 doubles.
+// (eight entries of a thread requested together, clamped + selected like final_quarter_sum's rows: at 32 k parameters a thread has
+// 125 entries, and one L2 round trip per entry would cost more than the launch)
+PROMP_DEV double outer_sq_sum(const float* x, int n, float inv, double s) {
+    const int t = threadIdx.x;
+    for (int jb = t; jb < n; jb += 8 * 256) {
+        float g[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int j = jb + 256 * u;
+            const float v = x[j < n ? j : jb];
+            g[u] = j < n ? v * inv : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s += (double)g[u] * (double)g[u];
+    }
+    return s;
+}
+template <bool SS>
+PROMP_DEV double outer_sq_norm(const AdamArgs& a, double* buf) {
+    const int t = threadIdx.x;
+    double s = outer_sq_sum(a.red, a.n_trainable, a.inv_tasks, 0.0);
+    if (SS) s = outer_sq_sum(a.red + a.NP + a.K + 2, a.n_trainable, a.inv_tasks, s);
+    buf[t] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (t < w) buf[t] += buf[t + w];
+        __syncthreads();
+    }
+    return buf[0];
+}
+
+// k_mean_adam under any rule, with the clip.  scale = n > c ? c / n : 1 is exactly 1 when the clip is off or not active
+// (tf.clip_by_global_norm computes c * min(1 / n, 1 / c): the same up to the last bit); a non-finite norm makes every update
+// non-finite, as there.  grad_mean keeps the unclipped gradient; one thread leaves n for promp_get_grad_norm.
+// grid as k_mean_adam / k_mean_adam_ss, block = 256
+template <bool SS>
+PROMP_DEV void mean_outer_body(const AdamArgs& a, const StepSizeArgs& ss, const OuterOptArgs& o, float* norm_out, double* buf) {
+    float scale = 1.f;
+    if (o.max_norm > 0.f) {       // (uniform over the grid: every thread reaches the barriers inside)
+        const float n = (float)sqrt(outer_sq_norm<SS>(a, buf));
+        scale = n > o.max_norm ? o.max_norm / n : 1.f;
+        if (!(fabsf(n) <= 3.402823466e38f)) scale = n - n;       // inf or NaN: NaN
+        if (blockIdx.x == 0 && threadIdx.x == 0) *norm_out = n;
+    }
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j < a.NP) {
+        const float g = a.red[j] * a.inv_tasks;
+        a.grad_mean[j] = g;
+        if (a.do_update && j < a.n_trainable) outer_rule_step(o, a.theta, a.m, a.v, j, g * scale, a.lr_t);
+    } else if (j == a.NP) {
+        float pen = 0.f;
+        for (int k = 0; k < a.K; ++k) {
+            const float ikl = a.red[a.NP + 1 + k] * a.inv_tasks;
+            a.stats[1 + k] = ikl;
+            pen += a.eta[k] * ikl;
+        }
+        a.stats[0] = a.red[a.NP] * a.inv_tasks + pen / (float)a.K;
+        a.stats[1 + a.K] = a.red[a.NP + 1 + a.K] * a.inv_tasks;
+        publish_stats(a);
+    } else if (SS && j <= 2 * a.NP) {
+        const int ja = j - a.NP - 1;
+        step_size_outer(o, ss.alpha, ss.alpha_m, ss.alpha_v, ss.alpha_grad_mean, ja, a.red[a.NP + a.K + 2 + ja] * a.inv_tasks, scale,
+                        a.do_update && ja < a.n_trainable, ja < a.n_trainable, a.lr_t);
+    }
+}
+__global__ void __launch_bounds__(256) k_mean_outer(AdamArgs a, OuterOptArgs o, float* norm_out) {
+    __shared__ double buf[256];
+    mean_outer_body<false>(a, StepSizeArgs{}, o, norm_out, buf);
+}
+__global__ void __launch_bounds__(256) k_mean_outer_ss(AdamArgs a, StepSizeArgs ss, OuterOptArgs o, float* norm_out) {
+    __shared__ double buf[256];
+    mean_outer_body<true>(a, ss, o, norm_out, buf);
+}
+
+// k_final_adam under any rule (no clip: a column's thread steps its entry before the other columns' sums exist).
+// grid and block as k_final_adam / k_final_adam_ss
+template <bool SS>
+PROMP_DEV void final_outer_body(const FinalArgs& a, const AdamArgs& ad, const StepSizeArgs& ss, const OuterOptArgs& o, float (*part)[64],
+                                float* sums) {
+    const int c = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const bool stats_block = blockIdx.x == gridDim.x - 1;
+    const int j = stats_block ? a.NP + c : blockIdx.x * 64 + c;
+    const int jend = a.NP + a.K + 2 + (SS && !stats_block ? a.NP : 0);
+    float s = 0.f;
+    if (j < a.NP) {
+        if (a.want_grad) s = final_quarter_sum(a.lam, a.NP, a.n_tasks, j, q);
+    } else if (j == a.NP) {
+        for (int i = q; i < a.n_tasks; i += 4) s += a.scal_outer[i * 2 + 0];
+    } else if (j <= a.NP + a.K) {
+        const int k = j - a.NP - 1;
+        for (int i = q; i < a.n_tasks; i += 4) s += a.scal_inner[((long long)k * a.n_tasks + i) * 2 + 1];
+    } else if (j == a.NP + a.K + 1) {
+        for (int i = q; i < a.n_tasks; i += 4) s += a.scal_outer[i * 2 + 1];
+    } else if (SS && j < jend) {
+        s = final_quarter_sum(ss.galpha, a.NP, a.n_tasks, j - (a.NP + a.K + 2), q);
+    }
+    part[q][c] = s;
+    __syncthreads();
+    if (q == 0 && j < jend) {
+        const float t = (part[0][c] + part[1][c]) + (part[2][c] + part[3][c]);
+        if (!stats_block) a.red[j] = t;
+        sums[c] = t;
+        if (!stats_block && j < a.NP) {
+            const float g = t * ad.inv_tasks;
+            ad.grad_mean[j] = g;
+            if (ad.do_update && j < ad.n_trainable) outer_rule_step(o, ad.theta, ad.m, ad.v, j, g, ad.lr_t);
+        } else if (SS && !stats_block && j >= a.NP + a.K + 2) {
+            const int ja = j - (a.NP + a.K + 2);
+            step_size_outer(o, ss.alpha, ss.alpha_m, ss.alpha_v, ss.alpha_grad_mean, ja, t * ad.inv_tasks, 1.f,
+                            ad.do_update && ja < ad.n_trainable, ja < ad.n_trainable, ad.lr_t);
+        }
+    }
+    if (!stats_block) return;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float pen = 0.f;
+        for (int k = 0; k < a.K; ++k) {
+            const float ikl = sums[1 + k] * ad.inv_tasks;
+            ad.stats[1 + k] = ikl;
+            pen += ad.eta[k] * ikl;
+        }
+        ad.stats[0] = sums[0] * ad.inv_tasks + pen / (float)a.K;
+        ad.stats[1 + a.K] = sums[1 + a.K] * ad.inv_tasks;
+        publish_stats(ad);
+    }
+}
+__global__ void __launch_bounds__(256) k_final_outer(FinalArgs a, AdamArgs ad, OuterOptArgs o) {
+    __shared__ float part[4][64];
+    __shared__ float sums[64];
+    final_outer_body<false>(a, ad, StepSizeArgs{}, o, part, sums);
+}
+__global__ void __launch_bounds__(256) k_final_outer_ss(FinalArgs a, AdamArgs ad, StepSizeArgs ss, OuterOptArgs o) {
+    __shared__ float part[4][64];
+    __shared__ float sums[64];
+    final_outer_body<true>(a, ad, ss, o, part, sums);
 }
 
 // dst[i][:] = src[:] for i < n_tasks   (MetaPolicy.switch_to_pre_update)

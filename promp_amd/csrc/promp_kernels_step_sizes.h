@@ -10,8 +10,11 @@
 //
 //   k_step_size_grad : galpha[i] = (first ? 0 : galpha[i]) - lam[i] * g_k[i]        one launch per inner step, k = K-1 .. 0
 //   step_size_adam   : the Adam step of one alpha entry (k_mean_adam / k_final_adam, behind the task sum of galpha)
+//   outer_rule_step  : one entry's step under the rule promp_set_outer_optimizer asked for (the general final-stage kernels
+//                      k_mean_outer / k_final_outer of promp_kernels_policy.h: theta's entries and, step_size_outer, alpha's)
 #pragma once
 #include "promp_device.h"
+#include "promp_plan.h"            // OuterOptArgs
 
 // grid = (ceil(NP / 256), tasks)
 __global__ void __launch_bounds__(256) k_step_size_grad(float* galpha, const float* lam, const float* ginner, int NP, int first) {
@@ -34,4 +37,30 @@ PROMP_DEV void step_size_adam(float* alpha, float* am, float* av, float* grad_me
     am[j] = m;
     av[j] = v;
     alpha[j] -= lr_t * m / (sqrtf(v) + 1e-8f);
+}
+
+// One entry's step under any rule (include/promp_hip.h, promp_set_outer_optimizer): p the parameter, s1 / s2 its slots (Adam's m
+// and v; Momentum's accumulator in s1), g the task-mean gradient after clipping, lr_t from outer_lr_t.  The Adam lines are the
+// plain kernels' lines with the constants as arguments, in the same operation order: default arguments give the same bits.
+PROMP_DEV void outer_rule_step(const OuterOptArgs& o, float* p, float* s1, float* s2, int j, float g, float lr_t) {
+    if (o.rule == PROMP_OUTER_ADAM) {
+        const float m = o.b1 * s1[j] + o.one_minus_b1 * g;
+        const float v = o.b2 * s2[j] + o.one_minus_b2 * g * g;
+        s1[j] = m;
+        s2[j] = v;
+        p[j] -= lr_t * m / (sqrtf(v) + o.eps);
+    } else if (o.rule == PROMP_OUTER_SGD) {
+        p[j] -= lr_t * g;
+    } else {
+        const float a = o.mu * s1[j] + g;
+        s1[j] = a;
+        p[j] -= lr_t * (o.nesterov ? g + o.mu * a : a);
+    }
+}
+// step_size_adam under any rule; g unclipped, scale the clip's factor (exactly 1 when it is off or not active)
+PROMP_DEV void step_size_outer(const OuterOptArgs& o, float* alpha, float* am, float* av, float* grad_mean, int j, float g, float scale,
+                               bool update, bool trained, float lr_t) {
+    grad_mean[j] = trained ? g : 0.f;
+    if (!update) return;
+    outer_rule_step(o, alpha, am, av, j, g * scale, lr_t);
 }

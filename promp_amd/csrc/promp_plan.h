@@ -7,6 +7,7 @@
 //   selections   which paths of a step a subsampled constraint product keeps, and the layout of the compact slab that holds them
 //   partitions   a step's paths dealt to the compact slabs of its minibatches
 //   table blocks the one block of ints that holds a copy launch's table and the pass tables of the compact slabs it fills
+//   outer step   the update rule, its arguments and the gradient clip of the final stage, and which kernel family runs it
 //   switches     the PROMP_* environment switches the above depend on, read once
 //
 // HIP-free: the C ABI header and the standard library only, so plain `g++ -std=c++17` compiles it alone and
@@ -53,6 +54,8 @@ struct PlanSwitches {
     bool gen_fp32 = false;         // PROMP_GEN_FP32=1: the layer-by-layer GEMMs on the exact-FP32 kernels
     int max_cus = 0;               // PROMP_MAX_CUS > 0: work tables for at most this many compute units (tests: a wave then walks
                                    // several tiles of a small batch)
+    bool outer_generic = false;    // PROMP_OUTER_GENERIC=1: the general final-stage kernels under default settings too (A/B runs and
+                                   // the bit-for-bit test against the plain ones)
 };
 inline PlanSwitches plan_switches_from_env() {
     auto is1 = [](const char* name) { const char* e = getenv(name); return e && e[0] == '1'; };
@@ -61,6 +64,7 @@ inline PlanSwitches plan_switches_from_env() {
     sw.gram_untiled = is1("PROMP_GRAM_UNTILED");
     sw.gramt_single = is1("PROMP_GRAMT_SINGLE");
     sw.gen_fp32 = is1("PROMP_GEN_FP32");
+    sw.outer_generic = is1("PROMP_OUTER_GENERIC");
     { const char* e = getenv("PROMP_WIDE_FP32"); sw.wide_fp32 = e && atoi(e) != 0; }
     { const char* e = getenv("PROMP_MAX_CUS"); sw.max_cus = e ? atoi(e) : 0; }
     return sw;
@@ -665,4 +669,107 @@ inline void pack_table_block(const TableBlock& blk, const std::vector<int>& copy
     memcpy(dst, copy.data(), sizeof(int) * copy.size());
     memcpy(dst + blk.shift, shifts.data(), sizeof(int) * shifts.size());
     for (size_t j = 0; j < shifts.size(); ++j) pack_slab_tables(blk, tables[j], dst + blk.slab((int)j));
+}
+
+// ---- outer step (promp_set_outer_optimizer) ----------------------------------------------------------------------------------
+// What the general final-stage kernels (k_final_outer / k_mean_outer, promp_kernels_policy.h) take by value.  one_minus_b* are
+// rounded on the host from the double difference, so that default arguments give the 0.1f and 0.001f of the plain kernels.
+struct OuterOptArgs {
+    int rule;                  // PROMP_OUTER_*
+    float b1, one_minus_b1, b2, one_minus_b2, eps;      // Adam
+    float mu;                  // Momentum
+    int nesterov;
+    float max_norm;            // > 0: clip the task-mean gradient by its global norm (split kernels only); 0: off
+};
+// The context's settings.  The betas are doubles: lr_t is computed in double, and the defaults are the double constants 0.9 and
+// 0.999 -- a float argument that equals a default's float32 value means that default (outer_opt_plan), so that asking for the
+// default by name changes no bit.
+struct OuterOptPlan {
+    int rule = PROMP_OUTER_ADAM;
+    double b1 = 0.9, b2 = 0.999;
+    float eps = 1e-8f;
+    float mu = 0.f;
+    int nesterov = 0;
+    float max_norm = 0.f;
+};
+inline const char* outer_rule_name(int rule) {
+    return rule == PROMP_OUTER_ADAM ? "adam" : rule == PROMP_OUTER_SGD ? "sgd" : rule == PROMP_OUTER_MOMENTUM ? "momentum" : nullptr;
+}
+// 'adam' | 'sgd' / 'gradient_descent' | 'momentum', or TF1's class names; -1: not a rule of this library (RMSProp and the rest)
+inline int outer_rule_by_name(const char* name) {
+    if (!name) return -1;
+    const std::string n(name);
+    if (n == "adam" || n == "AdamOptimizer") return PROMP_OUTER_ADAM;
+    if (n == "sgd" || n == "gradient_descent" || n == "GradientDescentOptimizer") return PROMP_OUTER_SGD;
+    if (n == "momentum" || n == "MomentumOptimizer") return PROMP_OUTER_MOMENTUM;
+    return -1;
+}
+// Validates promp_set_outer_optimizer's arguments (args may be NULL: the rule's defaults) and writes the plan; nothing is written
+// on refusal.  Only the arguments of the rule asked for are read.
+inline int outer_opt_plan(int rule, const float* args, float max_grad_norm, OuterOptPlan* out, std::string* why) {
+    if (!outer_rule_name(rule))
+        return plan_fail(why, -1, "outer optimiser rule %d unknown (0 adam, 1 sgd, 2 momentum; RMSProp and others are not built)", rule);
+    if (!(max_grad_norm >= 0.f) || !std::isfinite(max_grad_norm))
+        return plan_fail(why, -1, "max_grad_norm %g must be finite and >= 0 (0: no clipping)", (double)max_grad_norm);
+    OuterOptPlan p;
+    p.rule = rule;
+    p.max_norm = max_grad_norm;
+    if (rule == PROMP_OUTER_ADAM && args) {
+        if (!(args[0] >= 0.f && args[0] < 1.f)) return plan_fail(why, -1, "beta1 %g outside [0, 1)", (double)args[0]);
+        if (!(args[1] >= 0.f && args[1] < 1.f)) return plan_fail(why, -1, "beta2 %g outside [0, 1)", (double)args[1]);
+        if (!(args[2] > 0.f) || !std::isfinite(args[2])) return plan_fail(why, -1, "epsilon %g must be positive and finite", (double)args[2]);
+        p.b1 = args[0] == 0.9f ? 0.9 : (double)args[0];
+        p.b2 = args[1] == 0.999f ? 0.999 : (double)args[1];
+        p.eps = args[2];
+    }
+    if (rule == PROMP_OUTER_MOMENTUM && args) {
+        if (!(args[0] >= 0.f && args[0] < 1.f)) return plan_fail(why, -1, "momentum %g outside [0, 1)", (double)args[0]);
+        if (args[1] != 0.f && args[1] != 1.f) return plan_fail(why, -1, "use_nesterov %g must be 0 or 1", (double)args[1]);
+        p.mu = args[0];
+        p.nesterov = args[1] != 0.f;
+    }
+    *out = p;
+    return 0;
+}
+// (promp_get_outer_optimizer: the arguments in promp_set_outer_optimizer's layout)
+inline void outer_opt_unplan(const OuterOptPlan& p, int* rule, float* args, float* max_grad_norm) {
+    if (rule) *rule = p.rule;
+    if (max_grad_norm) *max_grad_norm = p.max_norm;
+    if (!args) return;
+    args[0] = args[1] = args[2] = args[3] = 0.f;
+    if (p.rule == PROMP_OUTER_ADAM) { args[0] = (float)p.b1; args[1] = (float)p.b2; args[2] = p.eps; }
+    if (p.rule == PROMP_OUTER_MOMENTUM) { args[0] = p.mu; args[1] = (float)p.nesterov; }
+}
+inline bool outer_opt_is_default(const OuterOptPlan& p) {
+    return p.rule == PROMP_OUTER_ADAM && p.b1 == 0.9 && p.b2 == 0.999 && p.eps == 1e-8f && p.max_norm == 0.f;
+}
+inline OuterOptArgs outer_opt_args(const OuterOptPlan& p) {
+    OuterOptArgs o;
+    o.rule = p.rule;
+    o.b1 = (float)p.b1; o.one_minus_b1 = (float)(1.0 - p.b1);
+    o.b2 = (float)p.b2; o.one_minus_b2 = (float)(1.0 - p.b2);
+    o.eps = p.eps; o.mu = p.mu; o.nesterov = p.nesterov; o.max_norm = p.max_norm;
+    return o;
+}
+// The learning rate a step's launch carries, t the step count INCLUDING this step: Adam's bias-corrected lr_t, in double; the
+// call's own learning rate under the other rules.
+inline float outer_lr_t(const OuterOptPlan& p, float lr, long long t) {
+    if (p.rule != PROMP_OUTER_ADAM) return lr;
+    const double td = (double)t;
+    return (float)((double)lr * std::sqrt(1.0 - std::pow(p.b2, td)) / (1.0 - std::pow(p.b1, td)));
+}
+// Which kernels run the final stage of an evaluation.  Default settings: the plain instances (k_final_adam on one rank,
+// k_reduce_final -> exchange -> k_mean_adam where the sums cross ranks: split_wanted), as in a library without the settings.
+// Anything else, or PROMP_OUTER_GENERIC=1, on a STEPPING evaluation: the general family (k_final_outer / k_mean_outer).
+// Clipping needs the norm before any entry is stepped: always the split route.  An evaluation that does not step has no use for
+// a rule or a norm and stays on the plain instances.
+struct FinalPlan {
+    bool general;
+    bool split;
+};
+inline FinalPlan final_stage_plan(const OuterOptPlan& p, const PlanSwitches& sw, bool stepping, bool split_wanted) {
+    FinalPlan f;
+    f.general = stepping && (sw.outer_generic || !outer_opt_is_default(p));
+    f.split = split_wanted || (stepping && p.max_norm > 0.f);
+    return f;
 }

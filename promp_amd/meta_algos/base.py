@@ -45,6 +45,20 @@ class MAMLAlgo(MetaAlgo):
         """[Theta] inner step sizes: np.full(Theta, inner_lr) unless trainable_inner_step_size moves them"""
         return self.session.get_step_sizes()
 
+    def _init_outer_optimizer(self, tf_optimizer_cls=None, tf_optimizer_args=None, max_grad_norm=None):
+        """the rule of the outer step, its arguments and the gradient clip (MAMLFirstOrderOptimizer's arguments, which the
+        reference's algorithms do not pass on) -> the session; a learning_rate among the arguments replaces the algorithm's"""
+        rule = _lib.outer_rule_id(tf_optimizer_cls)
+        args, lr = _lib.outer_rule_args(rule, tf_optimizer_args)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.session.set_outer_optimizer(rule, args, self.max_grad_norm)
+        if lr is not None:
+            self.learning_rate = lr
+
+    def _log_grad_norm(self):
+        if getattr(self, 'max_grad_norm', None):
+            logger.logkv('GradNorm', self.session.grad_norm())
+
     def _log_step_sizes(self):
         if self.session.train_step_sizes:
             s = self.step_sizes

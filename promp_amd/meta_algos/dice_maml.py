@@ -20,13 +20,16 @@ from .base import MAMLAlgo
 
 class DICEMAML(MAMLAlgo):
     """Args (dice_maml.py:24-41): max_path_length, policy, name='dice_maml', learning_rate=1e-3, inner_lr, meta_batch_size,
-    num_inner_grad_steps, trainable_inner_step_size"""
+    num_inner_grad_steps, trainable_inner_step_size; tf_optimizer_cls, tf_optimizer_args, max_grad_norm (the outer step's rule,
+    its arguments and the clip by the meta-gradient's global norm: MAMLFirstOrderOptimizer's, which the reference does not pass on)"""
     inner_kind = _lib.INNER_DICE
 
-    def __init__(self, max_path_length, *args, name='dice_maml', learning_rate=1e-3, **kwargs):
+    def __init__(self, max_path_length, *args, name='dice_maml', learning_rate=1e-3, tf_optimizer_cls=None, tf_optimizer_args=None,
+                 max_grad_norm=None, **kwargs):
         super(DICEMAML, self).__init__(*args, **kwargs)
         self.max_path_length = max_path_length
         self.learning_rate = learning_rate
+        self._init_outer_optimizer(tf_optimizer_cls, tf_optimizer_args, max_grad_norm)
         self.name = name
         self._optimization_keys = ['observations', 'actions', 'adjusted_rewards', 'mask', 'agent_infos']
         self.last_stats = None
@@ -95,6 +98,7 @@ class DICEMAML(MAMLAlgo):
         if log:
             logger.logkv('LossBefore', loss)
             logger.logkv('LossAfter', loss)
+            self._log_grad_norm()
             self._log_step_sizes()
         self.last_stats = dict(loss_before=loss, loss_after=loss)
         self.session.param_version += 1

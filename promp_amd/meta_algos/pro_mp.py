@@ -14,14 +14,16 @@ class ProMP(MAMLAlgo):
     unimplemented in the reference, maml_first_order_optimizer.py:16-17,41,97-99; 1: full-batch epochs; LossBefore, LossAfter,
     KLInner and the KL-coefficient rule stay whole-batch quantities), clip_eps, target_inner_step, init_inner_kl_penalty,
     adaptive_inner_kl_penalty, anneal_factor (unused in the reference too: clip_eps is fed un-annealed,
-    pro_mp.py:182), inner_lr, meta_batch_size, num_inner_grad_steps, trainable_inner_step_size
+    pro_mp.py:182), inner_lr, meta_batch_size, num_inner_grad_steps, trainable_inner_step_size; tf_optimizer_cls,
+    tf_optimizer_args, max_grad_norm (MAMLPPOOptimizer's: the rule of the outer step, its arguments, the clip by the
+    meta-gradient's global norm -- logged as GradNorm when set)
     """
     inner_kind = _lib.INNER_RATIO
     outer_kind = _lib.OUTER_CLIP
 
     def __init__(self, *args, name='ppo_maml', learning_rate=1e-3, num_ppo_steps=5, num_minibatches=1, clip_eps=0.2,
                  target_inner_step=0.01, init_inner_kl_penalty=1e-2, adaptive_inner_kl_penalty=True, anneal_factor=1.0,
-                 **kwargs):
+                 tf_optimizer_cls=None, tf_optimizer_args=None, max_grad_norm=None, **kwargs):
         super(ProMP, self).__init__(*args, **kwargs)
         self.learning_rate = learning_rate
         self.num_ppo_steps = num_ppo_steps
@@ -35,7 +37,10 @@ class ProMP(MAMLAlgo):
         self._optimization_keys = ['observations', 'actions', 'advantages', 'agent_infos']
         self.name = name
         # pro_mp.py:59-62: the optimiser object a caller may reach for (algo.optimizer.loss / optimize / compute_stats)
-        self.optimizer = MAMLPPOOptimizer(learning_rate=learning_rate, max_epochs=num_ppo_steps, num_minibatches=num_minibatches)
+        self.optimizer = MAMLPPOOptimizer(tf_optimizer_cls, tf_optimizer_args, learning_rate=learning_rate, max_epochs=num_ppo_steps,
+                                          num_minibatches=num_minibatches, max_grad_norm=max_grad_norm)
+        self.learning_rate = self.optimizer._learning_rate        # (tf_optimizer_args['learning_rate'], if given)
+        self.max_grad_norm = self.optimizer._max_grad_norm
         self.optimizer.build_graph(self)
 
     def optimize_policy(self, all_samples_data, log=True):
@@ -58,6 +63,7 @@ class ProMP(MAMLAlgo):
             logger.logkv('LossAfter', loss_after)
             logger.logkv('KLInner', np.mean(inner_kls))
             logger.logkv('KLCoeffInner', np.mean(self.inner_kl_coeff))
+            self._log_grad_norm()
             self._log_step_sizes()
         self.last_stats = res
 

@@ -18,7 +18,7 @@ from .dice_maml import DICEMAML
 
 class VPG_DICEMAML(DICEMAML):
     """Args (vpg_dice_maml.py:21-28): max_path_length, policy, name='vpg_dice_maml', learning_rate=1e-3, inner_lr,
-    meta_batch_size, num_inner_grad_steps, trainable_inner_step_size"""
+    meta_batch_size, num_inner_grad_steps, trainable_inner_step_size; tf_optimizer_cls, tf_optimizer_args, max_grad_norm as DICEMAML"""
 
     def __init__(self, max_path_length, *args, name='vpg_dice_maml', **kwargs):
         super(VPG_DICEMAML, self).__init__(max_path_length, *args, name=name, **kwargs)
@@ -51,6 +51,7 @@ class VPG_DICEMAML(DICEMAML):
         if log:
             logger.logkv('LossBefore', res['loss_before'])
             logger.logkv('LossAfter', res['loss_after'])
+            self._log_grad_norm()
             self._log_step_sizes()
         self.last_stats = dict(loss_before=res['loss_before'], loss_after=res['loss_after'])
         self.session.param_version += 1

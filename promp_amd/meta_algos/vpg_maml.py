@@ -20,10 +20,12 @@ from .base import MAMLAlgo
 
 
 class VPGMAML(MAMLAlgo):
-    def __init__(self, *args, name='vpg_maml', learning_rate=1e-3, inner_type='likelihood_ratio', exploration=False, **kwargs):
+    def __init__(self, *args, name='vpg_maml', learning_rate=1e-3, inner_type='likelihood_ratio', exploration=False,
+                 tf_optimizer_cls=None, tf_optimizer_args=None, max_grad_norm=None, **kwargs):
         super(VPGMAML, self).__init__(*args, **kwargs)
         assert inner_type in ('log_likelihood', 'likelihood_ratio')
         self.name, self.learning_rate = name, learning_rate
+        self._init_outer_optimizer(tf_optimizer_cls, tf_optimizer_args, max_grad_norm)
         self.inner_type, self.exploration = inner_type, exploration
         self.inner_kind = _lib.INNER_LOGLIK if inner_type == 'log_likelihood' else _lib.INNER_RATIO
         self._optimization_keys = ['observations', 'actions', 'advantages', 'agent_infos'] + (['adj_avg_rewards'] if exploration else [])
@@ -72,6 +74,7 @@ class VPGMAML(MAMLAlgo):
         if log:
             logger.logkv('LossBefore', loss_before)
             logger.logkv('LossAfter', loss_after)
+            self._log_grad_norm()
             self._log_step_sizes()
         self.last_stats = dict(loss_before=loss_before, loss_after=loss_after)
         self.session.param_version += 1

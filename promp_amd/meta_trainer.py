@@ -96,6 +96,12 @@ class Trainer(object):
         self.policy.set_params(snapshot['policy_params'])
         self.policy.switch_to_pre_update()
         sess = self.policy.session
+        # the outer step's rule, arguments and clip (in front of the slots: a change of rule zeroes them); a snapshot from before
+        # they were kept loads as Adam with its defaults
+        oo = snapshot.get('outer_optimizer') or dict(rule='adam', args=None, max_grad_norm=None)
+        sess.set_outer_optimizer(oo['rule'], oo['args'], oo['max_grad_norm'])
+        if hasattr(self.algo, 'max_grad_norm'):
+            self.algo.max_grad_norm = oo['max_grad_norm']
         if snapshot.get('adam_m') is not None:
             sess.adam = (snapshot['adam_m'], snapshot['adam_v'], int(snapshot['adam_t']))
             if sess.ctx is not None:
@@ -114,12 +120,14 @@ class Trainer(object):
         self.start_itr = int(snapshot['itr']) + 1
 
     def get_itr_snapshot(self, itr):
-        """what is needed to resume: flat policy parameters, Adam state, KL coefficients, baseline coefficients"""
+        """what is needed to resume: flat policy parameters, the outer optimiser's rule, arguments and slots, KL coefficients,
+        baseline coefficients"""
         sess = self.policy.session
         ctx = sess.ctx
         adam_m, adam_v, adam_t = ctx.get_adam_state() if ctx is not None else (sess.adam or (None, None, 0))
         snap = dict(itr=itr, policy_params=self.policy.get_param_values(), adam_m=adam_m, adam_v=adam_v, adam_t=adam_t,
                     inner_kl_coeff=getattr(self.algo, 'inner_kl_coeff', None), baseline=self.baseline.get_param_values())
+        snap['outer_optimizer'] = sess.get_outer_optimizer()
         if sess.train_step_sizes:          # trainable_inner_step_size: the step sizes and their Adam slots are state too
             step_adam = sess.get_step_adam() or (None, None)
             snap.update(inner_step_sizes=sess.get_step_sizes(), step_adam_m=step_adam[0], step_adam_v=step_adam[1])

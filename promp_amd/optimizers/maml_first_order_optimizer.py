@@ -3,7 +3,8 @@
 Behaviour contract (reference: meta_policy_search/optimizers/maml_first_order_optimizer.py:5-163; what ProMP and VPG-MAML call
 through `self.optimizer`):
 
-  * `optimize(inputs)` takes `max_epochs` full-batch steps of tf.train.AdamOptimizer(learning_rate) on the meta-objective and returns
+  * `optimize(inputs)` takes `max_epochs` full-batch steps of tf_optimizer_cls(**tf_optimizer_args) -- tf.train.AdamOptimizer(learning_rate)
+    unless told otherwise -- on the meta-objective, the gradient clipped by its global norm first when `max_grad_norm` is set, and returns
     the loss BEFORE the first step (:82-115; `tolerance` is accepted and unused, as there, :97-113).  `num_minibatches` = B > 1 --
     documented there (:16-17) and left unimplemented (:41, :97-99) -- makes an epoch B Adam steps, one per minibatch: every task's
     paths of every sampling step are dealt to B shares (minibatch_assignment, drawn anew per epoch), minibatch j is the
@@ -55,15 +56,19 @@ class Optimizer(object):
 
 class MAMLFirstOrderOptimizer(Optimizer):
     """
-    Args (maml_first_order_optimizer.py:22-46): tf_optimizer_cls / tf_optimizer_args -- only Adam exists on the device; the class
-    argument is accepted for call compatibility and `tf_optimizer_args['learning_rate']` is honoured --, learning_rate, max_epochs,
-    tolerance (unused), num_minibatches (Adam steps per epoch, see above), verbose.
+    Args (maml_first_order_optimizer.py:22-46): tf_optimizer_cls -- None / 'adam', 'sgd' / 'gradient_descent', 'momentum', or a class
+    named AdamOptimizer, GradientDescentOptimizer or MomentumOptimizer; anything else is refused by name (_lib.outer_rule_id) --,
+    tf_optimizer_args -- beta1, beta2, epsilon (Adam), momentum, use_nesterov (Momentum), learning_rate; an unknown key is refused --,
+    learning_rate, max_epochs, tolerance (unused), num_minibatches (steps per epoch, see above), verbose, max_grad_norm (None: no
+    clipping; the reference has none).
     """
 
     def __init__(self, tf_optimizer_cls=None, tf_optimizer_args=None, learning_rate=1e-3, max_epochs=1, tolerance=1e-6,
-                 num_minibatches=1, verbose=False):
-        args = dict(tf_optimizer_args or {})
-        self._learning_rate = float(args.get('learning_rate', learning_rate))
+                 num_minibatches=1, verbose=False, max_grad_norm=None):
+        self._rule = _lib.outer_rule_id(tf_optimizer_cls)
+        self._rule_args, lr = _lib.outer_rule_args(self._rule, tf_optimizer_args)
+        self._max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self._learning_rate = float(learning_rate if lr is None else lr)
         self._max_epochs = int(max_epochs)
         self._tolerance = tolerance
         self._num_minibatches = int(num_minibatches)
@@ -77,6 +82,7 @@ class MAMLFirstOrderOptimizer(Optimizer):
         """`loss`: the algorithm plugin (a MAMLAlgo with a DeviceSession: .session, .inner_kind, .outer_kind and -- ProMP --
         .clip_eps, .inner_kl_coeff).  `target` / `input_ph_dict` are the reference's policy and placeholders: nothing to bind."""
         assert hasattr(loss, 'session'), 'build_graph binds the optimiser to an algorithm plugin (promp_amd.meta_algos.*)'
+        loss.session.set_outer_optimizer(self._rule, self._rule_args, self._max_grad_norm)
         self._algo = loss
         self._memo = None
 

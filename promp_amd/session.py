@@ -50,6 +50,7 @@ class DeviceSession:
         self.param_version = 0        # bumped by whatever changes the tasks' parameters (host-side caches key on it)
         self.learn_std = True
         self.min_std = 1e-6
+        self.outer = None             # set_outer_optimizer: (rule id, float32 [4] arguments, max_grad_norm); None: Adam's defaults
         self._upload_counter = 0      # never reset: a SamplesData from before a context re-creation can never match a later upload
         self._comm_ready = False      # the RCCL communicator is created once per session and moved across context re-creations
         # host-side statistics that span the whole meta-batch (reward moments, path statistics, E-MAML sums) cross the ranks
@@ -166,6 +167,8 @@ class DeviceSession:
                 self.ctx.set_step_sizes(self.step_sizes)
             self.ctx.set_learn_std(self.learn_std)
             self.ctx.set_min_std(self.min_std)
+            if self.outer is not None:             # (in front of the slots: a change of rule zeroes them)
+                self.ctx.set_outer_optimizer(*self.outer)
             if self.adam is not None:
                 self.ctx.set_adam_state(*self.adam)
             if self.train_step_sizes:
@@ -217,6 +220,32 @@ class DeviceSession:
         if self.ctx is not None and self.train_step_sizes:
             self.step_adam = self.ctx.get_step_size_adam_state()
         return self.step_adam
+
+    def set_outer_optimizer(self, rule=None, args=None, max_grad_norm=None):
+        """The rule every outer step takes (promp_set_outer_optimizer): `rule` as _lib.outer_rule_id takes it, `args` a dict with
+        tf_optimizer_args' keys (learning_rate is the caller's business) or the float[4], max_grad_norm None / 0: no clipping.
+        Kept by the session: a context re-created with more capacity carries it along."""
+        rid = _lib.outer_rule_id(rule) if not isinstance(rule, (int, np.integer)) else int(rule)
+        if args is None or isinstance(args, dict):
+            args = _lib.outer_rule_args(rid, args)[0]
+        c = 0.0 if max_grad_norm is None else float(max_grad_norm)
+        if not (c >= 0.0 and np.isfinite(c)):
+            raise _lib.PrompError('max_grad_norm %r must be finite and >= 0 (None / 0: no clipping)' % (max_grad_norm,))
+        outer = (rid, np.ascontiguousarray(args, dtype=np.float32), c)
+        if self.ctx is not None:
+            self.ctx.set_outer_optimizer(*outer)
+        if self.outer is not None and self.outer[0] != rid or self.outer is None and rid != 0:
+            self.adam = self.step_adam = None       # a new rule starts from zeroed slots and step count
+        self.outer = outer
+
+    def get_outer_optimizer(self):
+        """dict(rule=name, args=float32 [4], max_grad_norm=float or None)"""
+        rid, args, c = self.outer if self.outer is not None else (0, _lib.outer_rule_args(0)[0], 0.0)
+        return dict(rule=_lib.outer_rule_name(rid), args=np.array(args, dtype=np.float32), max_grad_norm=c if c > 0 else None)
+
+    def grad_norm(self):
+        """the unclipped global norm of the last gradient a clipped step was taken on (promp_get_grad_norm)"""
+        return self.ensure().grad_norm()
 
     def next_slot(self):
         slot = self.step_cursor % (self.K + 1)

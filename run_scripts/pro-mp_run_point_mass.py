@@ -57,6 +57,8 @@ def main(config):
     algo = ProMP(policy=policy, inner_lr=config['inner_lr'], meta_batch_size=config['meta_batch_size'],
                  num_inner_grad_steps=config['num_inner_grad_steps'], learning_rate=config['learning_rate'],
                  num_ppo_steps=config['num_promp_steps'], num_minibatches=config.get('num_minibatches', 1), clip_eps=config['clip_eps'],
+                 tf_optimizer_cls=config.get('outer_optimizer'), tf_optimizer_args=config.get('outer_optimizer_args'),
+                 max_grad_norm=config.get('max_grad_norm'),
                  target_inner_step=config['target_inner_step'], init_inner_kl_penalty=config['init_inner_kl_penalty'],
                  adaptive_inner_kl_penalty=config['adaptive_inner_kl_penalty'])
     trainer = Trainer(algo=algo, policy=policy, env=env, sampler=sampler, sample_processor=sample_processor,
@@ -72,6 +74,10 @@ if __name__ == '__main__':
     ap.add_argument('--n_itr', type=int, default=None)
     ap.add_argument('--num_minibatches', type=int, default=None,
                     help='Adam steps per epoch of the outer step: every task\'s paths are dealt to this many minibatches (default 1)')
+    ap.add_argument('--outer_optimizer', type=str, default=None, choices=['adam', 'sgd', 'gradient_descent', 'momentum'],
+                    help='update rule of the outer step (default adam)')
+    ap.add_argument('--adam_epsilon', type=float, default=None, help='epsilon of the outer Adam step (default 1e-8; PPO runs often use 1e-5)')
+    ap.add_argument('--max_grad_norm', type=float, default=None, help='clip the meta-gradient by its global norm (default: no clipping)')
     ap.add_argument('--quiet', action='store_true')
     args = ap.parse_args()
     cfg = dict(DEFAULT)
@@ -81,6 +87,12 @@ if __name__ == '__main__':
         cfg['n_itr'] = args.n_itr
     if args.num_minibatches is not None:
         cfg['num_minibatches'] = args.num_minibatches
+    if args.outer_optimizer is not None:
+        cfg['outer_optimizer'] = args.outer_optimizer
+    if args.adam_epsilon is not None:
+        cfg['outer_optimizer_args'] = dict(cfg.get('outer_optimizer_args') or {}, epsilon=args.adam_epsilon)
+    if args.max_grad_norm is not None:
+        cfg['max_grad_norm'] = args.max_grad_norm
     logger.configure(dir=args.dump_path or None, snapshot_mode='last_gap', snapshot_gap=50, quiet=args.quiet)
     if args.dump_path:
         json.dump({k: (list(v) if isinstance(v, tuple) else v) for k, v in cfg.items()}, open(os.path.join(args.dump_path, 'params.json'), 'w'))
