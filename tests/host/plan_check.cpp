@@ -9,7 +9,8 @@
 //                observation class
 //   step tables  the invariants the kernels rely on, for small, ragged, large and many-task layouts at 2, 8 and 256 CUs;
 //                malformed offsets are refused with their message (and, under the sanitizer, without a stray access);
-//                one item per task at 1 CU and the 256-row cut of 513 rows at 2 CUs (what tests/layered_checks.py builds on)
+//                one item per task at 1 CU and the 256-row cut of 513 rows at 2 CUs (what tests/layered_checks.py builds on);
+//                items, chain segments and workgroup offsets of the row cases of tests/fused_checks.py at 1 and 2 CUs
 //   gramt        the wave -> square map of k_gram_tiled
 #include "../../promp_amd/csrc/promp_plan.h"
 
@@ -250,6 +251,26 @@ static void check_shapes() {
     check_family(33, 9, {33, 65}, PROMP_ACT_TANH, Layered, 0, Layered);
     check_family(5, 2, {33, 20}, PROMP_ACT_TANH, Chain, 0, Chain);
     check_family(5, 9, {33, 20}, PROMP_ACT_TANH, Layered, 0, Layered);
+    // the shapes of tests/fused_checks.py (ROW_SHAPES, DICE_SHAPES, RANGE_SHAPES, EMU_SHAPES), one per instantiation of the three
+    // fused families: its cases reach the kernels they name only while these rows hold
+    check_family(7, 3, {32, 32}, PROMP_ACT_TANH, Chain, 0, Chain);
+    check_family(20, 6, {32, 64}, PROMP_ACT_TANH, Chain, 0, Chain);
+    check_family(29, 8, {64, 32}, PROMP_ACT_TANH, Chain, 0, Chain);
+    check_family(32, 1, {64, 64}, PROMP_ACT_TANH, Chain, 0, Chain);
+    check_family(11, 7, {48, 20}, PROMP_ACT_TANH, Chain, 0, Chain);                // padded to (64, 32)
+    check_family(9, 3, {32, 64}, PROMP_ACT_TANH, Chain, 0, Chain);
+    check_family(33, 3, {64, 64}, PROMP_ACT_TANH, Fp32, 0, Fp32);
+    check_family(64, 5, {64, 64}, PROMP_ACT_TANH, Fp32, 0, Fp32);
+    check_family(111, 8, {64, 64}, PROMP_ACT_TANH, Fp32, 0, Fp32);
+    check_family(40, 3, {48, 20}, PROMP_ACT_TANH, Fp32, 0, Fp32);                  // padded to (64, 64)
+    check_family(40, 3, {64, 64}, PROMP_ACT_TANH, Fp32, 0, Fp32);
+    check_family(20, 6, {128, 128}, PROMP_ACT_TANH, Split, 1, Fp32);               // k_wide<128, 2> under the FP32 switch
+    check_family(20, 8, {128, 128}, PROMP_ACT_TANH, Split, 1, Fp32);
+    check_family(127, 1, {128, 128}, PROMP_ACT_TANH, Split, 3, Fp32);
+    check_family(50, 4, {100, 100}, PROMP_ACT_TANH, Split, 1, Fp32);               // padded to (128, 128)
+    check_padding(11, 7, {48, 20}, {64, 32});
+    check_padding(40, 3, {48, 20}, {64, 64});
+    check_padding(50, 4, {100, 100}, {128, 128});
     // instances the launches are written for
     EXPECT(chain_ksteps(8) == 2 && chain_ksteps(9) == 5 && chain_ksteps(20) == 5 && chain_ksteps(21) == 8 && chain_ksteps(32) == 8, "chain_ksteps");
     EXPECT(wide_nob(32) == 2 && wide_nob(33) == 4 && wide_nob(64) == 4 && wide_nob(65) == 8 && wide_nob(128) == 8, "wide_nob");
@@ -374,7 +395,65 @@ static void check_long_items(const char* name, const std::vector<std::vector<int
         EXPECT(W[k].row_begin == want[k].first && W[k].row_end == want[k].second, "%s at %d CUs: item %zu is rows [%d, %d), expected [%d, %d)", name, n_cus,
                k, W[k].row_begin, W[k].row_end, want[k].first, want[k].second);
 }
+// The chain kernels' segment list (task, tile0, ntiles) and the workgroups' offsets into it must be exactly `want` / `want_wg`.
+// tests/fused_checks.py relies on it as on check_long_items: which of its row cases gives a wave several tiles, a workgroup
+// several segments, a task two partial rows or a segment with tile0 > 0 is decided here.
+struct Seg { int task, tile0, ntiles; };
+static void check_chain_segments(const char* name, const std::vector<std::vector<int>>& lengths, int n_cus, const std::vector<Seg>& want,
+                                 const std::vector<int>& want_wg) {
+    const Offsets o = offsets_of(lengths);
+    const int M = o.M, R = o.pro[o.n_paths];
+    StepTables T;
+    std::string why;
+    const int rc = build_step_tables(n_cus, 2 * n_cus + M, R, o.n_paths, M, o.n_paths, o.tpo.get(), o.pro.get(), &T, &why);
+    EXPECT(rc == 0, "%s at %d CUs: refused (%d): %s", name, n_cus, rc, why.c_str());
+    if (rc) return;
+    EXPECT(T.segs.size() == want.size(), "%s at %d CUs: %zu segments, expected %zu", name, n_cus, T.segs.size(), want.size());
+    if (T.segs.size() != want.size()) return;
+    for (size_t k = 0; k < want.size(); ++k)
+        EXPECT(T.segs[k].task == want[k].task && T.segs[k].tile0 == want[k].tile0 && T.segs[k].ntiles == want[k].ntiles,
+               "%s at %d CUs: segment %zu is task %d tiles [%d, +%d), expected task %d tiles [%d, +%d)", name, n_cus, k, T.segs[k].task,
+               T.segs[k].tile0, T.segs[k].ntiles, want[k].task, want[k].tile0, want[k].ntiles);
+    EXPECT(T.wg_off == want_wg, "%s at %d CUs: the workgroups' segment offsets differ (%zu workgroups, expected %zu)", name, n_cus,
+           T.wg_off.size() - 1, want_wg.size() - 1);
+    // a task's partial rows are its segments
+    int slot = 0;
+    for (int i = 0; i < M; ++i) {
+        int n = 0;
+        for (const Seg& s : want) n += s.task == i;
+        EXPECT(T.slot_chain[i] == slot && T.slot_chain[i + 1] == slot + n, "%s at %d CUs: task %d has partial rows [%d, %d), expected [%d, %d)", name, n_cus,
+               i, T.slot_chain[i], T.slot_chain[i + 1], slot, slot + n);
+        slot += n;
+    }
+}
+// the row cases of tests/fused_checks.py (ROW_CASES A-E, DICE_LENGTHS, the split-range batch): work table 0 and the segment table
+static void check_fused_row_cases() {
+    const std::vector<std::vector<int>> A{{16}, {17}, {64, 1}, {80}}, B{{200, 55}, {256}, {256, 1}}, C{{300, 21}, {1}, {130}},
+        D{{100}, {100}, {100}}, E{{513}}, dice{{256, 65}, {64, 1, 129}}, range{{160, 160}, {160, 160}};
+    // A: waves without a tile (1, 2 tiles on four waves), a second tile of one row (65 rows); a third 32-row round of one row and a
+    //    second 64-row round of one row on the cooperative kernels
+    check_long_items("fused rows A", A, 1, {{0, 16}, {16, 33}, {33, 98}, {98, 178}});
+    check_chain_segments("fused rows A", A, 1, {{0, 0, 1}, {1, 0, 2}, {2, 0, 5}, {3, 0, 5}}, {0, 4});
+    // B: four and five tiles per wave; 3 rounds of 64 + 63 rows, exactly 4, 4 + 1 row
+    check_long_items("fused rows B", B, 1, {{0, 255}, {255, 511}, {511, 768}});
+    check_chain_segments("fused rows B", B, 1, {{0, 0, 16}, {1, 0, 16}, {2, 0, 17}}, {0, 3});
+    // C: a one-row task between a 21-tile and a 9-tile one
+    check_long_items("fused rows C", C, 1, {{0, 321}, {321, 322}, {322, 452}});
+    check_chain_segments("fused rows C", C, 1, {{0, 0, 21}, {1, 0, 1}, {2, 0, 9}}, {0, 3});
+    // D: the middle task split between the two workgroups at tile 4 (two partial rows, a segment with tile0 != 0)
+    check_long_items("fused rows D", D, 2, {{0, 100}, {100, 200}, {200, 300}});
+    check_chain_segments("fused rows D", D, 2, {{0, 0, 7}, {1, 0, 4}, {1, 4, 3}, {2, 0, 7}}, {0, 2, 4});
+    // E: tile0 = 20; cooperative items that begin 256 rows into the task
+    check_long_items("fused rows E", E, 2, {{0, 256}, {256, 513}});
+    check_chain_segments("fused rows E", E, 2, {{0, 0, 20}, {0, 20, 13}}, {0, 1, 2});
+    check_long_items("fused dice lengths", dice, 1, {{0, 321}, {321, 515}});
+    check_chain_segments("fused dice lengths", dice, 1, {{0, 0, 21}, {1, 0, 13}}, {0, 2});
+    // check_split_range at M = 2, P = 2, T = 160 on one unit: one workgroup walks two 20-tile segments
+    check_long_items("fused split range", range, 1, {{0, 320}, {320, 640}});
+    check_chain_segments("fused split range", range, 1, {{0, 0, 20}, {1, 0, 20}}, {0, 2});
+}
 static void check_step_tables() {
+    check_fused_row_cases();
     // one compute unit: one item per task, whatever the row counts (the work-item lengths of tests/layered_checks.py)
     check_long_items("one task, one item", {{300, 21}}, 1, {{0, 321}});
     check_long_items("three ragged tasks, one item each", {{300, 21}, {256, 256, 1}, {1}}, 1, {{0, 321}, {321, 834}, {834, 835}});

@@ -80,15 +80,20 @@ WIDTH_CASES = {
 }
 
 
-def long_items(monkeypatch, lib, max_cus=1, gen_fp32=False):
+def long_items(monkeypatch, lib, max_cus=1, gen_fp32=False, wide_fp32=None):
     """Plan every context from here on for `max_cus` compute units (PROMP_MAX_CUS), optionally on the exact-FP32 GEMMs
     (PROMP_GEN_FP32=1: k_gen_linear / k_gen_wgrad), and see that a context took the figure: with it ignored the tests of this
-    module would run 16-row items and check nothing new."""
+    module would run 16-row items and check nothing new.  wide_fp32 (tests/fused_checks.py): True sets PROMP_WIDE_FP32=1 (the
+    (128,128) shapes on k_wide_* instead of k_wb_*), False clears it, None leaves it as it is."""
     monkeypatch.setenv('PROMP_MAX_CUS', str(max_cus))
     if gen_fp32:
         monkeypatch.setenv('PROMP_GEN_FP32', '1')
     else:
         monkeypatch.delenv('PROMP_GEN_FP32', raising=False)
+    if wide_fp32:
+        monkeypatch.setenv('PROMP_WIDE_FP32', '1')
+    elif wide_fp32 is not None:
+        monkeypatch.delenv('PROMP_WIDE_FP32', raising=False)
     ctx = _lib.Context(1, 3, 2, (8, 8, 8), 1, max_rows=16, max_paths=1, lib=lib)
     try:
         n_cus = ctx.device_info()['n_cus']
@@ -106,34 +111,41 @@ def shape_kwargs(lengths, hidden, O, A, hidden_act='tanh', output_act=None, laye
                 output_act=output_act)
 
 
-def report(label, worst):
-    print('layered %s: %s' % (label, '  '.join('%s %.2e' % kv for kv in sorted(worst.items())) or 'nothing compared'))
+def report(label, worst, family='layered'):
+    print('%s %s: %s' % (family, label, '  '.join('%s %.2e' % kv for kv in sorted(worst.items())) or 'nothing compared'))
 
 
-def run_check(lib, label, what, seed, shape, **kw):
+def run_check(lib, label, what, seed, shape, family='layered', **kw):
     """one of parity_checks' comparisons on explicit path lengths; its worst figures are printed whether it passes or not
-    (loss / kl: fraction of rtol 1e-4 + atol 1e-6; grad / hvp / meta_grad / adapt: of the reference's max-norm, bound 1e-4)"""
+    (loss / kl: fraction of rtol 1e-4 + atol 1e-6; grad / hvp / meta_grad / adapt: of the reference's max-norm, bound 1e-4).
+    family: the first word of the printed line (tests/fused_checks.py prints 'fused').  meta: K = 1 and one epoch unless given."""
     worst = {}
     fn = dict(loss_grad=pc.check_loss_grad, hvp=pc.check_hvp, meta=pc.check_meta)[what]
     if what == 'meta':
-        kw = dict(kw, K=1, epochs=1)
+        kw = dict(dict(K=1, epochs=1), **kw)
     try:
         fn(lib, seed, worst=worst, **dict(shape, **kw))
     finally:
-        report('%s %s' % (label, what), worst)
+        report('%s %s' % (label, what), worst, family)
     return worst
 
 
 # ---- a condition on the INPUTS (oracle alone, no kernel): a dropped row must show
-@functools.lru_cache(maxsize=None)
 def last_row_sensitivity(case, shape):
-    """By how much (of the gradient's max-norm) the float64 oracle's gradient of the longest task moves when that task loses its last
-    row, at check_loss_grad's own inputs (seed, perturbed parameters, step 1's slab) for row case `case` at ROW_SHAPES[shape]: the
-    smallest figure over the three objectives and over two readings of "loses" (the task without the row; the row's terms missing
-    from the sums while the mean still divides by the full count, which is what a kernel that skipped the row would return --
-    exactly nothing under 'clip' when the clip is active on that row, so such a seed is not used)."""
-    lengths, seed = ROW_CASES[case]['lengths'], ROW_SEEDS[case, shape]
+    """dropped_row_sensitivity for row case `case` at ROW_SHAPES[shape], under the seed ROW_SEEDS holds for the pair"""
     O, A, hidden = (ROW_SHAPES[shape][k] for k in ('O', 'A', 'hidden'))
+    return dropped_row_sensitivity(tuple(map(tuple, ROW_CASES[case]['lengths'])), ROW_SEEDS[case, shape], O, A, tuple(hidden))
+
+
+@functools.lru_cache(maxsize=None)
+def dropped_row_sensitivity(lengths, seed, O, A, hidden):
+    """By how much (of the gradient's max-norm) the float64 oracle's gradient of the longest task moves when that task loses its last
+    row, at check_loss_grad's own inputs (seed, perturbed parameters, step 1's slab) for the path lengths `lengths` (a tuple of
+    tuples) at a policy shape: the smallest figure over the three objectives and over two readings of "loses" (the task without the
+    row; the row's terms missing from the sums while the mean still divides by the full count, which is what a kernel that skipped
+    the row would return -- exactly nothing under 'clip' when the clip is active on that row, so such a seed is not used).
+    tests/fused_checks.py asks the same of its own cases."""
+    lengths = [list(lens) for lens in lengths]
     theta, all_slabs, _ = helpers.make_promp_case(seed, len(lengths), None, None, O, A, hidden, 1, lengths_per_task=lengths)
     spec = op.PolicySpec(O, A, hidden)
     rng = np.random.RandomState(seed + 1)

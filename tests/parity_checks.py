@@ -321,12 +321,14 @@ def of_tolerance(got, want, rtol, atol):
 
 
 def check_loss_grad(lib, seed, M, P, T, O, A, hidden, ragged=False, compact_log_std=False, low_log_std=False, min_std=1e-6,
-                    hidden_act='tanh', output_act=None, lengths_per_task=None, worst=None):
+                    hidden_act='tanh', output_act=None, lengths_per_task=None, worst=None, kl_objective=False):
     """low_log_std: some log_std entries below log(min_std), i.e. the tf.maximum clip is active.  At the default min_std = 1e-6
     values are not comparable in float32 (see below); with a benign min_std (0.5) they are, and are compared.
     lengths_per_task: explicit path lengths (helpers.make_promp_case) instead of P paths of T rows.
     worst: a dict that collects the largest errors ('loss' and 'kl' as fractions of their tolerance, 'grad' of the max-norm),
-    noted BEFORE each assertion."""
+    noted BEFORE each assertion.
+    kl_objective: objective kind 3 as well, the mean KL itself (LOSS_KL, the TRPO constraint): its value against the oracle's KL and
+    its gradient against the oracle's grad_kl, at the same tolerances ('grad_kl' in worst)."""
     theta, all_slabs, all_paths = helpers.make_promp_case(seed, M, P, T, O, A, hidden, 1, ragged=ragged,
                                                           low_log_std=low_log_std, min_std=min_std, lengths_per_task=lengths_per_task)
     spec = op.PolicySpec(O, A, hidden, min_std=min_std, hidden_act=hidden_act, output_act=output_act or 'identity')
@@ -337,18 +339,19 @@ def check_loss_grad(lib, seed, M, P, T, O, A, hidden, ragged=False, compact_log_
     rng = np.random.RandomState(seed + 1)
     th = (theta + (0.0 if low_log_std else 0.02) * rng.randn(M, theta.size)).astype(np.float32)
     ctx.set_task_thetas(th)
-    for kind, name in ((0, 'ratio'), (1, 'clip'), (2, 'loglik')):
+    for kind, name in ((0, 'ratio'), (1, 'clip'), (2, 'loglik')) + (((_lib.LOSS_KL, 'kl'),) if kl_objective else ()):
         for clip_ls in ((True,) if low_log_std else (False, True)):
             g, l, k = ctx.eval_loss_grad(1, kind, clip_eps=0.3, clip_log_std=clip_ls)
             for i in range(M):
                 r = pm.loss_and_grad(spec, th[i].astype(np.float64), all_slabs[1][i], name, clip_ls, clip_eps=0.3)
+                g_ref, g_key = (r['grad_kl'], 'grad_kl') if name == 'kl' else (r['grad'], 'grad')
                 if comparable:
                     note_worst(worst, 'loss', of_tolerance(l[i], r['loss'], 1e-4, 1e-6))
                     note_worst(worst, 'kl', of_tolerance(k[i], r['kl'], 1e-4, 1e-6))
-                    note_worst(worst, 'grad', rel_max(g[i], r['grad']))
+                    note_worst(worst, g_key, rel_max(g[i], g_ref))
                     np.testing.assert_allclose(l[i], r['loss'], rtol=1e-4, atol=1e-6)
                     np.testing.assert_allclose(k[i], r['kl'], rtol=1e-4, atol=1e-6)
-                    assert rel_max(g[i], r['grad']) < 1e-4, (name, i, rel_max(g[i], r['grad']))
+                    assert rel_max(g[i], g_ref) < 1e-4, (name, i, rel_max(g[i], g_ref))
                 else:
                     # sigma = 1e-6 makes z = (a-mu)/sigma amplify the float32 rounding of mu by 1e6, so values
                     # are not comparable in float32 (the oracle's mask arithmetic is pinned in float64 by
@@ -423,7 +426,7 @@ def check_split_accuracy(lib, hidden, O, A, seed=11, M=2, P=2, T=48, tol=2.5e-6,
     ctx.close()
 
 
-def check_split_range(lib, hidden, O, A, seed=17, M=2, P=2, T=48, tol=2.5e-6, expect_redo=True, tail_from=7 / 16):
+def check_split_range(lib, hidden, O, A, seed=17, M=2, P=2, T=48, tol=2.5e-6, expect_redo=True, tail_from=7 / 16, min_pass_redo=0):
     """The FP16 split of the fused kernels has a range; the kernels keep every split operand inside it with exact powers of two that
     follow the data (promp_device.h: split_pair; promp_kernels_pass.h: pass_cotangent_scale, k_obs_range).  Float32 has no such
     range, so the results must not depend on any of this:
@@ -433,7 +436,9 @@ def check_split_range(lib, hidden, O, A, seed=17, M=2, P=2, T=48, tol=2.5e-6, ex
       * observations of size 3e3 and 3e-4, the hidden_0 kernel scaled the other way so that the network computes the same function
         (per-task power of two on the observations, its inverse on the kernel, taken off the kernel's gradient again),
       * a direction of size 1e-9 and 1e6 in the R-operator pass.
-    Each against the float64 oracle at the accuracy guard's tolerance."""
+    Each against the float64 oracle at the accuracy guard's tolerance.
+    min_pass_redo: the heavy-tailed case's two gradient passes must have walked at least this many segments again
+    (split_events()['pass_segments']; 2 where one workgroup walks two segments and the second has to be redone like the first)."""
     theta, all_slabs, all_paths = helpers.make_promp_case(seed, M, P, T, O, A, hidden, 1)
     spec = op.PolicySpec(O, A, hidden)
     rng = np.random.RandomState(seed + 1)
@@ -476,6 +481,8 @@ def check_split_range(lib, hidden, O, A, seed=17, M=2, P=2, T=48, tol=2.5e-6, ex
         ev = ctx.split_events()
         if name == 'heavy_tail':
             redone = ev['pass_segments']
+            print('split_range %s obs %d act %d M=%d P=%d T=%d: heavy tail walked %d pass segment(s) again' % (hidden, O, A, M, P, T, redone))
+            assert redone >= min_pass_redo, (redone, min_pass_redo)
         for vscale in (1.0, 1e-9, 1e6):
             v = (vscale * rng.randn(M, theta.size)).astype(np.float32)
             v[:, :O * hidden[0]] *= np.float32(1.0 / oscale)      # (a direction in the parameters' own units)
@@ -601,11 +608,14 @@ def check_meta(lib, seed, M, P, T, O, A, hidden, K, ragged=False, epochs=2, comp
     return res
 
 
-def check_primal_cache(lib, seed, M, P, T, O, A, hidden, K=1, ragged=True):
+def check_primal_cache(lib, seed, M, P, T, O, A, hidden, K=1, ragged=True, lengths_per_task=None, worst=None):
     """the second-order pass reading the gradient pass's activations / means back from the primal cache must agree with
     the recomputing path to float32 rounding (tile blocks of ragged tasks, partial last tiles, every adaptation step),
-    and both with the oracle; everything that does not go through the cache must not change at all"""
-    theta, all_slabs, all_paths = helpers.make_promp_case(seed, M, P, T, O, A, hidden, K, ragged=ragged)
+    and both with the oracle; everything that does not go through the cache must not change at all.
+    lengths_per_task (then ragged is not looked at), worst ('cache_on_off', 'cache_on', 'cache_off': of the meta-gradient's
+    max-norm): as check_loss_grad's"""
+    theta, all_slabs, all_paths = helpers.make_promp_case(seed, M, P, T, O, A, hidden, K, ragged=ragged and lengths_per_task is None,
+                                                          lengths_per_task=lengths_per_task)
     spec = op.PolicySpec(O, A, hidden)
     alpha = np.full(spec.n_params, 0.1, np.float32)
     eta = np.array([5e-4, 1e-3, 2e-3][:K], np.float32)
@@ -624,8 +634,11 @@ def check_primal_cache(lib, seed, M, P, T, O, A, hidden, K=1, ragged=True):
     (g_on, st_on), (g_off, st_off) = out
     for key in ('loss', 'inner_kl', 'outer_kl'):
         np.testing.assert_array_equal(st_on[key], st_off[key])
+    note_worst(worst, 'cache_on_off', rel_max(g_on, g_off.astype(np.float64)))
     assert rel_max(g_on, g_off.astype(np.float64)) < 2e-6
     r = pm.meta_objective_and_grad(spec, theta.astype(np.float64), all_slabs, alpha.astype(np.float64), eta.astype(np.float64), 0.3)
+    note_worst(worst, 'cache_on', rel_max(g_on, r['grad']))
+    note_worst(worst, 'cache_off', rel_max(g_off, r['grad']))
     assert rel_max(g_on, r['grad']) < 1e-4
     assert rel_max(g_off, r['grad']) < 1e-4
 

@@ -21,19 +21,23 @@ def lib():
     return devlib.gpu_library()
 
 
-# The cooperative kernels walk a work item in rounds of 32 rows, the layer-by-layer ones in blocks of 64 / 256.
-# `trim` entries (step, task, path, length) cut paths short: a path of ONE row, row counts that leave a partial last round.
+# The cooperative kernels walk a work item in rounds of 64 rows (32 in the R-operator pass), the layer-by-layer ones in blocks of
+# 64 / 256 -- but a work item is what build_step_tables deals: one workgroup per compute unit, capped at one per 16-row tile.  On the
+# 256 compute units of an MI355X every item of these small batches is ONE tile of at most 16 rows, so no case here takes a second
+# round on hardware (the row counts noted below are those of a task, not of an item); tests/fused_checks.py and
+# tests/layered_checks.py plan for one compute unit and do.
+# `trim` entries (step, task, path, length) cut paths short: a path of ONE row, row counts that leave a partial last tile.
 CASES = OrderedDict([
     # ---- CoopFp32: (64,64) with obs_dim > 32
     ('coopfp32_64_obs40', ds.case(401, M=3, P=3, T=50, O=40, A=3, hidden=(64, 64), ragged=True, trim=[(0, 1, 2, 1)])),
-    ('coopfp32_64_obs111', ds.case(402, M=3, P=4, T=45, O=111, A=8, hidden=(64, 64))),                     # 180 rows = 5 x 32 + 20
+    ('coopfp32_64_obs111', ds.case(402, M=3, P=4, T=45, O=111, A=8, hidden=(64, 64))),                     # 180 rows a task: eleven tiles + 4 rows
     # ---- CoopSplit: (128,128), one per observation class (obs_dim <= 63 / <= 111 / <= 127)
     ('coopsplit_obs20', ds.case(403, M=3, P=3, T=60, O=20, A=6, hidden=(128, 128), ragged=True)),
     ('coopsplit_obs111', ds.case(404, M=3, P=4, T=45, O=111, A=8, hidden=(128, 128), trim=[(0, 0, 3, 1), (1, 2, 0, 7)])),
     ('coopsplit_obs127', ds.case(405, M=2, P=3, T=70, O=127, A=8, hidden=(128, 128), ragged=True)),
     # ---- zero-padded widths: (100,100) runs in (128,128), (48,20) at obs 40 in (64,64)
     ('padded_100_100', ds.case(406, M=3, P=3, T=50, O=50, A=4, hidden=(100, 100), ragged=True)),
-    ('padded_48_20', ds.case(407, M=2, P=4, T=37, O=40, A=3, hidden=(48, 20))),                             # 148 rows = 4 x 32 + 20
+    ('padded_48_20', ds.case(407, M=2, P=4, T=37, O=40, A=3, hidden=(48, 20))),                             # 148 rows a task: nine tiles + 4 rows
     # ---- Layered
     ('layered_64x3_k2', ds.case(408, M=2, P=3, T=40, O=20, A=6, hidden=(64, 64, 64), K=2, alpha=0.05, ragged=True)),
     ('layered_256_256', ds.case(409, M=2, P=3, T=90, O=20, A=6, hidden=(256, 256), trim=[(0, 0, 0, 1)])),  # task 0: 181 rows
