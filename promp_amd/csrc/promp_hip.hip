@@ -798,15 +798,63 @@ static int exchange_sums_raw(promp_ctx* c, float* buf, size_t n) {
 // exchange buffer); the ones that would go on to USE a mean (an Adam step, a conjugate-gradient product) refuse instead.
 static bool sharded_without_comm(const promp_ctx* c) { return c->d.n_tasks_global > c->d.n_tasks && c->comm == nullptr; }
 
-// the floats of c->red one exchange moves: [grad Theta | K + 2 scalars], and behind them the step-size gradient's Theta sums
-static size_t red_count(const promp_ctx* c, bool with_sizes) {
-    return (size_t)(with_sizes ? 2 : 1) * c->NP + c->d.num_inner_steps + 2;
-}
 // what the *_ss instances of the final stage take beside theta's arguments (promp_kernels_step_sizes.h)
 static StepSizeArgs step_size_args(const promp_ctx* c) {
     StepSizeArgs s;
     s.galpha = c->galpha; s.alpha = c->step_sizes; s.alpha_m = c->ss_m; s.alpha_v = c->ss_v; s.alpha_grad_mean = c->ss_grad;
     return s;
+}
+
+// ---- the final stage of an evaluation (promp_kernels_policy.h), launched from final_stage_launch's decision (promp_plan.h) ----
+static FinalLaunch final_launch(const promp_ctx* c, bool stepping, bool split_wanted, bool sizes) {
+    return final_stage_launch(final_stage_plan(c->outer, c->sw, stepping, split_wanted), c->NP, c->d.num_inner_steps, sizes);
+}
+// The mean kernels' arguments: everything but lr_t (outer_step_begins).  stats: the slot to write; publish: promp_optimize_begin's
+// last launch.
+static AdamArgs adam_args(const promp_ctx* c, float* stats, const float* eta, bool publish, bool do_update) {
+    AdamArgs ad;
+    ad.theta = c->theta; ad.m = c->adam_m; ad.v = c->adam_v; ad.red = c->red; ad.grad_mean = c->grad_mean;
+    ad.stats = stats; ad.NP = c->NP; ad.K = c->d.num_inner_steps; ad.A = c->d.act_dim;
+    for (int k = 0; k < PROMP_ETA_MAX; ++k) ad.eta[k] = k < ad.K ? eta[k] : 0.f;
+    ad.host_stats = publish ? c->stats_host.p : nullptr; ad.host_seq = c->stats_seq_host; ad.seq = c->stats_seq;
+    ad.inv_tasks = 1.0f / (float)c->d.n_tasks_global;
+    ad.do_update = do_update ? 1 : 0;
+    ad.n_trainable = c->learn_std ? c->NP : c->NP - c->d.act_dim;
+    ad.lr_t = 0.f;
+    return ad;
+}
+// A step is about to be enqueued: what was derived from theta (and, sizes, from the step sizes) is stale, the smallest log_std
+// entry is unknown until the next publication, and the step count advances.  Returns the lr_t the launch carries.
+static float outer_step_begins(promp_ctx* c, bool sizes, float lr) {
+    c->theta_version = ++c->version_counter;
+    if (sizes) c->sizes_version = ++c->version_counter;
+    c->ls_known = false;
+    c->adam_t += 1;
+    return outer_lr_t(c->outer, lr, c->adam_t);
+}
+// One launch of the final stage.  f alone: the task sums (the split route's first half; promp_constraint_hvp); ad alone: mean +
+// step on the exchanged sums (its second half; promp_adam_step); both: sum + step in one launch.
+static int launch_final_stage(promp_ctx* c, const FinalLaunch& L, const FinalArgs* f, const AdamArgs* ad) {
+    const StepSizeArgs ss = step_size_args(c);
+    const OuterOptArgs oo = outer_opt_args(c->outer);
+    hipStream_t s = c->stream;
+    if (!ad) {
+        if (L.sizes) PROMP_LAUNCH(k_reduce_final_ss, dim3(L.reduce_grid), 256, 0, s, *f, ss.galpha);
+        else PROMP_LAUNCH(k_reduce_final, dim3(L.reduce_grid), 256, 0, s, *f);
+    } else if (!f) {
+        if (L.general && L.sizes) PROMP_LAUNCH(k_mean_outer_ss, dim3(L.mean_grid), 256, 0, s, *ad, ss, oo, c->grad_norm.p);
+        else if (L.general) PROMP_LAUNCH(k_mean_outer, dim3(L.mean_grid), 256, 0, s, *ad, oo, c->grad_norm.p);
+        else if (L.sizes) PROMP_LAUNCH(k_mean_adam_ss, dim3(L.mean_grid), 256, 0, s, *ad, ss);
+        else PROMP_LAUNCH(k_mean_adam, dim3(L.mean_grid), 256, 0, s, *ad);
+    } else {
+        if (L.general && L.sizes) PROMP_LAUNCH(k_final_outer_ss, dim3(L.fused_grid), 256, 0, s, *f, *ad, ss, oo);
+        else if (L.general) PROMP_LAUNCH(k_final_outer, dim3(L.fused_grid), 256, 0, s, *f, *ad, oo);
+        else if (L.sizes) PROMP_LAUNCH(k_final_adam_ss, dim3(L.fused_grid), 256, 0, s, *f, *ad, ss);
+        else PROMP_LAUNCH(k_final_adam, dim3(L.fused_grid), 256, 0, s, *f, *ad);
+    }
+    if (ad && L.general && oo.max_norm > 0.f) c->norm_valid = true;
+    HIPCHECK(hipGetLastError());
+    return 0;
 }
 
 // The step as a policy pass is to see it.  The counts, flags and version that the step's entry points keep in StepData reach
@@ -906,50 +954,17 @@ int enqueue_meta_on(promp_ctx* c, const EvalSet& E, float clip_eps, const float*
     f.lam = c->lam; f.NP = NP; f.K = K; f.n_tasks = M;
     f.scal_inner = E.scal_inner; f.scal_outer = c->scal_outer; f.red = c->red; f.want_grad = want_grad ? 1 : 0;
     c->red_has_sizes = ag;
-    const unsigned final_blocks = (unsigned)((red_count(c, ag) + 63) / 64);
-    // several ranks (or an external collective: more global than local tasks): sums first, mean + Adam after the exchange;
+    // several ranks (or an external collective: more global than local tasks): sums first, mean + step after the exchange;
     // a clipped step as well (the norm of ALL entries comes first), and settings that are not the default ones step in the
-    // general kernels (final_stage_plan)
-    const FinalPlan fp = final_stage_plan(c->outer, c->sw, do_adam, c->nranks > 1 || c->force_split || c->d.n_tasks_global != c->d.n_tasks);
-    const bool split = fp.split;
-    if (split) {
-        if (ag) PROMP_LAUNCH(k_reduce_final_ss, dim3(final_blocks), 256, 0, c->stream, f, (const float*)c->galpha);
-        else PROMP_LAUNCH(k_reduce_final, dim3(final_blocks), 256, 0, c->stream, f);
-        HIPCHECK(hipGetLastError());
-        if (exchange_sums(c, c->red, red_count(c, ag))) return -4;      // (one exchange per epoch, with or without the step sizes)
+    // general kernels (final_stage_plan).  One rank: nothing in between, one launch.
+    const FinalLaunch L = final_launch(c, do_adam, c->nranks > 1 || c->force_split || c->d.n_tasks_global != c->d.n_tasks, ag);
+    if (L.split) {
+        if (launch_final_stage(c, L, &f, nullptr)) return -2;
+        if (exchange_sums(c, c->red, L.red_count)) return -4;      // (one exchange per epoch, with or without the step sizes)
     }
-    AdamArgs ad;
-    ad.theta = c->theta; ad.m = c->adam_m; ad.v = c->adam_v; ad.red = c->red; ad.grad_mean = c->grad_mean;
-    ad.stats = c->stats + (size_t)c->stats_slot * (K + 2); ad.NP = NP; ad.K = K; ad.A = c->d.act_dim;
-    for (int k = 0; k < PROMP_ETA_MAX; ++k) ad.eta[k] = k < K ? eta_host[k] : 0.f;
-    ad.host_stats = c->publish_next ? c->stats_host.p : nullptr; ad.host_seq = c->stats_seq_host; ad.seq = c->stats_seq;
-    ad.inv_tasks = 1.0f / (float)c->d.n_tasks_global;
-    ad.do_update = do_adam ? 1 : 0;
-    ad.n_trainable = c->learn_std ? NP : NP - c->d.act_dim;
-    ad.lr_t = 0.f;
-    if (do_adam) {
-        c->theta_version = ++c->version_counter;     // (the smallest log_std entry is unknown until the next publication)
-        if (ag) c->sizes_version = ++c->version_counter;
-        c->ls_known = false;
-        c->adam_t += 1;
-        ad.lr_t = outer_lr_t(c->outer, lr, c->adam_t);
-    }
-    if (fp.general) {
-        const OuterOptArgs oo = outer_opt_args(c->outer);
-        if (ag) {
-            const StepSizeArgs ss = step_size_args(c);
-            if (split) PROMP_LAUNCH(k_mean_outer_ss, dim3((2 * NP + 1 + 255) / 256), 256, 0, c->stream, ad, ss, oo, c->grad_norm.p);
-            else PROMP_LAUNCH(k_final_outer_ss, dim3(final_blocks + 1), 256, 0, c->stream, f, ad, ss, oo);
-        } else if (split) PROMP_LAUNCH(k_mean_outer, dim3((NP + 1 + 255) / 256), 256, 0, c->stream, ad, oo, c->grad_norm.p);
-        else PROMP_LAUNCH(k_final_outer, dim3(final_blocks + 1), 256, 0, c->stream, f, ad, oo);
-        if (oo.max_norm > 0.f) c->norm_valid = true;
-    } else if (ag) {
-        const StepSizeArgs ss = step_size_args(c);
-        if (split) PROMP_LAUNCH(k_mean_adam_ss, dim3((2 * NP + 1 + 255) / 256), 256, 0, c->stream, ad, ss);
-        else PROMP_LAUNCH(k_final_adam_ss, dim3(final_blocks + 1), 256, 0, c->stream, f, ad, ss);
-    } else if (split) PROMP_LAUNCH(k_mean_adam, dim3((NP + 1 + 255) / 256), 256, 0, c->stream, ad);
-    else PROMP_LAUNCH(k_final_adam, dim3(final_blocks + 1), 256, 0, c->stream, f, ad);   // one rank: nothing in between
-    HIPCHECK(hipGetLastError());
+    AdamArgs ad = adam_args(c, c->stats + (size_t)c->stats_slot * (K + 2), eta_host, c->publish_next, do_adam);
+    if (do_adam) ad.lr_t = outer_step_begins(c, ag, lr);
+    if (launch_final_stage(c, L, L.split ? nullptr : &f, &ad)) return -2;
     for (int k = 0; k <= K && E.full; ++k) E.full[k].dirty = true;
     return 0;
 }
@@ -1323,7 +1338,7 @@ int promp_ctx_create(promp_ctx** out, int device_id, const promp_dims* user_dims
     if (c->partials.alloc((size_t)c->max_work * c->partial_stride)) return -2;
     if (c->scal_inner.alloc((size_t)K * M * 2) || c->scal_outer.alloc((size_t)M * 2)) return -2;
     if (c->scal_tmp.alloc((size_t)M * 2)) return -2;
-    if (c->red.alloc(NP + K + 2) || c->grad_mean.alloc(NP)) return -2;
+    if (c->red.alloc(final_red_count(NP, K, false)) || c->grad_mean.alloc(NP)) return -2;
     if (c->stats.alloc((size_t)2 * (K + 2))) return -2;
     // (the baseline fit's partial Gram blocks and scratch matrices -- 2.7 GB per set at Humanoid's 757 columns -- are allocated by the
     //  first promp_process_samples that fits a baseline on that stream: fit_buffers())
@@ -1871,7 +1886,7 @@ int promp_set_train_step_sizes(promp_ctx* c, int on) {
         if (c->ss_grad.alloc(c->NP) || c->ss_m.alloc(c->NP) || c->ss_v.alloc(c->NP) || c->galpha.alloc(MNP)) return -2;
         {   // (into a temporary: a failed allocation leaves the context with the exchange buffer it had)
             DevBuf<float> red;
-            if (red.alloc(red_count(c, true))) return -2;
+            if (red.alloc(final_red_count(c->NP, c->d.num_inner_steps, true))) return -2;
             c->red = std::move(red);
         }
         // (ginner last: the guard above stands for all six)
@@ -2357,8 +2372,7 @@ static int enqueue_constraint_hvp(promp_ctx* c, const EvalSet& E, int inner_kind
     f.lam = c->wbuf; f.NP = NP; f.K = K; f.n_tasks = M;
     f.scal_inner = E.scal_inner; f.scal_outer = c->scal_outer; f.red = c->red; f.want_grad = 1;
     c->red_has_sizes = false;
-    PROMP_LAUNCH(k_reduce_final, dim3((NP + K + 2 + 63) / 64), 256, 0, c->stream, f);
-    HIPCHECK(hipGetLastError());
+    if (launch_final_stage(c, final_launch(c, false, true, false), &f, nullptr)) return -2;
     if (exchange_sums(c, c->red, (size_t)NP)) return -4;
     for (int k = 0; k <= K && E.full; ++k) E.full[k].dirty = true;
     return 0;
@@ -2472,29 +2486,10 @@ int promp_adam_step(promp_ctx* c, float lr) {
     if (c->train_sizes && !c->red_has_sizes)
         return fail(-3, "promp_adam_step: the step sizes are trained, but the exchange buffer holds no step-size gradient: the last "
                         "evaluation ran with the flag off, or was promp_constraint_hvp / promp_cg_solve (promp_meta_grad first)");
-    AdamArgs ad;
-    ad.theta = c->theta; ad.m = c->adam_m; ad.v = c->adam_v; ad.red = c->red; ad.grad_mean = c->grad_mean;
-    ad.stats = c->stats; ad.NP = c->NP; ad.K = c->d.num_inner_steps;
-    for (int k = 0; k < PROMP_ETA_MAX; ++k) ad.eta[k] = k < ad.K ? c->eta_last[k] : 0.f;
-    ad.host_stats = nullptr; ad.host_seq = nullptr; ad.seq = 0;
-    ad.inv_tasks = 1.0f / (float)c->d.n_tasks_global;
-    ad.do_update = 1;
-    ad.n_trainable = c->learn_std ? c->NP : c->NP - c->d.act_dim;
-    ad.A = c->d.act_dim;
-    c->theta_version = ++c->version_counter;
-    if (c->train_sizes) c->sizes_version = ++c->version_counter;
-    c->ls_known = false;
-    c->adam_t += 1;
-    ad.lr_t = outer_lr_t(c->outer, lr, c->adam_t);
-    if (final_stage_plan(c->outer, c->sw, true, true).general) {
-        const OuterOptArgs oo = outer_opt_args(c->outer);
-        if (c->train_sizes) PROMP_LAUNCH(k_mean_outer_ss, dim3((2 * c->NP + 1 + 255) / 256), 256, 0, c->stream, ad, step_size_args(c), oo, c->grad_norm.p);
-        else PROMP_LAUNCH(k_mean_outer, dim3((c->NP + 1 + 255) / 256), 256, 0, c->stream, ad, oo, c->grad_norm.p);
-        if (oo.max_norm > 0.f) c->norm_valid = true;
-    } else if (c->train_sizes) PROMP_LAUNCH(k_mean_adam_ss, dim3((2 * c->NP + 1 + 255) / 256), 256, 0, c->stream, ad, step_size_args(c));
-    else PROMP_LAUNCH(k_mean_adam, dim3((c->NP + 1 + 255) / 256), 256, 0, c->stream, ad);
-    HIPCHECK(hipGetLastError());
-    return 0;
+    // the split route's second half, on its own
+    AdamArgs ad = adam_args(c, c->stats, c->eta_last, false, true);
+    ad.lr_t = outer_step_begins(c, c->train_sizes, lr);
+    return launch_final_stage(c, final_launch(c, true, true, c->train_sizes), nullptr, &ad);
 }
 
 // MAMLFirstOrderOptimizer's tf_optimizer_cls(**tf_optimizer_args) and max_grad_norm (include/promp_hip.h).  Validated in the plan

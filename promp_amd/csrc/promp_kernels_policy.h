@@ -1,14 +1,18 @@
 // promp_kernels_policy.h -- task-level reductions, Adam and the rollout-time forward pass (reference rows a10-a14).
 //
-//   k_reduce_task  : fixed-order sum of a task's per-workgroup partials + the update that consumes it (the cooperative
-//                    kernels of promp_kernels_policy_wide.h; the chain kernels do this inside the pass launch)
+//   k_reduce_task  : fixed-order sum of a task's per-workgroup partials + the update that consumes it, in a launch of its own
+//                    behind the pass (every pass family's default since it was measured; k_chain_hvp's reduction inside the
+//                    pass launch stays available: promp_set_schedule)
+//   The final stage of an evaluation, each piece stated once: final_column_sum (one column of red, by task quarters),
+//   final_stats_row (the statistics from the K + 2 scalar sums), theta_entry_step / alpha_entry_step (one entry's step under a
+//   rule type of promp_kernels_step_sizes.h), and three bodies over them:
 //   k_reduce_final : task sum of the per-task gradients and scalars                          (K14)
 //   k_mean_adam    : mean over the global meta-batch + tf.train.AdamOptimizer step            (K14)
 //   k_final_adam   : the two above in one launch (single rank)
-//   k_mean_outer / k_final_outer : the general twins of k_mean_adam / k_final_adam -- any rule and arguments of
+//   k_mean_outer / k_final_outer : the mean and the fused body's general instances -- any rule and arguments of
 //                    promp_set_outer_optimizer, and in k_mean_outer the clip by the global norm; launched only when the settings
-//                    are not the default ones (final_stage_plan, promp_plan.h)
-//                    (their *_ss instances carry Theta more columns: trainable step sizes, promp_kernels_step_sizes.h;
+//                    are not the default ones (final_stage_plan, promp_plan.h, which also decides every grid)
+//                    (the *_ss instances carry Theta more columns: trainable step sizes, promp_kernels_step_sizes.h;
 //                    the plain ones are the launches and arguments of a library without the feature)
 //   k_policy_forward : mean network under each task's current parameters (get_actions)
 #pragma once
@@ -97,7 +101,6 @@ __global__ void __launch_bounds__(256) k_reduce_task_keep(ReduceArgs a, float* g
 //   red[NP+1+k]     = sum_i KL^k_i
 //   red[NP+1+K]     = sum_i outer KL_i
 //   red[NP+K+2+j]   = sum_i galpha[i][j]            (trainable step sizes only: Theta more columns behind the others)
-// grid = ceil((NP+K+2)/256)
 struct FinalArgs {
     const float* lam;
     int NP, K, n_tasks;
@@ -132,13 +135,9 @@ PROMP_DEV float final_quarter_sum(const float* rows, int NP, int n_tasks, int j,
     return s;
 }
 
-// grid = ceil((NP + K + 2) / 64) -- k_reduce_final_ss: ceil((2 NP + K + 2) / 64) --, block = 256: 64 columns x 4 task quarters.  Thread (c, q) adds the tasks i = q, q+4, ...
-// of column c (10 dependent-latency steps instead of 40 at M = 40); the four quarter sums are added in a fixed order.
+// The column sum: task quarter q of column j of red's layout above (0 past jend, the launch's last column + 1).
 template <bool SS>
-PROMP_DEV void reduce_final_body(const FinalArgs& a, const float* galpha, float (*part)[64]) {
-    const int c = threadIdx.x & 63, q = threadIdx.x >> 6;
-    const int j = blockIdx.x * 64 + c;
-    const int jend = a.NP + a.K + 2 + (SS ? a.NP : 0);
+PROMP_DEV float final_column_sum(const FinalArgs& a, const float* galpha, int j, int q, int jend) {
     float s = 0.f;
     if (j < a.NP) {
         if (a.want_grad) s = final_quarter_sum(a.lam, a.NP, a.n_tasks, j, q);
@@ -152,9 +151,22 @@ PROMP_DEV void reduce_final_body(const FinalArgs& a, const float* galpha, float 
     } else if (SS && j < jend) {
         s = final_quarter_sum(galpha, a.NP, a.n_tasks, j - (a.NP + a.K + 2), q);
     }
-    part[q][c] = s;
+    return s;
+}
+// the four quarter sums of column c, added in a fixed order
+PROMP_DEV float final_column_total(const float (*part)[64], int c) { return (part[0][c] + part[1][c]) + (part[2][c] + part[3][c]); }
+
+// grid = final_stage_launch's reduce_grid (promp_plan.h): ceil((NP + K + 2) / 64) -- k_reduce_final_ss: ceil((2 NP + K + 2) / 64) --,
+// block = 256: 64 columns x 4 task quarters.  Thread (c, q) adds the tasks i = q, q+4, ... of column c (10 dependent-latency
+// steps instead of 40 at M = 40).
+template <bool SS>
+PROMP_DEV void reduce_final_body(const FinalArgs& a, const float* galpha, float (*part)[64]) {
+    const int c = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const int j = blockIdx.x * 64 + c;
+    const int jend = a.NP + a.K + 2 + (SS ? a.NP : 0);
+    part[q][c] = final_column_sum<SS>(a, galpha, j, q, jend);
     __syncthreads();
-    if (q == 0 && j < jend) a.red[j] = (part[0][c] + part[1][c]) + (part[2][c] + part[3][c]);
+    if (q == 0 && j < jend) a.red[j] = final_column_total(part, c);
 }
 __global__ void __launch_bounds__(256) k_reduce_final(FinalArgs a) {
     __shared__ float part[4][64];
@@ -198,38 +210,47 @@ PROMP_DEV void publish_stats(const AdamArgs& a) {
     release_store_system(a.host_seq, a.seq);
 }
 
-// SS (k_mean_adam_ss, grid = ceil((2 NP + 1) / 256)): the step sizes' Adam step from red[NP + K + 2 + j] behind theta's
-template <bool SS>
-PROMP_DEV void mean_adam_body(const AdamArgs& a, const StepSizeArgs& ss) {
+// The statistics row, by one thread: sums[0] = sum_i J_i, sums[1..K] = sum_i KL^k_i, sums[K + 1] = sum_i outer KL_i
+PROMP_DEV void final_stats_row(const AdamArgs& a, const float* sums) {
+    float pen = 0.f;
+    for (int k = 0; k < a.K; ++k) {
+        const float ikl = sums[1 + k] * a.inv_tasks;
+        a.stats[1 + k] = ikl;
+        pen += a.eta[k] * ikl;
+    }
+    a.stats[0] = sums[0] * a.inv_tasks + pen / (float)a.K;
+    a.stats[1 + a.K] = sums[1 + a.K] * a.inv_tasks;
+    publish_stats(a);
+}
+// One entry of theta: the task-mean gradient g (kept unclipped) and the rule's step (R: promp_kernels_step_sizes.h)
+template <class R>
+PROMP_DEV void theta_entry_step(const R& r, const AdamArgs& a, int j, float g) {
+    a.grad_mean[j] = g;
+    if (a.do_update && j < a.n_trainable) r.step(a.theta, a.m, a.v, j, r.clipped(g), a.lr_t);
+}
+// and of alpha, from the sum t of its column
+template <class R>
+PROMP_DEV void alpha_entry_step(const R& r, const AdamArgs& a, const StepSizeArgs& ss, int ja, float t) {
+    step_size_entry_step(r, ss.alpha, ss.alpha_m, ss.alpha_v, ss.alpha_grad_mean, ja, t * a.inv_tasks, a.do_update && ja < a.n_trainable,
+                         ja < a.n_trainable, a.lr_t);
+}
+
+// Mean + step.  grid = final_stage_launch's mean_grid: ceil((NP + 1) / 256) -- SS (the *_ss instances): ceil((2 NP + 1) / 256), the
+// step sizes' step from red[NP + K + 2 + j] behind theta's --, block = 256
+template <bool SS, class R>
+PROMP_DEV void mean_step_body(const AdamArgs& a, const StepSizeArgs& ss, const R& r) {
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j < a.NP) {
-        const float g = a.red[j] * a.inv_tasks;
-        a.grad_mean[j] = g;
-        if (a.do_update && j < a.n_trainable) {
-            const float m = 0.9f * a.m[j] + 0.1f * g;
-            const float v = 0.999f * a.v[j] + 0.001f * g * g;
-            a.m[j] = m;
-            a.v[j] = v;
-            a.theta[j] -= a.lr_t * m / (sqrtf(v) + 1e-8f);
-        }
+        theta_entry_step(r, a, j, a.red[j] * a.inv_tasks);
     } else if (j == a.NP) {
-        float pen = 0.f;
-        for (int k = 0; k < a.K; ++k) {
-            const float ikl = a.red[a.NP + 1 + k] * a.inv_tasks;
-            a.stats[1 + k] = ikl;
-            pen += a.eta[k] * ikl;
-        }
-        a.stats[0] = a.red[a.NP] * a.inv_tasks + pen / (float)a.K;
-        a.stats[1 + a.K] = a.red[a.NP + 1 + a.K] * a.inv_tasks;
-        publish_stats(a);
+        final_stats_row(a, a.red + a.NP);
     } else if (SS && j <= 2 * a.NP) {
         const int ja = j - a.NP - 1;
-        step_size_adam(ss.alpha, ss.alpha_m, ss.alpha_v, ss.alpha_grad_mean, ja, a.red[a.NP + a.K + 2 + ja] * a.inv_tasks,
-                       a.do_update && ja < a.n_trainable, ja < a.n_trainable, a.lr_t);
+        alpha_entry_step(r, a, ss, ja, a.red[a.NP + a.K + 2 + ja]);
     }
 }
-__global__ void __launch_bounds__(256) k_mean_adam(AdamArgs a) { mean_adam_body<false>(a, StepSizeArgs{}); }
-__global__ void __launch_bounds__(256) k_mean_adam_ss(AdamArgs a, StepSizeArgs ss) { mean_adam_body<true>(a, ss); }
+__global__ void __launch_bounds__(256) k_mean_adam(AdamArgs a) { mean_step_body<false>(a, StepSizeArgs{}, PlainAdamRule{}); }
+__global__ void __launch_bounds__(256) k_mean_adam_ss(AdamArgs a, StepSizeArgs ss) { mean_step_body<true>(a, ss, PlainAdamRule{}); }
 
 // Fixed-order exchange: the ranks' vectors side by side ([nranks][n], ncclAllGather) added in rank order -- the same additions in
 // the same order on every rank.
@@ -241,79 +262,43 @@ __global__ void __launch_bounds__(256) k_sum_ranks(const float* gathered, float*
     out[j] = s;
 }
 
-// k_reduce_final + k_mean_adam in one launch, for the single-rank case (no all-reduce in between).  Column sums in the
-// same order as k_reduce_final (bitwise the same red[]); the thread that finishes a parameter column applies its Adam
-// update; one extra workgroup re-sums the K + 2 scalar columns and writes the statistics.
-// grid = ceil((NP + K + 2) / 64) + 1 -- k_final_adam_ss: ceil((2 NP + K + 2) / 64) + 1 --, block = 256
-template <bool SS>
-PROMP_DEV void final_adam_body(const FinalArgs& a, const AdamArgs& ad, const StepSizeArgs& ss, float (*part)[64], float* sums) {
+// Sum + step in one launch, for the single-rank case (no all-reduce in between): k_reduce_final + the mean kernel.  Column sums
+// in the same order as k_reduce_final (bitwise the same red[]); the thread that finishes a parameter column steps its entry (so
+// no clip: the other columns' sums do not exist yet); one extra workgroup re-sums the K + 2 scalar columns and writes the statistics.
+// grid = final_stage_launch's fused_grid: the reduce grid + 1, block = 256
+template <bool SS, class R>
+PROMP_DEV void final_step_body(const FinalArgs& a, const AdamArgs& ad, const StepSizeArgs& ss, const R& r, float (*part)[64], float* sums) {
     const int c = threadIdx.x & 63, q = threadIdx.x >> 6;
     const bool stats_block = blockIdx.x == gridDim.x - 1;
     const int j = stats_block ? a.NP + c : blockIdx.x * 64 + c;
     const int jend = a.NP + a.K + 2 + (SS && !stats_block ? a.NP : 0);
-    float s = 0.f;
-    if (j < a.NP) {
-        if (a.want_grad) s = final_quarter_sum(a.lam, a.NP, a.n_tasks, j, q);
-    } else if (j == a.NP) {
-        for (int i = q; i < a.n_tasks; i += 4) s += a.scal_outer[i * 2 + 0];
-    } else if (j <= a.NP + a.K) {
-        const int k = j - a.NP - 1;
-        for (int i = q; i < a.n_tasks; i += 4) s += a.scal_inner[((long long)k * a.n_tasks + i) * 2 + 1];
-    } else if (j == a.NP + a.K + 1) {
-        for (int i = q; i < a.n_tasks; i += 4) s += a.scal_outer[i * 2 + 1];
-    } else if (SS && j < jend) {
-        s = final_quarter_sum(ss.galpha, a.NP, a.n_tasks, j - (a.NP + a.K + 2), q);
-    }
-    part[q][c] = s;
+    part[q][c] = final_column_sum<SS>(a, ss.galpha, j, q, jend);
     __syncthreads();
     if (q == 0 && j < jend) {
-        const float t = (part[0][c] + part[1][c]) + (part[2][c] + part[3][c]);
+        const float t = final_column_total(part, c);
         if (!stats_block) a.red[j] = t;
         sums[c] = t;
-        if (!stats_block && j < a.NP) {
-            const float g = t * ad.inv_tasks;
-            ad.grad_mean[j] = g;
-            if (ad.do_update && j < ad.n_trainable) {
-                const float m = 0.9f * ad.m[j] + 0.1f * g;
-                const float v = 0.999f * ad.v[j] + 0.001f * g * g;
-                ad.m[j] = m;
-                ad.v[j] = v;
-                ad.theta[j] -= ad.lr_t * m / (sqrtf(v) + 1e-8f);
-            }
-        } else if (SS && !stats_block && j >= a.NP + a.K + 2) {
-            const int ja = j - (a.NP + a.K + 2);
-            step_size_adam(ss.alpha, ss.alpha_m, ss.alpha_v, ss.alpha_grad_mean, ja, t * ad.inv_tasks,
-                           ad.do_update && ja < ad.n_trainable, ja < ad.n_trainable, ad.lr_t);
-        }
+        if (!stats_block && j < a.NP) theta_entry_step(r, ad, j, t * ad.inv_tasks);
+        else if (SS && !stats_block && j >= a.NP + a.K + 2) alpha_entry_step(r, ad, ss, j - (a.NP + a.K + 2), t);
     }
     if (!stats_block) return;
     __syncthreads();
-    if (threadIdx.x == 0) {      // sums[0] = J, sums[1..K] = inner KLs, sums[K+1] = outer KL (sums over the tasks)
-        float pen = 0.f;
-        for (int k = 0; k < a.K; ++k) {
-            const float ikl = sums[1 + k] * ad.inv_tasks;
-            ad.stats[1 + k] = ikl;
-            pen += ad.eta[k] * ikl;
-        }
-        ad.stats[0] = sums[0] * ad.inv_tasks + pen / (float)a.K;
-        ad.stats[1 + a.K] = sums[1 + a.K] * ad.inv_tasks;
-        publish_stats(ad);
-    }
+    if (threadIdx.x == 0) final_stats_row(ad, sums);
 }
 __global__ void __launch_bounds__(256) k_final_adam(FinalArgs a, AdamArgs ad) {
     __shared__ float part[4][64];
     __shared__ float sums[64];
-    final_adam_body<false>(a, ad, StepSizeArgs{}, part, sums);
+    final_step_body<false>(a, ad, StepSizeArgs{}, PlainAdamRule{}, part, sums);
 }
 __global__ void __launch_bounds__(256) k_final_adam_ss(FinalArgs a, AdamArgs ad, StepSizeArgs ss) {
     __shared__ float part[4][64];
     __shared__ float sums[64];
-    final_adam_body<true>(a, ad, ss, part, sums);
+    final_step_body<true>(a, ad, ss, PlainAdamRule{}, part, sums);
 }
 
 // ---------------------------------------------------------------------------------------------
-// The general final stage (promp_set_outer_optimizer): the kernels above with the rule, its arguments and the clip as launch
-// arguments.  The plain kernels stay as they are -- a run-time branch in them is paid by every default step
+// The general final stage (promp_set_outer_optimizer): the bodies above over GeneralRule, with the rule, its arguments and the
+// clip as launch arguments.  The plain instances carry none of them -- a run-time branch in them is paid by every default step
 // (profiles/step_size_timing.txt) --, and final_stage_plan launches these only for settings that are not the default ones.
 // ---------------------------------------------------------------------------------------------
 // Sum of squares of the task-mean gradient over the trained entries -- theta's [0, n_trainable) and, SS, alpha's --, by EVERY
@@ -352,12 +337,11 @@ PROMP_DEV double outer_sq_norm(const AdamArgs& a, double* buf) {
     return buf[0];
 }
 
-// k_mean_adam under any rule, with the clip.  scale = n > c ? c / n : 1 is exactly 1 when the clip is off or not active
+// The clip's factor, by every thread of k_mean_outer: scale = n > c ? c / n : 1 is exactly 1 when the clip is off or not active
 // (tf.clip_by_global_norm computes c * min(1 / n, 1 / c): the same up to the last bit); a non-finite norm makes every update
-// non-finite, as there.  grad_mean keeps the unclipped gradient; one thread leaves n for promp_get_grad_norm.
-// grid as k_mean_adam / k_mean_adam_ss, block = 256
+// non-finite, as there.  One thread leaves n for promp_get_grad_norm.
 template <bool SS>
-PROMP_DEV void mean_outer_body(const AdamArgs& a, const StepSizeArgs& ss, const OuterOptArgs& o, float* norm_out, double* buf) {
+PROMP_DEV float outer_clip_scale(const AdamArgs& a, const OuterOptArgs& o, float* norm_out, double* buf) {
     float scale = 1.f;
     if (o.max_norm > 0.f) {       // (uniform over the grid: every thread reaches the barriers inside)
         const float n = (float)sqrt(outer_sq_norm<SS>(a, buf));
@@ -365,97 +349,27 @@ PROMP_DEV void mean_outer_body(const AdamArgs& a, const StepSizeArgs& ss, const 
         if (!(fabsf(n) <= 3.402823466e38f)) scale = n - n;       // inf or NaN: NaN
         if (blockIdx.x == 0 && threadIdx.x == 0) *norm_out = n;
     }
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    if (j < a.NP) {
-        const float g = a.red[j] * a.inv_tasks;
-        a.grad_mean[j] = g;
-        if (a.do_update && j < a.n_trainable) outer_rule_step(o, a.theta, a.m, a.v, j, g * scale, a.lr_t);
-    } else if (j == a.NP) {
-        float pen = 0.f;
-        for (int k = 0; k < a.K; ++k) {
-            const float ikl = a.red[a.NP + 1 + k] * a.inv_tasks;
-            a.stats[1 + k] = ikl;
-            pen += a.eta[k] * ikl;
-        }
-        a.stats[0] = a.red[a.NP] * a.inv_tasks + pen / (float)a.K;
-        a.stats[1 + a.K] = a.red[a.NP + 1 + a.K] * a.inv_tasks;
-        publish_stats(a);
-    } else if (SS && j <= 2 * a.NP) {
-        const int ja = j - a.NP - 1;
-        step_size_outer(o, ss.alpha, ss.alpha_m, ss.alpha_v, ss.alpha_grad_mean, ja, a.red[a.NP + a.K + 2 + ja] * a.inv_tasks, scale,
-                        a.do_update && ja < a.n_trainable, ja < a.n_trainable, a.lr_t);
-    }
+    return scale;
 }
+// mean + step under any rule, with the clip; sum + step under any rule (no clip: see final_step_body).
+// Grids and blocks as the plain instances'.
 __global__ void __launch_bounds__(256) k_mean_outer(AdamArgs a, OuterOptArgs o, float* norm_out) {
     __shared__ double buf[256];
-    mean_outer_body<false>(a, StepSizeArgs{}, o, norm_out, buf);
+    mean_step_body<false>(a, StepSizeArgs{}, GeneralRule{o, outer_clip_scale<false>(a, o, norm_out, buf)});
 }
 __global__ void __launch_bounds__(256) k_mean_outer_ss(AdamArgs a, StepSizeArgs ss, OuterOptArgs o, float* norm_out) {
     __shared__ double buf[256];
-    mean_outer_body<true>(a, ss, o, norm_out, buf);
-}
-
-// k_final_adam under any rule (no clip: a column's thread steps its entry before the other columns' sums exist).
-// grid and block as k_final_adam / k_final_adam_ss
-template <bool SS>
-PROMP_DEV void final_outer_body(const FinalArgs& a, const AdamArgs& ad, const StepSizeArgs& ss, const OuterOptArgs& o, float (*part)[64],
-                                float* sums) {
-    const int c = threadIdx.x & 63, q = threadIdx.x >> 6;
-    const bool stats_block = blockIdx.x == gridDim.x - 1;
-    const int j = stats_block ? a.NP + c : blockIdx.x * 64 + c;
-    const int jend = a.NP + a.K + 2 + (SS && !stats_block ? a.NP : 0);
-    float s = 0.f;
-    if (j < a.NP) {
-        if (a.want_grad) s = final_quarter_sum(a.lam, a.NP, a.n_tasks, j, q);
-    } else if (j == a.NP) {
-        for (int i = q; i < a.n_tasks; i += 4) s += a.scal_outer[i * 2 + 0];
-    } else if (j <= a.NP + a.K) {
-        const int k = j - a.NP - 1;
-        for (int i = q; i < a.n_tasks; i += 4) s += a.scal_inner[((long long)k * a.n_tasks + i) * 2 + 1];
-    } else if (j == a.NP + a.K + 1) {
-        for (int i = q; i < a.n_tasks; i += 4) s += a.scal_outer[i * 2 + 1];
-    } else if (SS && j < jend) {
-        s = final_quarter_sum(ss.galpha, a.NP, a.n_tasks, j - (a.NP + a.K + 2), q);
-    }
-    part[q][c] = s;
-    __syncthreads();
-    if (q == 0 && j < jend) {
-        const float t = (part[0][c] + part[1][c]) + (part[2][c] + part[3][c]);
-        if (!stats_block) a.red[j] = t;
-        sums[c] = t;
-        if (!stats_block && j < a.NP) {
-            const float g = t * ad.inv_tasks;
-            ad.grad_mean[j] = g;
-            if (ad.do_update && j < ad.n_trainable) outer_rule_step(o, ad.theta, ad.m, ad.v, j, g, ad.lr_t);
-        } else if (SS && !stats_block && j >= a.NP + a.K + 2) {
-            const int ja = j - (a.NP + a.K + 2);
-            step_size_outer(o, ss.alpha, ss.alpha_m, ss.alpha_v, ss.alpha_grad_mean, ja, t * ad.inv_tasks, 1.f,
-                            ad.do_update && ja < ad.n_trainable, ja < ad.n_trainable, ad.lr_t);
-        }
-    }
-    if (!stats_block) return;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float pen = 0.f;
-        for (int k = 0; k < a.K; ++k) {
-            const float ikl = sums[1 + k] * ad.inv_tasks;
-            ad.stats[1 + k] = ikl;
-            pen += ad.eta[k] * ikl;
-        }
-        ad.stats[0] = sums[0] * ad.inv_tasks + pen / (float)a.K;
-        ad.stats[1 + a.K] = sums[1 + a.K] * ad.inv_tasks;
-        publish_stats(ad);
-    }
+    mean_step_body<true>(a, ss, GeneralRule{o, outer_clip_scale<true>(a, o, norm_out, buf)});
 }
 __global__ void __launch_bounds__(256) k_final_outer(FinalArgs a, AdamArgs ad, OuterOptArgs o) {
     __shared__ float part[4][64];
     __shared__ float sums[64];
-    final_outer_body<false>(a, ad, StepSizeArgs{}, o, part, sums);
+    final_step_body<false>(a, ad, StepSizeArgs{}, GeneralRule{o, 1.f}, part, sums);
 }
 __global__ void __launch_bounds__(256) k_final_outer_ss(FinalArgs a, AdamArgs ad, StepSizeArgs ss, OuterOptArgs o) {
     __shared__ float part[4][64];
     __shared__ float sums[64];
-    final_outer_body<true>(a, ad, ss, o, part, sums);
+    final_step_body<true>(a, ad, ss, GeneralRule{o, 1.f}, part, sums);
 }
 
 // dst[i][:] = src[:] for i < n_tasks   (MetaPolicy.switch_to_pre_update)

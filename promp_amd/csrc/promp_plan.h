@@ -773,3 +773,23 @@ inline FinalPlan final_stage_plan(const OuterOptPlan& p, const PlanSwitches& sw,
     f.split = split_wanted || (stepping && p.max_norm > 0.f);
     return f;
 }
+// The whole launch decision of a final stage over Theta = NP parameters and K inner steps: the plan above, whether the step
+// sizes' Theta columns ride along (the *_ss instances), the floats of the exchange buffer -- [grad Theta | K + 2 scalars] and
+// behind them the step-size gradient's Theta sums --, and every grid.  Reduce and fused launches: 64 columns per block, the fused
+// one with one more block for the statistics; the mean launch: 256 threads per block, theta's entries, the statistics thread
+// and the step sizes' entries.
+struct FinalLaunch {
+    bool general, split, sizes;
+    size_t red_count;
+    unsigned reduce_grid, mean_grid, fused_grid;
+};
+inline size_t final_red_count(int NP, int K, bool sizes) { return (size_t)(sizes ? 2 : 1) * NP + K + 2; }
+inline FinalLaunch final_stage_launch(const FinalPlan& f, int NP, int K, bool sizes) {
+    FinalLaunch L;
+    L.general = f.general; L.split = f.split; L.sizes = sizes;
+    L.red_count = final_red_count(NP, K, sizes);
+    L.reduce_grid = (unsigned)((L.red_count + 63) / 64);
+    L.mean_grid = (unsigned)(((size_t)(sizes ? 2 : 1) * NP + 1 + 255) / 256);
+    L.fused_grid = L.reduce_grid + 1;
+    return L;
+}

@@ -9,6 +9,8 @@
 //   constants    default arguments give the plain kernels' 0.9f / 0.1f / 0.999f / 0.001f / 1e-8f and their lr_t, bit for bit
 //   family       final_stage_plan: default settings give the plain instances; anything else, or the switch, the general family on
 //                stepping evaluations only; the clip gives the split route
+//   grids        final_stage_launch: the exchange buffer's floats and the grids of the reduce, mean and fused launches at the sizes
+//                where a column block, a thread block or the statistics thread sits on an edge, against literals
 #include "../../promp_amd/csrc/promp_plan.h"
 
 #include <cmath>
@@ -158,6 +160,44 @@ static void check_family() {
     }
 }
 
+static void check_grids() {
+    // Theta, K, step sizes trained, floats of the exchange buffer, blocks of the reduce / mean / fused launch
+    const struct { int NP, K; bool sizes; size_t red; unsigned reduce, mean, fused; } rows[] = {
+        {60, 1, false, 63, 1, 1, 2},           {60, 1, true, 123, 2, 1, 3},           {60, 2, false, 64, 1, 1, 2},
+        {60, 2, true, 124, 2, 1, 3},           {62, 1, false, 65, 2, 1, 3},           {62, 1, true, 127, 2, 1, 3},
+        {62, 2, false, 66, 2, 1, 3},           {62, 2, true, 128, 2, 1, 3},           {255, 1, false, 258, 5, 1, 6},
+        {255, 1, true, 513, 9, 2, 10},         {255, 2, false, 259, 5, 1, 6},         {255, 2, true, 514, 9, 2, 10},
+        {256, 1, false, 259, 5, 2, 6},         {256, 1, true, 515, 9, 3, 10},         {256, 2, false, 260, 5, 2, 6},
+        {256, 2, true, 516, 9, 3, 10},         {5900, 1, false, 5903, 93, 24, 94},    {5900, 1, true, 11803, 185, 47, 186},
+        {5900, 2, false, 5904, 93, 24, 94},    {5900, 2, true, 11804, 185, 47, 186},  {31888, 1, false, 31891, 499, 125, 500},
+        {31888, 1, true, 63779, 997, 250, 998}, {31888, 2, false, 31892, 499, 125, 500}, {31888, 2, true, 63780, 997, 250, 998},
+    };
+    int n = 0;
+    for (const auto& r : rows)
+        for (int general = 0; general < 2; ++general)
+            for (int split = 0; split < 2; ++split) {
+                FinalPlan f;
+                f.general = general != 0; f.split = split != 0;
+                const FinalLaunch L = final_stage_launch(f, r.NP, r.K, r.sizes);
+                EXPECT(L.general == f.general && L.split == f.split && L.sizes == r.sizes, "Theta %d: the plan is passed on", r.NP);
+                EXPECT(L.red_count == r.red && final_red_count(r.NP, r.K, r.sizes) == r.red, "Theta %d K %d sizes %d: %zu floats, not %zu",
+                       r.NP, r.K, (int)r.sizes, L.red_count, r.red);
+                EXPECT(L.reduce_grid == r.reduce && L.mean_grid == r.mean && L.fused_grid == r.fused,
+                       "Theta %d K %d sizes %d: grids %u %u %u, not %u %u %u", r.NP, r.K, (int)r.sizes, L.reduce_grid, L.mean_grid,
+                       L.fused_grid, r.reduce, r.mean, r.fused);
+                // 64 columns per reduce block: the last block holds a valid column, and no valid column is outside the grid
+                EXPECT((size_t)(L.reduce_grid - 1) * 64 < L.red_count, "Theta %d: the last reduce block is empty", r.NP);
+                EXPECT((size_t)L.reduce_grid * 64 >= L.red_count, "Theta %d: columns outside the reduce grid", r.NP);
+                EXPECT(L.fused_grid == L.reduce_grid + 1, "Theta %d: the fused grid is the reduce grid and the statistics block", r.NP);
+                // 256 threads per mean block: exactly the blocks of Theta + 1 (2 Theta + 1) threads
+                const size_t threads = (size_t)(r.sizes ? 2 : 1) * r.NP + 1;
+                EXPECT((size_t)L.mean_grid * 256 >= threads && (size_t)(L.mean_grid - 1) * 256 < threads, "Theta %d: mean grid %u for %zu threads",
+                       r.NP, L.mean_grid, threads);
+                ++n;
+            }
+    EXPECT(n == 6 * 2 * 2 * 4, "%d rows", n);
+}
+
 static void check_env() {
     unsetenv("PROMP_OUTER_GENERIC");
     EXPECT(!plan_switches_from_env().outer_generic, "unset");
@@ -173,6 +213,7 @@ int main() {
     check_validation();
     check_constants();
     check_family();
+    check_grids();
     check_env();
     if (g_failed) {
         printf("%d expectation(s) failed\n", g_failed);

@@ -352,6 +352,89 @@ def check_routes_with_clip(lib, case, key='adam', epochs=2, sizes=False, lr=1e-3
         ctx.close()
 
 
+# ---- (8) the final stage's grid edges ------------------------------------------------------------------------------------------
+
+# Single-hidden-layer shapes (the layer-by-layer kernels; the final stage does not depend on the pass family) whose
+# Theta = H (O + 1 + A) + 2 A puts the scalar columns, the statistics thread and the last block on the edges of the final stage's
+# grids (final_stage_launch, promp_plan.h): 64 columns per reduce block, 256 threads per mean block.
+EDGE_SHAPES = {
+    # Theta 62: the scalar columns 62 .. 65 straddle two blocks; with trained step sizes 2 Theta + K + 2 = 128, an exactly full grid
+    'theta62': dict(M=2, O=4, A=4, hidden=(6,), K=2),
+    # Theta 60: Theta + K + 2 = 64, exactly one full reduce block
+    'theta60': dict(M=2, O=5, A=3, hidden=(6,), K=2),
+    # Theta 255: the surrogate's sum is a block's last column; the mean kernel's statistics thread is a block's last
+    'theta255': dict(M=2, O=8, A=4, hidden=(19,), K=1),
+    # Theta 256: the surrogate's sum opens a block, the statistics thread opens the second mean block, 2 Theta + 1 = 513 leaves one
+    # thread in the last; five tasks over four task quarters
+    'theta256': dict(M=5, O=6, A=3, hidden=(25,), K=1),
+}
+_edge_cases = {}
+
+
+def edge_case(name):
+    if name not in _edge_cases:
+        _edge_cases[name] = sc.PrompCase(720 + sorted(EDGE_SHAPES).index(name), P=1, T=20, ragged=True, **EDGE_SHAPES[name])
+        assert _edge_cases[name].n == int(name[5:])
+    return _edge_cases[name]
+
+
+def oracle_task_scalars(case):
+    """the float64 oracle's per-task scalars [M][K + 2]: J_i, KL^k_i, outer KL_i (computed once per case)"""
+    if getattr(case, '_task_scalars', None) is None:
+        rows = []
+        for i in range(case.M):
+            r = pm.meta_objective_and_grad(case.spec, case.t64, case.all_slabs, case.a64, case.e64, CLIP, want_grad=False,
+                                           tasks=[i], n_tasks_total=1)
+            rows.append(np.concatenate([[r['loss'] - np.mean(case.e64 * r['inner_kl'])], r['inner_kl'], [r['outer_kl']]]))
+        case._task_scalars = np.array(rows)
+    return case._task_scalars
+
+
+def check_stats_against_exchange(lib, case):
+    """The statistics row against the exchange buffer it is computed from, after meta_grad on the fused and on the forced split
+    route, step sizes fixed and trained.  The KL entries are ONE float32 multiplication each: exact.  The loss is
+    red[Theta] inv + (sum_k eta_k KL_k) / K: a product, the penalty's sum and quotient and the closing addition -- three roundings
+    of values no larger than the two terms, and a contraction of eta_k KL_k into the sum changes one of them -- held to
+    4 x 2^-24 of the terms' magnitudes.  The scalar sums themselves against the float64 oracle's per-task values at parity_checks'
+    tolerance for a loss or a KL (rtol 1e-4, atol 1e-6), summed over the tasks as the column is.  The routes: bit for bit."""
+    n, K, M = case.n, case.K, case.M
+    inv = np.float32(1.0) / np.float32(M)
+    eta = case.eta.astype(np.float32)
+    want = oracle_task_scalars(case)
+    bound = np.sum(1e-6 + 1e-4 * np.abs(want), axis=0)
+
+    def run(split, sizes):
+        ctx = case.ctx(lib)
+        if sizes:
+            ctx.set_train_step_sizes(True)
+        if split:
+            ctx.comm_split_path(True)
+        g, st = ctx.meta_grad(CLIP, case.eta)
+        out = dict(g=g, red=ctx.reduced_get(), stats=np.concatenate([[st['loss']], st['inner_kl'], [st['outer_kl']]]).astype(np.float32))
+        if sizes:
+            out['ga'] = ctx.get_step_size_grad()
+        ctx.close()
+        return out
+    for sizes in (False, True):
+        fused, split = run(False, sizes), run(True, sizes)
+        assert sorted(fused) == sorted(split)
+        for key in fused:
+            assert np.array_equal(fused[key], split[key]), (sizes, key)
+        red, stats = fused['red'], fused['stats']
+        assert red.shape == ((2 if sizes else 1) * n + K + 2,) and red.dtype == np.float32
+        for k in range(K + 1):
+            assert stats[1 + k] == np.float32(red[n + 1 + k] * inv), (sizes, k, stats[1 + k], red[n + 1 + k])
+        j64 = np.float64(red[n]) * np.float64(inv)
+        pen = [np.float64(eta[k]) * np.float64(stats[1 + k]) / K for k in range(K)]
+        err, lim = abs(np.float64(stats[0]) - (j64 + sum(pen))), 4.0 * U * (abs(j64) + sum(abs(p) for p in pen))
+        print('sizes=%s: |loss - float64| %.3e, bound %.3e' % (sizes, err, lim))
+        assert err <= lim, (sizes, err, lim)
+        err = np.abs(red[n:n + K + 2].astype(np.float64) - np.sum(want, axis=0))
+        print('sizes=%s: scalar sums against the oracle, worst %.3f of the bound' % (sizes, float(np.max(err / bound))))
+        assert np.all(err <= bound), (sizes, err, bound)
+        assert np.array_equal(fused['g'], (red[:n] * inv).astype(np.float32))
+
+
 def check_minibatch_sgd_clip(lib, seed, O=5, A=3, hidden=(32, 32), K=1, lengths=mb.LENGTHS, pattern=mb.ASSIGN_2, max_grad_norm=1e-3):
     """optimize_minibatch(B = 2) under SGD with the clip on against the same steps one by one on truncated batches:
     minibatch_checks' own construction, every context of it given the settings"""

@@ -36,6 +36,16 @@ def test_forced_general_kernels_equal_the_plain_ones(lib, case, monkeypatch):
     oc.check_generic_equals_plain(lib, case, monkeypatch)
 
 
+def test_final_stage_grid_edge(lib, monkeypatch):
+    """Theta 62, K 2 (outer_optimizer_checks.EDGE_SHAPES): the scalar columns straddle two column blocks, and with trained step
+    sizes the reduce grid is exactly full.  These two checks only -- measured at 57 s on the emulator (twelve contexts; the same
+    pair on the module's own shape takes 31 s for the first check alone) against 110 to 190 s for the five checks the GPU suite runs
+    on each edge shape"""
+    case = oc.edge_case('theta62')
+    oc.check_generic_equals_plain(lib, case, monkeypatch)
+    oc.check_stats_against_exchange(lib, case)
+
+
 def test_inactive_clip_is_no_clip(lib, case):
     oc.check_inactive_clip(lib, case, epochs=2)
     oc.check_inactive_clip(lib, case, epochs=2, sizes=True)

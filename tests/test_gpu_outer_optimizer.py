@@ -97,6 +97,37 @@ def test_routes_agree_with_clipping_on(lib, shape5):
     oc.check_routes_with_clip(lib, shape5, 'sgd', comm=False)
 
 
+# The final stage's grid edges (outer_optimizer_checks.EDGE_SHAPES: Theta 60, 62, 255, 256; M 2 or 5, 20 to 100 rows): the scalar
+# columns across a column block's edge, exactly full reduce grids, the statistics thread on a thread block's edge.
+EDGES = sorted(oc.EDGE_SHAPES)
+
+
+@pytest.mark.parametrize('edge', EDGES)
+def test_final_stage_edges_split_equals_fused(lib, edge):
+    sc.check_split_equals_fused(lib, oc.edge_case(edge))
+
+
+@pytest.mark.parametrize('edge', EDGES)
+def test_final_stage_edges_general_equals_plain(lib, edge, monkeypatch):
+    oc.check_generic_equals_plain(lib, oc.edge_case(edge), monkeypatch)
+
+
+@pytest.mark.parametrize('edge', EDGES)
+def test_final_stage_edges_rules(lib, edge):
+    oc.check_rule(lib, oc.edge_case(edge), 'adam', clip=True, sizes=True)
+    oc.check_rule(lib, oc.edge_case(edge), 'nesterov', clip=False)
+
+
+@pytest.mark.parametrize('edge', EDGES)
+def test_final_stage_edges_routes_with_clip(lib, edge):
+    oc.check_routes_with_clip(lib, oc.edge_case(edge), 'adam', sizes=True)
+
+
+@pytest.mark.parametrize('edge', EDGES)
+def test_final_stage_edges_statistics_against_the_exchange_buffer(lib, edge):
+    oc.check_stats_against_exchange(lib, oc.edge_case(edge))
+
+
 def test_minibatched_sgd_with_clip_equals_truncated_batches(lib):
     oc.check_minibatch_sgd_clip(lib, 715)
 

@@ -1,5 +1,5 @@
 """The outer step's planning in promp_amd/csrc/promp_plan.h -- rule names, the validation of promp_set_outer_optimizer's arguments,
-the constants default arguments give, and which final-stage kernels run -- on the host alone: tests/host/outer_opt_check.cpp
+the constants default arguments give, which final-stage kernels run and on which grids -- on the host alone: tests/host/outer_opt_check.cpp
 includes the plan header and nothing else of the project, is built with AddressSanitizer and UBSan, and says what does not hold.
 The binding's own table of names must agree with the header's.  No GPU, no emulator."""
 import os
