@@ -84,8 +84,19 @@ typedef struct promp_proc_opts {
     int32_t normalize_adv;
     int32_t positive_adv;
     int32_t baseline_kind;     /* PROMP_BASELINE_* */
-    int32_t reserved;
+    int32_t reserved;          /* 0, or pad_length > 0: normalise / shift over each task's zero-padded [paths, pad_length] array
+                                * (n = paths * pad_length, and a padded zero is a candidate for the minimum where the task has
+                                * any padding), as the DiCE sample processor does (samplers/dice_sample_processor.py:165-191) */
 } promp_proc_opts;
+
+/* DiceSampleProcessor.__init__ arguments (samplers/dice_sample_processor.py:25-47) + baseline choices */
+typedef struct promp_dice_opts {
+    double  discount, gae_lambda, reg_coeff, return_reg_coeff;
+    int32_t max_path_length, normalize_adv, positive_adv;
+    int32_t baseline_kind;          /* PROMP_BASELINE_* : fitted on the discounted rewards */
+    int32_t return_baseline_kind;   /* PROMP_BASELINE_* or -1: no GAE advantages */
+    int32_t reserved;
+} promp_dice_opts;
 
 /* ---- lifecycle ------------------------------------------------------------------------------ */
 int promp_ctx_create(promp_ctx** out, int device_id, const promp_dims* dims);
@@ -96,8 +107,9 @@ const char* promp_last_error(void);
  * new fields, so bindings must be rebuilt).  Entry points added since the first v2 header -- round 3: promp_set_reuse_adapt,
  * promp_begin_collection / promp_end_collection, promp_state_version, the two pass counters; round 4: promp_comm_fixed_order;
  * later: promp_set_train_step_sizes with promp_get_step_sizes / promp_get_step_size_grad / promp_{set,get}_step_size_adam_state
- * and promp_reduced_count; promp_set_outer_optimizer / promp_get_outer_optimizer / promp_get_grad_norm -- were additions and did
- * not move it. */
+ * and promp_reduced_count; promp_set_outer_optimizer / promp_get_outer_optimizer / promp_get_grad_norm;
+ * promp_process_samples_dice / promp_download_dice / promp_use_dice_advantages (and promp_proc_opts.reserved read as pad_length)
+ * -- were additions and did not move it. */
 int promp_abi_version(void);
 /* Theta = O*H1+H1 + H1*H2+H2 + H2*A+A + A */
 int promp_param_count(const promp_dims* dims);
@@ -172,6 +184,27 @@ int promp_set_advantages(promp_ctx* ctx, int step, const float* advantages);
  * that weight the log-likelihood gradient and installs them as the step's advantages; PROMP_INNER_DICE additionally
  * couples the time steps of a path in the second-order term (two extra launches per R-operator pass). */
 int promp_set_dice_rewards(promp_ctx* ctx, int step, const float* rewards);
+
+/* DiceSampleProcessor._compute_samples_data (samplers/dice_sample_processor.py:96-191) on the step's resident slab, per task:
+ * discounted rewards y_t = r_t gamma^t -> baseline fit on them -> adjusted = y - baseline -> normalise / shift over the
+ * zero-padded [paths, max_path_length] array -> the DiCE rewards of the valid rows (x * rows / (paths * max_path_length)) and
+ * their suffix sums.  Asynchronous, on the stream promp_process_samples would use.  Leaves the step as promp_set_dice_rewards
+ * does (DiCE rewards, gradient weights as advantages) and processed.  With return_baseline_kind >= 0 the ordinary pipeline
+ * (returns, fit, GAE, normalisation over the padded array) also runs on the step's rewards; its advantages, scaled the same way,
+ * are kept beside the DiCE weights until promp_use_dice_advantages installs them as the step's advantages -- VPG_DICEMAML's
+ * outer objective on the last step (meta_algos/vpg_dice_maml.py:46-49); the step is no DiCE data from then on.
+ * Refused: max_path_length shorter than the step's longest path, an unknown kind, discount / gae_lambda outside [0,1], a step
+ * without data. */
+int promp_process_samples_dice(promp_ctx* ctx, int step, const promp_dice_opts* opts);
+/* Results of promp_process_samples_dice (any pointer may be NULL; float64): adjusted / advantages [rows] = the normalised /
+ * shifted values of the valid rows, BEFORE the rows / n scaling (the reference's samples hold them at the valid positions);
+ * pad_adjusted / pad_advantages [n_tasks] = the value at every padded position of the task; coeffs / return_coeffs
+ * [n_tasks, feature_dim(kind)]; per path: sum of rewards, sum of discounted rewards ("discounted return"), sum of rewards^2. */
+int promp_download_dice(promp_ctx* ctx, int step, double* adjusted, double* advantages,
+                        double* pad_adjusted, double* pad_advantages,
+                        double* coeffs, double* return_coeffs,
+                        double* path_undiscounted, double* path_discounted, double* path_reward_sumsq);
+int promp_use_dice_advantages(promp_ctx* ctx, int step);
 
 /* ---- parameters (rows a14: policies/base.py:173-203, 234-240, 262-286) ---------------------- */
 int promp_set_theta(promp_ctx* ctx, const float* theta);                 /* [Theta] meta-parameters     */

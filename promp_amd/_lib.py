@@ -41,6 +41,12 @@ class ProcOpts(C.Structure):
                 ('reserved', C.c_int32)]
 
 
+class DiceOpts(C.Structure):
+    _fields_ = [('discount', C.c_double), ('gae_lambda', C.c_double), ('reg_coeff', C.c_double), ('return_reg_coeff', C.c_double),
+                ('max_path_length', C.c_int32), ('normalize_adv', C.c_int32), ('positive_adv', C.c_int32),
+                ('baseline_kind', C.c_int32), ('return_baseline_kind', C.c_int32), ('reserved', C.c_int32)]
+
+
 class PointEnvOpts(C.Structure):
     _fields_ = [('normalization_scale', C.c_double), ('max_step', C.c_double), ('sparse_radius', C.c_double),
                 ('reward_type', C.c_int32), ('clip_infos', C.c_int32), ('seed', C.c_uint64)]
@@ -117,6 +123,9 @@ SIGNATURES = {
     'promp_get_grad_norm': (C.c_int, [_P, _F]),
     'promp_optimize': (C.c_int, [_P, C.c_int, C.c_float, C.c_float, _F, C.c_int, C.c_int, _F, _F]),
     'promp_set_dice_rewards': (C.c_int, [_P, C.c_int, _F]),
+    'promp_process_samples_dice': (C.c_int, [_P, C.c_int, C.POINTER(DiceOpts)]),
+    'promp_download_dice': (C.c_int, [_P, C.c_int, _D, _D, _D, _D, _D, _D, _D, _D, _D]),
+    'promp_use_dice_advantages': (C.c_int, [_P, C.c_int]),
     'promp_optimize_begin': (C.c_int, [_P, C.c_int, C.c_float, C.c_float, _F, C.c_int, C.c_int]),
     'promp_optimize_end': (C.c_int, [_P, _F, _F]),
     'promp_optimize_minibatch': (C.c_int, [_P, C.c_int, C.c_int, _I, C.c_float, C.c_float, _F, C.c_int, C.c_int, _F, _F]),
@@ -564,7 +573,8 @@ class Context:
 
     # entry points that return only after the work enqueued before them has completed (the compute stream waits for every upload
     # enqueued before it, so an upload's sources are free once one of these has returned)
-    _WAITS = frozenset(('promp_sync', 'promp_download_processed', 'promp_download_raw', 'promp_get_theta', 'promp_stage_wait'))
+    _WAITS = frozenset(('promp_sync', 'promp_download_processed', 'promp_download_raw', 'promp_get_theta', 'promp_stage_wait',
+                        'promp_download_dice'))
 
     def _call(self, name, *args):
         rc = self.lib.check(getattr(self.lib.cdll, name)(self._h, *args))
@@ -709,6 +719,41 @@ class Context:
         rw = _f32(rw)
         assert rw.shape == (self.step_rows[step],)
         self._call('promp_set_dice_rewards', int(step), _ptr(rw, C.c_float))
+
+    def process_samples_dice(self, step, max_path_length, discount=0.99, gae_lambda=1.0, normalize_adv=True, positive_adv=False,
+                             baseline_kind=BASELINE_LINEAR_FEATURE, reg_coeff=1e-5, return_baseline_kind=None, return_reg_coeff=1e-5):
+        """promp_process_samples_dice: the DiCE sample processor's arithmetic on the resident slab; return_baseline_kind adds the
+        GAE advantages of VPG_DICEMAML's outer objective (use_dice_advantages installs them)"""
+        self._pre_write(step)
+        rkind = -1 if return_baseline_kind is None else int(return_baseline_kind)
+        o = DiceOpts(float(discount), float(gae_lambda), float(reg_coeff), float(return_reg_coeff), int(max_path_length),
+                     int(bool(normalize_adv)), int(bool(positive_adv)), int(baseline_kind), rkind, 0)
+        self._call('promp_process_samples_dice', int(step), C.byref(o))
+        self._dice_kinds = (int(baseline_kind), rkind)
+
+    def download_dice(self, step):
+        """promp_download_dice -> dict(adjusted, advantages [rows], pad_adjusted, pad_advantages [n_tasks], coeffs, return_coeffs
+        [n_tasks, D], path_undiscounted, path_discounted, path_reward_sumsq [paths]), float64; the entries of the GAE pass are
+        None when the step was processed without a return baseline"""
+        R, P, M = self.step_rows[step], self.step_paths[step], self.n_tasks
+        kind, rkind = self._dice_kinds
+        vpg = rkind >= 0
+        fdim = lambda k: self.lib.cdll.promp_feature_dim(C.byref(self.dims), int(k))
+        out = dict(adjusted=np.empty(R, np.float64), advantages=np.empty(R, np.float64) if vpg else None,
+                   pad_adjusted=np.empty(M, np.float64), pad_advantages=np.empty(M, np.float64) if vpg else None,
+                   coeffs=np.zeros((M, fdim(kind)), np.float64), return_coeffs=np.zeros((M, fdim(rkind)), np.float64) if vpg else None,
+                   path_undiscounted=np.empty(P, np.float64), path_discounted=np.empty(P, np.float64),
+                   path_reward_sumsq=np.empty(P, np.float64))
+        ptr = lambda k: _ptr(out[k], C.c_double) if out[k] is not None and out[k].size else None
+        self._call('promp_download_dice', int(step), *[ptr(k) for k in (
+            'adjusted', 'advantages', 'pad_adjusted', 'pad_advantages', 'coeffs', 'return_coeffs', 'path_undiscounted',
+            'path_discounted', 'path_reward_sumsq')])
+        return out
+
+    def use_dice_advantages(self, step):
+        """promp_use_dice_advantages: the GAE advantages of process_samples_dice become the step's advantages (no DiCE data after)"""
+        self._pre_write(step)
+        self._call('promp_use_dice_advantages', int(step))
 
     # ---- parameters ----
     def set_theta(self, theta):

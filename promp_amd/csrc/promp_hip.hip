@@ -143,6 +143,13 @@ struct StepData {
     DevBuf<float> dice_rw, dice_c, dice_u;
     DevBuf<double> dice_tmp;
     bool has_dice = false;
+    // promp_process_samples_dice (allocated on its first use): the normalised adjusted rewards and GAE advantages in float64,
+    // the advantages as slab weights, the tasks' pad values [2][tasks], the reward baseline's coefficients (coeffs holds the
+    // return baseline's after such a call), the per-path sums [3][paths]
+    DevBuf<double> dice_x64, dice_adv64, dice_pad, dice_coeffs, dice_path;
+    DevBuf<float> dice_vpg32;
+    bool dice_processed = false, has_dice_vpg = false;
+    int dice_feat_dim = 0, dice_ret_feat_dim = 0;
     bool has_rew64 = false;
     DevBuf<float> ret32, adv32;
     DevBuf<double> ret64, adv64;
@@ -1399,7 +1406,7 @@ static int set_step_layout(promp_ctx* c, StepData& S, hipStream_t st, bool async
     // (A match also means the offsets are well-formed: the set was built from them.)
     if ((int)S.lay_tpo.size() == M + 1 && (int)S.lay_pro.size() == n_paths + 1 && S.n_paths == n_paths &&
         memcmp(S.lay_tpo.data(), tpo, sizeof(int) * (M + 1)) == 0 && memcmp(S.lay_pro.data(), pro, sizeof(int) * (n_paths + 1)) == 0) {
-        S.processed = false; S.has_adv = false; S.has_rew64 = false; S.has_dice = false;
+        S.processed = false; S.has_adv = false; S.has_rew64 = false; S.has_dice = false; S.dice_processed = false; S.has_dice_vpg = false;
         return 0;
     }
     // every source of the copies below lives in `keep` (asynchronous mode: until the set is staged again)
@@ -1411,7 +1418,7 @@ static int set_step_layout(promp_ctx* c, StepData& S, hipStream_t st, bool async
     const int R = (int)k.row_t.size();
     S.lay_tpo.clear(); S.lay_pro.clear();         // (set again at the end; stays empty if a copy fails half-way)
     S.n_paths = n_paths; S.n_rows = R; S.n_work[0] = (int)k.work[0].size(); S.n_work[1] = (int)k.work[1].size();
-    S.processed = false; S.has_adv = false; S.has_rew64 = false; S.has_dice = false;
+    S.processed = false; S.has_adv = false; S.has_rew64 = false; S.has_dice = false; S.dice_processed = false; S.has_dice_vpg = false;
     HIPCHECK(hipMemcpyAsync(S.path_row_offsets, k.pro.data(), sizeof(int) * (n_paths + 1), hipMemcpyHostToDevice, st));
     HIPCHECK(hipMemcpyAsync(S.task_path_offsets, k.tpo.data(), sizeof(int) * (M + 1), hipMemcpyHostToDevice, st));
     HIPCHECK(hipMemcpyAsync(S.path_task, k.path_task.data(), sizeof(int) * n_paths, hipMemcpyHostToDevice, st));
@@ -1544,43 +1551,44 @@ static SampleArgs sample_args(const promp_ctx* c, const StepData& S, int kind) {
     return a;
 }
 
-int promp_process_samples(promp_ctx* c, int step, const promp_proc_opts* o) {
-    if (!c || !o) return fail(-1, "NULL argument");
-    StepScope sc(c, step, /*writes=*/true, /*needs_data=*/true);
-    if (sc.rc) return sc.rc;
-    StepData& S = sc.S();
-    if (!(o->discount >= 0 && o->discount <= 1)) return fail(-1, "discount factor must be in [0,1]");      // samplers/base.py:57
-    if (!(o->gae_lambda >= 0 && o->gae_lambda <= 1)) return fail(-1, "gae_lambda must be in [0,1]");       // samplers/base.py:58
-    if (o->baseline_kind < 0 || o->baseline_kind > 2) return fail(-1, "unknown baseline kind %d", o->baseline_kind);
-    // which Gram and fit kernels run (promp_plan.h: sample_plan; the table in tests/test_gpu_parity.py)
-    SamplePlan plan;
-    std::string why;
-    if (const int rc = sample_plan(o->baseline_kind, c->d.obs_dim, feature_dim(&c->d, o->baseline_kind), c->sw, &plan, &why))
-        return fail_plan(rc, why);
-    SampleArgs a = sample_args(c, S, o->baseline_kind);
-    a.work = S.work[0];                         // k_gram / k_fit: one workgroup per CU
-    a.task_wg_offsets = S.task_wg_offsets[0];
-    a.gamma = o->discount; a.lam = o->gae_lambda; a.reg = o->reg_coeff;
-    a.normalize = o->normalize_adv; a.positive = o->positive_adv;
-    a.ret64 = S.ret64; a.ret32 = S.ret32; a.adv32 = S.adv32;
-    a.path_ret0 = S.path_ret0; a.path_undisc = S.path_undisc; a.path_rsq = S.path_rsq;
-    S.feat_dim = a.D;
-    // Steps >= 1 go to the second stream (no data dependence on the step-0 work the host enqueued just before: their
-    // samples are resident), behind the last main-stream work that touched this step's slabs.  Per-kernel timing
-    // (promp_profile) keeps everything on the one stream it brackets.
-    const bool on_side = c->overlap && !c->prof && step >= 1;
-    hipStream_t st = on_side ? c->side : c->stream;
-    if (o->baseline_kind != PROMP_BASELINE_ZERO && fit_buffers(c, on_side, plan)) return -2;
-    a.gram_partials = on_side ? c->gram_partials_side : c->gram_partials;
-    double* fit_scratch = on_side ? c->fit_scratch_side : c->fit_scratch;
-    if (on_side) {
+// Where a step's sample processing runs.  Steps >= 1 go to the second stream (no data dependence on the step-0 work the host
+// enqueued just before: their samples are resident), behind the last main-stream work that touched this step's slabs.  Per-kernel
+// timing (promp_profile) keeps everything on the one stream it brackets.
+struct SampleStream {
+    bool on_side = false;
+    hipStream_t st = nullptr;
+    double* gram_partials = nullptr;
+    double* fit_scratch = nullptr;
+};
+// the prologue promp_process_samples and promp_process_samples_dice share: the stream, the fit's buffers for every plan the call
+// launches, the event waits
+static int sample_stream_begin(promp_ctx* c, int step, StepData& S, std::initializer_list<const SamplePlan*> plans, SampleStream* ss) {
+    ss->on_side = c->overlap && !c->prof && step >= 1;
+    ss->st = ss->on_side ? c->side : c->stream;
+    for (const SamplePlan* plan : plans)
+        if (plan->gram != GramKernel::None && fit_buffers(c, ss->on_side, *plan)) return -2;
+    ss->gram_partials = ss->on_side ? c->gram_partials_side : c->gram_partials;
+    ss->fit_scratch = ss->on_side ? c->fit_scratch_side : c->fit_scratch;
+    if (ss->on_side) {
         if (mark_use(c, S)) return -2;
         if (S.use_set) HIPCHECK(hipStreamWaitEvent(c->side, S.ev_use, 0));
         if (S.wait_ready_side) HIPCHECK(hipStreamWaitEvent(c->side, S.ev_ready, 0));
     }
     S.wait_ready_side = false;
-    PROMP_LAUNCH(k_returns, dim3(S.n_paths), 64, 0, st, a);
-    HIPCHECK(hipGetLastError());
+    return 0;
+}
+static int sample_stream_end(promp_ctx* c, StepData& S, const SampleStream& ss) {
+    if (ss.on_side) {
+        HIPCHECK(hipEventRecord(S.ev_done, c->side));
+        S.side_pending = true;
+    }
+    return 0;
+}
+
+// The Gram and fit kernels sample_plan() picked, on the target in a.ret64: the task's coefficients into a.coeffs
+static int launch_fit(promp_ctx* c, StepData& S, const SampleArgs& a, const SamplePlan& plan, const SampleStream& ss) {
+    hipStream_t st = ss.st;
+    double* fit_scratch = ss.fit_scratch;
     const int nblk = plan.nblk, DA = a.D + 1, M = c->d.n_tasks;
     if (plan.gram != GramKernel::None && prof_begin(c, PROMP_KERNEL_GRAM, S.n_rows)) return -2;
     switch (plan.gram) {
@@ -1641,17 +1649,60 @@ int promp_process_samples(promp_ctx* c, int step, const promp_proc_opts* o) {
     }
     }
     HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+// what promp_process_samples and promp_process_samples_dice hand their kernels: the step's arrays, the call's options
+static SampleArgs process_args(const promp_ctx* c, const StepData& S, const SampleStream& ss, int kind, double discount, double gae_lambda,
+                               double reg_coeff, int normalize_adv, int positive_adv) {
+    SampleArgs a = sample_args(c, S, kind);
+    a.work = S.work[0];                         // k_gram / k_fit: one workgroup per CU
+    a.task_wg_offsets = S.task_wg_offsets[0];
+    a.gamma = discount; a.lam = gae_lambda; a.reg = reg_coeff;
+    a.normalize = normalize_adv; a.positive = positive_adv;
+    a.ret64 = S.ret64; a.ret32 = S.ret32; a.adv32 = S.adv32;
+    a.path_ret0 = S.path_ret0; a.path_undisc = S.path_undisc; a.path_rsq = S.path_rsq;
+    a.gram_partials = ss.gram_partials;
+    return a;
+}
+// returns -> fit -> GAE -> normalise (a.work moves on to the second table for k_normalize)
+static int launch_gae_pipeline(promp_ctx* c, StepData& S, SampleArgs& a, const SamplePlan& plan, const SampleStream& ss) {
+    hipStream_t st = ss.st;
+    PROMP_LAUNCH(k_returns, dim3(S.n_paths), 64, 0, st, a);
+    HIPCHECK(hipGetLastError());
+    if (const int rc = launch_fit(c, S, a, plan, ss)) return rc;
     PROMP_LAUNCH(k_gae, dim3(S.n_paths), 64, sizeof(double) * (size_t)(a.D > 0 ? a.D : 1), st, a);
     HIPCHECK(hipGetLastError());
     a.work = S.work[1];                         // k_normalize: two workgroups per CU
     PROMP_LAUNCH(k_normalize, dim3(S.n_work[1]), 256, 0, st, a);
     HIPCHECK(hipGetLastError());
-    if (on_side) {
-        HIPCHECK(hipEventRecord(S.ev_done, c->side));
-        S.side_pending = true;
-    }
+    return 0;
+}
+
+int promp_process_samples(promp_ctx* c, int step, const promp_proc_opts* o) {
+    if (!c || !o) return fail(-1, "NULL argument");
+    StepScope sc(c, step, /*writes=*/true, /*needs_data=*/true);
+    if (sc.rc) return sc.rc;
+    StepData& S = sc.S();
+    if (!(o->discount >= 0 && o->discount <= 1)) return fail(-1, "discount factor must be in [0,1]");      // samplers/base.py:57
+    if (!(o->gae_lambda >= 0 && o->gae_lambda <= 1)) return fail(-1, "gae_lambda must be in [0,1]");       // samplers/base.py:58
+    if (o->baseline_kind < 0 || o->baseline_kind > 2) return fail(-1, "unknown baseline kind %d", o->baseline_kind);
+    if (o->reserved < 0) return fail(-1, "pad_length %d is negative", o->reserved);
+    // which Gram and fit kernels run (promp_plan.h: sample_plan; the table in tests/test_gpu_parity.py)
+    SamplePlan plan;
+    std::string why;
+    if (const int rc = sample_plan(o->baseline_kind, c->d.obs_dim, feature_dim(&c->d, o->baseline_kind), c->sw, &plan, &why))
+        return fail_plan(rc, why);
+    SampleStream ss;
+    if (const int rc = sample_stream_begin(c, step, S, {&plan}, &ss)) return rc;
+    SampleArgs a = process_args(c, S, ss, o->baseline_kind, o->discount, o->gae_lambda, o->reg_coeff, o->normalize_adv, o->positive_adv);
+    a.pad_length = o->reserved;                 // non-zero: the statistics of the zero-padded [paths, pad_length] array
+    S.feat_dim = a.D;
+    if (const int rc = launch_gae_pipeline(c, S, a, plan, ss)) return rc;
+    if (const int rc = sample_stream_end(c, S, ss)) return rc;
     S.processed = true;
     S.has_adv = true;
+    S.dice_processed = false;
     return 0;
 }
 
@@ -1793,17 +1844,28 @@ int promp_use_selection(promp_ctx* c, int on) {
     return 0;
 }
 
+// The step's DiCE buffers, allocated on first use: the four of the objective (promp_set_dice_rewards and
+// promp_process_samples_dice) and, processing, what promp_process_samples_dice keeps beside them
+static int dice_buffers(promp_ctx* c, StepData& S, bool processing) {
+    const size_t R = c->d.max_rows, P = c->d.max_paths, M = c->d.n_tasks;
+    // (dice_rw / dice_path last: the guards stand for their groups)
+    if (!S.dice_rw && (S.dice_c.alloc(R) || S.dice_u.alloc(R) || S.dice_tmp.alloc(R) || S.dice_rw.alloc(R))) return -2;
+    if (processing && !S.dice_path &&
+        (S.dice_x64.alloc(R) || S.dice_adv64.alloc(R) || S.dice_vpg32.alloc(R) || S.dice_pad.alloc(2 * M) ||
+         S.dice_coeffs.alloc(M * c->coeff_stride) || S.dice_path.alloc(3 * P)))
+        return -2;
+    return 0;
+}
+
 int promp_set_dice_rewards(promp_ctx* c, int step, const float* rw) {
     if (!c || !rw) return fail(-1, "NULL argument");
     StepScope sc(c, step);
     if (sc.rc) return sc.rc;
     if (sc.open(/*writes=*/true, /*needs_data=*/true)) return sc.rc;
     StepData& S = sc.S();
-    if (!S.dice_rw) {
-        const size_t R = c->d.max_rows;
-        // (dice_rw last: the guard above stands for all four)
-        if (S.dice_c.alloc(R) || S.dice_u.alloc(R) || S.dice_tmp.alloc(R) || S.dice_rw.alloc(R)) return -2;
-    }
+    if (dice_buffers(c, S, /*processing=*/false)) return -2;
+    S.dice_processed = false;
+    S.has_dice_vpg = false;
     HIPCHECK(hipMemcpyAsync(S.dice_rw, rw, sizeof(float) * S.n_rows, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipStreamSynchronize(c->stream));      // (the source may be a temporary of the caller)
     // the gradient weights w_t = sum_{t' >= t} rw_t' take the advantages' place in the log-likelihood objective
@@ -1813,6 +1875,114 @@ int promp_set_dice_rewards(promp_ctx* c, int step, const float* rw) {
     HIPCHECK(hipGetLastError());
     S.has_adv = true;
     S.has_dice = true;
+    return 0;
+}
+
+int promp_process_samples_dice(promp_ctx* c, int step, const promp_dice_opts* o) {
+    if (!c || !o) return fail(-1, "NULL argument");
+    StepScope sc(c, step);
+    if (sc.rc) return sc.rc;
+    if (!(o->discount >= 0 && o->discount <= 1)) return fail(-1, "discount factor must be in [0,1]");      // dice_sample_processor.py:38
+    if (!(o->gae_lambda >= 0 && o->gae_lambda <= 1)) return fail(-1, "gae_lambda must be in [0,1]");
+    if (o->baseline_kind < 0 || o->baseline_kind > 2) return fail(-1, "unknown baseline kind %d", o->baseline_kind);
+    const bool vpg = o->return_baseline_kind != -1;
+    if (vpg && (o->return_baseline_kind < 0 || o->return_baseline_kind > 2)) return fail(-1, "unknown return baseline kind %d", o->return_baseline_kind);
+    if (sc.open(/*writes=*/true, /*needs_data=*/true)) return sc.rc;
+    StepData& S = sc.S();
+    if ((int)S.lay_pro.size() != S.n_paths + 1) return fail(-3, "step %d has no data", step);
+    int longest = 0;
+    for (int p = 0; p < S.n_paths; ++p) longest = std::max(longest, S.lay_pro[p + 1] - S.lay_pro[p]);
+    if (o->max_path_length < longest)
+        return fail(-1, "max_path_length %d is shorter than the step's longest path (%d rows)", o->max_path_length, longest);
+    SamplePlan plan, rplan;
+    std::string why;
+    if (const int rc = sample_plan(o->baseline_kind, c->d.obs_dim, feature_dim(&c->d, o->baseline_kind), c->sw, &plan, &why)) return fail_plan(rc, why);
+    if (vpg)
+        if (const int rc = sample_plan(o->return_baseline_kind, c->d.obs_dim, feature_dim(&c->d, o->return_baseline_kind), c->sw, &rplan, &why))
+            return fail_plan(rc, why);
+    if (dice_buffers(c, S, /*processing=*/true)) return -2;
+    SampleStream ss;
+    if (const int rc = sample_stream_begin(c, step, S, {&plan, &rplan}, &ss)) return rc;
+    hipStream_t st = ss.st;
+    const int M = c->d.n_tasks, P = c->d.max_paths;
+    S.processed = false; S.has_adv = false; S.has_dice = false; S.dice_processed = false; S.has_dice_vpg = false;
+    // the DiCE rewards: targets -> fit -> adjust -> finish.  The reward baseline's coefficients and the path sums have places of
+    // their own: the pass below overwrites the step's.
+    SampleArgs a = process_args(c, S, ss, o->baseline_kind, o->discount, o->gae_lambda, o->reg_coeff, o->normalize_adv, o->positive_adv);
+    a.pad_length = o->max_path_length;
+    a.coeffs = S.dice_coeffs;
+    a.path_undisc = S.dice_path; a.path_ret0 = S.dice_path + P; a.path_rsq = S.dice_path + 2 * (size_t)P;
+    a.x64 = S.dice_x64; a.dice_rw = S.dice_rw; a.pad_out = S.dice_pad;
+    PROMP_LAUNCH(k_dice_targets, dim3(S.n_paths), 64, 0, st, a);
+    HIPCHECK(hipGetLastError());
+    if (const int rc = launch_fit(c, S, a, plan, ss)) return rc;
+    PROMP_LAUNCH(k_dice_adjust, dim3(S.n_paths), 64, sizeof(double) * (size_t)(a.D > 0 ? a.D : 1), st, a);
+    HIPCHECK(hipGetLastError());
+    PROMP_LAUNCH(k_dice_finish, dim3(S.n_paths), 64, 0, st, a);
+    HIPCHECK(hipGetLastError());
+    S.dice_feat_dim = a.D;
+    S.dice_ret_feat_dim = 0;
+    S.feat_dim = 0;
+    if (vpg) {
+        // the ordinary pipeline on the slab's true rewards, normalised over the padded array; its advantages, as slab weights,
+        // beside the DiCE weights
+        SampleArgs g = process_args(c, S, ss, o->return_baseline_kind, o->discount, o->gae_lambda, o->return_reg_coeff, o->normalize_adv, o->positive_adv);
+        g.pad_length = o->max_path_length;
+        g.pad_scale = 1;
+        g.adv32 = S.dice_vpg32; g.x64 = S.dice_adv64; g.pad_out = S.dice_pad + M;
+        if (const int rc = launch_gae_pipeline(c, S, g, rplan, ss)) return rc;
+        S.dice_ret_feat_dim = S.feat_dim = g.D;
+    }
+    if (const int rc = sample_stream_end(c, S, ss)) return rc;
+    S.processed = true; S.has_adv = true; S.has_dice = true; S.dice_processed = true; S.has_dice_vpg = vpg;
+    return 0;
+}
+
+int promp_download_dice(promp_ctx* c, int step, double* adjusted, double* advantages, double* pad_adjusted, double* pad_advantages,
+                        double* coeffs, double* return_coeffs, double* path_undisc, double* path_disc, double* path_rsq) {
+    StepScope sc(c, step, /*writes=*/false, /*needs_data=*/false);
+    if (sc.rc) return sc.rc;
+    StepData& S = sc.S();
+    if (!S.dice_processed) return fail(-3, "step %d has not been processed by promp_process_samples_dice", step);
+    if ((advantages || pad_advantages || return_coeffs) && !S.has_dice_vpg)
+        return fail(-3, "step %d was processed without a return baseline: it has no GAE advantages", step);
+    hipStream_t st = c->stream;
+    const size_t R = (size_t)S.n_rows, P = (size_t)S.n_paths, PS = (size_t)c->d.max_paths, M = (size_t)c->d.n_tasks, CS = (size_t)c->coeff_stride;
+    if (adjusted) HIPCHECK(hipMemcpyAsync(adjusted, S.dice_x64, sizeof(double) * R, hipMemcpyDeviceToHost, st));
+    if (advantages) HIPCHECK(hipMemcpyAsync(advantages, S.dice_adv64, sizeof(double) * R, hipMemcpyDeviceToHost, st));
+    // the small results through the page-locked staging area, behind one synchronisation (as promp_download_processed)
+    if (c->small_host.reserve(2 * M + 2 * M * CS + 3 * P, 1)) return -2;
+    double* h = c->small_host;
+    double *hpad = h, *hco = h + 2 * M, *hrco = hco + M * CS, *hpath = hrco + M * CS;
+    const bool co = coeffs && S.dice_feat_dim > 0, rco = return_coeffs && S.dice_ret_feat_dim > 0;
+    if (pad_adjusted || pad_advantages) HIPCHECK(hipMemcpyAsync(hpad, S.dice_pad, sizeof(double) * 2 * M, hipMemcpyDeviceToHost, st));
+    if (co) HIPCHECK(hipMemcpyAsync(hco, S.dice_coeffs, sizeof(double) * M * CS, hipMemcpyDeviceToHost, st));
+    if (rco) HIPCHECK(hipMemcpyAsync(hrco, S.coeffs, sizeof(double) * M * CS, hipMemcpyDeviceToHost, st));
+    double* const sums[3] = {path_undisc, path_disc, path_rsq};
+    for (int k = 0; k < 3; ++k)
+        if (sums[k]) HIPCHECK(hipMemcpyAsync(hpath + k * P, S.dice_path + k * PS, sizeof(double) * P, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    if (pad_adjusted) memcpy(pad_adjusted, hpad, sizeof(double) * M);
+    if (pad_advantages) memcpy(pad_advantages, hpad + M, sizeof(double) * M);
+    for (size_t i = 0; i < M; ++i) {
+        if (co) memcpy(coeffs + i * S.dice_feat_dim, hco + i * CS, sizeof(double) * S.dice_feat_dim);
+        if (rco) memcpy(return_coeffs + i * S.dice_ret_feat_dim, hrco + i * CS, sizeof(double) * S.dice_ret_feat_dim);
+    }
+    for (int k = 0; k < 3; ++k)
+        if (sums[k]) memcpy(sums[k], hpath + k * P, sizeof(double) * P);
+    return 0;
+}
+
+int promp_use_dice_advantages(promp_ctx* c, int step) {
+    StepScope sc(c, step);
+    if (sc.rc) return sc.rc;
+    if (!sc.S().dice_processed || !sc.S().has_dice_vpg)
+        return fail(-3, "step %d holds no GAE advantages: promp_process_samples_dice with a return baseline comes first", step);
+    if (sc.open(/*writes=*/true, /*needs_data=*/true)) return sc.rc;
+    StepData& S = sc.S();
+    HIPCHECK(hipMemcpyAsync(S.adv32, S.dice_vpg32, sizeof(float) * S.n_rows, hipMemcpyDeviceToDevice, c->stream));
+    S.has_adv = true;
+    S.has_dice = false;      // the step's weights are advantages now: it is no longer DiCE data (vpg_dice_maml.py:46-49)
     return 0;
 }
 

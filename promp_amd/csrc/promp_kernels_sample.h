@@ -26,7 +26,10 @@
 //   k_gae            per path  b = Phi w ; delta ; GAE scan ; moments    baselines/linear_baseline.py:17-33, samplers/base.py:151-162
 //                    every call (ZeroBaseline: b = 0)
 //   k_normalize      per work item  (adv - mean) / (std + 1e-8) [, shift > 0]  utils/utils.py:59-71
-//                    every call
+//                    every call (pad_length: the statistics of the zero-padded array)
+//   k_dice_targets, k_dice_adjust, k_dice_finish   per path  r_t gamma^t ; y - Phi w, moments ; normalise over the padded array,
+//                    DiCE rewards and their suffix sums    samplers/dice_sample_processor.py:96-191
+//                    promp_process_samples_dice, around the same Gram / fit kernels
 // What several of them share is written once, in front of its first user: suffix_scan_chunk; linfeat_obs / linfeat_row_tail (the
 // feature row); tri_pair_blocks / tri_pair_index / gram_store_block / gram_scatter_entry (the partial-block layout);
 // fit_any_nan; fitw_back_substitute and the chol_* panel steps (the blocked Cholesky).
@@ -70,6 +73,12 @@ struct SampleArgs {
     double* coeffs;         // [tasks][coeff_stride]
     int coeff_stride;
     double* bl64;           // optional [rows]: the baseline predictions Phi.w (LinearBaseline.predict), else NULL
+    // statistics over a task's zero-padded [paths, pad_length] array (the DiCE sample processor); 0: over the task's rows
+    int pad_length;
+    int pad_scale;          // k_normalize: adv32 receives x * rows / (paths * pad_length), the weight of a slab mean
+    double* x64;            // optional [rows]: the normalised / shifted values in float64
+    double* pad_out;        // optional [tasks]: what a padded zero maps to
+    float* dice_rw;         // [rows] k_dice_finish: x * rows / (paths * pad_length)
 };
 
 // Suffix scan of one 64-step chunk, a step per lane: y[lane] = sum_{d >= 0, lane + d < 64} c^d x[lane + d] in six shuffle steps
@@ -588,17 +597,39 @@ __global__ void __launch_bounds__(FITWV_NT) k_fit_wave(SampleArgs a, int NBLK) {
 #endif
 }
 
+// The task's coefficients into wc (k_gae, k_dice_adjust: the workgroup's dynamic LDS), and one row's prediction b = Phi . w with
+// them (LinearBaseline.predict; BASE_ZERO: 0)
+PROMP_DEV void baseline_load_coeffs(const SampleArgs& a, int task, int lane, double* wc) {
+    if (a.kind != BASE_ZERO)
+        for (int i = lane; i < a.D; i += 64) wc[i] = a.coeffs[(long long)task * a.coeff_stride + i];
+    __syncthreads();
+}
+PROMP_DEV double baseline_row(const SampleArgs& a, const double* wc, long long row, int t) {
+    const int O = a.O;
+    double b = 0.0;
+    if (a.kind != BASE_ZERO) {
+        int q = 0;
+        if (a.kind == BASE_LINFEAT) {
+            for (int c = 0; c < O; ++c) {
+                double f[2];
+                linfeat_obs(a.obs[row * O + c], true, f, 0, 1);
+                b += wc[c] * f[0] + wc[O + c] * f[1];
+            }
+            q = 2 * O;
+        }
+        const double tau = linfeat_tau(t);
+        b += wc[q] * tau + wc[q + 1] * (tau * tau) + wc[q + 2] * (tau * tau * tau) + wc[q + 3];
+    }
+    return b;
+}
+
 // grid = paths, block = 64.  smem: D doubles (the task's coefficients)
 __global__ void __launch_bounds__(64) k_gae(SampleArgs a) {
     PROMP_SMEM_DECL;
     double* wc = (double*)PROMP_SMEM_PTR;
     const int p = blockIdx.x, lane = threadIdx.x;
     const int row0 = a.path_row_offsets[p], T = a.path_row_offsets[p + 1] - row0;
-    const int task = a.path_task[p];
-    const int O = a.O, D = a.D;
-    if (a.kind != BASE_ZERO)
-        for (int i = lane; i < D; i += 64) wc[i] = a.coeffs[(long long)task * a.coeff_stride + i];
-    __syncthreads();
+    baseline_load_coeffs(a, a.path_task[p], lane, wc);
     const double g = a.gamma, gl = a.gamma * a.lam;
     const double f = pow(gl, (double)(64 - lane));
     double carry = 0.0, bcarry = 0.0, s1 = 0.0, s2 = 0.0, mn = 1e300;
@@ -606,20 +637,7 @@ __global__ void __launch_bounds__(64) k_gae(SampleArgs a) {
         const int t = end - 64 + lane;
         const bool valid = t >= 0;
         const long long row = (long long)row0 + t;
-        double b = 0.0;
-        if (valid && a.kind != BASE_ZERO) {
-            int q = 0;
-            if (a.kind == BASE_LINFEAT) {
-                for (int c = 0; c < O; ++c) {
-                    double f[2];
-                    linfeat_obs(a.obs[row * O + c], true, f, 0, 1);
-                    b += wc[c] * f[0] + wc[O + c] * f[1];
-                }
-                q = 2 * O;
-            }
-            const double tau = linfeat_tau(t);
-            b += wc[q] * tau + wc[q + 1] * (tau * tau) + wc[q + 2] * (tau * tau * tau) + wc[q + 3];
-        }
+        const double b = valid ? baseline_row(a, wc, row, t) : 0.0;
         double bn = shfl_down_f64(b, 1);
         if (lane == 63) bn = bcarry;
         const double rw = a.rew64 ? a.rew64[valid ? row : 0] : (double)a.rew[valid ? row : 0];
@@ -646,9 +664,38 @@ __global__ void __launch_bounds__(64) k_gae(SampleArgs a) {
     }
 }
 
+// The statistics of a task's values from its paths' moments (path_mom).  pad_length = 0: over the task's rows.  Otherwise over
+// the zero-padded [paths, pad_length] array the DiCE sample processor normalises (samplers/dice_sample_processor.py:165-191): the
+// zeros add nothing to the sums, count in n, and are the minimum's rival wherever the task has any.
+struct TaskStats {
+    double mean, sd, mn, scale;   // mn: the raw minimum; scale = rows / n
+};
+PROMP_DEV TaskStats task_stats(double s1, double s2, double mn, int rows, int paths, int pad_length) {
+    double n = (double)rows;
+    if (pad_length != 0) {
+        n = (double)paths * (double)pad_length;
+        if ((long long)rows < (long long)paths * pad_length) mn = mn < 0.0 ? mn : 0.0;
+    }
+    TaskStats s;
+    s.mean = s1 / n;
+    double var = s2 / n - s.mean * s.mean;
+    var = var > 0.0 ? var : 0.0;
+    s.sd = sqrt(var);
+    s.mn = mn;
+    s.scale = (double)rows / n;
+    return s;
+}
+// what a padded zero becomes (0 where nothing is normalised or shifted); mn: the minimum AFTER normalisation
+PROMP_DEV double padded_zero(const TaskStats& s, double mn, int normalize, int positive) {
+    double z = 0.0;
+    if (normalize) z = (z - s.mean) / (s.sd + 1e-8);
+    if (positive) z = (z - mn) + 1e-8;
+    return z;
+}
+
 // grid = work items, block = 256
 __global__ void __launch_bounds__(256) k_normalize(SampleArgs a) {
-    __shared__ double st[3];
+    __shared__ double st[4];
     const int tid = threadIdx.x;
     const WorkItem wk = a.work[blockIdx.x];
     const int task = wk.task;
@@ -659,13 +706,15 @@ __global__ void __launch_bounds__(256) k_normalize(SampleArgs a) {
             s2 += a.path_mom[3 * p + 1];
             mn = a.path_mom[3 * p + 2] < mn ? a.path_mom[3 * p + 2] : mn;
         }
-        const double n = (double)(a.task_row_offsets[task + 1] - a.task_row_offsets[task]);
-        const double mean = s1 / n;
-        double var = s2 / n - mean * mean;
-        var = var > 0.0 ? var : 0.0;
-        st[0] = mean;
-        st[1] = sqrt(var);
-        st[2] = mn;
+        const int row0 = a.task_row_offsets[task];
+        const TaskStats s = task_stats(s1, s2, mn, a.task_row_offsets[task + 1] - row0, a.task_path_offsets[task + 1] - a.task_path_offsets[task],
+                                       a.pad_length);
+        st[0] = s.mean;
+        st[1] = s.sd;
+        st[2] = s.mn;
+        st[3] = a.pad_scale ? s.scale : 1.0;
+        if (a.pad_out != nullptr && wk.row_begin == row0)       // (the task's first work item)
+            a.pad_out[task] = padded_zero(s, a.normalize ? (s.mn - s.mean) / (s.sd + 1e-8) : s.mn, a.normalize, a.positive);
     }
     __syncthreads();
     const double mean = st[0], sd = st[1];
@@ -675,7 +724,108 @@ __global__ void __launch_bounds__(256) k_normalize(SampleArgs a) {
         double x = a.adv64[row];
         if (a.normalize) x = (x - mean) / (sd + 1e-8);
         if (a.positive) x = (x - mn) + 1e-8;
-        a.adv32[row] = (float)x;
+        if (a.x64 != nullptr) a.x64[row] = x;
+        a.adv32[row] = a.pad_scale ? (float)(x * st[3]) : (float)x;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// DiCE sample processing (samplers/dice_sample_processor.py:96-191, utils/utils.py:59-71; float64 restatement:
+// oracle/dice.py process_samples_dice): k_dice_targets -> the plan's Gram and fit kernels on that target -> k_dice_adjust ->
+// k_dice_finish.  One wave per path, grid = paths, block = 64.
+// ---------------------------------------------------------------------------------------------
+// y_t = r_t gamma^t into the regression target's place (ret64 / ret32); per path: sum r (path_undisc), sum y (path_ret0: DiCE's
+// "discounted return"), sum r^2 (path_rsq).  gamma^t is pow(), not the reference's running product: they differ by rounding.
+__global__ void __launch_bounds__(64) k_dice_targets(SampleArgs a) {
+    const int p = blockIdx.x, lane = threadIdx.x;
+    const int row0 = a.path_row_offsets[p], T = a.path_row_offsets[p + 1] - row0;
+    double usum = 0.0, ysum = 0.0, rsq = 0.0;
+    for (int t = lane; t < T; t += 64) {
+        const long long row = (long long)row0 + t;
+        const double x = a.rew64 ? a.rew64[row] : (double)a.rew[row];
+        const double y = x * pow(a.gamma, (double)t);
+        a.ret64[row] = y;
+        a.ret32[row] = (float)y;
+        usum += x;
+        ysum += y;
+        rsq += x * x;
+    }
+    usum = wave_sum_f64(usum);
+    ysum = wave_sum_f64(ysum);
+    rsq = wave_sum_f64(rsq);
+    if (lane == 0) {
+        a.path_undisc[p] = usum;
+        a.path_ret0[p] = ysum;
+        a.path_rsq[p] = rsq;
+    }
+}
+
+// adj = y - Phi . w into adv64, its moments into path_mom.  smem: D doubles (the task's coefficients), as k_gae
+__global__ void __launch_bounds__(64) k_dice_adjust(SampleArgs a) {
+    PROMP_SMEM_DECL;
+    double* wc = (double*)PROMP_SMEM_PTR;
+    const int p = blockIdx.x, lane = threadIdx.x;
+    const int row0 = a.path_row_offsets[p], T = a.path_row_offsets[p + 1] - row0;
+    baseline_load_coeffs(a, a.path_task[p], lane, wc);
+    double s1 = 0.0, s2 = 0.0, mn = 1e300;
+    for (int t = lane; t < T; t += 64) {
+        const long long row = (long long)row0 + t;
+        const double adj = a.ret64[row] - baseline_row(a, wc, row, t);
+        a.adv64[row] = adj;
+        s1 += adj;
+        s2 += adj * adj;
+        mn = adj < mn ? adj : mn;
+    }
+    s1 = wave_sum_f64(s1);
+    s2 = wave_sum_f64(s2);
+    mn = wave_min_f64(mn);
+    if (lane == 0) {
+        a.path_mom[3 * p + 0] = s1;
+        a.path_mom[3 * p + 1] = s2;
+        a.path_mom[3 * p + 2] = mn;
+    }
+}
+
+// The adjusted rewards normalised / shifted over the task's padded array (x64), the rewards of the DiCE objective
+// dice_rw = float(x rows / n), their suffix sums within the path (adv32: the gradient weights, k_dice_scan's mode 0) and the
+// task's pad value.  Every wave of a task sums the task's path moments itself, lane by lane in path order and then across the
+// wave: the same order whatever the grid.
+__global__ void __launch_bounds__(64) k_dice_finish(SampleArgs a) {
+    const int p = blockIdx.x, lane = threadIdx.x;
+    const int row0 = a.path_row_offsets[p], T = a.path_row_offsets[p + 1] - row0;
+    const int task = a.path_task[p];
+    const int p0 = a.task_path_offsets[task], p1 = a.task_path_offsets[task + 1];
+    double s1 = 0.0, s2 = 0.0, mn = 1e300;
+    for (int q = p0 + lane; q < p1; q += 64) {
+        s1 += a.path_mom[3 * q];
+        s2 += a.path_mom[3 * q + 1];
+        mn = a.path_mom[3 * q + 2] < mn ? a.path_mom[3 * q + 2] : mn;
+    }
+    s1 = wave_sum_f64(s1);
+    s2 = wave_sum_f64(s2);
+    mn = wave_min_f64(mn);
+    const TaskStats s = task_stats(s1, s2, mn, a.task_row_offsets[task + 1] - a.task_row_offsets[task], p1 - p0, a.pad_length);
+    const double mean = s.mean, sd = s.sd;
+    mn = s.mn;
+    if (a.normalize) mn = (mn - mean) / (sd + 1e-8);
+    if (p == p0 && lane == 0) a.pad_out[task] = padded_zero(s, mn, a.normalize, a.positive);
+    double carry = 0.0;
+    for (int end = T; end > 0; end -= 64) {
+        const int t = end - 64 + lane;
+        const long long row = (long long)row0 + t;
+        double w = 0.0;
+        if (t >= 0) {
+            double x = a.adv64[row];
+            if (a.normalize) x = (x - mean) / (sd + 1e-8);
+            if (a.positive) x = (x - mn) + 1e-8;
+            a.x64[row] = x;
+            const float rw = (float)(x * s.scale);
+            a.dice_rw[row] = rw;
+            w = (double)rw;
+        }
+        const double y = suffix_scan_chunk<false>(w, lane) + carry;
+        if (t >= 0) a.adv32[row] = (float)y;
+        carry = shfl_idx_f64(y, 0);
     }
 }
 

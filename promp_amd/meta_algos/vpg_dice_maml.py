@@ -32,15 +32,20 @@ class VPG_DICEMAML(DICEMAML):
             "the last step's samples carry no 'advantages': build the DiCE sample processor with a return_baseline"
         self._place_dice_steps(all_samples_data)
         ctx = self.session.ctx
-        # the last step's weights: advantage * mask of the valid entries; rows / (paths * max_path_length) turns the slab mean
-        # (1 / rows) into the reference's mean over the padded array
-        adv = []
-        for sd in all_samples_data[K]:
-            m = np.asarray(sd['mask']) > 0.5
-            n = m.sum(axis=1).astype(np.int64)
-            a = np.asarray(sd['advantages'], dtype=np.float64)
-            adv.append(np.concatenate([a[p, :n[p]] for p in range(len(n))]) * (n.sum() / float(m.size)))
-        ctx.set_advantages(K, np.concatenate(adv).astype(np.float32))
+        last = all_samples_data[K]
+        if self.session.resident_slot(last) == K and all(getattr(sd, 'dice_advantages_resident', False) for sd in last):
+            # straight from DiceSampleProcessor with a return_baseline: the weights below already lie beside the slab
+            ctx.use_dice_advantages(K)
+        else:
+            # the last step's weights: advantage * mask of the valid entries; rows / (paths * max_path_length) turns the slab mean
+            # (1 / rows) into the reference's mean over the padded array
+            adv = []
+            for sd in last:
+                m = np.asarray(sd['mask']) > 0.5
+                n = m.sum(axis=1).astype(np.int64)
+                a = np.asarray(sd['advantages'], dtype=np.float64)
+                adv.append(np.concatenate([a[p, :n[p]] for p in range(len(n))]) * (n.sum() / float(m.size)))
+            ctx.set_advantages(K, np.concatenate(adv).astype(np.float32))
         if log: logger.log('Optimizing')
         res = self.session.optimize(1, self.learning_rate, 0.0, np.zeros(K, np.float32), _lib.INNER_DICE, _lib.OUTER_LOGLIK)
         # slot K's weights are the GAE advantages now, not the DiCE suffix sums promp_set_dice_rewards wrote: the samples are no

@@ -5,11 +5,14 @@ Contract: discounted rewards r_t gamma^t, a reward baseline fitted on them, adju
 every path zero-padded to max_path_length with a mask, adjusted rewards normalised / shifted over the PADDED [paths,
 max_path_length] array, path statistics logged from the discounted rewards.
 
-Where the arithmetic runs: the baseline regression (features, normal equations, solve, predictions) is the device pipeline of
-promp_process_samples with the regression target expressed as rewards whose undiscounted return IS the target
-(r'_t = y_t - y_{t+1}, discount 1).  Padding, masks and the normalisation over the padded array are array bookkeeping on the
-host.  The step's slab (observations, actions, agent_infos) stays resident on the device and receives the DiCE rewards of the
-valid rows (promp_set_dice_rewards), so DICEMAML._adapt / optimize_policy need no second upload.
+Where the arithmetic runs: on the device, in one call (promp_process_samples_dice: discounted rewards, baseline fit, adjusted
+rewards, the normalisation over the padded array from the paths' moments, the DiCE rewards of the valid rows and their suffix
+sums; with a return_baseline also returns, fit, GAE and the padded normalisation of the advantages), on the step's slab -- a
+batch a device sampler left resident (DevicePaths) is not uploaded, anything else is uploaded once, with its true rewards.  One
+download brings the valid rows and each task's pad value back; masks and the padded copies of the inputs are array bookkeeping
+on the host.  DICEMAML._adapt / optimize_policy find the slab and its DiCE rewards resident; VPG_DICEMAML finds the advantages
+beside them (promp_use_dice_advantages).  The path dicts' 'adjusted_rewards' are the rows of the samples' array (normalised /
+shifted wherever the processor does either).
 """
 from collections import OrderedDict
 
@@ -67,84 +70,81 @@ class DiceSampleProcessor(SampleProcessor):
     def _process_meta_batch(self, paths_meta_batch):
         """-> (list of DiceSamplesData per task, all paths with 'discounted_rewards' / 'adjusted_rewards' added)"""
         T = self.max_path_length
-        disc = np.cumprod(np.concatenate([np.ones(1), np.ones(T - 1) * self.discount]))
-        shadow = OrderedDict()
-        for i, plist in paths_meta_batch.items():
-            sh = []
-            for p in plist:
-                n = len(p['rewards'])
-                assert T >= n
-                p['discounted_rewards'] = np.asarray(p['rewards']) * disc[:n]
-                y = np.asarray(p['discounted_rewards'], dtype=np.float64)
-                q = dict(p)
-                q['rewards'] = y - np.append(y[1:], 0.0)            # undiscounted return of r' == the regression target
-                sh.append(q)
-            shadow[i] = sh
         M = len(paths_meta_batch)
-        fl = _lib.flatten_paths(shadow)
-        first = next(iter(paths_meta_batch.values()))[0]
-        A = int(np.asarray(first['actions']).reshape(len(first['rewards']), -1).shape[1])
-        sess = self._session_for(M, fl['obs'].shape[1], A)
-        slot = sess.next_slot()
-        upload = sess.upload_flat(slot, fl)
-        ctx = sess.ctx
-        kind = self._baseline_kind()
-        ctx.process_samples(slot, discount=1.0, gae_lambda=1.0, normalize_adv=False, positive_adv=False, baseline_kind=kind,
-                            reg_coeff=getattr(self.baseline, '_reg_coeff', 1e-5))
-        if kind != _lib.BASELINE_ZERO:
-            self.baseline._coeffs = ctx.download_processed(slot, kind)['coeffs'][-1].copy()
-        base = ctx.predict_baseline(slot, kind)                    # Phi . w per valid row, float64
-        pro, tpo = fl['path_row_offsets'], fl['task_path_offsets']
-        gae = None
+        if hasattr(paths_meta_batch, 'settle'):
+            paths_meta_batch.settle()             # a pending side effect of an earlier processor goes in first: this call adds its own
+        path_lists = list(paths_meta_batch.values())
+        kind, rkind = self._baseline_kind(), None
         if self.return_baseline is not None:
-            # GAE advantages from a baseline fitted on the returns: the ordinary pipeline (returns, fit, predict, GAE) on the true
-            # rewards of the same slab; normalisation happens below, over the padded array
             rkind = getattr(self.return_baseline, 'kind', None)
             if rkind is None:
                 raise TypeError('%s has no device-side `kind`' % type(self.return_baseline).__name__)
-            true_rewards = np.concatenate([np.asarray(p['rewards'], dtype=np.float64) for plist in paths_meta_batch.values() for p in plist])
-            ctx.set_rewards(slot, true_rewards)
-            ctx.process_samples(slot, discount=self.discount, gae_lambda=self.gae_lambda, normalize_adv=False, positive_adv=False,
-                                baseline_kind=rkind, reg_coeff=getattr(self.return_baseline, '_reg_coeff', 1e-5))
-            if rkind != _lib.BASELINE_ZERO:
-                self.return_baseline._coeffs = ctx.download_processed(slot, rkind)['coeffs'][-1].copy()
-            ret64, gae = ctx.download_raw(slot)
-            for i, (_, plist) in enumerate(paths_meta_batch.items()):
-                for j, p in enumerate(plist):
-                    a, b = pro[tpo[i] + j], pro[tpo[i] + j + 1]
-                    p['returns'], p['advantages'] = ret64[a:b], gae[a:b]
-        result, rw_rows = [], []
-        for i, (_, plist) in enumerate(paths_meta_batch.items()):
-            for j, p in enumerate(plist):
-                a, b = pro[tpo[i] + j], pro[tpo[i] + j + 1]
-                p['adjusted_rewards'] = p['discounted_rewards'] - base[a:b]
-            adj = self._stack_padded(plist, 'adjusted_rewards')
-            if self.normalize_adv:
-                adj = (adj - np.mean(adj)) / (np.std(adj) + 1e-8)   # over the padded array, zeros included (utils/utils.py:59-66)
-            if self.positive_adv:
-                adj = (adj - np.min(adj)) + 1e-8
-            sd = DiceSamplesData(
-                mask=np.stack([self._pad(np.ones(len(p['rewards'])), len(p['rewards'])) for p in plist], axis=0),
+        opts = dict(max_path_length=T, discount=self.discount, gae_lambda=self.gae_lambda, normalize_adv=self.normalize_adv,
+                    positive_adv=self.positive_adv, baseline_kind=kind, reg_coeff=getattr(self.baseline, '_reg_coeff', 1e-5),
+                    return_baseline_kind=rkind, return_reg_coeff=getattr(self.return_baseline, '_reg_coeff', 1e-5))
+        # the resident test of SampleProcessor._process_on_device: a batch a device sampler wrote into its slab is not uploaded
+        sess, ref = session_mod.current(), getattr(paths_meta_batch, 'device_ref', None)
+        resident = ref is not None and sess is not None and sess.ctx is not None and ref[0] == sess.serial \
+            and sess.upload_serial[ref[2]] == ref[1]
+        if resident:
+            fl, upload, slot = paths_meta_batch.flat, ref[1], ref[2]
+        else:
+            fl = _lib.flatten_paths(paths_meta_batch)
+        pro, tpo = np.asarray(fl['path_row_offsets']), np.asarray(fl['task_path_offsets'])
+        lens_all = np.diff(pro)
+        assert T >= int(lens_all.max()), 'a path is longer than max_path_length'
+        if not resident:
+            first = path_lists[0][0]
+            A = int(np.asarray(first['actions']).reshape(len(first['rewards']), -1).shape[1])
+            sess = self._session_for(M, fl['obs'].shape[1], A)
+            slot = sess.next_slot()
+            upload = sess.upload_flat(slot, fl)        # the true rewards: the device forms the discounted ones itself
+        ctx = sess.ctx
+        ctx.process_samples_dice(slot, **opts)
+        # host work while the device is busy: the discounted rewards of the path dicts, masks, padded copies of the inputs
+        disc = np.cumprod(np.concatenate([np.ones(1), np.ones(T - 1) * self.discount]))
+        padded = []
+        for i, plist in enumerate(path_lists):
+            for p in plist:
+                p['discounted_rewards'] = np.asarray(p['rewards']) * disc[:len(p['rewards'])]
+            lens = lens_all[tpo[i]:tpo[i + 1]]
+            padded.append(dict(
+                mask=(np.arange(T)[None, :] < lens[:, None]).astype(np.float64),
                 observations=self._stack_padded(plist, 'observations'),
                 actions=self._stack_padded(plist, 'actions'),
                 rewards=self._stack_padded(plist, 'rewards'),
                 env_infos={k: self._stack_padded(plist, 'env_infos', k) for k in plist[0].get('env_infos', {})},
-                agent_infos={k: self._stack_padded(plist, 'agent_infos', k) for k in plist[0].get('agent_infos', {})},
-                adjusted_rewards=adj)
-            if gae is not None:
-                adv = self._stack_padded(plist, 'advantages')
-                if self.normalize_adv:
-                    adv = (adv - np.mean(adv)) / (np.std(adv) + 1e-8)
-                if self.positive_adv:
-                    adv = (adv - np.min(adv)) + 1e-8
-                sd['advantages'] = adv
+                agent_infos={k: self._stack_padded(plist, 'agent_infos', k) for k in plist[0].get('agent_infos', {})}))
+        out = ctx.download_dice(slot)
+        if kind != _lib.BASELINE_ZERO:
+            self.baseline._coeffs = out['coeffs'][-1].copy()       # the shared baseline ends on the last task's fit
+        ret64 = gae = None
+        if rkind is not None:
+            if rkind != _lib.BASELINE_ZERO:
+                self.return_baseline._coeffs = out['return_coeffs'][-1].copy()
+            ret64, gae = ctx.download_raw(slot)                     # the path dicts' float64 returns and raw GAE advantages
+
+        def pad_rows(rows, mask, pad_value):
+            a = np.full(mask.shape, pad_value, dtype=np.float64)
+            a[mask > 0.5] = rows                                     # path-major, time-major: the slab's order
+            return a
+        result = []
+        ends = pro.tolist()
+        for i, plist in enumerate(path_lists):
+            for j, p in enumerate(plist):
+                a, b = ends[tpo[i] + j], ends[tpo[i] + j + 1]
+                # (the rows of the samples' array: normalised / shifted wherever the processor does either)
+                p['adjusted_rewards'] = out['adjusted'][a:b]
+                if gae is not None:
+                    p['returns'], p['advantages'] = ret64[a:b], gae[a:b]
+            r0, r1 = ends[tpo[i]], ends[tpo[i + 1]]
+            sd = DiceSamplesData(adjusted_rewards=pad_rows(out['adjusted'][r0:r1], padded[i]['mask'], out['pad_adjusted'][i]), **padded[i])
+            if rkind is not None:
+                sd['advantages'] = pad_rows(out['advantages'][r0:r1], padded[i]['mask'], out['pad_advantages'][i])
             sd.device_ref = (sess.serial, upload, slot, i)
+            sd.dice_advantages_resident = rkind is not None         # VPG_DICEMAML: promp_use_dice_advantages instead of an upload
             result.append(sd)
-            rows = sum(len(p['rewards']) for p in plist)
-            scale = rows / float(len(plist) * T)                     # slab mean (1 / rows) -> mean over the padded array
-            rw_rows.append(np.concatenate([adj[j, :len(p['rewards'])] for j, p in enumerate(plist)]) * scale)
-        ctx.set_dice_rewards(slot, np.concatenate(rw_rows))
-        return result, [p for plist in paths_meta_batch.values() for p in plist]
+        return result, [p for plist in path_lists for p in plist]
 
     # -- reference API ---------------------------------------------------------------------------------------------------
     def process_samples(self, paths, log=False, log_prefix=''):
