@@ -108,8 +108,8 @@ const char* promp_last_error(void);
  * promp_begin_collection / promp_end_collection, promp_state_version, the two pass counters; round 4: promp_comm_fixed_order;
  * later: promp_set_train_step_sizes with promp_get_step_sizes / promp_get_step_size_grad / promp_{set,get}_step_size_adam_state
  * and promp_reduced_count; promp_set_outer_optimizer / promp_get_outer_optimizer / promp_get_grad_norm;
- * promp_process_samples_dice / promp_download_dice / promp_use_dice_advantages (and promp_proc_opts.reserved read as pad_length)
- * -- were additions and did not move it. */
+ * promp_process_samples_dice / promp_download_dice / promp_use_dice_advantages (and promp_proc_opts.reserved read as pad_length);
+ * promp_rollout_point_family -- were additions and did not move it. */
 int promp_abi_version(void);
 /* Theta = O*H1+H1 + H1*H2+H2 + H2*A+A + A */
 int promp_param_count(const promp_dims* dims);
@@ -345,6 +345,32 @@ typedef struct {
 } promp_point_env_opts;
 int promp_rollout_point_env(promp_ctx* ctx, int step, int envs_per_task, int path_length, const double* goals,
                             const double* start, const float* noise, const promp_point_env_opts* opts);
+
+/* (b') the point-mass FAMILY: the reference's three fixed-horizon meta-environments with corner goals, the wrapper, the policy
+ *     side, the noise and the slab exactly as in (b).  kind selects the environment; obs_dim of the context = state_dim:
+ *       PROMP_POINT_CORNER   task_dim 2 (goal), state_dim 2: the environment of (b), same results bit for bit
+ *       PROMP_POINT_WALLS    task_dim 6 (goal, gap_1, gap_2), state_dim 2        envs/point_envs/point_env_2d_walls.py:36-51, 71-83
+ *           s' = p + clip(e, -max_step, max_step); the reward is taken on this s', before any wall acts:
+ *           0 dense -|s' - goal|, 1 dense_squared, 2 sparse |p - goal| - |s' - goal| if |s' - goal| < sparse_radius.  Outside the
+ *           radius the reference returns None, which its own normalize wrapper raises on and no sampler can sum: it is 0.0 here.
+ *           if |p| < 1 and |s'| > 1:       s' <- s' / (|s'| + 1e-6)       unless |s' - gap_1| <= 1
+ *           else if |p| < 2 and |s'| > 2:  s' <- s' / (0.5 |s'| + 1e-6)   unless |s' - gap_2| <= 1
+ *           (every norm: squares, sum, root in float64; the reference's assertions are not reproduced)
+ *       PROMP_POINT_MOMENTUM task_dim 2 (goal), state_dim 4 (position, velocity)  envs/point_envs/point_env_2d_momentum.py:36-42, 63-71
+ *           v <- v + clip(e, -max_step, max_step); s' = s + v; observation (s', v);
+ *           0 dense, 1 dense_squared, 2 sparse max(sparse_radius - |s' - goal|, 0)
+ *     Neither environment ends an episode.  task_params [n_tasks][task_dim], start [n_tasks][envs_per_task][state_dim] (float64);
+ *     noise as in (b).  An unknown kind, a task_dim that is not the kind's, a context whose obs_dim is not state_dim or whose
+ *     act_dim is not 2 are refused.  Asynchronous. */
+enum { PROMP_POINT_CORNER = 0, PROMP_POINT_WALLS = 1, PROMP_POINT_MOMENTUM = 2 };
+typedef struct {
+    int32_t kind;          /* PROMP_POINT_* */
+    int32_t reward_type, clip_infos, task_dim;
+    double normalization_scale, max_step, sparse_radius;
+    uint64_t seed;
+} promp_point_family_opts;
+int promp_rollout_point_family(promp_ctx* ctx, int step, int envs_per_task, int path_length, const double* task_params,
+                               const double* start, const float* noise, const promp_point_family_opts* opts);
 
 /* Step slab back on the host (any pointer may be NULL): obs [rows][O], act [rows][A], rew [rows],
  * old_mean [rows][A], old_log_std [rows | n_tasks][A] as uploaded / produced by a device rollout. */

@@ -52,7 +52,14 @@ class PointEnvOpts(C.Structure):
                 ('reward_type', C.c_int32), ('clip_infos', C.c_int32), ('seed', C.c_uint64)]
 
 
+class PointFamilyOpts(C.Structure):
+    _fields_ = [('kind', C.c_int32), ('reward_type', C.c_int32), ('clip_infos', C.c_int32), ('task_dim', C.c_int32),
+                ('normalization_scale', C.c_double), ('max_step', C.c_double), ('sparse_radius', C.c_double), ('seed', C.c_uint64)]
+
+
 POINT_REWARD = dict(dense=0, dense_squared=1, sparse=2)
+POINT_KIND = dict(corner=0, walls=1, momentum=2)
+POINT_KIND_DIMS = dict(corner=(2, 2), walls=(6, 2), momentum=(2, 4))       # kind -> (task_dim, state_dim)
 
 _F = C.POINTER(C.c_float)
 _D = C.POINTER(C.c_double)
@@ -110,6 +117,7 @@ SIGNATURES = {
     'promp_inner_adapt': (C.c_int, [_P, C.c_int, C.c_int]),
     'promp_policy_forward': (C.c_int, [_P, _F, C.c_int, _F]),
     'promp_rollout_point_env': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _D, _D, _F, C.POINTER(PointEnvOpts)]),
+    'promp_rollout_point_family': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _D, _D, _F, C.POINTER(PointFamilyOpts)]),
     'promp_begin_rollout': (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     'promp_begin_collection': (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     'promp_end_collection': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _F]),
@@ -843,6 +851,35 @@ class Context:
         opts = PointEnvOpts(float(normalization_scale), float(max_step), float(sparse_radius), POINT_REWARD[reward_type],
                             int(bool(clip_infos)), int(seed))
         self._call('promp_rollout_point_env', int(step), int(B), int(T), _ptr(goals, C.c_double), _ptr(start, C.c_double),
+                   _ptr(noise, C.c_float) if noise is not None else None, C.byref(opts))
+        self.step_rows[step], self.step_paths[step] = M * B * T, M * B
+        self.step_tpo[step] = np.arange(M + 1, dtype=np.int64) * B
+        self.step_ls_rows[step] = M
+
+    def rollout_point_family(self, step, kind, task_params, start, noise=None, clip_infos=True, reward_type='dense',
+                             normalization_scale=0.0, max_step=0.2, sparse_radius=2.0, seed=0, path_length=None, task_dim=None):
+        """Device rollout of a point-mass meta-environment with corner goals, kind 'corner' | 'walls' | 'momentum' (or its number):
+        task_params [M, task_dim] (corner, momentum: the goal; walls: goal, gap_1, gap_2), start [M, B, state_dim] (float64;
+        momentum: position, velocity), noise [M,B,T,2] or None as in rollout_point_env -> fills step `step`'s slab with M*B
+        paths of length T, observations of width state_dim (see promp_rollout_point_family)."""
+        self._pre_write(step)
+        task_params = np.ascontiguousarray(task_params, dtype=np.float64)
+        start = np.ascontiguousarray(start, dtype=np.float64)
+        assert task_params.ndim == 2 and start.ndim == 3
+        M, B = self.n_tasks, start.shape[1]
+        if noise is not None:
+            noise = _f32(noise)
+            T = noise.shape[2]
+            assert noise.shape == (M, B, T, 2)
+        else:
+            T = int(path_length)
+        if kind in POINT_KIND:
+            assert (task_params.shape[1], start.shape[2]) == POINT_KIND_DIMS[kind], (kind, task_params.shape, start.shape)
+        assert task_params.shape[0] == M and start.shape[0] == M
+        opts = PointFamilyOpts(int(POINT_KIND.get(kind, kind)), POINT_REWARD[reward_type], int(bool(clip_infos)),
+                               int(task_params.shape[1] if task_dim is None else task_dim), float(normalization_scale),
+                               float(max_step), float(sparse_radius), int(seed))
+        self._call('promp_rollout_point_family', int(step), int(B), int(T), _ptr(task_params, C.c_double), _ptr(start, C.c_double),
                    _ptr(noise, C.c_float) if noise is not None else None, C.byref(opts))
         self.step_rows[step], self.step_paths[step] = M * B * T, M * B
         self.step_tpo[step] = np.arange(M + 1, dtype=np.int64) * B

@@ -2292,6 +2292,53 @@ int promp_rollout_point_env(promp_ctx* c, int step, int envs_per_task, int path_
     return 0;
 }
 
+int promp_rollout_point_family(promp_ctx* c, int step, int envs_per_task, int path_length, const double* task_params,
+                               const double* start, const float* noise, const promp_point_family_opts* o) {
+    if (!c || !task_params || !start || !o) return fail(-1, "NULL argument");
+    StepScope sc(c, step);
+    if (sc.rc) return sc.rc;
+    if (o->kind < POINT_KIND_CORNER || o->kind > POINT_KIND_MOMENTUM) return fail(-1, "unknown environment kind %d", o->kind);
+    const int task_dim = o->kind == POINT_KIND_WALLS ? 6 : 2, state_dim = o->kind == POINT_KIND_MOMENTUM ? 4 : 2;
+    if (o->task_dim != task_dim) return fail(-1, "task_dim = %d, environment kind %d has task_dim = %d", o->task_dim, o->kind, task_dim);
+    if (c->d.obs_dim != state_dim) return fail(-1, "environment kind %d has obs_dim = %d (context: %d)", o->kind, state_dim, c->d.obs_dim);
+    if (c->d.act_dim != 2) return fail(-1, "the point environments have act_dim = 2 (context: %d)", c->d.act_dim);
+    if (o->reward_type < 0 || o->reward_type > 2) return fail(-1, "unknown reward type %d", o->reward_type);
+    if (begin_fixed_rollout(sc, envs_per_task, path_length)) return -2;
+    const int M = c->d.n_tasks, B = envs_per_task, T = path_length;
+    const long long rows = (long long)M * B * T;
+    StepData& S = sc.S();
+    S.data_version = ++c->version_counter;
+    const size_t n_task = (size_t)M * task_dim, n_start = (size_t)M * B * state_dim;
+    if (c->rollout_buf.reserve(sizeof(double) * (n_task + n_start) + sizeof(float) * (size_t)rows * 2, 2)) return -2;
+    double* d_task = (double*)c->rollout_buf.p;
+    double* d_start = d_task + n_task;
+    float* d_noise = (float*)(d_start + n_start);
+    hipStream_t st = c->stream;
+    HIPCHECK(hipMemcpyAsync(d_task, task_params, sizeof(double) * n_task, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(d_start, start, sizeof(double) * n_start, hipMemcpyHostToDevice, st));
+    if (noise) HIPCHECK(hipMemcpyAsync(d_noise, noise, sizeof(float) * rows * 2, hipMemcpyHostToDevice, st));
+    PointFamilyArgs f;
+    PointRolloutArgs& a = f.p;
+    if (tasks_materialize(c)) return -2;
+    a.theta_tasks = c->theta_tasks; a.NP = c->NP; a.H1 = c->d.hidden1; a.H2 = c->d.hidden2;
+    a.B = B; a.T = T; a.goals = d_task; a.start = d_start; a.noise = noise ? d_noise : nullptr;
+    a.seed = o->seed; a.stream = (unsigned)step;
+    a.obs = S.obs; a.act = S.act; a.rew = S.rew; a.mean = S.old_mean; a.old_ls = S.old_ls;
+    a.clip_infos = o->clip_infos; a.min_log_std = c->min_log_std;
+    a.normalization_scale = o->normalization_scale; a.max_step = o->max_step; a.reward_type = o->reward_type; a.sparse_radius = o->sparse_radius;
+    f.kind = o->kind; f.task_dim = task_dim; f.state_dim = state_dim;
+    if (c->family == PassFamily::Layered) {
+        GenPointFamilyArgs g;
+        g.f = f; g.act_kind = gen_act_kinds(&c->d);
+        copy_layers(g, c);
+        PROMP_LAUNCH(k_gen_point_family_rollout, dim3(B, M), 256, gen_rollout_smem(state_dim), st, g);
+    } else
+    PROMP_LAUNCH(k_point_family_rollout, dim3(M), 64, 0, st, f);
+    HIPCHECK(hipGetLastError());
+    S.ps.obs_range_valid = false;
+    return 0;
+}
+
 int promp_begin_rollout(promp_ctx* c, int step, int envs_per_task, int path_length) {
     NEED_CTX(c);
     StepScope sc(c, step);

@@ -558,7 +558,9 @@ __global__ void __launch_bounds__(256) k_gen_policy_forward(GenForwardArgs a) {
 PROMP_HD size_t gen_rollout_smem(int O) { return sizeof(float) * (size_t)(O + 2 * 256); }
 
 // xs [lin[0].K] holds the observation; returns the mean [A] (in LDS, valid for every thread: the last barrier has been passed)
-PROMP_DEV const float* gen_mlp_block(const float* th, const GenLin* lin, int n_lin, int act_kind, const float* xs, float* hs, int tid) {
+// exact_tanh: tanhf instead of fast_tanh (k_gen_point_family_rollout, as k_point_family_rollout)
+PROMP_DEV const float* gen_mlp_block(const float* th, const GenLin* lin, int n_lin, int act_kind, const float* xs, float* hs, int tid,
+                                     bool exact_tanh = false) {
     const float* in = xs;
     for (int l = 0; l < n_lin; ++l) {
         const GenLin Ly = lin[l];
@@ -566,7 +568,8 @@ PROMP_DEV const float* gen_mlp_block(const float* th, const GenLin* lin, int n_l
         if (tid < Ly.N) {
             float z = th[Ly.b_off + tid];
             for (int k = 0; k < Ly.K; ++k) z = fmaf(in[k], th[Ly.w_off + k * Ly.N + tid], z);
-            out[tid] = gen_act(l == n_lin - 1 ? gen_out(act_kind) : gen_hidden(act_kind), z);
+            const int kind = l == n_lin - 1 ? gen_out(act_kind) : gen_hidden(act_kind);
+            out[tid] = exact_tanh && kind == GEN_ACT_TANH ? tanhf(z) : gen_act(kind, z);
         }
         __syncthreads();
         in = out;
@@ -665,6 +668,57 @@ __global__ void __launch_bounds__(256) k_gen_point_rollout(GenPointRolloutArgs g
             a.mean[row * 2] = m[0];  a.mean[row * 2 + 1] = m[1];
             a.act[row * 2] = a0;  a.act[row * 2 + 1] = a1;
             const double r = point_env_step(a, s0, s1, g0, g1, a0, a1);
+            a.rew[row] = (float)r;
+        }
+        __syncthreads();       // the next step's observation and hidden vectors overwrite what thread 0 has just read
+    }
+}
+
+struct GenPointFamilyArgs {
+    PointFamilyArgs f;         // k_point_family_rollout's arguments (H1 / H2 unused)
+    int n_lin, act_kind;
+    GenLin lin[GEN_MAX_LIN];
+};
+
+// grid = (B, tasks), block = 256: k_gen_point_rollout for any kind.  smem: gen_rollout_smem(state_dim)
+__global__ void __launch_bounds__(256) k_gen_point_family_rollout(GenPointFamilyArgs g) {
+    PROMP_SMEM_DECL;
+    const PointRolloutArgs& a = g.f.p;
+    const int O = g.f.state_dim;
+    float* xs = (float*)PROMP_SMEM_PTR;
+    float* hs = xs + O;
+    const int task = blockIdx.y, b = blockIdx.x, tid = threadIdx.x;
+    const float* th = a.theta_tasks + (long long)task * a.NP;
+    const int oS = a.NP - 2;
+    const float ls0 = th[oS], ls1 = th[oS + 1];
+    if (b == 0 && tid == 0) {
+        a.old_ls[task * 2 + 0] = a.clip_infos ? fmaxf(ls0, a.min_log_std) : ls0;
+        a.old_ls[task * 2 + 1] = a.clip_infos ? fmaxf(ls1, a.min_log_std) : ls1;
+    }
+    const float sd0 = expf(ls0), sd1 = expf(ls1);
+    const double* tp = a.goals + (long long)task * g.f.task_dim;
+    const long long env = (long long)task * a.B + b;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};                             // (advanced by thread 0 only)
+    for (int k = 0; k < O; ++k) s[k] = a.start[env * O + k];
+    for (int t = 0; t < a.T; ++t) {
+        const long long row = env * a.T + t;
+        if (tid == 0)
+            for (int k = 0; k < O; ++k) xs[k] = (float)s[k];
+        __syncthreads();
+        const float* m = gen_mlp_block(th, g.lin, g.n_lin, g.act_kind, xs, hs, tid, g.f.kind != POINT_KIND_CORNER);
+        if (tid == 0) {
+            float n0, n1;
+            if (a.noise != nullptr) {
+                n0 = a.noise[row * 2];
+                n1 = a.noise[row * 2 + 1];
+            } else {
+                action_noise(a.seed, (unsigned long long)row, 0u, a.stream, n0, n1);
+            }
+            const float a0 = fmaf(sd0, n0, m[0]), a1 = fmaf(sd1, n1, m[1]);
+            for (int k = 0; k < O; ++k) a.obs[row * O + k] = xs[k];
+            a.mean[row * 2] = m[0];  a.mean[row * 2 + 1] = m[1];
+            a.act[row * 2] = a0;  a.act[row * 2 + 1] = a1;
+            const double r = point_family_step(g.f, s, tp, a0, a1);
             a.rew[row] = (float)r;
         }
         __syncthreads();       // the next step's observation and hidden vectors overwrite what thread 0 has just read

@@ -17,6 +17,8 @@
 //                     no early termination (point_env_2d_corner.py:39).  The exploration noise is either given by the caller
 //                     (reproducible from a host RNG; the parity tests compare with the reference environment step by step)
 //                     or drawn on the device.
+//   k_point_family_rollout : the same launch for the reference's three fixed-horizon point-mass meta-environments (corner, walls,
+//                     momentum; envs/point_envs/point_env_2d_walls.py, point_env_2d_momentum.py), at the end of this file.
 #pragma once
 #include "promp_device.h"
 
@@ -55,25 +57,31 @@ PROMP_HD void action_noise(unsigned long long seed, unsigned long long row, unsi
     box_muller(r.x, r.y, n0, n1);
 }
 
-// mean network of one observation row under flat parameters th (hidden widths <= 128, act_dim <= 8)
-PROMP_DEV void mlp_mean(const float* th, const float* x, int O, int A, int H1, int H2, float* mean) {
+// mean network of one observation row under flat parameters th (hidden widths <= 128, act_dim <= 8).  EXACT_TANH: tanhf instead of
+// fast_tanh, whose absolute error of ~1e-7 per unit is what the momentum environment's double integrator sums up (see
+// k_point_family_rollout)
+template <bool EXACT_TANH>
+PROMP_DEV void mlp_mean_t(const float* th, const float* x, int O, int A, int H1, int H2, float* mean) {
     const Mlp2Layout lay = mlp2_layout(O, H1, H2, A);
     float h1[128], h2[128];
     for (int j = 0; j < H1; ++j) {
         float z = th[lay.b1 + j];
         for (int k = 0; k < O; ++k) z = fmaf(x[k], th[k * H1 + j], z);
-        h1[j] = fast_tanh(z);
+        h1[j] = EXACT_TANH ? tanhf(z) : fast_tanh(z);
     }
     for (int j = 0; j < H2; ++j) {
         float z = th[lay.b2 + j];
         for (int k = 0; k < H1; ++k) z = fmaf(h1[k], th[lay.W2 + k * H2 + j], z);
-        h2[j] = fast_tanh(z);
+        h2[j] = EXACT_TANH ? tanhf(z) : fast_tanh(z);
     }
     for (int j = 0; j < A; ++j) {
         float z = th[lay.b3 + j];
         for (int k = 0; k < H2; ++k) z = fmaf(h2[k], th[lay.W3 + k * A + j], z);
         mean[j] = z;
     }
+}
+PROMP_DEV void mlp_mean(const float* th, const float* x, int O, int A, int H1, int H2, float* mean) {
+    mlp_mean_t<false>(th, x, O, A, H1, H2, mean);
 }
 
 struct PolicyStepArgs {
@@ -236,14 +244,18 @@ struct PointRolloutArgs {
     double sparse_radius;       // 0.5
 };
 
+// one coordinate of the move a policy action asks for
+PROMP_DEV double point_env_move(const PointRolloutArgs& a, float act) {
+    const double lb = -a.max_step, ub = a.max_step, sc = a.normalization_scale;
+    const double e = sc > 0.0 ? lb + ((double)act + sc) * (ub - lb) / (2.0 * sc) : (double)act;
+    return fmin(fmax(e, lb), ub);
+}
+
 // one step of the normalised point environment: the state advances in place, the reward comes back
 PROMP_DEV double point_env_step(const PointRolloutArgs& a, double& s0, double& s1, double g0, double g1, float a0, float a1) {
     // normalize wrapper: lb + (a + s) (ub - lb) / (2 s), clipped to the action box; then the environment's own clip
     // (same bounds).  Same operation order as normalized_env.py:113-114 so that float64 states agree bit for bit.
-    const double lb = -a.max_step, ub = a.max_step, sc = a.normalization_scale;
-    const double e0 = sc > 0.0 ? lb + ((double)a0 + sc) * (ub - lb) / (2.0 * sc) : (double)a0;
-    const double e1 = sc > 0.0 ? lb + ((double)a1 + sc) * (ub - lb) / (2.0 * sc) : (double)a1;
-    const double d0 = fmin(fmax(e0, lb), ub), d1 = fmin(fmax(e1, lb), ub);
+    const double d0 = point_env_move(a, a0), d1 = point_env_move(a, a1);
     const double p0 = s0, p1 = s1;
     s0 += d0;
     s1 += d1;
@@ -298,6 +310,116 @@ __global__ void __launch_bounds__(64) k_point_rollout(PointRolloutArgs a) {
             a.mean[row * 2] = m[0];  a.mean[row * 2 + 1] = m[1];
             a.act[row * 2] = a0;  a.act[row * 2 + 1] = a1;
             const double r = point_env_step(a, s0, s1, g0, g1, a0, a1);
+            a.rew[row] = (float)r;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The point-mass FAMILY: the reference's other two fixed-horizon meta-environments with corner goals, beside the corner
+// environment above.  Per-task parameters [task_dim], per-environment start state [state_dim], obs_dim = state_dim:
+//   POINT_KIND_CORNER   (2, 2)  point_env_step above
+//   POINT_KIND_WALLS    (6, 2)  envs/point_envs/point_env_2d_walls.py:36-51, 71-83: task = (goal, gap_1, gap_2); two circular walls
+//                               of radius 1 and 2, each open within distance 1 of its gap.  The reward is taken on the state
+//                               BEFORE a wall acts.  sparse: the progress towards the goal within sparse_radius of it; outside
+//                               the reference returns None, which no sampler can sum: 0.0 here.
+//   POINT_KIND_MOMENTUM (2, 4)  envs/point_envs/point_env_2d_momentum.py:36-42, 63-71: the action accelerates, state = (position,
+//                               velocity) and both are observed.  sparse: max(sparse_radius - |s' - g|, 0).
+// Neither ends an episode (done = False in both).  State, projection and reward stay in double: a projected state has norm
+// 1 - ~1e-6, which the next step's |p| < 1 must see.
+// The mean network of walls and momentum evaluates its hidden units with tanhf, not fast_tanh: an action inside the bare
+// environment's box enters momentum's velocity at gain 1 and its position with weights T, T - 1, ..., so fast_tanh's absolute error
+// (~1e-7 per unit, a few 1e-7 in the mean) came out as 4e-6 in the observations after 8 steps.  Corner keeps fast_tanh: it is
+// k_point_rollout bit for bit.
+// ---------------------------------------------------------------------------------------------
+enum { POINT_KIND_CORNER = 0, POINT_KIND_WALLS = 1, POINT_KIND_MOMENTUM = 2 };
+
+struct PointFamilyArgs {
+    PointRolloutArgs p;        // goals: the task parameters [tasks][task_dim]; start: [tasks][B][state_dim]
+    int kind, task_dim, state_dim;
+};
+
+// tp = (goal, gap_1, gap_2)
+PROMP_DEV double walls_env_step(const PointRolloutArgs& a, double& s0, double& s1, const double* tp, float a0, float a1) {
+    const double p0 = s0, p1 = s1;
+    double n0 = p0 + point_env_move(a, a0), n1 = p1 + point_env_move(a, a1);
+    const double dist = point_distance(n0, n1, tp[0], tp[1]);
+    double r;
+    if (a.reward_type == POINT_REWARD_DENSE) r = -dist;
+    else if (a.reward_type == POINT_REWARD_DENSE_SQUARED) r = -(dist * dist);
+    else r = dist < a.sparse_radius ? point_distance(p0, p1, tp[0], tp[1]) - dist : 0.0;
+    const double before = point_distance(p0, p1, 0.0, 0.0), after = point_distance(n0, n1, 0.0, 0.0);
+    if (before < 1.0 && after > 1.0) {
+        if (point_distance(n0, n1, tp[2], tp[3]) > 1.0) {
+            const double den = after + 1e-6;
+            n0 /= den;
+            n1 /= den;
+        }
+    } else if (before < 2.0 && after > 2.0) {
+        if (point_distance(n0, n1, tp[4], tp[5]) > 1.0) {
+            const double den = 0.5 * after + 1e-6;
+            n0 /= den;
+            n1 /= den;
+        }
+    }
+    s0 = n0;
+    s1 = n1;
+    return r;
+}
+
+// s = (position, velocity)
+PROMP_DEV double momentum_env_step(const PointRolloutArgs& a, double* s, double g0, double g1, float a0, float a1) {
+    s[2] += point_env_move(a, a0);
+    s[3] += point_env_move(a, a1);
+    s[0] += s[2];
+    s[1] += s[3];
+    const double dist = point_distance(s[0], s[1], g0, g1);
+    if (a.reward_type == POINT_REWARD_DENSE) return -dist;
+    if (a.reward_type == POINT_REWARD_DENSE_SQUARED) return -(dist * dist);
+    return fmax(a.sparse_radius - dist, 0.0);
+}
+
+// s [state_dim] advances in place
+PROMP_DEV double point_family_step(const PointFamilyArgs& f, double* s, const double* tp, float a0, float a1) {
+    if (f.kind == POINT_KIND_WALLS) return walls_env_step(f.p, s[0], s[1], tp, a0, a1);
+    if (f.kind == POINT_KIND_MOMENTUM) return momentum_env_step(f.p, s, tp[0], tp[1], a0, a1);
+    return point_env_step(f.p, s[0], s[1], tp[0], tp[1], a0, a1);
+}
+
+// grid = tasks, block = 64: k_point_rollout for any kind
+__global__ void __launch_bounds__(64) k_point_family_rollout(PointFamilyArgs f) {
+    const PointRolloutArgs& a = f.p;
+    const int task = blockIdx.x, O = f.state_dim;
+    const float* th = a.theta_tasks + (long long)task * a.NP;
+    const int oS = a.NP - 2;
+    const float ls0 = th[oS], ls1 = th[oS + 1];
+    if (threadIdx.x == 0) {
+        a.old_ls[task * 2 + 0] = a.clip_infos ? fmaxf(ls0, a.min_log_std) : ls0;
+        a.old_ls[task * 2 + 1] = a.clip_infos ? fmaxf(ls1, a.min_log_std) : ls1;
+    }
+    const float sd0 = expf(ls0), sd1 = expf(ls1);
+    const double* tp = a.goals + (long long)task * f.task_dim;
+    for (int b = threadIdx.x; b < a.B; b += 64) {
+        const long long env = (long long)task * a.B + b;
+        double s[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int k = 0; k < O; ++k) s[k] = a.start[env * O + k];
+        for (int t = 0; t < a.T; ++t) {
+            const long long row = env * a.T + t;
+            float o[4], m[2], n0, n1;
+            for (int k = 0; k < O; ++k) o[k] = (float)s[k];
+            if (f.kind == POINT_KIND_CORNER) mlp_mean(th, o, O, 2, a.H1, a.H2, m);
+            else mlp_mean_t<true>(th, o, O, 2, a.H1, a.H2, m);
+            if (a.noise != nullptr) {
+                n0 = a.noise[row * 2];
+                n1 = a.noise[row * 2 + 1];
+            } else {
+                action_noise(a.seed, (unsigned long long)row, 0u, a.stream, n0, n1);
+            }
+            const float a0 = fmaf(sd0, n0, m[0]), a1 = fmaf(sd1, n1, m[1]);
+            for (int k = 0; k < O; ++k) a.obs[row * O + k] = o[k];
+            a.mean[row * 2] = m[0];  a.mean[row * 2 + 1] = m[1];
+            a.act[row * 2] = a0;  a.act[row * 2 + 1] = a1;
+            const double r = point_family_step(f, s, tp, a0, a1);
             a.rew[row] = (float)r;
         }
     }

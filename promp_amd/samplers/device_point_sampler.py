@@ -1,9 +1,11 @@
-"""Rollouts of the 2-D point-mass meta-environment collected ON THE DEVICE.
+"""Rollouts of the 2-D point-mass meta-environments collected ON THE DEVICE.
 
 Same interface as MetaSampler (update_tasks / obtain_samples / total_timesteps_sampled), for the environment of BASELINE
-config 1: promp_amd.envs.point_env.MetaPointEnvCorner, bare or wrapped in promp_amd.envs.normalized_env.normalize.  One kernel launch runs every environment for the whole horizon under its task's
-current policy parameters and writes the trajectories straight into the sampling step's slab
-(promp_rollout_point_env); MetaSampleProcessor.process_samples then finds the data resident and uploads nothing.
+config 1, promp_amd.envs.point_env.MetaPointEnvCorner, and its fixed-horizon siblings MetaPointEnvWalls and MetaPointEnvMomentum,
+bare or wrapped in promp_amd.envs.normalized_env.normalize.  One kernel launch runs every environment for the whole horizon under
+its task's current policy parameters and writes the trajectories straight into the sampling step's slab (promp_rollout_point_env
+for the corner environment, promp_rollout_point_family for the other two); MetaSampleProcessor.process_samples then finds the data
+resident and uploads nothing.
 The host keeps what it is good at: drawing tasks, start states and the exploration noise from NumPy's RNG, and
 materialising the path dicts the plugin API returns (one small download per sampling step)."""
 from collections import OrderedDict
@@ -57,10 +59,18 @@ class DevicePaths(OrderedDict):
         return OrderedDict.popitem(self, *args, **kw)
 
 
+def _point_env_kind(bare):
+    from ..envs.point_env import MetaPointEnvCorner, MetaPointEnvMomentum, MetaPointEnvWalls
+    for cls, kind in ((MetaPointEnvCorner, 'corner'), (MetaPointEnvWalls, 'walls'), (MetaPointEnvMomentum, 'momentum')):
+        if isinstance(bare, cls):
+            return kind
+    return None
+
+
 def _point_env_options(env):
-    """(bare environment, kernel options) of MetaPointEnvCorner, wrapped in normalize(...) or not"""
+    """(bare environment, kernel options) of MetaPointEnvCorner / MetaPointEnvWalls / MetaPointEnvMomentum, wrapped in
+    normalize(...) or not"""
     from ..envs.normalized_env import NormalizedEnv
-    from ..envs.point_env import MetaPointEnvCorner
     scale = 0.0                              # bare environment
     if isinstance(env, NormalizedEnv):
         assert not (env._normalize_obs or env._normalize_reward), 'running observation / reward normalisation is host-side state'
@@ -69,7 +79,8 @@ def _point_env_options(env):
         assert np.allclose(bare.action_space.low, -bare.action_space.high)
     else:
         bare = env
-    assert isinstance(bare, MetaPointEnvCorner), 'the device environment is MetaPointEnvCorner (optionally normalize()d)'
+    assert _point_env_kind(bare) is not None, \
+        'the device environments are MetaPointEnvCorner, MetaPointEnvWalls and MetaPointEnvMomentum (optionally normalize()d)'
     return bare, dict(reward_type=bare.reward_type, normalization_scale=scale, max_step=float(bare.action_space.high[0]),
                       sparse_radius=float(bare.sparse_reward_radius))
 
@@ -82,9 +93,12 @@ class DevicePointEnvSampler(object):
     def __init__(self, env, policy, rollouts_per_meta_task, meta_batch_size, max_path_length, envs_per_task=None,
                  parallel=False, device_noise=False):
         assert hasattr(env, 'sample_tasks') and hasattr(env, 'set_task')
-        assert policy.obs_dim == 2 and policy.action_dim == 2, 'the device environment is the 2-D point mass'
         self.env, self.policy = env, policy
         self._bare, self._env_opts = _point_env_options(env)
+        self.kind = _point_env_kind(self._bare)
+        self.obs_dim = int(np.prod(self._bare.observation_space.shape))        # 2; momentum observes (position, velocity): 4
+        assert policy.obs_dim == self.obs_dim and policy.action_dim == 2, \
+            'the %s point mass has obs_dim %d and act_dim 2' % (self.kind, self.obs_dim)
         self.device_noise = device_noise
         self.batch_size = rollouts_per_meta_task
         self.meta_batch_size = meta_batch_size
@@ -97,7 +111,9 @@ class DevicePointEnvSampler(object):
     def update_tasks(self):
         tasks = self.env.sample_tasks(self.meta_batch_size)
         assert len(tasks) == self.meta_batch_size
-        self.goals = np.asarray(tasks, dtype=np.float64).reshape(self.meta_batch_size, 2)
+        if self.kind == 'walls':            # a task is dict(goal, gap_1, gap_2): the kernel's [M][6]
+            tasks = [np.concatenate([np.asarray(t[k], dtype=np.float64) for k in ('goal', 'gap_1', 'gap_2')]) for t in tasks]
+        self.goals = np.asarray(tasks, dtype=np.float64).reshape(self.meta_batch_size, 6 if self.kind == 'walls' else 2)
 
     def obtain_samples(self, log=False, log_prefix=''):
         assert self.goals is not None, 'call update_tasks() first'
@@ -107,14 +123,20 @@ class DevicePointEnvSampler(object):
         if sess.task_thetas is not None:           # parameters set while no context existed yet
             ctx.set_task_thetas(sess.task_thetas)
             sess.task_thetas = None
-        start = np.random.uniform(-0.2, 0.2, size=(M, B, 2))         # MetaPointEnvCorner.reset
+        start = np.random.uniform(-0.2, 0.2, size=(M, B, 2))         # reset() of all three classes
+        if self.kind == 'momentum':                                  # MetaPointEnvMomentum.reset: and a velocity
+            start = np.concatenate((start, np.random.uniform(-0.1, 0.1, size=(M, B, 2))), axis=2)
         slot = sess.next_slot()
+        if self.kind == 'corner':
+            rollout = ctx.rollout_point_env
+        else:
+            rollout = lambda slot, *args, **kw: ctx.rollout_point_family(slot, self.kind, *args, **kw)
         if self.device_noise:
-            ctx.rollout_point_env(slot, self.goals, start, None, clip_infos=self.policy._pre_update_mode, path_length=T,
-                                  seed=int(np.random.randint(0, 2 ** 31 - 1)), **self._env_opts)
+            rollout(slot, self.goals, start, None, clip_infos=self.policy._pre_update_mode, path_length=T,
+                    seed=int(np.random.randint(0, 2 ** 31 - 1)), **self._env_opts)
         else:
             noise = np.random.normal(size=(M, B, T, 2)).astype(np.float32)
-            ctx.rollout_point_env(slot, self.goals, start, noise, clip_infos=self.policy._pre_update_mode, **self._env_opts)
+            rollout(slot, self.goals, start, noise, clip_infos=self.policy._pre_update_mode, **self._env_opts)
         sess._upload_counter += 1
         sess.upload_serial[slot] = sess._upload_counter
         slab = ctx.download_step(slot)

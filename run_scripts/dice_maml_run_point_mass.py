@@ -16,7 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from promp_amd.baselines.linear_baseline import LinearFeatureBaseline, LinearTimeBaseline  # noqa: E402
 from promp_amd.envs.normalized_env import normalize  # noqa: E402
-from promp_amd.envs.point_env import MetaPointEnvCorner  # noqa: E402
+from promp_amd.envs.point_env import make_point_env  # noqa: E402
 from promp_amd.meta_algos.dice_maml import DICEMAML  # noqa: E402
 from promp_amd.meta_algos.vpg_dice_maml import VPG_DICEMAML  # noqa: E402
 from promp_amd.meta_trainer import Trainer  # noqa: E402
@@ -43,10 +43,11 @@ BASELINES = {'LinearFeatureBaseline': LinearFeatureBaseline, 'LinearTimeBaseline
 
 def main(config):
     np.random.seed(config['seed'])
-    env = MetaPointEnvCorner(reward_type=config.get('reward_type', 'sparse'))
+    env = make_point_env(config.get('env', 'corner'), config.get('reward_type', 'sparse'))
     if config.get('normalize_env', True):
         env = normalize(env)
-    policy = MetaGaussianMLPPolicy(name='meta-policy', obs_dim=2, action_dim=2, meta_batch_size=config['meta_batch_size'],
+    policy = MetaGaussianMLPPolicy(name='meta-policy', obs_dim=int(np.prod(env.observation_space.shape)), action_dim=2,
+                                   meta_batch_size=config['meta_batch_size'],
                                    hidden_sizes=config['hidden_sizes'])
     sampler_kwargs = dict(env=env, policy=policy, rollouts_per_meta_task=config['rollouts_per_meta_task'],
                           meta_batch_size=config['meta_batch_size'], max_path_length=config['max_path_length'],
@@ -73,12 +74,19 @@ if __name__ == '__main__':
     ap.add_argument('--config_file', type=str, default='')
     ap.add_argument('--dump_path', type=str, default='')
     ap.add_argument('--n_itr', type=int, default=None)
+    ap.add_argument('--env', type=str, default=None, choices=['corner', 'walls', 'momentum'],
+                    help='the point-mass meta-environment (default corner); walls and momentum take their own default reward type '
+                         'unless the config file names one')
     ap.add_argument('--vpg', action='store_true', help='VPG_DICEMAML: DiCE inner steps, advantages from a return baseline outside')
     ap.add_argument('--quiet', action='store_true')
     args = ap.parse_args()
     cfg = dict(DEFAULT)
     if args.config_file:
         cfg.update(json.load(open(args.config_file)))
+    if args.env is not None:
+        cfg['env'] = args.env
+        if not (args.config_file and 'reward_type' in json.load(open(args.config_file))):
+            cfg['reward_type'] = None          # the class's default
     if args.n_itr is not None:
         cfg['n_itr'] = args.n_itr
     if args.vpg:

@@ -17,7 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from promp_amd.baselines.linear_baseline import LinearFeatureBaseline  # noqa: E402
 from promp_amd.envs.normalized_env import normalize  # noqa: E402
-from promp_amd.envs.point_env import MetaPointEnvCorner  # noqa: E402
+from promp_amd.envs.point_env import make_point_env  # noqa: E402
 from promp_amd.meta_algos.trpo_maml import TRPOMAML  # noqa: E402
 from promp_amd.meta_trainer import Trainer  # noqa: E402
 from promp_amd.policies.meta_gaussian_mlp_policy import MetaGaussianMLPPolicy  # noqa: E402
@@ -45,7 +45,7 @@ DEFAULT = {
 def main(config):
     set_seed(config['seed'])
     baseline = {'LinearFeatureBaseline': LinearFeatureBaseline}[config['baseline']]()
-    env = normalize({'MetaPointEnvCorner': MetaPointEnvCorner}[config['env']](reward_type=config.get('reward_type', 'dense')))
+    env = normalize(make_point_env(config['env'], config.get('reward_type', 'dense')))
     policy = MetaGaussianMLPPolicy(name='meta-policy', obs_dim=int(np.prod(env.observation_space.shape)),
                                    action_dim=int(np.prod(env.action_space.shape)), meta_batch_size=config['meta_batch_size'],
                                    hidden_sizes=config['hidden_sizes'], learn_std=config.get('learn_std', True))
@@ -69,6 +69,9 @@ if __name__ == '__main__':
     ap.add_argument('--config_file', type=str, default='', help='json file with run specifications')
     ap.add_argument('--dump_path', type=str, default='')
     ap.add_argument('--n_itr', type=int, default=None)
+    ap.add_argument('--env', type=str, default=None, choices=['corner', 'walls', 'momentum'],
+                    help='the point-mass meta-environment (default corner); walls and momentum take their own default reward type '
+                         'unless the config file names one')
     ap.add_argument('--exploration', action='store_true', help='E-MAML (e-maml_run_mujoco.py)')
     ap.add_argument('--hvp', type=str, default=None, choices=['finite_difference', 'exact'])
     ap.add_argument('--subsample_factor', type=float, default=None,
@@ -78,6 +81,10 @@ if __name__ == '__main__':
     cfg = dict(DEFAULT)
     if args.config_file:
         cfg.update(json.load(open(args.config_file)))
+    if args.env is not None:
+        cfg['env'] = args.env
+        if not (args.config_file and 'reward_type' in json.load(open(args.config_file))):
+            cfg['reward_type'] = None          # the class's default
     if args.n_itr is not None:
         cfg['n_itr'] = args.n_itr
     if args.exploration:

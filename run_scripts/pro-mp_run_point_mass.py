@@ -15,7 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from promp_amd.baselines.linear_baseline import LinearFeatureBaseline  # noqa: E402
 from promp_amd.envs.normalized_env import normalize  # noqa: E402
-from promp_amd.envs.point_env import MetaPointEnvCorner  # noqa: E402
+from promp_amd.envs.point_env import make_point_env  # noqa: E402
 from promp_amd.meta_algos.pro_mp import ProMP  # noqa: E402
 from promp_amd.meta_trainer import Trainer  # noqa: E402
 from promp_amd.policies.meta_gaussian_mlp_policy import MetaGaussianMLPPolicy  # noqa: E402
@@ -40,10 +40,11 @@ DEFAULT = {
 def main(config):
     np.random.seed(config['seed'])
     baseline = {'LinearFeatureBaseline': LinearFeatureBaseline}[config['baseline']]()
-    env = MetaPointEnvCorner(reward_type=config.get('reward_type', 'sparse'))
+    env = make_point_env(config.get('env', 'corner'), config.get('reward_type', 'sparse'))
     if config.get('normalize_env', True):
         env = normalize(env)                      # as the reference script (pro-mp_run_point_mass.py:27-28)
-    policy = MetaGaussianMLPPolicy(name='meta-policy', obs_dim=2, action_dim=2, meta_batch_size=config['meta_batch_size'],
+    policy = MetaGaussianMLPPolicy(name='meta-policy', obs_dim=int(np.prod(env.observation_space.shape)), action_dim=2,
+                                   meta_batch_size=config['meta_batch_size'],
                                    hidden_sizes=config['hidden_sizes'])
     sampler_kwargs = dict(env=env, policy=policy, rollouts_per_meta_task=config['rollouts_per_meta_task'],
                           meta_batch_size=config['meta_batch_size'], max_path_length=config['max_path_length'],
@@ -72,6 +73,9 @@ if __name__ == '__main__':
     ap.add_argument('--config_file', type=str, default='')
     ap.add_argument('--dump_path', type=str, default='')
     ap.add_argument('--n_itr', type=int, default=None)
+    ap.add_argument('--env', type=str, default=None, choices=['corner', 'walls', 'momentum'],
+                    help='the point-mass meta-environment (default corner); walls and momentum take their own default reward type '
+                         'unless the config file names one')
     ap.add_argument('--num_minibatches', type=int, default=None,
                     help='Adam steps per epoch of the outer step: every task\'s paths are dealt to this many minibatches (default 1)')
     ap.add_argument('--outer_optimizer', type=str, default=None, choices=['adam', 'sgd', 'gradient_descent', 'momentum'],
@@ -83,6 +87,10 @@ if __name__ == '__main__':
     cfg = dict(DEFAULT)
     if args.config_file:
         cfg.update(json.load(open(args.config_file)))
+    if args.env is not None:
+        cfg['env'] = args.env
+        if not (args.config_file and 'reward_type' in json.load(open(args.config_file))):
+            cfg['reward_type'] = None          # the class's default
     if args.n_itr is not None:
         cfg['n_itr'] = args.n_itr
     if args.num_minibatches is not None:

@@ -1,25 +1,98 @@
-"""Developer measurement for SURVEY 8f rows 1/3: env-steps/s of rollout collection on the point-mass meta-environment,
-host loop (MetaSampler: one device policy query per environment step) vs device rollout (DevicePointEnvSampler)."""
+"""Developer measurement for SURVEY 8f rows 1/3, rollout collection on the point-mass meta-environments.
+
+    python tools/rollout_timing.py                       env-steps/s of a sampling step, host loop (MetaSampler: one device policy
+                                                         query per environment step) vs device rollout (DevicePointEnvSampler)
+    python tools/rollout_timing.py --launch [--kinds corner walls momentum] [--lib PATH] [--repeats N] [--launches W]
+                                                         time of ONE rollout launch through the C ABI (upload of tasks, start states
+                                                         and host noise + the kernel, ended by a device synchronise), per kind and
+                                                         noise mode, at BASELINE config 1's shapes: median and spread over N windows
+                                                         of W launches.  --lib binds another build of the library (an A/B against
+                                                         another commit: run the two alternately in one job); corner goes through
+                                                         promp_rollout_point_env, which every build has."""
+import argparse
 import sys
 import time
-import numpy as np
-sys.path.insert(0, '.')
-from promp_amd.envs.point_env import MetaPointEnv
-from promp_amd.policies.meta_gaussian_mlp_policy import MetaGaussianMLPPolicy
-from promp_amd.samplers.device_point_sampler import DevicePointEnvSampler
-from promp_amd.samplers.meta_sampler import MetaSampler
 
-for M, B, T in ((4, 20, 100), (40, 20, 200)):
-    np.random.seed(0)
-    env = MetaPointEnv()
-    policy = MetaGaussianMLPPolicy(name='p', obs_dim=2, action_dim=2, meta_batch_size=M, hidden_sizes=(32, 32))
-    policy.switch_to_pre_update()
-    for name, cls, reps in (('host loop   ', MetaSampler, 2), ('device kernel', DevicePointEnvSampler, 20)):
-        s = cls(env=env, policy=policy, rollouts_per_meta_task=B, meta_batch_size=M, max_path_length=T)
-        s.update_tasks()
-        s.obtain_samples()
-        t0 = time.time()
-        for _ in range(reps):
-            s.obtain_samples()
-        dt = (time.time() - t0) / reps
-        print('M=%d B=%d T=%d  %s %9.3f ms per sampling step  %12.0f env-steps/s' % (M, B, T, name, 1e3 * dt, M * B * T / dt))
+import numpy as np
+
+sys.path.insert(0, '.')
+
+
+def sampler_rates():
+    from promp_amd.envs.point_env import make_point_env
+    from promp_amd.policies.meta_gaussian_mlp_policy import MetaGaussianMLPPolicy
+    from promp_amd.samplers.device_point_sampler import DevicePointEnvSampler
+    from promp_amd.samplers.meta_sampler import MetaSampler
+    for kind in ('corner', 'walls', 'momentum'):
+        for M, B, T in ((4, 20, 100), (40, 20, 200)):
+            np.random.seed(0)
+            env = make_point_env(kind)
+            policy = MetaGaussianMLPPolicy(name='p', obs_dim=int(np.prod(env.observation_space.shape)), action_dim=2, meta_batch_size=M,
+                                           hidden_sizes=(32, 32))
+            policy.switch_to_pre_update()
+            for name, cls, reps in (('host loop   ', MetaSampler, 2), ('device kernel', DevicePointEnvSampler, 20)):
+                s = cls(env=env, policy=policy, rollouts_per_meta_task=B, meta_batch_size=M, max_path_length=T)
+                s.update_tasks()
+                s.obtain_samples()
+                t0 = time.time()
+                for _ in range(reps):
+                    s.obtain_samples()
+                dt = (time.time() - t0) / reps
+                print('%-8s M=%d B=%d T=%d  %s %9.3f ms per sampling step  %12.0f env-steps/s' % (
+                    kind, M, B, T, name, 1e3 * dt, M * B * T / dt))
+
+
+def launch_times(kinds, lib_path, repeats, launches, label):
+    from promp_amd import _lib, synthetic
+    M, B, T, hidden = 4, 20, 100, (32, 32)                    # BASELINE config 1
+    try:
+        lib = _lib.Library(lib_path) if lib_path else _lib.Library()
+    except AttributeError:                                     # a build from before promp_rollout_point_family: corner only
+        family = _lib.SIGNATURES.pop('promp_rollout_point_family')
+        lib = _lib.Library(lib_path)
+        _lib.SIGNATURES['promp_rollout_point_family'] = family
+        assert kinds == ['corner'], 'this library has the corner environment only'
+    rng = np.random.RandomState(0)
+    for kind in kinds:
+        task_dim, O = _lib.POINT_KIND_DIMS[kind]
+        ctx = _lib.Context(M, O, 2, hidden, 1, max_rows=M * B * T, max_paths=M * B, lib=lib)
+        ctx.set_theta(synthetic.init_theta(rng, O, hidden, 2))
+        ctx.switch_to_pre_update()
+        tasks, start = rng.randn(M, task_dim), rng.uniform(-0.2, 0.2, size=(M, B, O))
+        z = rng.randn(M, B, T, 2).astype(np.float32)
+        env = dict(reward_type='dense', normalization_scale=10.0, max_step=0.2 if kind != 'momentum' else 0.1)
+        for noise in ('host', 'device'):
+            kw = dict(noise=z if noise == 'host' else None, seed=12345, path_length=T, **env)
+            if kind == 'corner':
+                run = lambda: ctx.rollout_point_env(0, tasks, start, **kw)
+            else:
+                run = lambda: ctx.rollout_point_family(0, kind, tasks, start, **kw)
+            for _ in range(20):                                # warm-up: code objects, buffers
+                run()
+            ctx.sync()
+            times = []
+            for _ in range(repeats):
+                t0 = time.perf_counter()
+                for _ in range(launches):
+                    run()
+                ctx.sync()
+                times.append((time.perf_counter() - t0) / launches)
+            us = 1e6 * np.array(times)
+            print('%s%-8s %-6s noise  median %8.2f us per launch  min %8.2f  max %8.2f  (%d windows of %d launches)' % (
+                label, kind, noise, np.median(us), us.min(), us.max(), repeats, launches), flush=True)
+        ctx.close()
+
+
+if __name__ == '__main__':
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--launch', action='store_true')
+    ap.add_argument('--kinds', nargs='+', default=['corner', 'walls', 'momentum'], choices=['corner', 'walls', 'momentum'])
+    ap.add_argument('--lib', type=str, default='')
+    ap.add_argument('--label', type=str, default='')
+    ap.add_argument('--repeats', type=int, default=7)
+    ap.add_argument('--launches', type=int, default=300)
+    args = ap.parse_args()
+    if args.launch:
+        launch_times(args.kinds, args.lib, args.repeats, args.launches, args.label and args.label + ' ')
+    else:
+        sampler_rates()
