@@ -109,7 +109,7 @@ const char* promp_last_error(void);
  * later: promp_set_train_step_sizes with promp_get_step_sizes / promp_get_step_size_grad / promp_{set,get}_step_size_adam_state
  * and promp_reduced_count; promp_set_outer_optimizer / promp_get_outer_optimizer / promp_get_grad_norm;
  * promp_process_samples_dice / promp_download_dice / promp_use_dice_advantages (and promp_proc_opts.reserved read as pad_length);
- * promp_rollout_point_family -- were additions and did not move it. */
+ * promp_rollout_point_family, promp_collect_point_family -- were additions and did not move it. */
 int promp_abi_version(void);
 /* Theta = O*H1+H1 + H1*H2+H2 + H2*A+A + A */
 int promp_param_count(const promp_dims* dims);
@@ -362,7 +362,7 @@ int promp_rollout_point_env(promp_ctx* ctx, int step, int envs_per_task, int pat
  *     Neither environment ends an episode.  task_params [n_tasks][task_dim], start [n_tasks][envs_per_task][state_dim] (float64);
  *     noise as in (b).  An unknown kind, a task_dim that is not the kind's, a context whose obs_dim is not state_dim or whose
  *     act_dim is not 2 are refused.  Asynchronous. */
-enum { PROMP_POINT_CORNER = 0, PROMP_POINT_WALLS = 1, PROMP_POINT_MOMENTUM = 2 };
+enum { PROMP_POINT_CORNER = 0, PROMP_POINT_WALLS = 1, PROMP_POINT_MOMENTUM = 2, PROMP_POINT_GOAL = 3 /* (b'') only */ };
 typedef struct {
     int32_t kind;          /* PROMP_POINT_* */
     int32_t reward_type, clip_infos, task_dim;
@@ -371,6 +371,36 @@ typedef struct {
 } promp_point_family_opts;
 int promp_rollout_point_family(promp_ctx* ctx, int step, int envs_per_task, int path_length, const double* task_params,
                                const double* start, const float* noise, const promp_point_family_opts* opts);
+
+/* (b'') the family with EARLY TERMINATION, collected without a host loop: what (a') does with one call per environment step, in a
+ *     handful of launches (samplers/meta_sampler.py:87-130, samplers/vectorized_env_executor.py:25-52).  Every environment runs
+ *     max_steps vectorised steps s; an episode ends when the environment says so or after max_path_length steps, and the
+ *     environment then continues from start[s + 1][env], its next reset().  Step s is filed under the staging row
+ *     s * n_envs + env of (a') -- the Philox counter when noise is NULL -- with its reward.  Collection stops at s*, the first step
+ *     after which total_samples steps belong to finished episodes; all episodes that end at s* count (the rows may exceed
+ *     total_samples, as in the reference's loop), episodes still running are dropped.  The finished episodes are listed per task
+ *     in the reference's order -- by the step they end at, then by environment -- and copied into the slab with their rewards.
+ *       kind PROMP_POINT_CORNER / WALLS / MOMENTUM: the environments of (b'); their episodes end by max_path_length alone
+ *       kind PROMP_POINT_GOAL  task_dim 2 (goal), state_dim 2      envs/point_envs/point_env_2d.py, point_env_2d_v2.py
+ *           s' = s + clip(e, -max_step, max_step); reward -|s' - goal|; done = |s'_0| < done_radius and |s'_1| < done_radius,
+ *           the box around the ORIGIN (as both reference classes have it).  point_env_2d.py is goal = (0, 0).  reward_type and
+ *           sparse_radius are not read.
+ *     task_params [n_tasks][task_dim]; start [max_steps][n_envs][state_dim]: row 0 the initial states, row s + 1 the state an
+ *     environment whose episode ends at step s continues from (n_envs = n_tasks * envs_per_task, environment = task *
+ *     envs_per_task + b); noise [max_steps][n_envs][2] or NULL.
+ *     Out: n_paths, n_steps = s* + 1, task_path_offsets [n_tasks + 1], path_env / path_start / path_len [max_paths of the context]
+ *     (the first n_paths are written): the arguments promp_end_collection takes.  The step is left as promp_end_collection leaves
+ *     it.  Refused, with no layout installed: max_steps too small to reach total_samples; more rows than max_rows or more paths
+ *     than max_paths; a task without a finished episode; max_path_length < 1; and what (b') refuses.  Synchronous. */
+typedef struct {
+    promp_point_family_opts env;      /* kind 0..3, clip_infos, seed, the wrapper's scale, the action box */
+    double  done_radius;              /* PROMP_POINT_GOAL: 0.01 */
+    int32_t max_path_length, max_steps;
+    int64_t total_samples;
+} promp_point_collect_opts;
+int promp_collect_point_family(promp_ctx* ctx, int step, int envs_per_task, const double* task_params, const double* start,
+                               const float* noise, const promp_point_collect_opts* opts, int32_t* n_paths, int32_t* n_steps,
+                               int32_t* task_path_offsets, int32_t* path_env, int32_t* path_start, int32_t* path_len);
 
 /* Step slab back on the host (any pointer may be NULL): obs [rows][O], act [rows][A], rew [rows],
  * old_mean [rows][A], old_log_std [rows | n_tasks][A] as uploaded / produced by a device rollout. */

@@ -58,8 +58,13 @@ class PointFamilyOpts(C.Structure):
 
 
 POINT_REWARD = dict(dense=0, dense_squared=1, sparse=2)
-POINT_KIND = dict(corner=0, walls=1, momentum=2)
-POINT_KIND_DIMS = dict(corner=(2, 2), walls=(6, 2), momentum=(2, 4))       # kind -> (task_dim, state_dim)
+class PointCollectOpts(C.Structure):
+    _fields_ = [('env', PointFamilyOpts), ('done_radius', C.c_double), ('max_path_length', C.c_int32), ('max_steps', C.c_int32),
+                ('total_samples', C.c_int64)]
+
+
+POINT_KIND = dict(corner=0, walls=1, momentum=2, goal=3)                   # goal: collect_point_family only
+POINT_KIND_DIMS = dict(corner=(2, 2), walls=(6, 2), momentum=(2, 4), goal=(2, 2))       # kind -> (task_dim, state_dim)
 
 _F = C.POINTER(C.c_float)
 _D = C.POINTER(C.c_double)
@@ -118,6 +123,7 @@ SIGNATURES = {
     'promp_policy_forward': (C.c_int, [_P, _F, C.c_int, _F]),
     'promp_rollout_point_env': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _D, _D, _F, C.POINTER(PointEnvOpts)]),
     'promp_rollout_point_family': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _D, _D, _F, C.POINTER(PointFamilyOpts)]),
+    'promp_collect_point_family': (C.c_int, [_P, C.c_int, C.c_int, _D, _D, _F, C.POINTER(PointCollectOpts), _I, _I, _I, _I, _I, _I]),
     'promp_begin_rollout': (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     'promp_begin_collection': (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     'promp_end_collection': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _F]),
@@ -884,6 +890,45 @@ class Context:
         self.step_rows[step], self.step_paths[step] = M * B * T, M * B
         self.step_tpo[step] = np.arange(M + 1, dtype=np.int64) * B
         self.step_ls_rows[step] = M
+
+    def collect_point_family(self, step, kind, task_params, start, noise=None, total_samples=None, max_path_length=None,
+                             clip_infos=True, reward_type='dense', normalization_scale=0.0, max_step=0.1, sparse_radius=2.0, seed=0,
+                             done_radius=0.01, task_dim=None):
+        """Device collection with early termination (promp_collect_point_family), kind 'corner' | 'walls' | 'momentum' | 'goal' (or
+        its number): task_params [M, task_dim], start [max_steps, M * B, state_dim] (float64; row 0 the initial states, row s + 1
+        the states that environments whose episode ends at step s continue from), noise [max_steps, M * B, 2] or None (drawn on
+        the device from `seed`) -> the step's slab holds the finished episodes in the reference's order; returns
+        dict(n_steps, task_path_offsets, path_row_offsets, path_env, path_start, path_len)."""
+        self._pre_write(step)
+        task_params = np.ascontiguousarray(task_params, dtype=np.float64)
+        start = np.ascontiguousarray(start, dtype=np.float64)
+        assert task_params.ndim == 2 and start.ndim == 3
+        M = self.n_tasks
+        max_steps, n_envs = start.shape[:2]
+        assert n_envs % M == 0 and task_params.shape[0] == M, (start.shape, task_params.shape)
+        if noise is not None:
+            noise = _f32(noise)
+            assert noise.shape == (max_steps, n_envs, 2), noise.shape
+        if kind in POINT_KIND:
+            assert (task_params.shape[1], start.shape[2]) == POINT_KIND_DIMS[kind], (kind, task_params.shape, start.shape)
+        env = PointFamilyOpts(int(POINT_KIND.get(kind, kind)), POINT_REWARD[reward_type], int(bool(clip_infos)),
+                              int(task_params.shape[1] if task_dim is None else task_dim), float(normalization_scale),
+                              float(max_step), float(sparse_radius), int(seed))
+        opts = PointCollectOpts(env, float(done_radius), int(max_path_length), int(max_steps), int(total_samples))
+        cap = int(self.dims.max_paths)
+        n_paths, n_steps = C.c_int32(0), C.c_int32(0)
+        tpo = np.zeros(M + 1, np.int32)
+        p_env, p_start, p_len = (np.zeros(cap, np.int32) for _ in range(3))
+        self._call('promp_collect_point_family', int(step), int(n_envs // M), _ptr(task_params, C.c_double), _ptr(start, C.c_double),
+                   _ptr(noise, C.c_float) if noise is not None else None, C.byref(opts), C.byref(n_paths), C.byref(n_steps),
+                   _ptr(tpo, C.c_int32), _ptr(p_env, C.c_int32), _ptr(p_start, C.c_int32), _ptr(p_len, C.c_int32))
+        n = int(n_paths.value)
+        p_env, p_start, p_len = p_env[:n].copy(), p_start[:n].copy(), p_len[:n].copy()
+        pro = np.concatenate([[0], np.cumsum(p_len)]).astype(np.int32)
+        self.step_rows[step], self.step_paths[step], self.step_ls_rows[step] = int(pro[-1]), n, M
+        self.step_tpo[step] = np.array(tpo, dtype=np.int64)
+        return dict(n_steps=int(n_steps.value), task_path_offsets=tpo, path_row_offsets=pro, path_env=p_env, path_start=p_start,
+                    path_len=p_len)
 
     def begin_rollout(self, step, envs_per_task, path_length):
         """lay step `step` out as n_tasks * envs_per_task fixed-length paths for policy_step to fill"""

@@ -2360,6 +2360,42 @@ int promp_begin_collection(promp_ctx* c, int step, int envs_per_task, int max_st
     return 0;
 }
 
+// The tail of a ragged collection, shared by promp_end_collection (tables from the host: h_env / h_start, rewards h_rewards in path
+// order) and promp_collect_point_family (tables already on the device: d_env / d_start, rewards gathered from the staged d_rew):
+// the layout, the finished episodes copied from the staging rows into the slab, the step's flags.  sc is open.
+static int finish_collection(StepScope& sc, int n_paths, const int32_t* tpo, const int32_t* pro, const int32_t* h_env, const int32_t* h_start,
+                             const int32_t* d_env, const int32_t* d_start, const float* h_rewards, const float* d_rew) {
+    promp_ctx* c = sc.c;
+    StepData& S = sc.S();
+    const int M = c->d.n_tasks, B = S.rollout_B, O = c->d.obs_dim, A = c->d.act_dim;
+    clear_selection(c, sc.step);
+    if (set_step_layout(c, S, c->stream, false, n_paths, tpo, pro)) return -2;
+    // the finished episodes: staging rows -> slab rows in path order
+    if (h_env) {
+        if (c->rollout_buf.reserve(sizeof(int32_t) * 2 * (size_t)n_paths, 2)) return -2;
+        int32_t* up_env = (int32_t*)c->rollout_buf.p;
+        int32_t* up_start = up_env + n_paths;
+        HIPCHECK(hipMemcpyAsync(up_env, h_env, sizeof(int32_t) * n_paths, hipMemcpyHostToDevice, c->stream));
+        HIPCHECK(hipMemcpyAsync(up_start, h_start, sizeof(int32_t) * n_paths, hipMemcpyHostToDevice, c->stream));
+        d_env = up_env; d_start = up_start;
+    }
+    GatherPathsArgs g;
+    const size_t n_rows = (size_t)S.rollout_T * M * B;
+    g.obs_in = c->stage_rows; g.act_in = c->stage_rows + n_rows * O; g.mean_in = g.act_in + n_rows * A;
+    g.obs = S.obs; g.act = S.act; g.mean = S.old_mean;
+    g.path_env = d_env; g.path_start = d_start; g.path_row_offsets = S.path_row_offsets;
+    g.n_envs = M * B; g.O = O; g.A = A;
+    g.rew_in = d_rew; g.rew = S.rew;
+    PROMP_LAUNCH(k_gather_paths, dim3(n_paths), 256, 0, c->stream, g);
+    HIPCHECK(hipGetLastError());
+    if (h_rewards) HIPCHECK(hipMemcpyAsync(S.rew, h_rewards, sizeof(float) * pro[n_paths], hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    S.has_policy = true; S.ls_per_row = 0; S.has_rew64 = false; S.processed = false; S.has_adv = false;
+    S.rollout_ragged = false; S.rollout_B = 0;
+    S.ps.obs_range_valid = false;
+    return 0;
+}
+
 int promp_end_collection(promp_ctx* c, int step, int n_paths, const int32_t* task_path_offsets, const int32_t* path_env,
                          const int32_t* path_start, const int32_t* path_len, const float* rewards) {
     if (!c || !task_path_offsets || !path_env || !path_start || !path_len || !rewards) return fail(-1, "NULL argument");
@@ -2367,7 +2403,7 @@ int promp_end_collection(promp_ctx* c, int step, int n_paths, const int32_t* tas
     if (sc.rc) return sc.rc;
     StepData& S = sc.S();
     if (!S.rollout_ragged || S.rollout_B < 1) return fail(-3, "promp_begin_collection has not been called for step %d", step);
-    const int M = c->d.n_tasks, B = S.rollout_B, O = c->d.obs_dim, A = c->d.act_dim;
+    const int M = c->d.n_tasks, B = S.rollout_B;
     if (n_paths < 1 || n_paths > c->d.max_paths) return fail(-1, "%d paths outside [1, max_paths = %d]", n_paths, c->d.max_paths);
     std::vector<int32_t> pro((size_t)n_paths + 1, 0);
     for (int p = 0; p < n_paths; ++p) {
@@ -2377,27 +2413,121 @@ int promp_end_collection(promp_ctx* c, int step, int n_paths, const int32_t* tas
     }
     if (pro[n_paths] > c->d.max_rows) return fail(-1, "%d collected rows exceed max_rows = %d", pro[n_paths], c->d.max_rows);
     if (sc.open(/*writes=*/true, /*needs_data=*/false)) return sc.rc;
-    clear_selection(c, step);
-    if (set_step_layout(c, S, c->stream, false, n_paths, task_path_offsets, pro.data())) return -2;
-    // the finished episodes: staging rows -> slab rows in path order
-    if (c->rollout_buf.reserve(sizeof(int32_t) * 2 * (size_t)n_paths, 2)) return -2;
-    int32_t* d_env = (int32_t*)c->rollout_buf.p;
-    int32_t* d_start = d_env + n_paths;
-    HIPCHECK(hipMemcpyAsync(d_env, path_env, sizeof(int32_t) * n_paths, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(hipMemcpyAsync(d_start, path_start, sizeof(int32_t) * n_paths, hipMemcpyHostToDevice, c->stream));
-    GatherPathsArgs g;
-    const size_t n_rows = (size_t)S.rollout_T * M * B;
-    g.obs_in = c->stage_rows; g.act_in = c->stage_rows + n_rows * O; g.mean_in = g.act_in + n_rows * A;
-    g.obs = S.obs; g.act = S.act; g.mean = S.old_mean;
-    g.path_env = d_env; g.path_start = d_start; g.path_row_offsets = S.path_row_offsets;
-    g.n_envs = M * B; g.O = O; g.A = A;
-    PROMP_LAUNCH(k_gather_paths, dim3(n_paths), 256, 0, c->stream, g);
+    return finish_collection(sc, n_paths, task_path_offsets, pro.data(), path_env, path_start, nullptr, nullptr, rewards, nullptr);
+}
+
+// Whole collection on the device: k_point_collect, k_collect_stop, k_collect_tables (promp_kernels_rollout.h); only the tables come
+// back.  Every refusal leaves the step without a layout of this call: the slab is touched by finish_collection alone.
+int promp_collect_point_family(promp_ctx* c, int step, int envs_per_task, const double* task_params, const double* start,
+                               const float* noise, const promp_point_collect_opts* o, int32_t* n_paths_out, int32_t* n_steps_out,
+                               int32_t* task_path_offsets, int32_t* path_env, int32_t* path_start, int32_t* path_len) {
+    if (!c || !task_params || !start || !o || !n_paths_out || !n_steps_out || !task_path_offsets || !path_env || !path_start || !path_len)
+        return fail(-1, "NULL argument");
+    StepScope sc(c, step);
+    if (sc.rc) return sc.rc;
+    const promp_point_family_opts& e = o->env;
+    if (e.kind < POINT_KIND_CORNER || e.kind > POINT_KIND_GOAL) return fail(-1, "unknown environment kind %d", e.kind);
+    const int task_dim = e.kind == POINT_KIND_WALLS ? 6 : 2, state_dim = e.kind == POINT_KIND_MOMENTUM ? 4 : 2;
+    if (e.task_dim != task_dim) return fail(-1, "task_dim = %d, environment kind %d has task_dim = %d", e.task_dim, e.kind, task_dim);
+    if (c->d.obs_dim != state_dim) return fail(-1, "environment kind %d has obs_dim = %d (context: %d)", e.kind, state_dim, c->d.obs_dim);
+    if (c->d.act_dim != 2) return fail(-1, "the point environments have act_dim = 2 (context: %d)", c->d.act_dim);
+    if (e.reward_type < 0 || e.reward_type > 2) return fail(-1, "unknown reward type %d", e.reward_type);
+    if (o->max_path_length < 1) return fail(-1, "max_path_length = %d must be positive", o->max_path_length);
+    if (envs_per_task < 1 || o->max_steps < 1) return fail(-1, "envs_per_task and max_steps must be positive");
+    if (o->total_samples < 1) return fail(-1, "total_samples must be positive");
+    const int M = c->d.n_tasks, B = envs_per_task, O = state_dim, A = 2, S_max = o->max_steps, max_paths = c->d.max_paths;
+    const long long n_envs = (long long)M * B, stage = n_envs * S_max;
+    if (stage > 0x7FFFFFFFll / 4) return fail(-1, "max_steps * environments = %lld staging rows are too many", stage);
+    if (sc.open(/*writes=*/true, /*needs_data=*/false)) return sc.rc;
+    StepData& S = sc.S();
+    if (c->stage_rows.reserve((size_t)stage * (O + 2 * A), 1)) return -2;
+    S.has_policy = false; S.processed = false; S.has_adv = false;
+    // one block: doubles (task parameters, start table), the stop record, floats (noise, staged rewards), then the integer tables
+    const size_t n_task = (size_t)M * task_dim, n_start = (size_t)stage * O, n_noise = noise ? (size_t)stage * 2 : 0;
+    const size_t n_int = (size_t)stage + S_max + M + (M + 1) + 3 * (size_t)max_paths;
+    if (c->rollout_buf.reserve(sizeof(double) * (n_task + n_start) + sizeof(long long) * 4 + sizeof(float) * (n_noise + (size_t)stage) +
+                               sizeof(int32_t) * n_int, 2)) return -2;
+    double* d_task = (double*)c->rollout_buf.p;
+    double* d_start = d_task + n_task;
+    long long* d_stop = (long long*)(d_start + n_start);
+    float* d_noise = (float*)(d_stop + 4);
+    float* d_rew = d_noise + n_noise;
+    int32_t* d_end = (int32_t*)(d_rew + stage);
+    int32_t* d_sum = d_end + stage;
+    int32_t* d_count = d_sum + S_max;
+    int32_t* d_tpo = d_count + M;
+    int32_t* d_env = d_tpo + (M + 1);
+    int32_t* d_pstart = d_env + max_paths;
+    int32_t* d_len = d_pstart + max_paths;
+    hipStream_t st = c->stream;
+    HIPCHECK(hipMemcpyAsync(d_task, task_params, sizeof(double) * n_task, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(d_start, start, sizeof(double) * n_start, hipMemcpyHostToDevice, st));
+    if (noise) HIPCHECK(hipMemcpyAsync(d_noise, noise, sizeof(float) * n_noise, hipMemcpyHostToDevice, st));
+    if (tasks_materialize(c)) return -2;
+    PointCollectArgs k;
+    PointRolloutArgs& a = k.f.p;
+    a.theta_tasks = c->theta_tasks; a.NP = c->NP; a.H1 = c->d.hidden1; a.H2 = c->d.hidden2;
+    a.B = B; a.T = S_max; a.goals = d_task; a.start = d_start; a.noise = noise ? d_noise : nullptr;
+    a.seed = e.seed; a.stream = (unsigned)step;
+    a.obs = c->stage_rows; a.act = c->stage_rows + (size_t)stage * O; a.mean = a.act + (size_t)stage * A; a.rew = nullptr;
+    a.old_ls = S.old_ls;
+    a.clip_infos = e.clip_infos; a.min_log_std = c->min_log_std;
+    a.normalization_scale = e.normalization_scale; a.max_step = e.max_step; a.reward_type = e.reward_type; a.sparse_radius = e.sparse_radius;
+    k.f.kind = e.kind; k.f.task_dim = task_dim; k.f.state_dim = state_dim;
+    k.rew_stage = d_rew; k.end_len = d_end;
+    k.max_steps = S_max; k.max_path_length = o->max_path_length; k.n_envs = (int)n_envs; k.done_radius = o->done_radius;
+    if (c->family == PassFamily::Layered) {
+        GenPointCollectArgs g;
+        g.c = k; g.act_kind = gen_act_kinds(&c->d);
+        copy_layers(g, c);
+        PROMP_LAUNCH(k_gen_point_collect, dim3(B, M), 256, gen_rollout_smem(state_dim), st, g);
+    } else
+    PROMP_LAUNCH(k_point_collect, dim3(M), 64, 0, st, k);
     HIPCHECK(hipGetLastError());
-    HIPCHECK(hipMemcpyAsync(S.rew, rewards, sizeof(float) * pro[n_paths], hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(hipStreamSynchronize(c->stream));
-    S.has_policy = true; S.ls_per_row = 0; S.has_rew64 = false; S.processed = false; S.has_adv = false;
-    S.rollout_ragged = false; S.rollout_B = 0;
-    S.ps.obs_range_valid = false;
+    CollectStopArgs cs;
+    cs.end_len = d_end; cs.step_sum = d_sum; cs.out = d_stop; cs.max_steps = S_max; cs.n_envs = (int)n_envs; cs.total_samples = o->total_samples;
+    PROMP_LAUNCH(k_collect_stop, dim3(1), 256, 0, st, cs);
+    CollectTablesArgs ct;
+    ct.end_len = d_end; ct.stop = d_stop; ct.task_count = d_count; ct.task_path_offsets = d_tpo;
+    ct.path_env = d_env; ct.path_start = d_pstart; ct.path_len = d_len;
+    ct.B = B; ct.max_steps = S_max; ct.n_envs = (int)n_envs; ct.n_tasks = M; ct.max_paths = max_paths; ct.write = 0;
+    PROMP_LAUNCH(k_collect_tables, dim3(M), 64, 0, st, ct);
+    PROMP_LAUNCH(k_collect_offsets, dim3(1), 64, 0, st, (const int*)d_count, d_tpo, M);
+    ct.write = 1;
+    PROMP_LAUNCH(k_collect_tables, dim3(M), 64, 0, st, ct);
+    HIPCHECK(hipGetLastError());
+    long long stop[3] = {-1, 0, 1};
+    std::vector<int32_t> tpo((size_t)M + 1, 0);
+    HIPCHECK(hipMemcpyAsync(stop, d_stop, sizeof stop, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(tpo.data(), d_tpo, sizeof(int32_t) * (M + 1), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    if (stop[2] != 0 || stop[0] < 0)
+        return fail(-1, "max_steps = %d vectorised steps do not reach total_samples = %lld", S_max, (long long)o->total_samples);
+    if (stop[1] > c->d.max_rows) return fail(-1, "%lld collected rows exceed max_rows = %d", stop[1], c->d.max_rows);
+    const int n_paths = tpo[M];
+    if (n_paths < 1 || n_paths > max_paths) return fail(-1, "%d paths outside [1, max_paths = %d]", n_paths, max_paths);
+    std::string empty;
+    for (int i = 0; i < M; ++i)
+        if (tpo[i + 1] == tpo[i]) empty += (empty.empty() ? "" : ", ") + std::to_string(i);
+    if (!empty.empty())
+        return fail(-1, "no finished episode for task(s) [%s] within total_samples = %lld (envs_per_task = %d, max_path_length = %d)",
+                    empty.c_str(), (long long)o->total_samples, B, o->max_path_length);
+    HIPCHECK(hipMemcpyAsync(path_env, d_env, sizeof(int32_t) * n_paths, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(path_start, d_pstart, sizeof(int32_t) * n_paths, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(path_len, d_len, sizeof(int32_t) * n_paths, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    std::vector<int32_t> pro((size_t)n_paths + 1, 0);
+    for (int p = 0; p < n_paths; ++p) {
+        if (path_len[p] < 1 || path_start[p] < 0 || path_start[p] + path_len[p] > S_max || path_env[p] < 0 || path_env[p] >= n_envs)
+            return fail(-2, "path %d (environment %d, steps [%d, %d)) lies outside the collection", p, path_env[p], path_start[p], path_start[p] + path_len[p]);
+        pro[p + 1] = pro[p] + path_len[p];
+    }
+    if (pro[n_paths] != stop[1]) return fail(-2, "the path tables hold %d rows, the stop record %lld", pro[n_paths], stop[1]);
+    S.rollout_B = B; S.rollout_T = S_max; S.rollout_ragged = true;       // (what finish_collection reads, and clears)
+    if (finish_collection(sc, n_paths, tpo.data(), pro.data(), nullptr, nullptr, d_env, d_pstart, nullptr, d_rew)) return -2;
+    for (int i = 0; i <= M; ++i) task_path_offsets[i] = tpo[i];
+    *n_paths_out = n_paths;
+    *n_steps_out = (int32_t)stop[0] + 1;
     return 0;
 }
 

@@ -137,6 +137,8 @@ struct GatherPathsArgs {
     float *obs, *act, *mean;                  // the slab
     const int *path_env, *path_start, *path_row_offsets;
     int n_envs, O, A;
+    const float* rew_in = nullptr;            // staged rewards [steps][n_envs], or NULL: the caller uploads the slab's rewards itself
+    float* rew = nullptr;                     // the slab's rewards (read only with rew_in)
 };
 // grid = paths, block = 256
 __global__ void __launch_bounds__(256) k_gather_paths(GatherPathsArgs a) {
@@ -149,6 +151,8 @@ __global__ void __launch_bounds__(256) k_gather_paths(GatherPathsArgs a) {
         else if (k < a.O + a.A) a.act[dst * a.A + (k - a.O)] = a.act_in[src * a.A + (k - a.O)];
         else a.mean[dst * a.A + (k - a.O - a.A)] = a.mean_in[src * a.A + (k - a.O - a.A)];
     }
+    if (a.rew_in != nullptr)
+        for (int t = threadIdx.x; t < n; t += 256) a.rew[r0 + t] = a.rew_in[(long long)(s0 + t) * a.n_envs + env];
 }
 
 // Some or all of a step's paths copied into B compact slabs in ONE launch -- the slabs of its minibatches (promp_optimize_minibatch;
@@ -423,4 +427,196 @@ __global__ void __launch_bounds__(64) k_point_family_rollout(PointFamilyArgs f) 
             a.rew[row] = (float)r;
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Collections whose episodes END EARLY, without a host loop (samplers/meta_sampler.py:87-130 + vectorized_env_executor.py:25-52 of
+// the reference: an environment that reports `done`, or whose episode has reached max_path_length, is reset and keeps collecting;
+// collection stops at the first vectorised step after which total_samples steps belong to finished episodes, all episodes that end
+// at that step count, and the ones still running are dropped).  Four phases, separate launches on one stream, no workgroup waits
+// for another, every loop bounded by a launch argument:
+//   k_point_collect / k_gen_point_collect   every environment runs max_steps vectorised steps; step s files float32(state), mean,
+//                                           action and reward under the staging row (s, env) = s * n_envs + env -- the rows
+//                                           promp_policy_step files in ragged mode, the Philox counter included -- and
+//                                           end_len[s][env] = the length of the episode that ends with this step, or 0
+//   k_collect_stop                          per-step sums of end_len, their running total, the stop step s*
+//   k_collect_tables (count, then write)    per task, (env, first step, length) of every episode that ends at a step <= s*, in the
+//                                           reference's order: step-major, environment-minor; k_collect_offsets between the two
+//                                           turns the tasks' counts into task_path_offsets
+//   k_gather_paths                          staging rows -> slab rows, rewards included
+// The fourth kind of the family ends episodes:
+//   POINT_KIND_GOAL     (2, 2)  envs/point_envs/point_env_2d.py (= corner_goals_point_env_2d.py) and point_env_2d_v2.py:
+//                               s' = s + clip(e, -max_step, max_step), reward -|s' - goal|, done = |s'_0| < done_radius and
+//                               |s'_1| < done_radius: the box around the ORIGIN in both classes (point_env_2d_v2.py:52-56 tests the
+//                               origin although its reward looks at the goal).  point_env_2d.py's reward -|s'| is goal (0, 0):
+//                               (0 - x)^2 and x^2 are the same bits.  tanhf in the mean network, as walls and momentum.
+// Kinds 0..2 go through point_family_step and never report done: their episodes end by max_path_length alone.
+// ---------------------------------------------------------------------------------------------
+enum { POINT_KIND_GOAL = 3 };
+
+struct PointCollectArgs {
+    PointFamilyArgs f;         // p.obs / act / mean: the staging rows; p.start: [max_steps][n_envs][state_dim]; p.noise: [max_steps][n_envs][2]
+                               // or NULL; p.B: environments per task; p.T unused
+    float* rew_stage;          // [max_steps][n_envs]
+    int* end_len;              // [max_steps][n_envs]
+    int max_steps, max_path_length, n_envs;
+    double done_radius;
+};
+
+// one step of any kind: s advances in place, the reward comes back, done says whether the environment ended the episode
+PROMP_DEV double point_collect_step(const PointCollectArgs& c, double* s, const double* tp, float a0, float a1, bool& done) {
+    if (c.f.kind != POINT_KIND_GOAL) {
+        done = false;
+        return point_family_step(c.f, s, tp, a0, a1);
+    }
+    s[0] += point_env_move(c.f.p, a0);
+    s[1] += point_env_move(c.f.p, a1);
+    done = fabs(s[0]) < c.done_radius && fabs(s[1]) < c.done_radius;
+    return -point_distance(s[0], s[1], tp[0], tp[1]);
+}
+
+// grid = tasks, block = 64: one thread per environment.  Consecutive lanes are consecutive environments of one staging step, so
+// the stores of a step coalesce.  Every lane runs max_steps trips; an episode's end is a select on the state, not a branch.
+__global__ void __launch_bounds__(64) k_point_collect(PointCollectArgs c) {
+    const PointFamilyArgs& f = c.f;
+    const PointRolloutArgs& a = f.p;
+    const int task = blockIdx.x, O = f.state_dim;
+    const float* th = a.theta_tasks + (long long)task * a.NP;
+    const int oS = a.NP - 2;
+    const float ls0 = th[oS], ls1 = th[oS + 1];
+    if (threadIdx.x == 0) {
+        a.old_ls[task * 2 + 0] = a.clip_infos ? fmaxf(ls0, a.min_log_std) : ls0;
+        a.old_ls[task * 2 + 1] = a.clip_infos ? fmaxf(ls1, a.min_log_std) : ls1;
+    }
+    const float sd0 = expf(ls0), sd1 = expf(ls1);
+    const double* tp = a.goals + (long long)task * f.task_dim;
+    for (int b = threadIdx.x; b < a.B; b += 64) {
+        const long long env = (long long)task * a.B + b;
+        double s[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int k = 0; k < O; ++k) s[k] = a.start[env * O + k];
+        int len = 0;
+        for (int st = 0; st < c.max_steps; ++st) {
+            const long long row = (long long)st * c.n_envs + env;
+            float o[4], m[2], n0, n1;
+            for (int k = 0; k < O; ++k) o[k] = (float)s[k];
+            if (f.kind == POINT_KIND_CORNER) mlp_mean(th, o, O, 2, a.H1, a.H2, m);
+            else mlp_mean_t<true>(th, o, O, 2, a.H1, a.H2, m);
+            if (a.noise != nullptr) {
+                n0 = a.noise[row * 2];
+                n1 = a.noise[row * 2 + 1];
+            } else {
+                action_noise(a.seed, (unsigned long long)row, 0u, a.stream, n0, n1);
+            }
+            const float a0 = fmaf(sd0, n0, m[0]), a1 = fmaf(sd1, n1, m[1]);
+            for (int k = 0; k < O; ++k) a.obs[row * O + k] = o[k];
+            a.mean[row * 2] = m[0];  a.mean[row * 2 + 1] = m[1];
+            a.act[row * 2] = a0;  a.act[row * 2 + 1] = a1;
+            bool done;
+            const double r = point_collect_step(c, s, tp, a0, a1, done);
+            ++len;
+            const bool end = done || len >= c.max_path_length;
+            c.rew_stage[row] = (float)r;
+            c.end_len[row] = end ? len : 0;
+            len = end ? 0 : len;
+            // the next episode's reset() (a uniform condition; the reload is a select).  Asking for it ahead of the network was
+            // tried and is slower (profiles/point_collect_timing.txt): the extra array is indexed by the runtime state width
+            if (st + 1 < c.max_steps) {
+                const long long nxt = row + c.n_envs;
+                for (int k = 0; k < O; ++k) {
+                    const double fresh = a.start[nxt * O + k];
+                    s[k] = end ? fresh : s[k];
+                }
+            }
+        }
+    }
+}
+
+// out[0] = s*, the first step at which the running total of finished-episode steps reaches total_samples (-1: max_steps did not
+// reach it), out[1] = that total at s* (the rows; all episodes ending at s* count, so it may exceed total_samples), out[2] = 1 if
+// max_steps did not reach total_samples.  step_sum [max_steps] is scratch and a by-product.
+struct CollectStopArgs {
+    const int* end_len;        // [max_steps][n_envs]
+    int* step_sum;             // [max_steps]
+    long long* out;            // [3]
+    int max_steps, n_envs;
+    long long total_samples;
+};
+// grid = 1, block = 256: wave w sums the steps w, w + 4, ...; then one thread walks the max_steps sums
+__global__ void __launch_bounds__(256) k_collect_stop(CollectStopArgs a) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int s = wave; s < a.max_steps; s += 4) {
+        double n = 0.0;                                            // (sums of int32 lengths: exact in double)
+        for (int e = lane; e < a.n_envs; e += 64) n += (double)a.end_len[(long long)s * a.n_envs + e];
+        n = wave_sum_f64(n);
+        if (lane == 0) a.step_sum[s] = (int)n;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long total = 0, rows = 0;
+        int stop = -1;
+        for (int s = 0; s < a.max_steps; ++s) {
+            total += a.step_sum[s];
+            const bool first = stop < 0 && total >= a.total_samples;
+            stop = first ? s : stop;
+            rows = first ? total : rows;
+        }
+        a.out[0] = stop;
+        a.out[1] = rows;
+        a.out[2] = stop < 0 ? 1 : 0;
+    }
+}
+
+struct CollectTablesArgs {
+    const int* end_len;        // [max_steps][n_envs]
+    const long long* stop;     // k_collect_stop's out
+    int* task_count;           // [tasks]: written when write == 0
+    const int* task_path_offsets;   // [tasks + 1]: read when write == 1
+    int *path_env, *path_start, *path_len;   // [max_paths]
+    int B, max_steps, n_envs, n_tasks, max_paths, write;
+};
+// exclusive prefix count of a flag over the wave's lanes, and the wave's total (Hillis-Steele over lane shuffles)
+PROMP_DEV int wave_prefix_count(bool flag, int lane, int& total) {
+    double v = flag ? 1.0 : 0.0;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const double o = shfl_idx_f64(v, lane >= d ? lane - d : lane);
+        v += lane >= d ? o : 0.0;
+    }
+    total = (int)shfl_idx_f64(v, 63);
+    return (int)v - (flag ? 1 : 0);
+}
+// grid = tasks, block = 64 (one wave): steps 0..s* in order, within a step the task's environments in index order, 64 at a time.
+// write == 0 counts the task's paths; write == 1 files them behind task_path_offsets[task] (nothing if they exceed max_paths).
+__global__ void __launch_bounds__(64) k_collect_tables(CollectTablesArgs a) {
+    const int task = blockIdx.x, lane = threadIdx.x;
+    const int s_stop = (int)a.stop[0];
+    const int base = a.write ? a.task_path_offsets[task] : 0;
+    const bool fits = a.write && a.task_path_offsets[a.n_tasks] <= a.max_paths;
+    int count = 0;
+    for (int s = 0; s < a.max_steps; ++s) {
+        if (s > s_stop) break;                                     // (uniform)
+        for (int b0 = 0; b0 < a.B; b0 += 64) {
+            const int b = b0 + lane, env = task * a.B + b;
+            const int len = b < a.B ? a.end_len[(long long)s * a.n_envs + env] : 0;
+            int total;
+            const int pos = base + count + wave_prefix_count(len > 0, lane, total);
+            if (fits && len > 0) {
+                a.path_env[pos] = env;
+                a.path_start[pos] = s - len + 1;
+                a.path_len[pos] = len;
+            }
+            count += total;
+        }
+    }
+    if (!a.write && lane == 0) a.task_count[task] = count;
+}
+// grid = 1, block = 64: task_path_offsets [tasks + 1] from the tasks' counts
+__global__ void __launch_bounds__(64) k_collect_offsets(const int* task_count, int* task_path_offsets, int n_tasks) {
+    if (threadIdx.x != 0) return;
+    int n = 0;
+    for (int i = 0; i < n_tasks; ++i) {
+        task_path_offsets[i] = n;
+        n += task_count[i];
+    }
+    task_path_offsets[n_tasks] = n;
 }

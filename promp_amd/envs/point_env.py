@@ -1,6 +1,7 @@
-"""2-D point-mass meta-environments with corner goals: MetaPointEnvCorner, the environment of BASELINE config 1
-(run_scripts/pro-mp_run_point_mass.py trains on normalize(MetaPointEnvCorner())), and its two fixed-horizon siblings
-MetaPointEnvWalls and MetaPointEnvMomentum (described at the classes).
+"""2-D point-mass meta-environments: MetaPointEnvCorner, the environment of BASELINE config 1
+(run_scripts/pro-mp_run_point_mass.py trains on normalize(MetaPointEnvCorner())), its two fixed-horizon siblings with corner goals,
+MetaPointEnvWalls and MetaPointEnvMomentum, and the two whose episodes end early, MetaPointEnv and MetaPointEnvV2 (described at
+the classes).
 
 Behaviour (reference: meta_policy_search/envs/point_envs/point_env_2d_corner.py:13-93, MetaEnv interface envs/base.py:6-49):
   * a task is a goal, one of the corners (-2,-2), (2,-2), (-2,2), (2,2), drawn uniformly;
@@ -77,9 +78,6 @@ class MetaPointEnvCorner(MetaEnv):
         if to_goal == min(self._distance(obs_next, corner) for corner in self.corners):
             return self._distance(obs, self.goal) - to_goal
         return 0
-
-
-MetaPointEnv = MetaPointEnvCorner      # (the name earlier revisions of this package used)
 
 
 def _norm(v):
@@ -218,11 +216,92 @@ class MetaPointEnvMomentum(MetaEnv):
         return max(self.sparse_reward_radius - to_goal, 0.0)
 
 
-POINT_ENVS = dict(corner=MetaPointEnvCorner, walls=MetaPointEnvWalls, momentum=MetaPointEnvMomentum)
+class MetaPointEnv(MetaEnv):
+    """The point mass that has to reach the origin, and whose episode ENDS there (reference: envs/point_envs/point_env_2d.py:7-71;
+    corner_goals_point_env_2d.py is the same class).
+
+      * a task is {}: every task is the same environment;
+      * reset: state ~ U(-2, 2)^2; step: s' = s + clip(action, -0.1, 0.1); reward -|s'|;
+      * done: |s'_0| < 0.01 and |s'_1| < 0.01 (a box around the origin, not a disc).
+    There is no reward_type.  The device runs the same arithmetic (promp_collect_point_family, kind goal with the goal (0, 0):
+    (0 - x)^2 and x^2 are the same bits); the trajectories of the reference class are tests/golden/point_env_origin.npz."""
+    DONE_RADIUS = 0.01
+
+    def __init__(self):
+        self.observation_space = ActionBox(-np.inf, np.inf, (2,))
+        self.action_space = ActionBox(-0.1, 0.1, (2,))
+        self._state = np.zeros(2)
+
+    # ---- MetaEnv ----
+    def sample_tasks(self, n_tasks):
+        return [{}] * n_tasks
+
+    def set_task(self, task):
+        pass
+
+    def get_task(self):
+        return {}
+
+    def log_diagnostics(self, *args, **kwargs):
+        pass
+
+    # ---- dynamics ----
+    def reset(self):
+        self._state = np.random.uniform(-2, 2, size=(2,))
+        return self._state.copy()
+
+    def step(self, action):
+        before = self._state
+        self._state = before + np.clip(action, self.action_space.low, self.action_space.high)
+        return self._state.copy(), self.reward(before, action, self._state), self.done(self._state), {}
+
+    def done(self, obs):
+        return bool(abs(obs[0]) < self.DONE_RADIUS and abs(obs[1]) < self.DONE_RADIUS)
+
+    def reward(self, obs, act, obs_next):
+        return -_norm(obs_next)
+
+
+class MetaPointEnvV2(MetaPointEnv):
+    """The point mass that starts at the origin and is rewarded for reaching a goal (reference: envs/point_envs/point_env_2d_v2.py:7-75).
+
+      * a task is a goal ~ U(-2, 2)^2;
+      * reset: state = (0, 0); step: s' = s + clip(action, -0.1, 0.1); reward -|goal - s'|;
+      * done: |s'_0| < 0.01 and |s'_1| < 0.01 -- the box around the ORIGIN, not around the goal, exactly as the reference has it: an
+        episode ends when the point is back where it started (so every first step smaller than 0.01 ends one).  The quirk is kept.
+    The reference's get_task reads self.task, an attribute it never sets; here get_task returns the goal.  The device runs the same
+    arithmetic (promp_collect_point_family, kind goal); the reference's trajectories are tests/golden/point_env_goal.npz."""
+
+    def __init__(self):
+        super(MetaPointEnvV2, self).__init__()
+        self.goal = np.random.uniform(-2, 2, size=(2,))
+
+    def sample_tasks(self, n_tasks):
+        return np.random.uniform(-2, 2, size=(n_tasks, 2))
+
+    def set_task(self, task):
+        self.goal = np.asarray(task, dtype=np.float64)
+
+    def get_task(self):
+        return self.goal
+
+    def reset(self):
+        self._state = np.zeros(2)
+        return self._state.copy()
+
+    def reward(self, obs, act, obs_next):
+        return -_norm(self.goal - obs_next)
+
+
+POINT_ENVS = dict(corner=MetaPointEnvCorner, walls=MetaPointEnvWalls, momentum=MetaPointEnvMomentum, origin=MetaPointEnv,
+                  goal=MetaPointEnvV2)
 
 
 def make_point_env(name='corner', reward_type=None):
-    """name: 'corner' | 'walls' | 'momentum' or the class's name; reward_type None: the class's default"""
+    """name: 'corner' | 'walls' | 'momentum' | 'origin' | 'goal' or the class's name; reward_type None: the class's default (the
+    two terminating classes, origin and goal, have none)"""
     classes = dict(POINT_ENVS, **{cls.__name__: cls for cls in POINT_ENVS.values()})
     assert name in classes, 'unknown point-mass environment %r (one of %s)' % (name, ', '.join(sorted(POINT_ENVS)))
+    if issubclass(classes[name], MetaPointEnv):
+        assert reward_type is None, 'MetaPointEnv and MetaPointEnvV2 have no reward_type (asked for %r)' % (reward_type,)
     return classes[name]() if reward_type is None else classes[name](reward_type=reward_type)

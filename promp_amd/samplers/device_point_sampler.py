@@ -6,6 +6,9 @@ bare or wrapped in promp_amd.envs.normalized_env.normalize.  One kernel launch r
 its task's current policy parameters and writes the trajectories straight into the sampling step's slab (promp_rollout_point_env
 for the corner environment, promp_rollout_point_family for the other two); MetaSampleProcessor.process_samples then finds the data
 resident and uploads nothing.
+MetaPointEnv and MetaPointEnvV2 end their episodes early (`done` at the origin): promp_collect_point_family runs every environment
+for as many vectorised steps as the reference's sampler could need, finds its stop step and lists the finished episodes on the
+device; the slab is ragged and envs_per_task is honoured (_obtain_terminating).
 The host keeps what it is good at: drawing tasks, start states and the exploration noise from NumPy's RNG, and
 materialising the path dicts the plugin API returns (one small download per sampling step)."""
 from collections import OrderedDict
@@ -59,17 +62,21 @@ class DevicePaths(OrderedDict):
         return OrderedDict.popitem(self, *args, **kw)
 
 
+TERMINATING = ('origin', 'goal')       # MetaPointEnv, MetaPointEnvV2: episodes end early, collected by promp_collect_point_family
+
+
 def _point_env_kind(bare):
-    from ..envs.point_env import MetaPointEnvCorner, MetaPointEnvMomentum, MetaPointEnvWalls
-    for cls, kind in ((MetaPointEnvCorner, 'corner'), (MetaPointEnvWalls, 'walls'), (MetaPointEnvMomentum, 'momentum')):
+    from ..envs.point_env import MetaPointEnv, MetaPointEnvCorner, MetaPointEnvMomentum, MetaPointEnvV2, MetaPointEnvWalls
+    for cls, kind in ((MetaPointEnvCorner, 'corner'), (MetaPointEnvWalls, 'walls'), (MetaPointEnvMomentum, 'momentum'),
+                      (MetaPointEnvV2, 'goal'), (MetaPointEnv, 'origin')):          # (V2 derives from MetaPointEnv: asked first)
         if isinstance(bare, cls):
             return kind
     return None
 
 
 def _point_env_options(env):
-    """(bare environment, kernel options) of MetaPointEnvCorner / MetaPointEnvWalls / MetaPointEnvMomentum, wrapped in
-    normalize(...) or not"""
+    """(bare environment, kernel options) of MetaPointEnvCorner / MetaPointEnvWalls / MetaPointEnvMomentum / MetaPointEnv /
+    MetaPointEnvV2, wrapped in normalize(...) or not"""
     from ..envs.normalized_env import NormalizedEnv
     scale = 0.0                              # bare environment
     if isinstance(env, NormalizedEnv):
@@ -79,8 +86,12 @@ def _point_env_options(env):
         assert np.allclose(bare.action_space.low, -bare.action_space.high)
     else:
         bare = env
-    assert _point_env_kind(bare) is not None, \
-        'the device environments are MetaPointEnvCorner, MetaPointEnvWalls and MetaPointEnvMomentum (optionally normalize()d)'
+    kind = _point_env_kind(bare)
+    assert kind is not None, \
+        'the device environments are MetaPointEnvCorner, MetaPointEnvWalls, MetaPointEnvMomentum, MetaPointEnv and MetaPointEnvV2 ' \
+        '(optionally normalize()d)'
+    if kind in TERMINATING:                  # no reward_type: the reward is -|s' - goal|
+        return bare, dict(normalization_scale=scale, max_step=float(bare.action_space.high[0]), done_radius=float(bare.DONE_RADIUS))
     return bare, dict(reward_type=bare.reward_type, normalization_scale=scale, max_step=float(bare.action_space.high[0]),
                       sparse_radius=float(bare.sparse_reward_radius))
 
@@ -103,7 +114,9 @@ class DevicePointEnvSampler(object):
         self.batch_size = rollouts_per_meta_task
         self.meta_batch_size = meta_batch_size
         self.max_path_length = max_path_length
-        self.envs_per_task = rollouts_per_meta_task       # one environment per rollout: every path runs the full horizon
+        # fixed horizon: one environment per rollout, every path runs the full horizon.  The terminating classes honour
+        # envs_per_task as MetaSampler does: an environment collects one episode after another
+        self.envs_per_task = rollouts_per_meta_task if envs_per_task is None or self.kind not in TERMINATING else int(envs_per_task)
         self.total_samples = meta_batch_size * rollouts_per_meta_task * max_path_length
         self.total_timesteps_sampled = 0
         self.goals = None
@@ -111,12 +124,16 @@ class DevicePointEnvSampler(object):
     def update_tasks(self):
         tasks = self.env.sample_tasks(self.meta_batch_size)
         assert len(tasks) == self.meta_batch_size
+        if self.kind == 'origin':           # a task is {}: the goal kind with the goal at the origin
+            tasks = np.zeros((self.meta_batch_size, 2))
         if self.kind == 'walls':            # a task is dict(goal, gap_1, gap_2): the kernel's [M][6]
             tasks = [np.concatenate([np.asarray(t[k], dtype=np.float64) for k in ('goal', 'gap_1', 'gap_2')]) for t in tasks]
         self.goals = np.asarray(tasks, dtype=np.float64).reshape(self.meta_batch_size, 6 if self.kind == 'walls' else 2)
 
     def obtain_samples(self, log=False, log_prefix=''):
         assert self.goals is not None, 'call update_tasks() first'
+        if self.kind in TERMINATING:
+            return self._obtain_terminating(log, log_prefix)
         M, B, T = self.meta_batch_size, self.envs_per_task, self.max_path_length
         sess = self.policy.session
         ctx = sess.ensure(M * B * T, M * B)
@@ -154,6 +171,58 @@ class DevicePointEnvSampler(object):
                           path_row_offsets=np.arange(M * B + 1, dtype=np.int32) * T,
                           obs=slab['obs'], act=slab['act'], rew=slab['rew'], old_mean=slab['old_mean'], old_log_std=slab['old_log_std'])
         self.total_timesteps_sampled += M * B * T
+        if log:
+            logger.logkv(log_prefix + 'PolicyExecTime', 0.0)
+            logger.logkv(log_prefix + 'EnvExecTime', 0.0)
+        return paths
+
+    def _obtain_terminating(self, log, log_prefix):
+        """MetaPointEnv / MetaPointEnvV2: one promp_collect_point_family instead of DeviceSlabSampler's call per environment step.
+        The start table holds a reset() for every (vectorised step, environment): row 0 the initial states, row s + 1 what an
+        environment whose episode ends at step s continues from -- max_steps * n_envs * 2 float64 uploaded per sampling step, of
+        which only the rows behind an episode's end are read (the price of drawing the start states on the host)."""
+        M, B, T = self.meta_batch_size, self.envs_per_task, self.max_path_length
+        n_envs = M * B
+        # (the bound of DeviceSlabSampler: after S steps at least n_envs (S - T + 1) steps lie in finished episodes)
+        max_steps = T - 1 + -(-self.total_samples // n_envs)
+        sess = self.policy.session
+        ctx = sess.ensure(max_steps * n_envs, max_steps * n_envs)
+        if sess.task_thetas is not None:           # parameters set while no context existed yet
+            ctx.set_task_thetas(sess.task_thetas)
+            sess.task_thetas = None
+        if self.kind == 'origin':                  # MetaPointEnv.reset
+            start = np.random.uniform(-2, 2, size=(max_steps, n_envs, 2))
+        else:                                      # MetaPointEnvV2.reset
+            start = np.zeros((max_steps, n_envs, 2))
+        slot = sess.next_slot()
+        kw = dict(total_samples=self.total_samples, max_path_length=T, clip_infos=self.policy._pre_update_mode, **self._env_opts)
+        try:
+            if self.device_noise:
+                tables = ctx.collect_point_family(slot, 'goal', self.goals, start, None, seed=int(np.random.randint(0, 2 ** 31 - 1)), **kw)
+            else:
+                noise = np.random.normal(size=(max_steps, n_envs, 2)).astype(np.float32)
+                tables = ctx.collect_point_family(slot, 'goal', self.goals, start, noise, **kw)
+        except RuntimeError as e:
+            if 'no finished episode' not in str(e):
+                raise
+            raise RuntimeError('DevicePointEnvSampler: %s (rollouts_per_meta_task = %d)' % (e, self.batch_size))
+        sess._upload_counter += 1
+        sess.upload_serial[slot] = sess._upload_counter
+        slab = ctx.download_step(slot)
+        tpo, pro = tables['task_path_offsets'], tables['path_row_offsets']
+        paths = DevicePaths()
+        for i in range(M):
+            paths[i] = []
+            for p in range(tpo[i], tpo[i + 1]):
+                rows = slice(pro[p], pro[p + 1])
+                paths[i].append(dict(observations=slab['obs'][rows], actions=slab['act'][rows], rewards=slab['rew'][rows],
+                                     env_infos={},
+                                     agent_infos=dict(mean=slab['old_mean'][rows],
+                                                      log_std=np.tile(slab['old_log_std'][i], (pro[p + 1] - pro[p], 1)))))
+        paths.device_ref = (sess.serial, sess.upload_serial[slot], slot)
+        paths.flat = dict(task_path_offsets=tpo, path_row_offsets=pro, path_env=tables['path_env'], path_start=tables['path_start'],
+                          obs=slab['obs'], act=slab['act'], rew=slab['rew'], old_mean=slab['old_mean'], old_log_std=slab['old_log_std'])
+        self.total_timesteps_sampled += self.total_samples
         if log:
             logger.logkv(log_prefix + 'PolicyExecTime', 0.0)
             logger.logkv(log_prefix + 'EnvExecTime', 0.0)

@@ -74,9 +74,10 @@ if __name__ == '__main__':
     ap.add_argument('--config_file', type=str, default='')
     ap.add_argument('--dump_path', type=str, default='')
     ap.add_argument('--n_itr', type=int, default=None)
-    ap.add_argument('--env', type=str, default=None, choices=['corner', 'walls', 'momentum'],
+    ap.add_argument('--env', type=str, default=None, choices=['corner', 'walls', 'momentum', 'origin', 'goal'],
                     help='the point-mass meta-environment (default corner); walls and momentum take their own default reward type '
-                         'unless the config file names one')
+                         'unless the config file names one; origin (MetaPointEnv) and goal (MetaPointEnvV2) end their episodes '
+                         'early and have no reward type')
     ap.add_argument('--vpg', action='store_true', help='VPG_DICEMAML: DiCE inner steps, advantages from a return baseline outside')
     ap.add_argument('--quiet', action='store_true')
     args = ap.parse_args()

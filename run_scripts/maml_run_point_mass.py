@@ -69,9 +69,10 @@ if __name__ == '__main__':
     ap.add_argument('--config_file', type=str, default='', help='json file with run specifications')
     ap.add_argument('--dump_path', type=str, default='')
     ap.add_argument('--n_itr', type=int, default=None)
-    ap.add_argument('--env', type=str, default=None, choices=['corner', 'walls', 'momentum'],
+    ap.add_argument('--env', type=str, default=None, choices=['corner', 'walls', 'momentum', 'origin', 'goal'],
                     help='the point-mass meta-environment (default corner); walls and momentum take their own default reward type '
-                         'unless the config file names one')
+                         'unless the config file names one; origin (MetaPointEnv) and goal (MetaPointEnvV2) end their episodes '
+                         'early and have no reward type')
     ap.add_argument('--exploration', action='store_true', help='E-MAML (e-maml_run_mujoco.py)')
     ap.add_argument('--hvp', type=str, default=None, choices=['finite_difference', 'exact'])
     ap.add_argument('--subsample_factor', type=float, default=None,

@@ -73,9 +73,10 @@ if __name__ == '__main__':
     ap.add_argument('--config_file', type=str, default='')
     ap.add_argument('--dump_path', type=str, default='')
     ap.add_argument('--n_itr', type=int, default=None)
-    ap.add_argument('--env', type=str, default=None, choices=['corner', 'walls', 'momentum'],
+    ap.add_argument('--env', type=str, default=None, choices=['corner', 'walls', 'momentum', 'origin', 'goal'],
                     help='the point-mass meta-environment (default corner); walls and momentum take their own default reward type '
-                         'unless the config file names one')
+                         'unless the config file names one; origin (MetaPointEnv) and goal (MetaPointEnvV2) end their episodes '
+                         'early and have no reward type')
     ap.add_argument('--num_minibatches', type=int, default=None,
                     help='Adam steps per epoch of the outer step: every task\'s paths are dealt to this many minibatches (default 1)')
     ap.add_argument('--outer_optimizer', type=str, default=None, choices=['adam', 'sgd', 'gradient_descent', 'momentum'],

@@ -1,0 +1,20 @@
+"""DevicePointEnvSampler on MetaPointEnvV2 on the kernel emulator, at the tiniest case
+(tests/point_collect_checks.py:run_sampler_scenario; tests/test_gpu_point_collect_sampler.py runs the rest on the MI355X)."""
+import pytest
+
+from promp_amd import _lib, session
+from tests import devlib, point_collect_checks as pc
+
+
+@pytest.fixture
+def emu(monkeypatch):
+    monkeypatch.setenv('PROMP_EMU_CUS', '2')
+    lib = devlib.emu_library()
+    _lib.set_library_for_testing(lib)
+    yield lib
+    _lib.set_library_for_testing(None)
+    session._current = None
+
+
+def test_sampler_on_the_goal_class(emu):
+    pc.run_sampler_scenario('goal', wrapped=True, M=2, B=2, R=3, T=4)

@@ -8,7 +8,15 @@
                                                          noise mode, at BASELINE config 1's shapes: median and spread over N windows
                                                          of W launches.  --lib binds another build of the library (an A/B against
                                                          another commit: run the two alternately in one job); corner goes through
-                                                         promp_rollout_point_env, which every build has."""
+                                                         promp_rollout_point_env, which every build has.
+    python tools/rollout_timing.py --launch --wide ...   the same at 40 tasks and a 2x64 MLP (M 40, B 20, T 100), corner through
+                                                         promp_rollout_point_family
+    python tools/rollout_timing.py --launch --collect [--kinds corner goal] ...
+                                                         time of ONE promp_collect_point_family call at M 40, B 20, T 100, (64,64):
+                                                         max_steps = 2 T - 1 = 199 vectorised steps, total_samples = M B T, the
+                                                         start table [199][800][2] float64 uploaded with every call; also per
+                                                         vectorised step, beside which `--wide` puts the fixed-horizon launch's
+                                                         time per step (its T = 100 steps)."""
 import argparse
 import sys
 import time
@@ -42,16 +50,75 @@ def sampler_rates():
                     kind, M, B, T, name, 1e3 * dt, M * B * T / dt))
 
 
-def launch_times(kinds, lib_path, repeats, launches, label):
-    from promp_amd import _lib, synthetic
-    M, B, T, hidden = 4, 20, 100, (32, 32)                    # BASELINE config 1
+def bind(lib_path, kinds, need_family=False):
+    """the library, or another build of it: entry points a build from before them lacks are left unbound"""
+    from promp_amd import _lib
+    if not lib_path:
+        return _lib.Library()
+    newest = ['promp_collect_point_family', 'promp_rollout_point_family']
+    held = {}
     try:
-        lib = _lib.Library(lib_path) if lib_path else _lib.Library()
-    except AttributeError:                                     # a build from before promp_rollout_point_family: corner only
-        family = _lib.SIGNATURES.pop('promp_rollout_point_family')
-        lib = _lib.Library(lib_path)
-        _lib.SIGNATURES['promp_rollout_point_family'] = family
-        assert kinds == ['corner'], 'this library has the corner environment only'
+        while True:
+            try:
+                return _lib.Library(lib_path)
+            except AttributeError:
+                name = newest.pop(0)                           # (raises IndexError when something else is missing)
+                held[name] = _lib.SIGNATURES.pop(name)
+                if name == 'promp_rollout_point_family':
+                    assert kinds == ['corner'] and not need_family, 'this library has the corner environment only'
+    finally:
+        _lib.SIGNATURES.update(held)
+
+
+def timed(run, ctx, repeats, launches, warm=20):
+    for _ in range(warm):                                      # warm-up: code objects, buffers
+        run()
+    ctx.sync()
+    times = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        for _ in range(launches):
+            run()
+        ctx.sync()
+        times.append((time.perf_counter() - t0) / launches)
+    return 1e6 * np.array(times)
+
+
+def collect_times(kinds, lib_path, repeats, launches, label):
+    from promp_amd import _lib, synthetic
+    M, B, T, hidden = 40, 20, 100, (64, 64)
+    S, N = 2 * T - 1, M * B
+    lib = bind(lib_path, kinds)
+    rng = np.random.RandomState(0)
+    for kind in kinds:
+        task_dim, O = _lib.POINT_KIND_DIMS[kind]
+        ctx = _lib.Context(M, O, 2, hidden, 1, max_rows=S * N, max_paths=S * N, lib=lib)
+        ctx.set_theta(synthetic.init_theta(rng, O, hidden, 2))
+        ctx.switch_to_pre_update()
+        if kind == 'goal':                                     # MetaPointEnvV2: goals in the square, every episode from the origin
+            tasks, start, max_step = rng.uniform(-2, 2, size=(M, 2)), np.zeros((S, N, O)), 0.1
+        else:
+            tasks, start, max_step = rng.randn(M, task_dim), rng.uniform(-0.2, 0.2, size=(S, N, O)), 0.2 if kind != 'momentum' else 0.1
+        z = rng.randn(S, N, 2).astype(np.float32)
+        out = {}
+        for noise in ('host', 'device'):
+            def run():
+                out['t'] = ctx.collect_point_family(0, kind, tasks, start, z if noise == 'host' else None, total_samples=N * T,
+                                                    max_path_length=T, seed=12345, reward_type='dense', normalization_scale=10.0,
+                                                    max_step=max_step)
+            us = timed(run, ctx, repeats, launches, warm=5)
+            t = out['t']
+            print('%scollect %-8s %-6s noise  median %9.2f us per call  min %9.2f  max %9.2f  = %7.2f us per vectorised step (%d steps); '
+                  'stop step %d, %d paths, %d rows  (%d windows of %d calls)' % (
+                      label, kind, noise, np.median(us), us.min(), us.max(), np.median(us) / S, S, t['n_steps'] - 1, len(t['path_len']),
+                      t['path_row_offsets'][-1], repeats, launches), flush=True)
+        ctx.close()
+
+
+def launch_times(kinds, lib_path, repeats, launches, label, wide=False):
+    from promp_amd import _lib, synthetic
+    M, B, T, hidden = (40, 20, 100, (64, 64)) if wide else (4, 20, 100, (32, 32))     # BASELINE config 1 (wide: 40 tasks, 2x64)
+    lib = bind(lib_path, kinds, need_family=wide)
     rng = np.random.RandomState(0)
     for kind in kinds:
         task_dim, O = _lib.POINT_KIND_DIMS[kind]
@@ -63,36 +130,32 @@ def launch_times(kinds, lib_path, repeats, launches, label):
         env = dict(reward_type='dense', normalization_scale=10.0, max_step=0.2 if kind != 'momentum' else 0.1)
         for noise in ('host', 'device'):
             kw = dict(noise=z if noise == 'host' else None, seed=12345, path_length=T, **env)
-            if kind == 'corner':
+            if kind == 'corner' and not wide:
                 run = lambda: ctx.rollout_point_env(0, tasks, start, **kw)
             else:
                 run = lambda: ctx.rollout_point_family(0, kind, tasks, start, **kw)
-            for _ in range(20):                                # warm-up: code objects, buffers
-                run()
-            ctx.sync()
-            times = []
-            for _ in range(repeats):
-                t0 = time.perf_counter()
-                for _ in range(launches):
-                    run()
-                ctx.sync()
-                times.append((time.perf_counter() - t0) / launches)
-            us = 1e6 * np.array(times)
-            print('%s%-8s %-6s noise  median %8.2f us per launch  min %8.2f  max %8.2f  (%d windows of %d launches)' % (
-                label, kind, noise, np.median(us), us.min(), us.max(), repeats, launches), flush=True)
+            us = timed(run, ctx, repeats, launches)
+            per_step = '  = %7.2f us per step (%d steps)' % (np.median(us) / T, T) if wide else ''
+            print('%s%-8s %-6s noise  median %8.2f us per launch  min %8.2f  max %8.2f%s  (%d windows of %d launches)' % (
+                label, kind, noise, np.median(us), us.min(), us.max(), per_step, repeats, launches), flush=True)
         ctx.close()
 
 
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--launch', action='store_true')
-    ap.add_argument('--kinds', nargs='+', default=['corner', 'walls', 'momentum'], choices=['corner', 'walls', 'momentum'])
+    ap.add_argument('--collect', action='store_true')
+    ap.add_argument('--wide', action='store_true')
+    ap.add_argument('--kinds', nargs='+', default=None, choices=['corner', 'walls', 'momentum', 'goal'])
     ap.add_argument('--lib', type=str, default='')
     ap.add_argument('--label', type=str, default='')
     ap.add_argument('--repeats', type=int, default=7)
     ap.add_argument('--launches', type=int, default=300)
     args = ap.parse_args()
-    if args.launch:
-        launch_times(args.kinds, args.lib, args.repeats, args.launches, args.label and args.label + ' ')
+    label = args.label and args.label + ' '
+    if args.launch and args.collect:
+        collect_times(args.kinds or ['corner', 'goal'], args.lib, args.repeats, args.launches, label)
+    elif args.launch:
+        launch_times(args.kinds or ['corner', 'walls', 'momentum'], args.lib, args.repeats, args.launches, label, args.wide)
     else:
         sampler_rates()
