@@ -452,8 +452,40 @@ static void check_fused_row_cases() {
     check_long_items("fused split range", range, 1, {{0, 320}, {320, 640}});
     check_chain_segments("fused split range", range, 1, {{0, 0, 20}, {1, 0, 20}}, {0, 2});
 }
+// More tasks than compute units (tests/count_axis_checks.py: M = n_cus + 1): 257 one-tile tasks on 256 units.  Every task is floored
+// to one work item in both tables -- 257 items each, nothing left to share out, room for max_work = 2 * 256 + 257 = 769 --, and there
+// are 257 chain segments of one tile.  A workgroup of one segment costs 6 quarter rounds; 257 of them are one too many, and the
+// smallest cost limit that admits a second segment (12) pairs them up: 128 workgroups of two tasks and one of the last task alone,
+// every workgroup but the last changing task mid-launch.
+static void check_more_tasks_than_units() {
+    const int M = 257, n_cus = 256;
+    const std::vector<std::vector<int>> lengths(M, std::vector<int>{16});
+    std::vector<std::pair<int, int>> items;
+    std::vector<Seg> segs;
+    std::vector<int> wg{0};
+    for (int i = 0; i < M; ++i) {
+        items.push_back({16 * i, 16 * i + 16});
+        segs.push_back({i, 0, 1});
+        if (i % 2 == 1 || i == M - 1) wg.push_back(i + 1);
+    }
+    check_long_items("257 one-tile tasks", lengths, n_cus, items);
+    check_chain_segments("257 one-tile tasks", lengths, n_cus, segs, wg);
+    EXPECT(wg.size() == 130, "257 one-tile tasks: %zu workgroups expected by the test itself", wg.size() - 1);
+    const Offsets o = offsets_of(lengths);
+    StepTables T;
+    std::string why;
+    const int rc = build_step_tables(n_cus, 2 * n_cus + M, 16 * M, M, M, M, o.tpo.get(), o.pro.get(), &T, &why);
+    EXPECT(rc == 0 && T.work[1].size() == (size_t)M, "257 one-tile tasks: table 1 has %zu items (%d): %s", T.work[1].size(), rc, why.c_str());
+    for (int i = 0; rc == 0 && i < M && i < (int)T.work[1].size(); ++i)
+        EXPECT(T.work[1][i].task == i && T.work[1][i].row_begin == 16 * i && T.work[1][i].row_end == 16 * i + 16, "257 one-tile tasks: table 1 item %d", i);
+    // the same tasks with a room one short of the items are refused by name, nothing written
+    StepTables S;
+    const int rc2 = build_step_tables(n_cus, M - 1, 16 * M, M, M, M, o.tpo.get(), o.pro.get(), &S, &why);
+    EXPECT(rc2 == -5 && why == "internal: work table overflow (257 > 256)" && S.segs.empty(), "257 one-tile tasks, room for 256: returned %d '%s'", rc2, why.c_str());
+}
 static void check_step_tables() {
     check_fused_row_cases();
+    check_more_tasks_than_units();
     // one compute unit: one item per task, whatever the row counts (the work-item lengths of tests/layered_checks.py)
     check_long_items("one task, one item", {{300, 21}}, 1, {{0, 321}});
     check_long_items("three ragged tasks, one item each", {{300, 21}, {256, 256, 1}, {1}}, 1, {{0, 321}, {321, 834}, {834, 835}});

@@ -34,7 +34,7 @@ def per_step(base, B, K):
 
 
 def eta_of(K):
-    return np.array([5e-4, 1e-3, 2e-3][:K], np.float32)
+    return helpers.eta_for(K)
 
 
 class Case(object):

@@ -567,7 +567,7 @@ def check_meta(lib, seed, M, P, T, O, A, hidden, K, ragged=False, epochs=2, comp
     ctx = make_ctx(lib, M, O, A, hidden, K, all_paths, hidden_act=hidden_act, output_act=output_act)
     helpers.upload_slabs(ctx, all_paths, all_slabs, compact_log_std=compact_log_std)
     alpha = np.full(spec.n_params, 0.1, np.float32)
-    eta = np.array([5e-4, 1e-3, 2e-3][:K], np.float32)
+    eta = helpers.eta_for(K)
     a64, e64, t64 = alpha.astype(np.float64), eta.astype(np.float64), theta.astype(np.float64)
     ctx.set_theta(theta)
     ctx.set_step_sizes(alpha)
@@ -618,7 +618,7 @@ def check_primal_cache(lib, seed, M, P, T, O, A, hidden, K=1, ragged=True, lengt
                                                           lengths_per_task=lengths_per_task)
     spec = op.PolicySpec(O, A, hidden)
     alpha = np.full(spec.n_params, 0.1, np.float32)
-    eta = np.array([5e-4, 1e-3, 2e-3][:K], np.float32)
+    eta = helpers.eta_for(K)
     out = []
     for on in (True, False):
         ctx = make_ctx(lib, M, O, A, hidden, K, all_paths)
@@ -1373,10 +1373,9 @@ def check_dice_case(lib, c, t64, all_slabs, tol=1e-4, golden_grad=None, worst=No
     return err
 
 
-def check_dice_path_lengths(lib, seed, lengths_per_task, O=5, A=3, hidden=(32, 32), K=1, alpha=0.1, tol=1e-4, worst=None):
-    """DICE-MAML's inner step and meta-gradient on paths of the given lengths (k_dice_scan's 64-row chunks: lengths on both sides
-    of one and two chunks), against the float64 oracle (oracle/dice.py) alone.  The inputs follow oracle/gen_golden.py's
-    make_dice_inputs: seeded paths per step, N(0,1) adjusted rewards, padded to the longest path."""
+def dice_path_lengths_case(seed, lengths_per_task, O=5, A=3, hidden=(32, 32), K=1, alpha=0.1):
+    """check_dice_path_lengths' inputs (CPU only) -> (c, theta float64, all_slabs): oracle/gen_golden.py's make_dice_inputs on explicit
+    path lengths -- seeded paths per step, N(0,1) adjusted rewards, padded to the longest path"""
     from oracle import dice
     from promp_amd import synthetic
     rng = np.random.RandomState(seed)
@@ -1401,8 +1400,15 @@ def check_dice_path_lengths(lib, seed, lengths_per_task, O=5, A=3, hidden=(32, 3
         all_slabs.append(step)
     for step in all_slabs:
         assert [list(np.diff(sl['path_row_offsets'])) for sl in step] == [list(lens) for lens in lengths_per_task]
-    c = dict(M=len(lengths_per_task), K=K, O=O, A=A, hidden=tuple(hidden), alpha=alpha)
-    err = check_dice_case(lib, c, theta.astype(np.float64), all_slabs, tol, worst=worst)
+    return dict(M=len(lengths_per_task), K=K, O=O, A=A, hidden=tuple(hidden), alpha=alpha), theta.astype(np.float64), all_slabs
+
+
+def check_dice_path_lengths(lib, seed, lengths_per_task, O=5, A=3, hidden=(32, 32), K=1, alpha=0.1, tol=1e-4, worst=None):
+    """DICE-MAML's inner step and meta-gradient on paths of the given lengths (k_dice_scan's 64-row chunks: lengths on both sides
+    of one and two chunks), against the float64 oracle (oracle/dice.py) alone.  The inputs follow oracle/gen_golden.py's
+    make_dice_inputs: seeded paths per step, N(0,1) adjusted rewards, padded to the longest path."""
+    c, t64, all_slabs = dice_path_lengths_case(seed, lengths_per_task, O, A, hidden, K, alpha)
+    err = check_dice_case(lib, c, t64, all_slabs, tol, worst=worst)
     print('sample_edges dice O=%d hidden=%s K=%d lengths=%s: meta-gradient %.2e of its max-norm against the oracle (tolerance %.0e)'
           % (O, 'x'.join(map(str, hidden)), K, lengths_per_task, err, tol))
     return err

@@ -17,8 +17,8 @@ unperturbed chain.  dice_frozen_objective evaluates F(theta, ref) = -(1/N) sum R
 steps by d/dtheta F, the outer value by F itself); at the unperturbed alpha it IS oracle.dice's loss and oracle.dice's chain,
 which check_references asserts before anything is differenced.
 
-Inputs: alpha seeded in [0.02, 0.2] and non-uniform, two entries exactly 0 (nothing may divide by alpha), eta = (5e-4, 1e-3)[:K],
-clip 0.3.  Tolerance: the project's own for a meta-gradient against the float64 oracle, rel_max < 1e-4; (a) against (b): 1e-7.
+Inputs: alpha seeded in [0.02, 0.2] and non-uniform, two entries exactly 0 (nothing may divide by alpha), eta = helpers.eta_for(K):
+5e-4, 1e-3, doubling on, clip 0.3.  Tolerance: the project's own for a meta-gradient against the float64 oracle, rel_max < 1e-4; (a) against (b): 1e-7.
 """
 import numpy as np
 import pytest
@@ -35,7 +35,7 @@ FD_STEP = 1e-5
 
 
 def eta_for(K):
-    return np.array([5e-4, 1e-3][:K], np.float32)
+    return helpers.eta_for(K)
 
 
 def fd_coords(seed, n, A):

@@ -31,6 +31,11 @@ def test_policy_algo_api_two_inner_steps():
     scen.run_algo_scenario(M=3, P=4, T=50, O=5, A=3, hidden=(32, 32), K=2, epochs=3)
 
 
+def test_policy_algo_api_four_inner_steps():
+    # ProMP(num_inner_grad_steps=4): five slabs through the session, the processor and _adapt (tests/count_axis_checks.py: the K axis)
+    scen.run_algo_scenario(M=2, P=2, T=20, O=4, A=2, hidden=(32, 32), K=4, epochs=2)
+
+
 def test_policy_algo_api_hidden_sizes_100():
     # the reference's other common policy size (hidden_sizes=(100, 100)): runs zero-padded on the (128, 128) kernels
     scen.run_algo_scenario(M=4, P=4, T=60, O=20, A=6, hidden=(100, 100), K=1, epochs=3)
