@@ -109,7 +109,8 @@ const char* promp_last_error(void);
  * later: promp_set_train_step_sizes with promp_get_step_sizes / promp_get_step_size_grad / promp_{set,get}_step_size_adam_state
  * and promp_reduced_count; promp_set_outer_optimizer / promp_get_outer_optimizer / promp_get_grad_norm;
  * promp_process_samples_dice / promp_download_dice / promp_use_dice_advantages (and promp_proc_opts.reserved read as pad_length);
- * promp_rollout_point_family, promp_collect_point_family -- were additions and did not move it. */
+ * promp_rollout_point_family, promp_collect_point_family; promp_point_norm_set / promp_point_norm_get /
+ * promp_collect_point_family_norm -- were additions and did not move it. */
 int promp_abi_version(void);
 /* Theta = O*H1+H1 + H1*H2+H2 + H2*A+A + A */
 int promp_param_count(const promp_dims* dims);
@@ -401,6 +402,40 @@ typedef struct {
 int promp_collect_point_family(promp_ctx* ctx, int step, int envs_per_task, const double* task_params, const double* start,
                                const float* noise, const promp_point_collect_opts* opts, int32_t* n_paths, int32_t* n_steps,
                                int32_t* task_path_offsets, int32_t* path_env, int32_t* path_start, int32_t* path_len);
+
+/* (b''') (b'') under the normalize wrapper's RUNNING observation / reward normalisation: normalize(env, normalize_obs=True,
+ *     normalize_reward=True) (envs/normalized_env.py:73-123; the executor and the sampler loop that drive it:
+ *     samplers/vectorized_env_executor.py:25-75, samplers/meta_sampler.py:87-130).  Every environment e = task * envs_per_task + b
+ *     owns one wrapper state of 2 state_dim + 2 float64: obs_mean [state_dim], obs_var [state_dim], rew_mean, rew_var (a fresh
+ *     wrapper: 0 / 1 / 0 / 1).  It lives in the context across calls -- the K + 1 sampling steps of an iteration and the iterations --
+ *     and no task change touches it.  One update with sample x and step size alpha, float64, every product rounded on its own:
+ *       mean <- (1 - alpha) mean + alpha x;   var <- (1 - alpha) var + alpha (x - mean)^2        (the NEW mean)
+ *     Per vectorised step s of environment e:
+ *       the call's first reset(): start[0][e] updates the obs moments                            normalized_env.py:91-96
+ *       the policy is handed float32((x - mean) / (sqrt(var) + 1e-8)) (normalize_obs 0: float32(x)); the bare environment steps
+ *         on its RAW state, `done` and every reward formula see raw values only                   normalized_env.py:109-118
+ *       normalize_obs: the raw next observation, the terminal one of an episode included, updates the obs moments    :119-120
+ *       normalize_reward: the raw reward r updates the reward moments; stored is float32(r / (sqrt(rew_var) + 1e-8))  :121-122
+ *       the episode ends: reset() at once, start[s + 1][e] updates the obs moments               vectorized_env_executor.py:45-52
+ *         -- at the stop step s* too, whose fresh observation nobody uses.
+ *     The state the call leaves is the state after step s*; the steps the device runs beyond s* leave no trace in it, and a
+ *     refused call leaves it bit for bit as it was.  start is [max_steps + 1][n_envs][state_dim].
+ *   promp_point_norm_set  allocates and fills the context's state: moments [n_envs][2 state_dim + 2], per environment obs_mean,
+ *     obs_var, rew_mean, rew_var.  promp_point_norm_get reads it back (refused when none was set, or for other sizes).
+ *   promp_collect_point_family_norm  promp_collect_point_family's arguments plus the options.  With both flags 0 it IS
+ *     promp_collect_point_family on the first max_steps rows of start, bit for bit, and the state is not read or written.
+ *     Refused by name: a flag set but no state set, or one set for another n_envs / state_dim; an alpha outside [0, 1] or not finite;
+ *     everything promp_collect_point_family refuses.  Synchronous. */
+typedef struct {
+    int32_t normalize_obs, normalize_reward;
+    double  obs_alpha, reward_alpha;
+} promp_point_norm_opts;
+int promp_point_norm_set(promp_ctx* ctx, int n_envs, int state_dim, const double* moments);
+int promp_point_norm_get(promp_ctx* ctx, int n_envs, int state_dim, double* moments);
+int promp_collect_point_family_norm(promp_ctx* ctx, int step, int envs_per_task, const double* task_params, const double* start,
+                                    const float* noise, const promp_point_collect_opts* opts, const promp_point_norm_opts* norm,
+                                    int32_t* n_paths, int32_t* n_steps, int32_t* task_path_offsets, int32_t* path_env,
+                                    int32_t* path_start, int32_t* path_len);
 
 /* Step slab back on the host (any pointer may be NULL): obs [rows][O], act [rows][A], rew [rows],
  * old_mean [rows][A], old_log_std [rows | n_tasks][A] as uploaded / produced by a device rollout. */

@@ -63,6 +63,10 @@ class PointCollectOpts(C.Structure):
                 ('total_samples', C.c_int64)]
 
 
+class PointNormOpts(C.Structure):
+    _fields_ = [('normalize_obs', C.c_int32), ('normalize_reward', C.c_int32), ('obs_alpha', C.c_double), ('reward_alpha', C.c_double)]
+
+
 POINT_KIND = dict(corner=0, walls=1, momentum=2, goal=3)                   # goal: collect_point_family only
 POINT_KIND_DIMS = dict(corner=(2, 2), walls=(6, 2), momentum=(2, 4), goal=(2, 2))       # kind -> (task_dim, state_dim)
 
@@ -124,6 +128,10 @@ SIGNATURES = {
     'promp_rollout_point_env': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _D, _D, _F, C.POINTER(PointEnvOpts)]),
     'promp_rollout_point_family': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _D, _D, _F, C.POINTER(PointFamilyOpts)]),
     'promp_collect_point_family': (C.c_int, [_P, C.c_int, C.c_int, _D, _D, _F, C.POINTER(PointCollectOpts), _I, _I, _I, _I, _I, _I]),
+    'promp_collect_point_family_norm': (C.c_int, [_P, C.c_int, C.c_int, _D, _D, _F, C.POINTER(PointCollectOpts), C.POINTER(PointNormOpts),
+                                                  _I, _I, _I, _I, _I, _I]),
+    'promp_point_norm_set': (C.c_int, [_P, C.c_int, C.c_int, _D]),
+    'promp_point_norm_get': (C.c_int, [_P, C.c_int, C.c_int, _D]),
     'promp_begin_rollout': (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     'promp_begin_collection': (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     'promp_end_collection': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _F]),
@@ -893,18 +901,22 @@ class Context:
 
     def collect_point_family(self, step, kind, task_params, start, noise=None, total_samples=None, max_path_length=None,
                              clip_infos=True, reward_type='dense', normalization_scale=0.0, max_step=0.1, sparse_radius=2.0, seed=0,
-                             done_radius=0.01, task_dim=None):
+                             done_radius=0.01, task_dim=None, norm=None):
         """Device collection with early termination (promp_collect_point_family), kind 'corner' | 'walls' | 'momentum' | 'goal' (or
         its number): task_params [M, task_dim], start [max_steps, M * B, state_dim] (float64; row 0 the initial states, row s + 1
         the states that environments whose episode ends at step s continue from), noise [max_steps, M * B, 2] or None (drawn on
         the device from `seed`) -> the step's slab holds the finished episodes in the reference's order; returns
-        dict(n_steps, task_path_offsets, path_row_offsets, path_env, path_start, path_len)."""
+        dict(n_steps, task_path_offsets, path_row_offsets, path_env, path_start, path_len).
+        norm: None, or dict(normalize_obs, normalize_reward, obs_alpha, reward_alpha) -- the normalize wrapper's running moments
+        (promp_collect_point_family_norm; set_point_norm first): start then has max_steps + 1 rows, the reset() behind every step."""
         self._pre_write(step)
         task_params = np.ascontiguousarray(task_params, dtype=np.float64)
         start = np.ascontiguousarray(start, dtype=np.float64)
         assert task_params.ndim == 2 and start.ndim == 3
         M = self.n_tasks
         max_steps, n_envs = start.shape[:2]
+        if norm is not None:
+            max_steps -= 1
         assert n_envs % M == 0 and task_params.shape[0] == M, (start.shape, task_params.shape)
         if noise is not None:
             noise = _f32(noise)
@@ -919,9 +931,16 @@ class Context:
         n_paths, n_steps = C.c_int32(0), C.c_int32(0)
         tpo = np.zeros(M + 1, np.int32)
         p_env, p_start, p_len = (np.zeros(cap, np.int32) for _ in range(3))
-        self._call('promp_collect_point_family', int(step), int(n_envs // M), _ptr(task_params, C.c_double), _ptr(start, C.c_double),
-                   _ptr(noise, C.c_float) if noise is not None else None, C.byref(opts), C.byref(n_paths), C.byref(n_steps),
-                   _ptr(tpo, C.c_int32), _ptr(p_env, C.c_int32), _ptr(p_start, C.c_int32), _ptr(p_len, C.c_int32))
+        outs = (C.byref(n_paths), C.byref(n_steps), _ptr(tpo, C.c_int32), _ptr(p_env, C.c_int32), _ptr(p_start, C.c_int32),
+                _ptr(p_len, C.c_int32))
+        ins = (int(step), int(n_envs // M), _ptr(task_params, C.c_double), _ptr(start, C.c_double),
+               _ptr(noise, C.c_float) if noise is not None else None, C.byref(opts))
+        if norm is None:
+            self._call('promp_collect_point_family', *(ins + outs))
+        else:
+            nopts = PointNormOpts(int(bool(norm.get('normalize_obs', False))), int(bool(norm.get('normalize_reward', False))),
+                                  float(norm.get('obs_alpha', 0.001)), float(norm.get('reward_alpha', 0.001)))
+            self._call('promp_collect_point_family_norm', *(ins + (C.byref(nopts),) + outs))
         n = int(n_paths.value)
         p_env, p_start, p_len = p_env[:n].copy(), p_start[:n].copy(), p_len[:n].copy()
         pro = np.concatenate([[0], np.cumsum(p_len)]).astype(np.int32)
@@ -929,6 +948,19 @@ class Context:
         self.step_tpo[step] = np.array(tpo, dtype=np.int64)
         return dict(n_steps=int(n_steps.value), task_path_offsets=tpo, path_row_offsets=pro, path_env=p_env, path_start=p_start,
                     path_len=p_len)
+
+    def set_point_norm(self, moments):
+        """the normalize wrapper's running moments of every environment (promp_point_norm_set): moments [n_envs, 2 * state_dim + 2]
+        float64, per environment obs_mean [state_dim], obs_var [state_dim], rew_mean, rew_var"""
+        moments = np.ascontiguousarray(moments, dtype=np.float64)
+        assert moments.ndim == 2 and moments.shape[1] in (6, 10), moments.shape
+        self._call('promp_point_norm_set', int(moments.shape[0]), int((moments.shape[1] - 2) // 2), _ptr(moments, C.c_double))
+
+    def get_point_norm(self, n_envs, state_dim):
+        """-> [n_envs, 2 * state_dim + 2] float64, the layout of set_point_norm (promp_point_norm_get)"""
+        out = np.empty((int(n_envs), 2 * int(state_dim) + 2), np.float64)
+        self._call('promp_point_norm_get', int(n_envs), int(state_dim), _ptr(out, C.c_double))
+        return out
 
     def begin_rollout(self, step, envs_per_task, path_length):
         """lay step `step` out as n_tasks * envs_per_task fixed-length paths for policy_step to fill"""

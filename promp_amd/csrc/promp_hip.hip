@@ -285,6 +285,9 @@ struct promp_ctx {
     DevBuf<double> gram_partials, red64;
     DevBuf<char> rollout_buf;            // goals, start states and noise of a device rollout (bytes)
     DevBuf<float> stage_rows;            // promp_begin_collection: staging rows [steps][tasks * B] of observations | actions | means
+    DevBuf<double> point_norm;           // promp_point_norm_set: the normalize wrapper's running moments [n_envs][2 state_dim + 2]
+    int point_norm_envs = 0, point_norm_dim = 0;   // what it was set for (0: not set)
+    DevBuf<double> point_norm_stage;     // promp_collect_point_family_norm: the moments behind every step [max_steps][2 state_dim + 2][n_envs]
     DevBuf<double> fit_scratch;          // k_fit_wide: [tasks][2][(D+1)^2] when the matrices do not fit in LDS
     size_t smem_fwd = 0, smem_hvp = 0;
     PlanSwitches sw;                     // the PROMP_* switches, as promp_ctx_create found them
@@ -2418,11 +2421,19 @@ int promp_end_collection(promp_ctx* c, int step, int n_paths, const int32_t* tas
 
 // Whole collection on the device: k_point_collect, k_collect_stop, k_collect_tables (promp_kernels_rollout.h); only the tables come
 // back.  Every refusal leaves the step without a layout of this call: the slab is touched by finish_collection alone.
-int promp_collect_point_family(promp_ctx* c, int step, int envs_per_task, const double* task_params, const double* start,
-                               const float* noise, const promp_point_collect_opts* o, int32_t* n_paths_out, int32_t* n_steps_out,
-                               int32_t* task_path_offsets, int32_t* path_env, int32_t* path_start, int32_t* path_len) {
+// nm: the normalize wrapper's options, or NULL / both flags 0: the plain collection.  With a flag set the start table has
+// max_steps + 1 rows and the context's running moments (promp_point_norm_set) advance to their state after the stop step.
+static int collect_point_family(promp_ctx* c, int step, int envs_per_task, const double* task_params, const double* start,
+                                const float* noise, const promp_point_collect_opts* o, const promp_point_norm_opts* nm,
+                                int32_t* n_paths_out, int32_t* n_steps_out,
+                                int32_t* task_path_offsets, int32_t* path_env, int32_t* path_start, int32_t* path_len) {
     if (!c || !task_params || !start || !o || !n_paths_out || !n_steps_out || !task_path_offsets || !path_env || !path_start || !path_len)
         return fail(-1, "NULL argument");
+    const bool norm = nm && (nm->normalize_obs || nm->normalize_reward);
+    if (nm) {
+        if (!(nm->obs_alpha >= 0.0 && nm->obs_alpha <= 1.0)) return fail(-1, "obs_alpha = %g outside [0, 1]", nm->obs_alpha);
+        if (!(nm->reward_alpha >= 0.0 && nm->reward_alpha <= 1.0)) return fail(-1, "reward_alpha = %g outside [0, 1]", nm->reward_alpha);
+    }
     StepScope sc(c, step);
     if (sc.rc) return sc.rc;
     const promp_point_family_opts& e = o->env;
@@ -2438,12 +2449,20 @@ int promp_collect_point_family(promp_ctx* c, int step, int envs_per_task, const 
     const int M = c->d.n_tasks, B = envs_per_task, O = state_dim, A = 2, S_max = o->max_steps, max_paths = c->d.max_paths;
     const long long n_envs = (long long)M * B, stage = n_envs * S_max;
     if (stage > 0x7FFFFFFFll / 4) return fail(-1, "max_steps * environments = %lld staging rows are too many", stage);
+    const int W = 2 * O + 2;                                       // moments per environment
+    if (norm) {
+        if (c->point_norm_envs == 0) return fail(-3, "a normalisation flag is set but promp_point_norm_set has not been called");
+        if (c->point_norm_envs != n_envs || c->point_norm_dim != O)
+            return fail(-1, "the normalisation state was set for %d environments of state_dim %d, the collection has %lld of %d",
+                        c->point_norm_envs, c->point_norm_dim, n_envs, O);
+    }
     if (sc.open(/*writes=*/true, /*needs_data=*/false)) return sc.rc;
     StepData& S = sc.S();
     if (c->stage_rows.reserve((size_t)stage * (O + 2 * A), 1)) return -2;
+    if (norm && c->point_norm_stage.reserve((size_t)stage * W, 1)) return -2;
     S.has_policy = false; S.processed = false; S.has_adv = false;
     // one block: doubles (task parameters, start table), the stop record, floats (noise, staged rewards), then the integer tables
-    const size_t n_task = (size_t)M * task_dim, n_start = (size_t)stage * O, n_noise = noise ? (size_t)stage * 2 : 0;
+    const size_t n_task = (size_t)M * task_dim, n_start = (size_t)(stage + (norm ? n_envs : 0)) * O, n_noise = noise ? (size_t)stage * 2 : 0;
     const size_t n_int = (size_t)stage + S_max + M + (M + 1) + 3 * (size_t)max_paths;
     if (c->rollout_buf.reserve(sizeof(double) * (n_task + n_start) + sizeof(long long) * 4 + sizeof(float) * (n_noise + (size_t)stage) +
                                sizeof(int32_t) * n_int, 2)) return -2;
@@ -2476,11 +2495,26 @@ int promp_collect_point_family(promp_ctx* c, int step, int envs_per_task, const 
     k.f.kind = e.kind; k.f.task_dim = task_dim; k.f.state_dim = state_dim;
     k.rew_stage = d_rew; k.end_len = d_end;
     k.max_steps = S_max; k.max_path_length = o->max_path_length; k.n_envs = (int)n_envs; k.done_radius = o->done_radius;
+    PointNormArgs pn = {};
+    if (norm) {
+        pn.normalize_obs = nm->normalize_obs != 0; pn.normalize_reward = nm->normalize_reward != 0;
+        pn.obs_alpha = nm->obs_alpha; pn.reward_alpha = nm->reward_alpha;
+        pn.moments = c->point_norm; pn.stage = c->point_norm_stage;
+    }
     if (c->family == PassFamily::Layered) {
         GenPointCollectArgs g;
         g.c = k; g.act_kind = gen_act_kinds(&c->d);
         copy_layers(g, c);
+        if (norm) {
+            GenPointNormCollectArgs gn;
+            gn.g = g; gn.n = pn;
+            PROMP_LAUNCH(k_gen_point_norm_collect, dim3(B, M), 256, gen_rollout_smem(state_dim), st, gn);
+        } else
         PROMP_LAUNCH(k_gen_point_collect, dim3(B, M), 256, gen_rollout_smem(state_dim), st, g);
+    } else if (norm) {
+        PointNormCollectArgs kn;
+        kn.c = k; kn.n = pn;
+        PROMP_LAUNCH(k_point_norm_collect, dim3(M), 64, 0, st, kn);
     } else
     PROMP_LAUNCH(k_point_collect, dim3(M), 64, 0, st, k);
     HIPCHECK(hipGetLastError());
@@ -2525,9 +2559,55 @@ int promp_collect_point_family(promp_ctx* c, int step, int envs_per_task, const 
     if (pro[n_paths] != stop[1]) return fail(-2, "the path tables hold %d rows, the stop record %lld", pro[n_paths], stop[1]);
     S.rollout_B = B; S.rollout_T = S_max; S.rollout_ragged = true;       // (what finish_collection reads, and clears)
     if (finish_collection(sc, n_paths, tpo.data(), pro.data(), nullptr, nullptr, d_env, d_pstart, nullptr, d_rew)) return -2;
+    if (norm) {                        // accepted and installed: the wrapper state after the stop step becomes the context's
+        PointNormCommitArgs pc;
+        pc.stage = c->point_norm_stage; pc.stop = d_stop; pc.moments = c->point_norm; pc.W = W; pc.n_envs = (int)n_envs; pc.max_steps = S_max;
+        PROMP_LAUNCH(k_point_norm_commit, dim3((unsigned)((n_envs + 255) / 256)), 256, 0, st, pc);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipStreamSynchronize(st));
+    }
     for (int i = 0; i <= M; ++i) task_path_offsets[i] = tpo[i];
     *n_paths_out = n_paths;
     *n_steps_out = (int32_t)stop[0] + 1;
+    return 0;
+}
+
+int promp_collect_point_family(promp_ctx* c, int step, int envs_per_task, const double* task_params, const double* start,
+                               const float* noise, const promp_point_collect_opts* o, int32_t* n_paths_out, int32_t* n_steps_out,
+                               int32_t* task_path_offsets, int32_t* path_env, int32_t* path_start, int32_t* path_len) {
+    return collect_point_family(c, step, envs_per_task, task_params, start, noise, o, nullptr, n_paths_out, n_steps_out,
+                                task_path_offsets, path_env, path_start, path_len);
+}
+
+int promp_collect_point_family_norm(promp_ctx* c, int step, int envs_per_task, const double* task_params, const double* start,
+                                    const float* noise, const promp_point_collect_opts* o, const promp_point_norm_opts* norm,
+                                    int32_t* n_paths_out, int32_t* n_steps_out, int32_t* task_path_offsets, int32_t* path_env,
+                                    int32_t* path_start, int32_t* path_len) {
+    if (!norm) return fail(-1, "NULL argument");
+    return collect_point_family(c, step, envs_per_task, task_params, start, noise, o, norm, n_paths_out, n_steps_out,
+                                task_path_offsets, path_env, path_start, path_len);
+}
+
+int promp_point_norm_set(promp_ctx* c, int n_envs, int state_dim, const double* moments) {
+    if (!c || !moments) return fail(-1, "NULL argument");
+    if (n_envs < 1 || (state_dim != 2 && state_dim != 4)) return fail(-1, "n_envs = %d must be positive and state_dim = %d 2 or 4", n_envs, state_dim);
+    const size_t n = (size_t)n_envs * (2 * state_dim + 2);
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    if (c->point_norm.reserve(n, 1)) return -2;
+    HIPCHECK(hipMemcpyAsync(c->point_norm.p, moments, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    c->point_norm_envs = n_envs; c->point_norm_dim = state_dim;
+    return 0;
+}
+
+int promp_point_norm_get(promp_ctx* c, int n_envs, int state_dim, double* moments) {
+    if (!c || !moments) return fail(-1, "NULL argument");
+    if (c->point_norm_envs == 0) return fail(-3, "promp_point_norm_set has not been called");
+    if (c->point_norm_envs != n_envs || c->point_norm_dim != state_dim)
+        return fail(-1, "the normalisation state was set for %d environments of state_dim %d, asked for %d of %d",
+                    c->point_norm_envs, c->point_norm_dim, n_envs, state_dim);
+    HIPCHECK(hipMemcpyAsync(moments, c->point_norm.p, sizeof(double) * (size_t)n_envs * (2 * state_dim + 2), hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(hipStreamSynchronize(c->stream));
     return 0;
 }
 

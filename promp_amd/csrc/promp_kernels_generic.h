@@ -790,3 +790,58 @@ __global__ void __launch_bounds__(256) k_gen_point_collect(GenPointCollectArgs g
         __syncthreads();       // the next step's observation and hidden vectors overwrite what thread 0 has just read
     }
 }
+
+struct GenPointNormCollectArgs {
+    GenPointCollectArgs g;     // c.f.p.start: [max_steps + 1][n_envs][state_dim]
+    PointNormArgs n;
+};
+// grid = (B, tasks), block = 256: k_gen_point_collect under the normalize wrapper's running moments (k_point_norm_collect), the
+// wrapper state in thread 0's registers beside the environment's state.  smem: gen_rollout_smem(state_dim)
+__global__ void __launch_bounds__(256) k_gen_point_norm_collect(GenPointNormCollectArgs gn) {
+    PROMP_SMEM_DECL;
+    const GenPointCollectArgs& g = gn.g;
+    const PointNormArgs& n = gn.n;
+    const PointCollectArgs& c = g.c;
+    const PointRolloutArgs& a = c.f.p;
+    const int O = c.f.state_dim;
+    float* xs = (float*)PROMP_SMEM_PTR;
+    float* hs = xs + O;
+    const int task = blockIdx.y, b = blockIdx.x, tid = threadIdx.x;
+    const float* th = a.theta_tasks + (long long)task * a.NP;
+    const int oS = a.NP - 2;
+    const float ls0 = th[oS], ls1 = th[oS + 1];
+    if (b == 0 && tid == 0) {
+        a.old_ls[task * 2 + 0] = a.clip_infos ? fmaxf(ls0, a.min_log_std) : ls0;
+        a.old_ls[task * 2 + 1] = a.clip_infos ? fmaxf(ls1, a.min_log_std) : ls1;
+    }
+    const float sd0 = expf(ls0), sd1 = expf(ls1);
+    const double* tp = a.goals + (long long)task * c.f.task_dim;
+    const long long env = (long long)task * a.B + b;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};                             // (advanced by thread 0 only)
+    for (int k = 0; k < O; ++k) s[k] = a.start[env * O + k];
+    PointNormState w;
+    if (tid == 0) point_norm_enter(n, w, s, O, env);
+    int len = 0;
+    for (int st = 0; st < c.max_steps; ++st) {
+        const long long row = (long long)st * c.n_envs + env;
+        if (tid == 0)
+            for (int k = 0; k < O; ++k) xs[k] = point_norm_obs(n, w, s, k);
+        __syncthreads();
+        const float* m = gen_mlp_block(th, g.lin, g.n_lin, g.act_kind, xs, hs, tid, c.f.kind != POINT_KIND_CORNER);
+        if (tid == 0) {
+            float n0, n1;
+            if (a.noise != nullptr) {
+                n0 = a.noise[row * 2];
+                n1 = a.noise[row * 2 + 1];
+            } else {
+                action_noise(a.seed, (unsigned long long)row, 0u, a.stream, n0, n1);
+            }
+            const float a0 = fmaf(sd0, n0, m[0]), a1 = fmaf(sd1, n1, m[1]);
+            for (int k = 0; k < O; ++k) a.obs[row * O + k] = xs[k];
+            a.mean[row * 2] = m[0];  a.mean[row * 2 + 1] = m[1];
+            a.act[row * 2] = a0;  a.act[row * 2 + 1] = a1;
+            point_norm_collect_tail(c, n, w, s, tp, a0, a1, row, env, st, len);
+        }
+        __syncthreads();       // the next step's observation and hidden vectors overwrite what thread 0 has just read
+    }
+}

@@ -444,6 +444,8 @@ __global__ void __launch_bounds__(64) k_point_family_rollout(PointFamilyArgs f) 
 //                                           reference's order: step-major, environment-minor; k_collect_offsets between the two
 //                                           turns the tasks' counts into task_path_offsets
 //   k_gather_paths                          staging rows -> slab rows, rewards included
+// k_point_norm_collect / k_gen_point_norm_collect are the first phase under the normalize wrapper's running observation / reward
+// normalisation, k_point_norm_commit its last (below, at PointNormArgs).
 // The fourth kind of the family ends episodes:
 //   POINT_KIND_GOAL     (2, 2)  envs/point_envs/point_env_2d.py (= corner_goals_point_env_2d.py) and point_env_2d_v2.py:
 //                               s' = s + clip(e, -max_step, max_step), reward -|s' - goal|, done = |s'_0| < done_radius and
@@ -529,6 +531,161 @@ __global__ void __launch_bounds__(64) k_point_collect(PointCollectArgs c) {
             }
         }
     }
+}
+
+// ---- running observation / reward normalisation (envs/normalized_env.py:73-123 of the reference: normalize(env, normalize_obs=True,
+// normalize_reward=True)).  Every environment owns one wrapper state -- obs_mean [O], obs_var [O], rew_mean, rew_var, float64, 2 O + 2
+// values -- that lives in the context across calls (promp_point_norm_set / _get).  Inside a collection it sits in registers of the
+// lane that owns the environment and is updated once per sample, in the wrapper's order:
+//   reset()            the raw start state updates the obs moments; the policy sees float32((x - mean) / (sqrt(var) + 1e-8))
+//   step()             the bare environment steps on its RAW state; the raw next observation (the terminal one included) updates the obs
+//                      moments, the raw reward the reward moments; the stored reward is float32(r / (sqrt(rew_var) + 1e-8))
+//   episode end        reset() at once: start[s + 1][env] updates the obs moments (vectorized_env_executor.py:45-52), also at the
+//                      step collection stops at -- the start table has max_steps + 1 rows
+// The state a call leaves is the state after the stop step s*, which only k_collect_stop knows: every step stages the moments behind
+// its events into norm.stage [max_steps][2 O + 2][n_envs] (environment-minor: a wave's stores coalesce), and k_point_norm_commit
+// copies row s* into the persistent buffer once the host has accepted the collection.  Steps beyond s* leave no trace.
+struct PointNormArgs {
+    int normalize_obs, normalize_reward;
+    double obs_alpha, reward_alpha;
+    const double* moments;     // [n_envs][2 O + 2]: obs_mean, obs_var, rew_mean, rew_var (read at entry)
+    double* stage;             // [max_steps][2 O + 2][n_envs]
+};
+struct PointNormState {
+    double om[4], ov[4], rm, rv;
+};
+
+// one sample: mean <- (1 - alpha) mean + alpha x; var <- (1 - alpha) var + alpha (x - NEW mean)^2, every product rounded on its own
+// (normalized_env.py:73-81 in NumPy's float64)
+PROMP_HD void point_norm_update(double& mean, double& var, double x, double alpha) {
+#pragma clang fp contract(off)
+    const double keep = 1.0 - alpha;
+    const double km = keep * mean, ax = alpha * x;
+    const double m = km + ax;
+    const double d = x - m;
+    const double q = d * d;
+    const double kv = keep * var, aq = alpha * q;
+    mean = m;
+    var = kv + aq;
+}
+PROMP_DEV void point_norm_see(const PointNormArgs& n, PointNormState& w, const double* s, int O) {
+    for (int k = 0; k < O; ++k) point_norm_update(w.om[k], w.ov[k], s[k], n.obs_alpha);
+}
+// what the policy is handed for the raw state s
+PROMP_DEV float point_norm_obs(const PointNormArgs& n, const PointNormState& w, const double* s, int k) {
+    if (n.normalize_obs) return (float)((s[k] - w.om[k]) / (sqrt(w.ov[k]) + 1e-8));
+    return (float)s[k];
+}
+// entry: the persistent state, then the first reset()
+PROMP_DEV void point_norm_enter(const PointNormArgs& n, PointNormState& w, const double* s, int O, long long env) {
+    const double* m = n.moments + env * (2 * O + 2);
+    for (int k = 0; k < O; ++k) {
+        w.om[k] = m[k];
+        w.ov[k] = m[O + k];
+    }
+    w.rm = m[2 * O];
+    w.rv = m[2 * O + 1];
+    if (n.normalize_obs) point_norm_see(n, w, s, O);
+}
+
+// The tail of vectorised step st of environment env under the wrapper, shared by k_point_norm_collect and k_gen_point_norm_collect:
+// k_point_collect's tail (the environment steps on (a0, a1), the step's reward and end_len are filed under `row`, the next
+// episode's reset() is taken from the start table) with the wrapper's events in it, and the moments staged behind them.
+PROMP_DEV void point_norm_collect_tail(const PointCollectArgs& c, const PointNormArgs& n, PointNormState& w, double* s, const double* tp,
+                                       float a0, float a1, long long row, long long env, int st, int& len) {
+    const PointRolloutArgs& a = c.f.p;
+    const int O = c.f.state_dim;
+    bool done;
+    double r = point_collect_step(c, s, tp, a0, a1, done);
+    ++len;
+    const bool end = done || len >= c.max_path_length;
+    if (n.normalize_obs) point_norm_see(n, w, s, O);              // the raw next observation, terminal or not
+    if (n.normalize_reward) {
+        point_norm_update(w.rm, w.rv, r, n.reward_alpha);
+        r = r / (sqrt(w.rv) + 1e-8);
+    }
+    c.rew_stage[row] = (float)r;
+    c.end_len[row] = end ? len : 0;
+    len = end ? 0 : len;
+    const long long nxt = row + c.n_envs;                         // (the table has a row behind the last step)
+    for (int k = 0; k < O; ++k) {
+        const double fresh = a.start[nxt * O + k];
+        s[k] = end ? fresh : s[k];
+    }
+    if (n.normalize_obs && end) point_norm_see(n, w, s, O);       // reset() at once, at the stop step too
+    const int W = 2 * O + 2;
+    double* out = n.stage + (long long)st * W * c.n_envs + env;
+    for (int k = 0; k < O; ++k) {
+        out[(long long)k * c.n_envs] = w.om[k];
+        out[(long long)(O + k) * c.n_envs] = w.ov[k];
+    }
+    out[(long long)(2 * O) * c.n_envs] = w.rm;
+    out[(long long)(2 * O + 1) * c.n_envs] = w.rv;
+}
+
+struct PointNormCollectArgs {
+    PointCollectArgs c;        // p.start: [max_steps + 1][n_envs][state_dim]
+    PointNormArgs n;
+};
+// grid = tasks, block = 64: k_point_collect under the normalize wrapper's running moments (a sibling: k_point_collect itself is
+// untouched, so the plain collection is the same machine code as before)
+__global__ void __launch_bounds__(64) k_point_norm_collect(PointNormCollectArgs g) {
+    const PointCollectArgs& c = g.c;
+    const PointNormArgs& n = g.n;
+    const PointFamilyArgs& f = c.f;
+    const PointRolloutArgs& a = f.p;
+    const int task = blockIdx.x, O = f.state_dim;
+    const float* th = a.theta_tasks + (long long)task * a.NP;
+    const int oS = a.NP - 2;
+    const float ls0 = th[oS], ls1 = th[oS + 1];
+    if (threadIdx.x == 0) {
+        a.old_ls[task * 2 + 0] = a.clip_infos ? fmaxf(ls0, a.min_log_std) : ls0;
+        a.old_ls[task * 2 + 1] = a.clip_infos ? fmaxf(ls1, a.min_log_std) : ls1;
+    }
+    const float sd0 = expf(ls0), sd1 = expf(ls1);
+    const double* tp = a.goals + (long long)task * f.task_dim;
+    for (int b = threadIdx.x; b < a.B; b += 64) {
+        const long long env = (long long)task * a.B + b;
+        double s[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int k = 0; k < O; ++k) s[k] = a.start[env * O + k];
+        PointNormState w;
+        point_norm_enter(n, w, s, O, env);
+        int len = 0;
+        for (int st = 0; st < c.max_steps; ++st) {
+            const long long row = (long long)st * c.n_envs + env;
+            float o[4], m[2], n0, n1;
+            for (int k = 0; k < O; ++k) o[k] = point_norm_obs(n, w, s, k);
+            if (f.kind == POINT_KIND_CORNER) mlp_mean(th, o, O, 2, a.H1, a.H2, m);
+            else mlp_mean_t<true>(th, o, O, 2, a.H1, a.H2, m);
+            if (a.noise != nullptr) {
+                n0 = a.noise[row * 2];
+                n1 = a.noise[row * 2 + 1];
+            } else {
+                action_noise(a.seed, (unsigned long long)row, 0u, a.stream, n0, n1);
+            }
+            const float a0 = fmaf(sd0, n0, m[0]), a1 = fmaf(sd1, n1, m[1]);
+            for (int k = 0; k < O; ++k) a.obs[row * O + k] = o[k];
+            a.mean[row * 2] = m[0];  a.mean[row * 2 + 1] = m[1];
+            a.act[row * 2] = a0;  a.act[row * 2 + 1] = a1;
+            point_norm_collect_tail(c, n, w, s, tp, a0, a1, row, env, st, len);
+        }
+    }
+}
+
+// the wrapper state a collection leaves: row s* of the staged moments -> the persistent buffer.  Launched only after the host has
+// accepted the collection.  grid = ceil(n_envs / 256), block = 256: one thread per environment
+struct PointNormCommitArgs {
+    const double* stage;       // [max_steps][W][n_envs]
+    const long long* stop;     // k_collect_stop's out
+    double* moments;           // [n_envs][W]
+    int W, n_envs, max_steps;
+};
+__global__ void __launch_bounds__(256) k_point_norm_commit(PointNormCommitArgs a) {
+    const int env = blockIdx.x * 256 + threadIdx.x;
+    const long long s = a.stop[0];
+    if (env >= a.n_envs || s < 0 || s >= a.max_steps) return;
+    const double* in = a.stage + s * a.W * a.n_envs + env;
+    for (int j = 0; j < a.W; ++j) a.moments[(long long)env * a.W + j] = in[(long long)j * a.n_envs];
 }
 
 // out[0] = s*, the first step at which the running total of finished-episode steps reaches total_samples (-1: max_steps did not

@@ -80,7 +80,6 @@ def _point_env_options(env):
     from ..envs.normalized_env import NormalizedEnv
     scale = 0.0                              # bare environment
     if isinstance(env, NormalizedEnv):
-        assert not (env._normalize_obs or env._normalize_reward), 'running observation / reward normalisation is host-side state'
         bare = env.wrapped_env
         scale = float(env._normalization_scale)
         assert np.allclose(bare.action_space.low, -bare.action_space.high)
@@ -96,6 +95,15 @@ def _point_env_options(env):
                       sparse_radius=float(bare.sparse_reward_radius))
 
 
+def _point_env_norm(env):
+    """the options of the wrapper's running observation / reward normalisation (promp_point_norm_opts), or None when both are off"""
+    from ..envs.normalized_env import NormalizedEnv
+    if not isinstance(env, NormalizedEnv) or not (env._normalize_obs or env._normalize_reward):
+        return None
+    return dict(normalize_obs=bool(env._normalize_obs), normalize_reward=bool(env._normalize_reward),
+                obs_alpha=float(env._obs.alpha), reward_alpha=float(env._rew.alpha))
+
+
 class DevicePointEnvSampler(object):
     """device_noise=False: start states and exploration noise come from NumPy's RNG (reproducible from np.random.seed, and
     comparable step by step with the NumPy environment); True: the noise is drawn on the device (Philox4x32-10 keyed by a
@@ -106,6 +114,7 @@ class DevicePointEnvSampler(object):
         assert hasattr(env, 'sample_tasks') and hasattr(env, 'set_task')
         self.env, self.policy = env, policy
         self._bare, self._env_opts = _point_env_options(env)
+        self._norm = _point_env_norm(env)          # running moments: device-resident state of this sampler
         self.kind = _point_env_kind(self._bare)
         self.obs_dim = int(np.prod(self._bare.observation_space.shape))        # 2; momentum observes (position, velocity): 4
         assert policy.obs_dim == self.obs_dim and policy.action_dim == 2, \
@@ -120,6 +129,43 @@ class DevicePointEnvSampler(object):
         self.total_samples = meta_batch_size * rollouts_per_meta_task * max_path_length
         self.total_timesteps_sampled = 0
         self.goals = None
+        # normalize(env, normalize_obs / normalize_reward): one wrapper state per environment, as the executor deep-copies the
+        # environment (vectorized_env_executor.py:25-30 of the reference) -- the wrapper's current moments, replicated.  _norm_host
+        # is uploaded in front of every collection and follows the device behind it, so the state does not depend on who else
+        # uses the context or on the context being re-created (session.ensure growing it, set_num_inner_steps)
+        self._norm_host = None
+        if self._norm is not None:
+            n_envs, O = meta_batch_size * self.envs_per_task, self.obs_dim
+            one = np.concatenate([np.broadcast_to(np.asarray(env._obs.mean, np.float64), (O,)),
+                                  np.broadcast_to(np.asarray(env._obs.var, np.float64), (O,)),
+                                  [float(env._rew.mean), float(env._rew.var)]])
+            self._norm_host = np.tile(one, (n_envs, 1))
+
+    def get_normalization_state(self):
+        """the running moments of every environment e = task * envs_per_task + b: dict(obs_mean [n_envs, O], obs_var [n_envs, O],
+        reward_mean [n_envs], reward_var [n_envs]), float64; None without normalize_obs / normalize_reward"""
+        if self._norm is None:
+            return None
+        m, O = self._norm_host, self.obs_dim
+        return dict(obs_mean=m[:, :O].copy(), obs_var=m[:, O:2 * O].copy(), reward_mean=m[:, 2 * O].copy(), reward_var=m[:, 2 * O + 1].copy())
+
+    def set_normalization_state(self, state):
+        """what get_normalization_state returned, e.g. of an earlier run; takes effect with the next obtain_samples"""
+        assert self._norm is not None, 'the environment has neither normalize_obs nor normalize_reward'
+        n_envs, O = self._norm_host.shape[0], self.obs_dim
+        m = np.concatenate([np.asarray(state['obs_mean'], np.float64).reshape(n_envs, O),
+                            np.asarray(state['obs_var'], np.float64).reshape(n_envs, O),
+                            np.asarray(state['reward_mean'], np.float64).reshape(n_envs, 1),
+                            np.asarray(state['reward_var'], np.float64).reshape(n_envs, 1)], axis=1)
+        self._norm_host = m
+
+    def _push_norm(self, ctx):
+        # before every collection (38 KB at config 1): whoever else used the context -- a re-created one, another sampler of the
+        # same session -- this sampler continues from its own state
+        ctx.set_point_norm(self._norm_host)
+
+    def _pull_norm(self, ctx):
+        self._norm_host = ctx.get_point_norm(self._norm_host.shape[0], self.obs_dim)
 
     def update_tasks(self):
         tasks = self.env.sample_tasks(self.meta_batch_size)
@@ -134,6 +180,8 @@ class DevicePointEnvSampler(object):
         assert self.goals is not None, 'call update_tasks() first'
         if self.kind in TERMINATING:
             return self._obtain_terminating(log, log_prefix)
+        if self._norm is not None:
+            return self._obtain_fixed_normalised(log, log_prefix)
         M, B, T = self.meta_batch_size, self.envs_per_task, self.max_path_length
         sess = self.policy.session
         ctx = sess.ensure(M * B * T, M * B)
@@ -154,6 +202,11 @@ class DevicePointEnvSampler(object):
         else:
             noise = np.random.normal(size=(M, B, T, 2)).astype(np.float32)
             rollout(slot, self.goals, start, noise, clip_infos=self.policy._pre_update_mode, **self._env_opts)
+        return self._rectangular_paths(sess, ctx, slot, log, log_prefix)
+
+    def _rectangular_paths(self, sess, ctx, slot, log, log_prefix):
+        """the fixed-horizon slab of step `slot` as MetaSampler's path dicts: path p of task i is rows [(i B + p) T, (i B + p + 1) T)"""
+        M, B, T = self.meta_batch_size, self.envs_per_task, self.max_path_length
         sess._upload_counter += 1
         sess.upload_serial[slot] = sess._upload_counter
         slab = ctx.download_step(slot)
@@ -176,6 +229,37 @@ class DevicePointEnvSampler(object):
             logger.logkv(log_prefix + 'EnvExecTime', 0.0)
         return paths
 
+    def _reset_states(self, shape):
+        """reset() of the three fixed-horizon classes: shape [..., 2] -> [..., obs_dim]"""
+        start = np.random.uniform(-0.2, 0.2, size=shape)
+        if self.kind == 'momentum':                                  # MetaPointEnvMomentum.reset: and a velocity
+            start = np.concatenate((start, np.random.uniform(-0.1, 0.1, size=shape)), axis=-1)
+        return start
+
+    def _obtain_fixed_normalised(self, log, log_prefix):
+        """corner / walls / momentum under running normalisation: promp_collect_point_family_norm with max_steps = T.  Every episode
+        ends at step T - 1, the stop step, so the finished episodes are listed in environment order and the slab is the
+        rectangular one of obtain_samples; the start table's last row is the reset() the executor performs behind the last step."""
+        M, B, T = self.meta_batch_size, self.envs_per_task, self.max_path_length
+        n_envs = M * B
+        sess = self.policy.session
+        ctx = sess.ensure(M * B * T, M * B)
+        if sess.task_thetas is not None:           # parameters set while no context existed yet
+            ctx.set_task_thetas(sess.task_thetas)
+            sess.task_thetas = None
+        self._push_norm(ctx)
+        start = self._reset_states((T + 1, n_envs, 2))
+        slot = sess.next_slot()
+        kw = dict(total_samples=n_envs * T, max_path_length=T, clip_infos=self.policy._pre_update_mode, norm=self._norm, **self._env_opts)
+        if self.device_noise:
+            tables = ctx.collect_point_family(slot, self.kind, self.goals, start, None, seed=int(np.random.randint(0, 2 ** 31 - 1)), **kw)
+        else:
+            noise = np.random.normal(size=(T, n_envs, 2)).astype(np.float32)
+            tables = ctx.collect_point_family(slot, self.kind, self.goals, start, noise, **kw)
+        assert tables['n_steps'] == T and np.array_equal(tables['path_env'], np.arange(n_envs))
+        self._pull_norm(ctx)
+        return self._rectangular_paths(sess, ctx, slot, log, log_prefix)
+
     def _obtain_terminating(self, log, log_prefix):
         """MetaPointEnv / MetaPointEnvV2: one promp_collect_point_family instead of DeviceSlabSampler's call per environment step.
         The start table holds a reset() for every (vectorised step, environment): row 0 the initial states, row s + 1 what an
@@ -190,12 +274,16 @@ class DevicePointEnvSampler(object):
         if sess.task_thetas is not None:           # parameters set while no context existed yet
             ctx.set_task_thetas(sess.task_thetas)
             sess.task_thetas = None
+        n_start = max_steps if self._norm is None else max_steps + 1       # normalised: and the reset() behind the last step
         if self.kind == 'origin':                  # MetaPointEnv.reset
-            start = np.random.uniform(-2, 2, size=(max_steps, n_envs, 2))
+            start = np.random.uniform(-2, 2, size=(n_start, n_envs, 2))
         else:                                      # MetaPointEnvV2.reset
-            start = np.zeros((max_steps, n_envs, 2))
+            start = np.zeros((n_start, n_envs, 2))
         slot = sess.next_slot()
         kw = dict(total_samples=self.total_samples, max_path_length=T, clip_infos=self.policy._pre_update_mode, **self._env_opts)
+        if self._norm is not None:
+            self._push_norm(ctx)
+            kw['norm'] = self._norm
         try:
             if self.device_noise:
                 tables = ctx.collect_point_family(slot, 'goal', self.goals, start, None, seed=int(np.random.randint(0, 2 ** 31 - 1)), **kw)
@@ -206,6 +294,8 @@ class DevicePointEnvSampler(object):
             if 'no finished episode' not in str(e):
                 raise
             raise RuntimeError('DevicePointEnvSampler: %s (rollouts_per_meta_task = %d)' % (e, self.batch_size))
+        if self._norm is not None:
+            self._pull_norm(ctx)
         sess._upload_counter += 1
         sess.upload_serial[slot] = sess._upload_counter
         slab = ctx.download_step(slot)

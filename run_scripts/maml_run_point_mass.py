@@ -45,7 +45,9 @@ DEFAULT = {
 def main(config):
     set_seed(config['seed'])
     baseline = {'LinearFeatureBaseline': LinearFeatureBaseline}[config['baseline']]()
-    env = normalize(make_point_env(config['env'], config.get('reward_type', 'dense')))
+    env = normalize(make_point_env(config['env'], config.get('reward_type', 'dense')),
+                    normalize_obs=bool(config.get('normalize_obs', False)), normalize_reward=bool(config.get('normalize_reward', False)),
+                    obs_alpha=config.get('obs_alpha', 0.001), reward_alpha=config.get('reward_alpha', 0.001))
     policy = MetaGaussianMLPPolicy(name='meta-policy', obs_dim=int(np.prod(env.observation_space.shape)),
                                    action_dim=int(np.prod(env.action_space.shape)), meta_batch_size=config['meta_batch_size'],
                                    hidden_sizes=config['hidden_sizes'], learn_std=config.get('learn_std', True))
@@ -77,6 +79,11 @@ if __name__ == '__main__':
     ap.add_argument('--hvp', type=str, default=None, choices=['finite_difference', 'exact'])
     ap.add_argument('--subsample_factor', type=float, default=None,
                     help='share of each task\'s paths the conjugate-gradient products see, in (0, 1]')
+    ap.add_argument('--normalize_obs', action='store_true',
+                    help='the normalize wrapper\'s running observation normalisation (with device_rollouts: device-resident moments)')
+    ap.add_argument('--normalize_reward', action='store_true', help='the normalize wrapper\'s running reward normalisation')
+    ap.add_argument('--obs_alpha', type=float, default=None, help='step size of the running observation moments (default 0.001)')
+    ap.add_argument('--reward_alpha', type=float, default=None, help='step size of the running reward moments (default 0.001)')
     ap.add_argument('--quiet', action='store_true')
     args = ap.parse_args()
     cfg = dict(DEFAULT)
@@ -94,6 +101,12 @@ if __name__ == '__main__':
         cfg['hvp_approach'] = args.hvp
     if args.subsample_factor is not None:
         cfg['subsample_factor'] = args.subsample_factor
+    for key in ('normalize_obs', 'normalize_reward'):
+        if getattr(args, key):
+            cfg[key] = True
+    for key in ('obs_alpha', 'reward_alpha'):
+        if getattr(args, key) is not None:
+            cfg[key] = getattr(args, key)
     logger.configure(dir=args.dump_path or None, snapshot_mode='last_gap', snapshot_gap=50, quiet=args.quiet)
     if args.dump_path:
         json.dump(cfg, open(os.path.join(args.dump_path, 'params.json'), 'w'), cls=ClassEncoder)

@@ -42,7 +42,9 @@ def main(config):
     baseline = {'LinearFeatureBaseline': LinearFeatureBaseline}[config['baseline']]()
     env = make_point_env(config.get('env', 'corner'), config.get('reward_type', 'sparse'))
     if config.get('normalize_env', True):
-        env = normalize(env)                      # as the reference script (pro-mp_run_point_mass.py:27-28)
+        # as the reference script (pro-mp_run_point_mass.py:27-28); the running normalisation is off unless asked for
+        env = normalize(env, normalize_obs=bool(config.get('normalize_obs', False)), normalize_reward=bool(config.get('normalize_reward', False)),
+                        obs_alpha=config.get('obs_alpha', 0.001), reward_alpha=config.get('reward_alpha', 0.001))
     policy = MetaGaussianMLPPolicy(name='meta-policy', obs_dim=int(np.prod(env.observation_space.shape)), action_dim=2,
                                    meta_batch_size=config['meta_batch_size'],
                                    hidden_sizes=config['hidden_sizes'])
@@ -83,6 +85,11 @@ if __name__ == '__main__':
                     help='update rule of the outer step (default adam)')
     ap.add_argument('--adam_epsilon', type=float, default=None, help='epsilon of the outer Adam step (default 1e-8; PPO runs often use 1e-5)')
     ap.add_argument('--max_grad_norm', type=float, default=None, help='clip the meta-gradient by its global norm (default: no clipping)')
+    ap.add_argument('--normalize_obs', action='store_true',
+                    help='the normalize wrapper\'s running observation normalisation (with device_rollouts: device-resident moments)')
+    ap.add_argument('--normalize_reward', action='store_true', help='the normalize wrapper\'s running reward normalisation')
+    ap.add_argument('--obs_alpha', type=float, default=None, help='step size of the running observation moments (default 0.001)')
+    ap.add_argument('--reward_alpha', type=float, default=None, help='step size of the running reward moments (default 0.001)')
     ap.add_argument('--quiet', action='store_true')
     args = ap.parse_args()
     cfg = dict(DEFAULT)
@@ -102,6 +109,12 @@ if __name__ == '__main__':
         cfg['outer_optimizer_args'] = dict(cfg.get('outer_optimizer_args') or {}, epsilon=args.adam_epsilon)
     if args.max_grad_norm is not None:
         cfg['max_grad_norm'] = args.max_grad_norm
+    for key in ('normalize_obs', 'normalize_reward'):
+        if getattr(args, key):
+            cfg[key] = True
+    for key in ('obs_alpha', 'reward_alpha'):
+        if getattr(args, key) is not None:
+            cfg[key] = getattr(args, key)
     logger.configure(dir=args.dump_path or None, snapshot_mode='last_gap', snapshot_gap=50, quiet=args.quiet)
     if args.dump_path:
         json.dump({k: (list(v) if isinstance(v, tuple) else v) for k, v in cfg.items()}, open(os.path.join(args.dump_path, 'params.json'), 'w'))

@@ -16,7 +16,13 @@
                                                          max_steps = 2 T - 1 = 199 vectorised steps, total_samples = M B T, the
                                                          start table [199][800][2] float64 uploaded with every call; also per
                                                          vectorised step, beside which `--wide` puts the fixed-horizon launch's
-                                                         time per step (its T = 100 steps)."""
+                                                         time per step (its T = 100 steps).
+    python tools/rollout_timing.py --launch --collect --normalize [--kinds corner goal] ...
+                                                         the same call through promp_collect_point_family_norm with the normalize
+                                                         wrapper's running moments off (the plain kernels), on the observations, and
+                                                         on observations and rewards: what staging the moments behind every step
+                                                         ([199][2 O + 2][800] float64) and the commit launch cost.  A --lib from before
+                                                         the entry point runs the plain call only."""
 import argparse
 import sys
 import time
@@ -55,7 +61,8 @@ def bind(lib_path, kinds, need_family=False):
     from promp_amd import _lib
     if not lib_path:
         return _lib.Library()
-    newest = ['promp_collect_point_family', 'promp_rollout_point_family']
+    newest = ['promp_collect_point_family_norm', 'promp_point_norm_set', 'promp_point_norm_get', 'promp_collect_point_family',
+              'promp_rollout_point_family']
     held = {}
     try:
         while True:
@@ -84,7 +91,7 @@ def timed(run, ctx, repeats, launches, warm=20):
     return 1e6 * np.array(times)
 
 
-def collect_times(kinds, lib_path, repeats, launches, label):
+def collect_times(kinds, lib_path, repeats, launches, label, normalize=False):
     from promp_amd import _lib, synthetic
     M, B, T, hidden = 40, 20, 100, (64, 64)
     S, N = 2 * T - 1, M * B
@@ -101,6 +108,10 @@ def collect_times(kinds, lib_path, repeats, launches, label):
             tasks, start, max_step = rng.randn(M, task_dim), rng.uniform(-0.2, 0.2, size=(S, N, O)), 0.2 if kind != 'momentum' else 0.1
         z = rng.randn(S, N, 2).astype(np.float32)
         out = {}
+        if normalize:
+            norm_times(ctx, lib, kind, tasks, start, z, max_step, S, N, T, O, repeats, launches, label)
+            ctx.close()
+            continue
         for noise in ('host', 'device'):
             def run():
                 out['t'] = ctx.collect_point_family(0, kind, tasks, start, z if noise == 'host' else None, total_samples=N * T,
@@ -113,6 +124,30 @@ def collect_times(kinds, lib_path, repeats, launches, label):
                       label, kind, noise, np.median(us), us.min(), us.max(), np.median(us) / S, S, t['n_steps'] - 1, len(t['path_len']),
                       t['path_row_offsets'][-1], repeats, launches), flush=True)
         ctx.close()
+
+
+def norm_times(ctx, lib, kind, tasks, start, z, max_step, S, N, T, O, repeats, launches, label):
+    """host noise; plain: promp_collect_point_family; off / obs / both: promp_collect_point_family_norm with a start table one row
+    longer.  The moments start as a fresh wrapper's and move on from call to call (step sizes 0.001, the wrapper's default)."""
+    modes = [('plain', None)]
+    if hasattr(lib.cdll, 'promp_collect_point_family_norm'):
+        modes += [(name, dict(normalize_obs=n_obs, normalize_reward=n_rew, obs_alpha=0.001, reward_alpha=0.001))
+                  for name, n_obs, n_rew in (('off', False, False), ('obs', True, False), ('both', True, True))]
+        longer = np.concatenate([start, start[:1]])
+        fresh = np.tile(np.concatenate([np.zeros(O), np.ones(O), [0.0, 1.0]]), (N, 1))
+        ctx.set_point_norm(fresh)
+    out = {}
+    for name, norm in modes:
+        def run():
+            out['t'] = ctx.collect_point_family(0, kind, tasks, start if norm is None else longer, z, total_samples=N * T, max_path_length=T,
+                                                seed=12345, reward_type='dense', normalization_scale=10.0, max_step=max_step, norm=norm)
+        us = timed(run, ctx, repeats, launches, warm=5)
+        t = out['t']
+        print('%scollect %-8s normalize %-5s  median %9.2f us per call  min %9.2f  max %9.2f  = %7.2f us per vectorised step (%d steps); '
+              'stop step %d, %d paths, %d rows; staged moments %.2f MB  (%d windows of %d calls)' % (
+                  label, kind, name, np.median(us), us.min(), us.max(), np.median(us) / S, S, t['n_steps'] - 1, len(t['path_len']),
+                  t['path_row_offsets'][-1], (8e-6 * S * (2 * O + 2) * N) if norm and (norm['normalize_obs'] or norm['normalize_reward']) else 0.0,
+                  repeats, launches), flush=True)
 
 
 def launch_times(kinds, lib_path, repeats, launches, label, wide=False):
@@ -146,6 +181,7 @@ if __name__ == '__main__':
     ap.add_argument('--launch', action='store_true')
     ap.add_argument('--collect', action='store_true')
     ap.add_argument('--wide', action='store_true')
+    ap.add_argument('--normalize', action='store_true')
     ap.add_argument('--kinds', nargs='+', default=None, choices=['corner', 'walls', 'momentum', 'goal'])
     ap.add_argument('--lib', type=str, default='')
     ap.add_argument('--label', type=str, default='')
@@ -154,7 +190,7 @@ if __name__ == '__main__':
     args = ap.parse_args()
     label = args.label and args.label + ' '
     if args.launch and args.collect:
-        collect_times(args.kinds or ['corner', 'goal'], args.lib, args.repeats, args.launches, label)
+        collect_times(args.kinds or ['corner', 'goal'], args.lib, args.repeats, args.launches, label, args.normalize)
     elif args.launch:
         launch_times(args.kinds or ['corner', 'walls', 'momentum'], args.lib, args.repeats, args.launches, label, args.wide)
     else:
