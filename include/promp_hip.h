@@ -110,7 +110,8 @@ const char* promp_last_error(void);
  * and promp_reduced_count; promp_set_outer_optimizer / promp_get_outer_optimizer / promp_get_grad_norm;
  * promp_process_samples_dice / promp_download_dice / promp_use_dice_advantages (and promp_proc_opts.reserved read as pad_length);
  * promp_rollout_point_family, promp_collect_point_family; promp_point_norm_set / promp_point_norm_get /
- * promp_collect_point_family_norm -- were additions and did not move it. */
+ * promp_collect_point_family_norm; promp_draw_point_starts / promp_rollout_point_family_dev / promp_collect_point_family_dev --
+ * were additions and did not move it. */
 int promp_abi_version(void);
 /* Theta = O*H1+H1 + H1*H2+H2 + H2*A+A + A */
 int promp_param_count(const promp_dims* dims);
@@ -436,6 +437,45 @@ int promp_collect_point_family_norm(promp_ctx* ctx, int step, int envs_per_task,
                                     const float* noise, const promp_point_collect_opts* opts, const promp_point_norm_opts* norm,
                                     int32_t* n_paths, int32_t* n_steps, int32_t* task_path_offsets, int32_t* path_env,
                                     int32_t* path_start, int32_t* path_len);
+
+/* (b'''') START STATES DRAWN ON THE DEVICE: (b'), (b'') and (b''') without a start table.  What replaces the table is the reset() of
+ *     the reference's classes -- np.random.uniform over a box, or zeros:
+ *       envs/point_envs/point_env_2d_corner.py:50        uniform(-0.2, 0.2, 2)
+ *       envs/point_envs/point_env_2d_walls.py:60         uniform(-0.2, 0.2, 2)
+ *       envs/point_envs/point_env_2d_momentum.py:51-52   uniform(-0.2, 0.2, 2) and a velocity uniform(-0.1, 0.1, 2)
+ *       envs/point_envs/point_env_2d.py:37               uniform(-2, 2, 2)
+ *       envs/point_envs/point_env_2d_v2.py:40            zeros(2)                 (lo = hi = 0)
+ *     Coordinates 2 p and 2 p + 1 of the reset() filed under start-table row r come from one Philox4x32-10 block:
+ *       counter (lo32(r), hi32(r), 0x80000000 | p, stream), key (lo32(seed), hi32(seed))
+ *     r = s * n_envs + env, s the row of the table of (b'') / (b''') -- row 0 the initial states, row s + 1 the state an environment
+ *     continues from after an episode that ends at step s; under (b''') the row behind the last step, s = max_steps, is drawn like
+ *     any other --; the fixed-horizon rollouts of (b') have r = env.  stream is the step slot, as for the noise of (a).  The high bit
+ *     of counter word 2 keeps these blocks apart from the action-noise blocks, whose word 2 is an action pair below 32, so one seed
+ *     may serve both.  Words (x, y) give coordinate 2 p, words (z, w) coordinate 2 p + 1:
+ *       u = ((a >> 5) * 2^26 + (b >> 6)) / 2^53, a float64 in [0, 1);  value = lo[k] + (hi[k] - lo[k]) * u, every operation rounded
+ *       on its own (no fused multiply-add), so lo[k] == hi[k] yields exactly lo[k].
+ *     The stream is a function of (seed, step slot, table row, environment) and of nothing else -- no launch geometry, no kernel.
+ *   promp_draw_point_starts  out [n_rows][n_envs][state_dim] (host): the table the other two calls behave as if they had been
+ *     handed.  state_dim 2 or 4.  Synchronous.
+ *   promp_rollout_point_family_dev / promp_collect_point_family_dev  the arguments of promp_rollout_point_family /
+ *     promp_collect_point_family_norm with `starts` in the place of `start`; norm may be NULL (the plain collection).  Results are
+ *     those of the table entry points on promp_draw_point_starts' table, bit for bit.  noise is host noise or NULL, independently of
+ *     the starts (opts->seed keys the noise, starts->seed the start states).  No start table is reserved or uploaded: a call uploads
+ *     the task parameters and, if given, the noise.  Refused by name, with nothing installed and, under norm, the moments bit for
+ *     bit as they were: starts NULL; lo[k] > hi[k] or a bound that is not finite for some k < state_dim; everything the table
+ *     entry points refuse. */
+typedef struct {
+    double   lo[4], hi[4];    /* coordinate k < state_dim of every reset(): lo[k] + (hi[k] - lo[k]) u, u in [0, 1) */
+    uint64_t seed;
+} promp_point_start_opts;
+int promp_draw_point_starts(promp_ctx* ctx, int step, int n_rows, int n_envs, int state_dim, const promp_point_start_opts* starts,
+                            double* out);
+int promp_rollout_point_family_dev(promp_ctx* ctx, int step, int envs_per_task, int path_length, const double* task_params,
+                                   const promp_point_start_opts* starts, const float* noise, const promp_point_family_opts* opts);
+int promp_collect_point_family_dev(promp_ctx* ctx, int step, int envs_per_task, const double* task_params,
+                                   const promp_point_start_opts* starts, const float* noise, const promp_point_collect_opts* opts,
+                                   const promp_point_norm_opts* norm /* or NULL */, int32_t* n_paths, int32_t* n_steps,
+                                   int32_t* task_path_offsets, int32_t* path_env, int32_t* path_start, int32_t* path_len);
 
 /* Step slab back on the host (any pointer may be NULL): obs [rows][O], act [rows][A], rew [rows],
  * old_mean [rows][A], old_log_std [rows | n_tasks][A] as uploaded / produced by a device rollout. */

@@ -67,6 +67,10 @@ class PointNormOpts(C.Structure):
     _fields_ = [('normalize_obs', C.c_int32), ('normalize_reward', C.c_int32), ('obs_alpha', C.c_double), ('reward_alpha', C.c_double)]
 
 
+class PointStartOpts(C.Structure):
+    _fields_ = [('lo', C.c_double * 4), ('hi', C.c_double * 4), ('seed', C.c_uint64)]
+
+
 POINT_KIND = dict(corner=0, walls=1, momentum=2, goal=3)                   # goal: collect_point_family only
 POINT_KIND_DIMS = dict(corner=(2, 2), walls=(6, 2), momentum=(2, 4), goal=(2, 2))       # kind -> (task_dim, state_dim)
 
@@ -130,6 +134,11 @@ SIGNATURES = {
     'promp_collect_point_family': (C.c_int, [_P, C.c_int, C.c_int, _D, _D, _F, C.POINTER(PointCollectOpts), _I, _I, _I, _I, _I, _I]),
     'promp_collect_point_family_norm': (C.c_int, [_P, C.c_int, C.c_int, _D, _D, _F, C.POINTER(PointCollectOpts), C.POINTER(PointNormOpts),
                                                   _I, _I, _I, _I, _I, _I]),
+    'promp_draw_point_starts': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PointStartOpts), _D]),
+    'promp_rollout_point_family_dev': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _D, C.POINTER(PointStartOpts), _F,
+                                                 C.POINTER(PointFamilyOpts)]),
+    'promp_collect_point_family_dev': (C.c_int, [_P, C.c_int, C.c_int, _D, C.POINTER(PointStartOpts), _F, C.POINTER(PointCollectOpts),
+                                                 C.POINTER(PointNormOpts), _I, _I, _I, _I, _I, _I]),
     'promp_point_norm_set': (C.c_int, [_P, C.c_int, C.c_int, _D]),
     'promp_point_norm_get': (C.c_int, [_P, C.c_int, C.c_int, _D]),
     'promp_begin_rollout': (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
@@ -870,58 +879,101 @@ class Context:
         self.step_tpo[step] = np.arange(M + 1, dtype=np.int64) * B
         self.step_ls_rows[step] = M
 
+    @staticmethod
+    def _start_opts(starts):
+        """dict(lo=, hi=, seed=) -> promp_point_start_opts (lo / hi: one bound per state coordinate, at most 4)"""
+        lo, hi = np.atleast_1d(np.asarray(starts['lo'], np.float64)), np.atleast_1d(np.asarray(starts['hi'], np.float64))
+        assert lo.shape == hi.shape and lo.ndim == 1 and lo.size <= 4, (lo.shape, hi.shape)
+        so = PointStartOpts()
+        for k in range(lo.size):
+            so.lo[k], so.hi[k] = float(lo[k]), float(hi[k])
+        so.seed = int(starts.get('seed', 0))
+        return so
+
+    def draw_point_starts(self, step, n_rows, n_envs, state_dim, lo, hi, seed):
+        """-> [n_rows, n_envs, state_dim] float64: the start table the device-start calls behave as if they had been handed, row s
+        of it for step slot `step` under `seed` (promp_draw_point_starts)"""
+        out = np.empty((int(n_rows), int(n_envs), int(state_dim)), np.float64)
+        so = self._start_opts(dict(lo=lo, hi=hi, seed=seed))
+        self._call('promp_draw_point_starts', int(step), int(n_rows), int(n_envs), int(state_dim), C.byref(so), _ptr(out, C.c_double))
+        return out
+
     def rollout_point_family(self, step, kind, task_params, start, noise=None, clip_infos=True, reward_type='dense',
-                             normalization_scale=0.0, max_step=0.2, sparse_radius=2.0, seed=0, path_length=None, task_dim=None):
+                             normalization_scale=0.0, max_step=0.2, sparse_radius=2.0, seed=0, path_length=None, task_dim=None,
+                             starts=None, envs_per_task=None):
         """Device rollout of a point-mass meta-environment with corner goals, kind 'corner' | 'walls' | 'momentum' (or its number):
         task_params [M, task_dim] (corner, momentum: the goal; walls: goal, gap_1, gap_2), start [M, B, state_dim] (float64;
         momentum: position, velocity), noise [M,B,T,2] or None as in rollout_point_env -> fills step `step`'s slab with M*B
-        paths of length T, observations of width state_dim (see promp_rollout_point_family)."""
+        paths of length T, observations of width state_dim (see promp_rollout_point_family).
+        start=None with starts=dict(lo=, hi=, seed=) and envs_per_task: the start states are drawn on the device
+        (promp_rollout_point_family_dev)."""
         self._pre_write(step)
         task_params = np.ascontiguousarray(task_params, dtype=np.float64)
-        start = np.ascontiguousarray(start, dtype=np.float64)
-        assert task_params.ndim == 2 and start.ndim == 3
-        M, B = self.n_tasks, start.shape[1]
+        assert task_params.ndim == 2
+        if start is None:
+            assert starts is not None and envs_per_task is not None, 'start=None needs starts=dict(lo, hi, seed) and envs_per_task'
+            M, B = self.n_tasks, int(envs_per_task)
+        else:
+            assert starts is None, 'a start table and starts= exclude one another'
+            start = np.ascontiguousarray(start, dtype=np.float64)
+            assert start.ndim == 3
+            M, B = self.n_tasks, start.shape[1]
         if noise is not None:
             noise = _f32(noise)
             T = noise.shape[2]
             assert noise.shape == (M, B, T, 2)
         else:
             T = int(path_length)
-        if kind in POINT_KIND:
+        if kind in POINT_KIND and start is not None:
             assert (task_params.shape[1], start.shape[2]) == POINT_KIND_DIMS[kind], (kind, task_params.shape, start.shape)
-        assert task_params.shape[0] == M and start.shape[0] == M
+        assert task_params.shape[0] == M and (start is None or start.shape[0] == M)
         opts = PointFamilyOpts(int(POINT_KIND.get(kind, kind)), POINT_REWARD[reward_type], int(bool(clip_infos)),
                                int(task_params.shape[1] if task_dim is None else task_dim), float(normalization_scale),
                                float(max_step), float(sparse_radius), int(seed))
-        self._call('promp_rollout_point_family', int(step), int(B), int(T), _ptr(task_params, C.c_double), _ptr(start, C.c_double),
-                   _ptr(noise, C.c_float) if noise is not None else None, C.byref(opts))
+        z = _ptr(noise, C.c_float) if noise is not None else None
+        if start is None:
+            so = starts if isinstance(starts, PointStartOpts) else self._start_opts(starts)
+            self._call('promp_rollout_point_family_dev', int(step), int(B), int(T), _ptr(task_params, C.c_double), C.byref(so), z,
+                       C.byref(opts))
+        else:
+            self._call('promp_rollout_point_family', int(step), int(B), int(T), _ptr(task_params, C.c_double),
+                       _ptr(start, C.c_double), z, C.byref(opts))
         self.step_rows[step], self.step_paths[step] = M * B * T, M * B
         self.step_tpo[step] = np.arange(M + 1, dtype=np.int64) * B
         self.step_ls_rows[step] = M
 
     def collect_point_family(self, step, kind, task_params, start, noise=None, total_samples=None, max_path_length=None,
                              clip_infos=True, reward_type='dense', normalization_scale=0.0, max_step=0.1, sparse_radius=2.0, seed=0,
-                             done_radius=0.01, task_dim=None, norm=None):
+                             done_radius=0.01, task_dim=None, norm=None, starts=None, envs_per_task=None, max_steps=None):
         """Device collection with early termination (promp_collect_point_family), kind 'corner' | 'walls' | 'momentum' | 'goal' (or
         its number): task_params [M, task_dim], start [max_steps, M * B, state_dim] (float64; row 0 the initial states, row s + 1
         the states that environments whose episode ends at step s continue from), noise [max_steps, M * B, 2] or None (drawn on
         the device from `seed`) -> the step's slab holds the finished episodes in the reference's order; returns
         dict(n_steps, task_path_offsets, path_row_offsets, path_env, path_start, path_len).
         norm: None, or dict(normalize_obs, normalize_reward, obs_alpha, reward_alpha) -- the normalize wrapper's running moments
-        (promp_collect_point_family_norm; set_point_norm first): start then has max_steps + 1 rows, the reset() behind every step."""
+        (promp_collect_point_family_norm; set_point_norm first): start then has max_steps + 1 rows, the reset() behind every step.
+        start=None with starts=dict(lo=, hi=, seed=), envs_per_task and max_steps: every reset() is drawn on the device and no table
+        exists (promp_collect_point_family_dev)."""
         self._pre_write(step)
         task_params = np.ascontiguousarray(task_params, dtype=np.float64)
-        start = np.ascontiguousarray(start, dtype=np.float64)
-        assert task_params.ndim == 2 and start.ndim == 3
+        assert task_params.ndim == 2
         M = self.n_tasks
-        max_steps, n_envs = start.shape[:2]
-        if norm is not None:
-            max_steps -= 1
-        assert n_envs % M == 0 and task_params.shape[0] == M, (start.shape, task_params.shape)
+        if start is None:
+            assert starts is not None and envs_per_task is not None and max_steps is not None, \
+                'start=None needs starts=dict(lo, hi, seed), envs_per_task and max_steps'
+            max_steps, n_envs = int(max_steps), M * int(envs_per_task)
+        else:
+            assert starts is None, 'a start table and starts= exclude one another'
+            start = np.ascontiguousarray(start, dtype=np.float64)
+            assert start.ndim == 3
+            max_steps, n_envs = start.shape[:2]
+            if norm is not None:
+                max_steps -= 1
+        assert n_envs % M == 0 and task_params.shape[0] == M, (n_envs, task_params.shape)
         if noise is not None:
             noise = _f32(noise)
             assert noise.shape == (max_steps, n_envs, 2), noise.shape
-        if kind in POINT_KIND:
+        if kind in POINT_KIND and start is not None:
             assert (task_params.shape[1], start.shape[2]) == POINT_KIND_DIMS[kind], (kind, task_params.shape, start.shape)
         env = PointFamilyOpts(int(POINT_KIND.get(kind, kind)), POINT_REWARD[reward_type], int(bool(clip_infos)),
                               int(task_params.shape[1] if task_dim is None else task_dim), float(normalization_scale),
@@ -933,13 +985,19 @@ class Context:
         p_env, p_start, p_len = (np.zeros(cap, np.int32) for _ in range(3))
         outs = (C.byref(n_paths), C.byref(n_steps), _ptr(tpo, C.c_int32), _ptr(p_env, C.c_int32), _ptr(p_start, C.c_int32),
                 _ptr(p_len, C.c_int32))
-        ins = (int(step), int(n_envs // M), _ptr(task_params, C.c_double), _ptr(start, C.c_double),
+        if start is None:
+            so = starts if isinstance(starts, PointStartOpts) else self._start_opts(starts)
+        ins = (int(step), int(n_envs // M), _ptr(task_params, C.c_double), _ptr(start, C.c_double) if start is not None else C.byref(so),
                _ptr(noise, C.c_float) if noise is not None else None, C.byref(opts))
-        if norm is None:
-            self._call('promp_collect_point_family', *(ins + outs))
-        else:
+        nopts = None
+        if norm is not None:
             nopts = PointNormOpts(int(bool(norm.get('normalize_obs', False))), int(bool(norm.get('normalize_reward', False))),
                                   float(norm.get('obs_alpha', 0.001)), float(norm.get('reward_alpha', 0.001)))
+        if start is None:
+            self._call('promp_collect_point_family_dev', *(ins + (C.byref(nopts) if nopts is not None else None,) + outs))
+        elif norm is None:
+            self._call('promp_collect_point_family', *(ins + outs))
+        else:
             self._call('promp_collect_point_family_norm', *(ins + (C.byref(nopts),) + outs))
         n = int(n_paths.value)
         p_env, p_start, p_len = p_env[:n].copy(), p_start[:n].copy(), p_len[:n].copy()

@@ -2295,9 +2295,45 @@ int promp_rollout_point_env(promp_ctx* c, int step, int envs_per_task, int path_
     return 0;
 }
 
-int promp_rollout_point_family(promp_ctx* c, int step, int envs_per_task, int path_length, const double* task_params,
-                               const double* start, const float* noise, const promp_point_family_opts* o) {
-    if (!c || !task_params || !start || !o) return fail(-1, "NULL argument");
+// the box of a device-side start draw: lo <= hi and finite in every coordinate the environment has -> the kernels' form
+static int point_start_box(const promp_point_start_opts* so, int state_dim, PointStartBox* bx) {
+    *bx = PointStartBox{};
+    for (int k = 0; k < state_dim; ++k) {
+        if (!std::isfinite(so->lo[k]) || !std::isfinite(so->hi[k]))
+            return fail(-1, "start bounds of coordinate %d are not finite: lo = %g, hi = %g", k, so->lo[k], so->hi[k]);
+        if (so->lo[k] > so->hi[k]) return fail(-1, "start bounds of coordinate %d: lo = %g > hi = %g", k, so->lo[k], so->hi[k]);
+        bx->lo[k] = so->lo[k];
+        bx->hi[k] = so->hi[k];
+    }
+    bx->seed = so->seed;
+    return 0;
+}
+
+int promp_draw_point_starts(promp_ctx* c, int step, int n_rows, int n_envs, int state_dim, const promp_point_start_opts* so, double* out) {
+    if (!c || !so || !out) return fail(-1, "NULL argument");
+    if (step < 0 || step > c->d.num_inner_steps) return fail(-1, "step %d out of range", step);
+    if (n_rows < 1 || n_envs < 1) return fail(-1, "n_rows = %d and n_envs = %d must be positive", n_rows, n_envs);
+    if (state_dim != 2 && state_dim != 4) return fail(-1, "state_dim = %d must be 2 or 4", state_dim);
+    PointStartsArgs a;
+    if (point_start_box(so, state_dim, &a.bx)) return -2;
+    a.n = (long long)n_rows * n_envs;
+    if (a.n > 0x7FFFFFFFll / 4) return fail(-1, "n_rows * n_envs = %lld start states are too many", a.n);
+    const size_t n = (size_t)a.n * state_dim;
+    if (c->rollout_buf.reserve(sizeof(double) * n, 2)) return -2;
+    a.stream = (unsigned)step; a.state_dim = state_dim; a.out = (double*)c->rollout_buf.p;
+    PROMP_LAUNCH(k_point_starts, dim3((unsigned)((a.n + 255) / 256)), 256, 0, c->stream, a);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(out, a.out, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// start: the table [n_tasks][envs_per_task][state_dim], or NULL: drawn on the device from so (nothing but the task parameters and
+// host noise is uploaded)
+static int rollout_point_family(promp_ctx* c, int step, int envs_per_task, int path_length, const double* task_params,
+                                const double* start, const promp_point_start_opts* so, const float* noise,
+                                const promp_point_family_opts* o) {
+    if (!c || !task_params || (!start && !so) || !o) return fail(-1, "NULL argument");
     StepScope sc(c, step);
     if (sc.rc) return sc.rc;
     if (o->kind < POINT_KIND_CORNER || o->kind > POINT_KIND_MOMENTUM) return fail(-1, "unknown environment kind %d", o->kind);
@@ -2306,25 +2342,27 @@ int promp_rollout_point_family(promp_ctx* c, int step, int envs_per_task, int pa
     if (c->d.obs_dim != state_dim) return fail(-1, "environment kind %d has obs_dim = %d (context: %d)", o->kind, state_dim, c->d.obs_dim);
     if (c->d.act_dim != 2) return fail(-1, "the point environments have act_dim = 2 (context: %d)", c->d.act_dim);
     if (o->reward_type < 0 || o->reward_type > 2) return fail(-1, "unknown reward type %d", o->reward_type);
+    PointStartBox bx = {};
+    if (!start && point_start_box(so, state_dim, &bx)) return -2;
     if (begin_fixed_rollout(sc, envs_per_task, path_length)) return -2;
     const int M = c->d.n_tasks, B = envs_per_task, T = path_length;
     const long long rows = (long long)M * B * T;
     StepData& S = sc.S();
     S.data_version = ++c->version_counter;
-    const size_t n_task = (size_t)M * task_dim, n_start = (size_t)M * B * state_dim;
+    const size_t n_task = (size_t)M * task_dim, n_start = start ? (size_t)M * B * state_dim : 0;
     if (c->rollout_buf.reserve(sizeof(double) * (n_task + n_start) + sizeof(float) * (size_t)rows * 2, 2)) return -2;
     double* d_task = (double*)c->rollout_buf.p;
     double* d_start = d_task + n_task;
     float* d_noise = (float*)(d_start + n_start);
     hipStream_t st = c->stream;
     HIPCHECK(hipMemcpyAsync(d_task, task_params, sizeof(double) * n_task, hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(d_start, start, sizeof(double) * n_start, hipMemcpyHostToDevice, st));
+    if (start) HIPCHECK(hipMemcpyAsync(d_start, start, sizeof(double) * n_start, hipMemcpyHostToDevice, st));
     if (noise) HIPCHECK(hipMemcpyAsync(d_noise, noise, sizeof(float) * rows * 2, hipMemcpyHostToDevice, st));
     PointFamilyArgs f;
     PointRolloutArgs& a = f.p;
     if (tasks_materialize(c)) return -2;
     a.theta_tasks = c->theta_tasks; a.NP = c->NP; a.H1 = c->d.hidden1; a.H2 = c->d.hidden2;
-    a.B = B; a.T = T; a.goals = d_task; a.start = d_start; a.noise = noise ? d_noise : nullptr;
+    a.B = B; a.T = T; a.goals = d_task; a.start = start ? d_start : nullptr; a.noise = noise ? d_noise : nullptr;
     a.seed = o->seed; a.stream = (unsigned)step;
     a.obs = S.obs; a.act = S.act; a.rew = S.rew; a.mean = S.old_mean; a.old_ls = S.old_ls;
     a.clip_infos = o->clip_infos; a.min_log_std = c->min_log_std;
@@ -2334,12 +2372,27 @@ int promp_rollout_point_family(promp_ctx* c, int step, int envs_per_task, int pa
         GenPointFamilyArgs g;
         g.f = f; g.act_kind = gen_act_kinds(&c->d);
         copy_layers(g, c);
-        PROMP_LAUNCH(k_gen_point_family_rollout, dim3(B, M), 256, gen_rollout_smem(state_dim), st, g);
-    } else
-    PROMP_LAUNCH(k_point_family_rollout, dim3(M), 64, 0, st, f);
+        if (start) PROMP_LAUNCH(k_gen_point_family_rollout<false>, dim3(B, M), 256, gen_rollout_smem(state_dim), st, g, bx);
+        else PROMP_LAUNCH(k_gen_point_family_rollout<true>, dim3(B, M), 256, gen_rollout_smem(state_dim), st, g, bx);
+    } else if (start)
+    PROMP_LAUNCH(k_point_family_rollout<false>, dim3(M), 64, 0, st, f, bx);
+    else
+    PROMP_LAUNCH(k_point_family_rollout<true>, dim3(M), 64, 0, st, f, bx);
     HIPCHECK(hipGetLastError());
     S.ps.obs_range_valid = false;
     return 0;
+}
+
+int promp_rollout_point_family(promp_ctx* c, int step, int envs_per_task, int path_length, const double* task_params,
+                               const double* start, const float* noise, const promp_point_family_opts* o) {
+    if (!start) return fail(-1, "NULL argument");
+    return rollout_point_family(c, step, envs_per_task, path_length, task_params, start, nullptr, noise, o);
+}
+
+int promp_rollout_point_family_dev(promp_ctx* c, int step, int envs_per_task, int path_length, const double* task_params,
+                                   const promp_point_start_opts* starts, const float* noise, const promp_point_family_opts* o) {
+    if (!starts) return fail(-1, "promp_rollout_point_family_dev: starts is NULL");
+    return rollout_point_family(c, step, envs_per_task, path_length, task_params, nullptr, starts, noise, o);
 }
 
 int promp_begin_rollout(promp_ctx* c, int step, int envs_per_task, int path_length) {
@@ -2423,11 +2476,13 @@ int promp_end_collection(promp_ctx* c, int step, int n_paths, const int32_t* tas
 // back.  Every refusal leaves the step without a layout of this call: the slab is touched by finish_collection alone.
 // nm: the normalize wrapper's options, or NULL / both flags 0: the plain collection.  With a flag set the start table has
 // max_steps + 1 rows and the context's running moments (promp_point_norm_set) advance to their state after the stop step.
+// start: the table, or NULL: every reset() drawn on the device from so -- no table is reserved or uploaded.
 static int collect_point_family(promp_ctx* c, int step, int envs_per_task, const double* task_params, const double* start,
+                                const promp_point_start_opts* so,
                                 const float* noise, const promp_point_collect_opts* o, const promp_point_norm_opts* nm,
                                 int32_t* n_paths_out, int32_t* n_steps_out,
                                 int32_t* task_path_offsets, int32_t* path_env, int32_t* path_start, int32_t* path_len) {
-    if (!c || !task_params || !start || !o || !n_paths_out || !n_steps_out || !task_path_offsets || !path_env || !path_start || !path_len)
+    if (!c || !task_params || (!start && !so) || !o || !n_paths_out || !n_steps_out || !task_path_offsets || !path_env || !path_start || !path_len)
         return fail(-1, "NULL argument");
     const bool norm = nm && (nm->normalize_obs || nm->normalize_reward);
     if (nm) {
@@ -2446,6 +2501,8 @@ static int collect_point_family(promp_ctx* c, int step, int envs_per_task, const
     if (o->max_path_length < 1) return fail(-1, "max_path_length = %d must be positive", o->max_path_length);
     if (envs_per_task < 1 || o->max_steps < 1) return fail(-1, "envs_per_task and max_steps must be positive");
     if (o->total_samples < 1) return fail(-1, "total_samples must be positive");
+    PointStartBox bx = {};
+    if (!start && point_start_box(so, state_dim, &bx)) return -2;
     const int M = c->d.n_tasks, B = envs_per_task, O = state_dim, A = 2, S_max = o->max_steps, max_paths = c->d.max_paths;
     const long long n_envs = (long long)M * B, stage = n_envs * S_max;
     if (stage > 0x7FFFFFFFll / 4) return fail(-1, "max_steps * environments = %lld staging rows are too many", stage);
@@ -2462,7 +2519,8 @@ static int collect_point_family(promp_ctx* c, int step, int envs_per_task, const
     if (norm && c->point_norm_stage.reserve((size_t)stage * W, 1)) return -2;
     S.has_policy = false; S.processed = false; S.has_adv = false;
     // one block: doubles (task parameters, start table), the stop record, floats (noise, staged rewards), then the integer tables
-    const size_t n_task = (size_t)M * task_dim, n_start = (size_t)(stage + (norm ? n_envs : 0)) * O, n_noise = noise ? (size_t)stage * 2 : 0;
+    const size_t n_task = (size_t)M * task_dim, n_start = start ? (size_t)(stage + (norm ? n_envs : 0)) * O : 0;
+    const size_t n_noise = noise ? (size_t)stage * 2 : 0;
     const size_t n_int = (size_t)stage + S_max + M + (M + 1) + 3 * (size_t)max_paths;
     if (c->rollout_buf.reserve(sizeof(double) * (n_task + n_start) + sizeof(long long) * 4 + sizeof(float) * (n_noise + (size_t)stage) +
                                sizeof(int32_t) * n_int, 2)) return -2;
@@ -2480,13 +2538,13 @@ static int collect_point_family(promp_ctx* c, int step, int envs_per_task, const
     int32_t* d_len = d_pstart + max_paths;
     hipStream_t st = c->stream;
     HIPCHECK(hipMemcpyAsync(d_task, task_params, sizeof(double) * n_task, hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(d_start, start, sizeof(double) * n_start, hipMemcpyHostToDevice, st));
+    if (start) HIPCHECK(hipMemcpyAsync(d_start, start, sizeof(double) * n_start, hipMemcpyHostToDevice, st));
     if (noise) HIPCHECK(hipMemcpyAsync(d_noise, noise, sizeof(float) * n_noise, hipMemcpyHostToDevice, st));
     if (tasks_materialize(c)) return -2;
     PointCollectArgs k;
     PointRolloutArgs& a = k.f.p;
     a.theta_tasks = c->theta_tasks; a.NP = c->NP; a.H1 = c->d.hidden1; a.H2 = c->d.hidden2;
-    a.B = B; a.T = S_max; a.goals = d_task; a.start = d_start; a.noise = noise ? d_noise : nullptr;
+    a.B = B; a.T = S_max; a.goals = d_task; a.start = start ? d_start : nullptr; a.noise = noise ? d_noise : nullptr;
     a.seed = e.seed; a.stream = (unsigned)step;
     a.obs = c->stage_rows; a.act = c->stage_rows + (size_t)stage * O; a.mean = a.act + (size_t)stage * A; a.rew = nullptr;
     a.old_ls = S.old_ls;
@@ -2508,15 +2566,21 @@ static int collect_point_family(promp_ctx* c, int step, int envs_per_task, const
         if (norm) {
             GenPointNormCollectArgs gn;
             gn.g = g; gn.n = pn;
-            PROMP_LAUNCH(k_gen_point_norm_collect, dim3(B, M), 256, gen_rollout_smem(state_dim), st, gn);
-        } else
-        PROMP_LAUNCH(k_gen_point_collect, dim3(B, M), 256, gen_rollout_smem(state_dim), st, g);
+            if (start) PROMP_LAUNCH(k_gen_point_norm_collect<false>, dim3(B, M), 256, gen_rollout_smem(state_dim), st, gn, bx);
+            else PROMP_LAUNCH(k_gen_point_norm_collect<true>, dim3(B, M), 256, gen_rollout_smem(state_dim), st, gn, bx);
+        } else if (start)
+        PROMP_LAUNCH(k_gen_point_collect<false>, dim3(B, M), 256, gen_rollout_smem(state_dim), st, g, bx);
+        else
+        PROMP_LAUNCH(k_gen_point_collect<true>, dim3(B, M), 256, gen_rollout_smem(state_dim), st, g, bx);
     } else if (norm) {
         PointNormCollectArgs kn;
         kn.c = k; kn.n = pn;
-        PROMP_LAUNCH(k_point_norm_collect, dim3(M), 64, 0, st, kn);
-    } else
-    PROMP_LAUNCH(k_point_collect, dim3(M), 64, 0, st, k);
+        if (start) PROMP_LAUNCH(k_point_norm_collect<false>, dim3(M), 64, 0, st, kn, bx);
+        else PROMP_LAUNCH(k_point_norm_collect<true>, dim3(M), 64, 0, st, kn, bx);
+    } else if (start)
+    PROMP_LAUNCH(k_point_collect<false>, dim3(M), 64, 0, st, k, bx);
+    else
+    PROMP_LAUNCH(k_point_collect<true>, dim3(M), 64, 0, st, k, bx);
     HIPCHECK(hipGetLastError());
     CollectStopArgs cs;
     cs.end_len = d_end; cs.step_sum = d_sum; cs.out = d_stop; cs.max_steps = S_max; cs.n_envs = (int)n_envs; cs.total_samples = o->total_samples;
@@ -2575,7 +2639,8 @@ static int collect_point_family(promp_ctx* c, int step, int envs_per_task, const
 int promp_collect_point_family(promp_ctx* c, int step, int envs_per_task, const double* task_params, const double* start,
                                const float* noise, const promp_point_collect_opts* o, int32_t* n_paths_out, int32_t* n_steps_out,
                                int32_t* task_path_offsets, int32_t* path_env, int32_t* path_start, int32_t* path_len) {
-    return collect_point_family(c, step, envs_per_task, task_params, start, noise, o, nullptr, n_paths_out, n_steps_out,
+    if (!start) return fail(-1, "NULL argument");
+    return collect_point_family(c, step, envs_per_task, task_params, start, nullptr, noise, o, nullptr, n_paths_out, n_steps_out,
                                 task_path_offsets, path_env, path_start, path_len);
 }
 
@@ -2583,8 +2648,17 @@ int promp_collect_point_family_norm(promp_ctx* c, int step, int envs_per_task, c
                                     const float* noise, const promp_point_collect_opts* o, const promp_point_norm_opts* norm,
                                     int32_t* n_paths_out, int32_t* n_steps_out, int32_t* task_path_offsets, int32_t* path_env,
                                     int32_t* path_start, int32_t* path_len) {
-    if (!norm) return fail(-1, "NULL argument");
-    return collect_point_family(c, step, envs_per_task, task_params, start, noise, o, norm, n_paths_out, n_steps_out,
+    if (!norm || !start) return fail(-1, "NULL argument");
+    return collect_point_family(c, step, envs_per_task, task_params, start, nullptr, noise, o, norm, n_paths_out, n_steps_out,
+                                task_path_offsets, path_env, path_start, path_len);
+}
+
+int promp_collect_point_family_dev(promp_ctx* c, int step, int envs_per_task, const double* task_params,
+                                   const promp_point_start_opts* starts, const float* noise, const promp_point_collect_opts* o,
+                                   const promp_point_norm_opts* norm, int32_t* n_paths_out, int32_t* n_steps_out,
+                                   int32_t* task_path_offsets, int32_t* path_env, int32_t* path_start, int32_t* path_len) {
+    if (!starts) return fail(-1, "promp_collect_point_family_dev: starts is NULL");
+    return collect_point_family(c, step, envs_per_task, task_params, nullptr, starts, noise, o, norm, n_paths_out, n_steps_out,
                                 task_path_offsets, path_env, path_start, path_len);
 }
 

@@ -681,7 +681,8 @@ struct GenPointFamilyArgs {
 };
 
 // grid = (B, tasks), block = 256: k_gen_point_rollout for any kind.  smem: gen_rollout_smem(state_dim)
-__global__ void __launch_bounds__(256) k_gen_point_family_rollout(GenPointFamilyArgs g) {
+template <bool DEVICE_START>
+__global__ void __launch_bounds__(256) k_gen_point_family_rollout(GenPointFamilyArgs g, PointStartBox bx) {
     PROMP_SMEM_DECL;
     const PointRolloutArgs& a = g.f.p;
     const int O = g.f.state_dim;
@@ -699,6 +700,8 @@ __global__ void __launch_bounds__(256) k_gen_point_family_rollout(GenPointFamily
     const double* tp = a.goals + (long long)task * g.f.task_dim;
     const long long env = (long long)task * a.B + b;
     double s[4] = {0.0, 0.0, 0.0, 0.0};                             // (advanced by thread 0 only)
+    if constexpr (DEVICE_START) point_start_state(bx, a.stream, (unsigned long long)env, O, s);
+    else
     for (int k = 0; k < O; ++k) s[k] = a.start[env * O + k];
     for (int t = 0; t < a.T; ++t) {
         const long long row = env * a.T + t;
@@ -733,7 +736,8 @@ struct GenPointCollectArgs {
 
 // grid = (B, tasks), block = 256: k_point_collect for any layer table, one workgroup per environment as k_gen_point_family_rollout.
 // smem: gen_rollout_smem(state_dim)
-__global__ void __launch_bounds__(256) k_gen_point_collect(GenPointCollectArgs g) {
+template <bool DEVICE_START>
+__global__ void __launch_bounds__(256) k_gen_point_collect(GenPointCollectArgs g, PointStartBox bx) {
     PROMP_SMEM_DECL;
     const PointCollectArgs& c = g.c;
     const PointRolloutArgs& a = c.f.p;
@@ -752,6 +756,8 @@ __global__ void __launch_bounds__(256) k_gen_point_collect(GenPointCollectArgs g
     const double* tp = a.goals + (long long)task * c.f.task_dim;
     const long long env = (long long)task * a.B + b;
     double s[4] = {0.0, 0.0, 0.0, 0.0};                             // (advanced by thread 0 only)
+    if constexpr (DEVICE_START) point_start_state(bx, a.stream, (unsigned long long)env, O, s);
+    else
     for (int k = 0; k < O; ++k) s[k] = a.start[env * O + k];
     int len = 0;
     for (int st = 0; st < c.max_steps; ++st) {
@@ -779,6 +785,9 @@ __global__ void __launch_bounds__(256) k_gen_point_collect(GenPointCollectArgs g
             c.rew_stage[row] = (float)r;
             c.end_len[row] = end ? len : 0;
             len = end ? 0 : len;
+            if constexpr (DEVICE_START) {
+                if (end && st + 1 < c.max_steps) point_start_state(bx, a.stream, (unsigned long long)(row + c.n_envs), O, s);
+            } else
             if (st + 1 < c.max_steps) {
                 const long long nxt = row + c.n_envs;
                 for (int k = 0; k < O; ++k) {
@@ -797,7 +806,8 @@ struct GenPointNormCollectArgs {
 };
 // grid = (B, tasks), block = 256: k_gen_point_collect under the normalize wrapper's running moments (k_point_norm_collect), the
 // wrapper state in thread 0's registers beside the environment's state.  smem: gen_rollout_smem(state_dim)
-__global__ void __launch_bounds__(256) k_gen_point_norm_collect(GenPointNormCollectArgs gn) {
+template <bool DEVICE_START>
+__global__ void __launch_bounds__(256) k_gen_point_norm_collect(GenPointNormCollectArgs gn, PointStartBox bx) {
     PROMP_SMEM_DECL;
     const GenPointCollectArgs& g = gn.g;
     const PointNormArgs& n = gn.n;
@@ -818,6 +828,8 @@ __global__ void __launch_bounds__(256) k_gen_point_norm_collect(GenPointNormColl
     const double* tp = a.goals + (long long)task * c.f.task_dim;
     const long long env = (long long)task * a.B + b;
     double s[4] = {0.0, 0.0, 0.0, 0.0};                             // (advanced by thread 0 only)
+    if constexpr (DEVICE_START) point_start_state(bx, a.stream, (unsigned long long)env, O, s);
+    else
     for (int k = 0; k < O; ++k) s[k] = a.start[env * O + k];
     PointNormState w;
     if (tid == 0) point_norm_enter(n, w, s, O, env);
@@ -840,7 +852,7 @@ __global__ void __launch_bounds__(256) k_gen_point_norm_collect(GenPointNormColl
             for (int k = 0; k < O; ++k) a.obs[row * O + k] = xs[k];
             a.mean[row * 2] = m[0];  a.mean[row * 2 + 1] = m[1];
             a.act[row * 2] = a0;  a.act[row * 2 + 1] = a1;
-            point_norm_collect_tail(c, n, w, s, tp, a0, a1, row, env, st, len);
+            point_norm_collect_tail<DEVICE_START>(c, n, bx, w, s, tp, a0, a1, row, env, st, len);
         }
         __syncthreads();       // the next step's observation and hidden vectors overwrite what thread 0 has just read
     }

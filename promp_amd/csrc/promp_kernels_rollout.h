@@ -57,6 +57,53 @@ PROMP_HD void action_noise(unsigned long long seed, unsigned long long row, unsi
     box_muller(r.x, r.y, n0, n1);
 }
 
+// ---- start states drawn on the device: the reset() of the point-mass classes (point_env_2d_corner.py:50, point_env_2d_walls.py:60,
+// point_env_2d_momentum.py:51-52, point_env_2d.py:37, point_env_2d_v2.py:40 of the reference: np.random.uniform over a box, or zeros).
+// Coordinates 2 p and 2 p + 1 of the reset() filed under start-table row `row` come from ONE Philox block:
+//   counter (lo32(row), hi32(row), 0x80000000 | p, stream), key (lo32(seed), hi32(seed))
+// row = s * n_envs + env, s the row of the host's start table (0: the initial states; s + 1: the state an environment continues from
+// after an episode that ends at step s); the fixed-horizon rollouts have row = env.  The high bit of word 2 keeps these blocks apart
+// from the action-noise blocks of the same (seed, stream), whose word 2 is an action pair below 32.  Words (x, y) give coordinate
+// 2 p, (z, w) coordinate 2 p + 1: u = ((a >> 5) 2^26 + (b >> 6)) / 2^53, a float64 in [0, 1) (53 bits, every step exact), and
+// value = lo + (hi - lo) u with every operation rounded on its own, so that NumPy restates it bit for bit; lo == hi yields lo.
+struct PointStartBox {
+    double lo[4], hi[4];       // coordinate k < state_dim of every reset()
+    unsigned long long seed;   // the key: its own, beside the action noise's
+};
+PROMP_HD double start_uniform(unsigned a, unsigned b) {
+    return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) * (1.0 / 9007199254740992.0);
+}
+PROMP_HD double start_value(double lo, double hi, double u) {
+#pragma clang fp contract(off)
+    const double width = hi - lo;
+    const double part = width * u;
+    return lo + part;
+}
+// the first O (2 or 4) coordinates of the reset() under `row`
+PROMP_HD void point_start_state(const PointStartBox& bx, unsigned stream, unsigned long long row, int O, double* s) {
+    for (int p = 0; 2 * p < O; ++p) {
+        const Philox4 r = philox4x32_10((unsigned)row, (unsigned)(row >> 32), 0x80000000u | (unsigned)p, stream, (unsigned)bx.seed,
+                                        (unsigned)(bx.seed >> 32));
+        s[2 * p] = start_value(bx.lo[2 * p], bx.hi[2 * p], start_uniform(r.x, r.y));
+        s[2 * p + 1] = start_value(bx.lo[2 * p + 1], bx.hi[2 * p + 1], start_uniform(r.z, r.w));
+    }
+}
+// the table a host would have uploaded: out [n_rows][n_envs][state_dim].  grid = ceil(n / 256), block = 256: one thread per reset()
+struct PointStartsArgs {
+    PointStartBox bx;
+    unsigned stream;
+    int state_dim;
+    long long n;               // n_rows * n_envs
+    double* out;
+};
+__global__ void __launch_bounds__(256) k_point_starts(PointStartsArgs a) {
+    const long long row = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (row >= a.n) return;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    point_start_state(a.bx, a.stream, (unsigned long long)row, a.state_dim, s);
+    for (int k = 0; k < a.state_dim; ++k) a.out[row * a.state_dim + k] = s[k];
+}
+
 // mean network of one observation row under flat parameters th (hidden widths <= 128, act_dim <= 8).  EXACT_TANH: tanhf instead of
 // fast_tanh, whose absolute error of ~1e-7 per unit is what the momentum environment's double integrator sums up (see
 // k_point_family_rollout)
@@ -390,8 +437,10 @@ PROMP_DEV double point_family_step(const PointFamilyArgs& f, double* s, const do
     return point_env_step(f.p, s[0], s[1], tp[0], tp[1], a0, a1);
 }
 
-// grid = tasks, block = 64: k_point_rollout for any kind
-__global__ void __launch_bounds__(64) k_point_family_rollout(PointFamilyArgs f) {
+// grid = tasks, block = 64: k_point_rollout for any kind.  DEVICE_START: the initial states are point_start_state's under row = env
+// (a.start is not read); false: the table, and bx is not read
+template <bool DEVICE_START>
+__global__ void __launch_bounds__(64) k_point_family_rollout(PointFamilyArgs f, PointStartBox bx) {
     const PointRolloutArgs& a = f.p;
     const int task = blockIdx.x, O = f.state_dim;
     const float* th = a.theta_tasks + (long long)task * a.NP;
@@ -406,6 +455,8 @@ __global__ void __launch_bounds__(64) k_point_family_rollout(PointFamilyArgs f) 
     for (int b = threadIdx.x; b < a.B; b += 64) {
         const long long env = (long long)task * a.B + b;
         double s[4] = {0.0, 0.0, 0.0, 0.0};
+        if constexpr (DEVICE_START) point_start_state(bx, a.stream, (unsigned long long)env, O, s);
+        else
         for (int k = 0; k < O; ++k) s[k] = a.start[env * O + k];
         for (int t = 0; t < a.T; ++t) {
             const long long row = env * a.T + t;
@@ -479,7 +530,9 @@ PROMP_DEV double point_collect_step(const PointCollectArgs& c, double* s, const 
 
 // grid = tasks, block = 64: one thread per environment.  Consecutive lanes are consecutive environments of one staging step, so
 // the stores of a step coalesce.  Every lane runs max_steps trips; an episode's end is a select on the state, not a branch.
-__global__ void __launch_bounds__(64) k_point_collect(PointCollectArgs c) {
+// DEVICE_START: every reset() is point_start_state's under the row the table would hold it in, drawn when an episode ends
+template <bool DEVICE_START>
+__global__ void __launch_bounds__(64) k_point_collect(PointCollectArgs c, PointStartBox bx) {
     const PointFamilyArgs& f = c.f;
     const PointRolloutArgs& a = f.p;
     const int task = blockIdx.x, O = f.state_dim;
@@ -495,6 +548,8 @@ __global__ void __launch_bounds__(64) k_point_collect(PointCollectArgs c) {
     for (int b = threadIdx.x; b < a.B; b += 64) {
         const long long env = (long long)task * a.B + b;
         double s[4] = {0.0, 0.0, 0.0, 0.0};
+        if constexpr (DEVICE_START) point_start_state(bx, a.stream, (unsigned long long)env, O, s);
+        else
         for (int k = 0; k < O; ++k) s[k] = a.start[env * O + k];
         int len = 0;
         for (int st = 0; st < c.max_steps; ++st) {
@@ -522,6 +577,11 @@ __global__ void __launch_bounds__(64) k_point_collect(PointCollectArgs c) {
             len = end ? 0 : len;
             // the next episode's reset() (a uniform condition; the reload is a select).  Asking for it ahead of the network was
             // tried and is slower (profiles/point_collect_timing.txt): the extra array is indexed by the runtime state width
+            if constexpr (DEVICE_START) {
+                // drawn only by the lanes whose episode ends: a wave none of whose episodes ends skips the block (a select
+                // would run the ten Philox rounds in every step; profiles/point_start_timing.txt)
+                if (end && st + 1 < c.max_steps) point_start_state(bx, a.stream, (unsigned long long)(row + c.n_envs), O, s);
+            } else
             if (st + 1 < c.max_steps) {
                 const long long nxt = row + c.n_envs;
                 for (int k = 0; k < O; ++k) {
@@ -591,8 +651,9 @@ PROMP_DEV void point_norm_enter(const PointNormArgs& n, PointNormState& w, const
 // The tail of vectorised step st of environment env under the wrapper, shared by k_point_norm_collect and k_gen_point_norm_collect:
 // k_point_collect's tail (the environment steps on (a0, a1), the step's reward and end_len are filed under `row`, the next
 // episode's reset() is taken from the start table) with the wrapper's events in it, and the moments staged behind them.
-PROMP_DEV void point_norm_collect_tail(const PointCollectArgs& c, const PointNormArgs& n, PointNormState& w, double* s, const double* tp,
-                                       float a0, float a1, long long row, long long env, int st, int& len) {
+template <bool DEVICE_START>
+PROMP_DEV void point_norm_collect_tail(const PointCollectArgs& c, const PointNormArgs& n, const PointStartBox& bx, PointNormState& w, double* s,
+                                       const double* tp, float a0, float a1, long long row, long long env, int st, int& len) {
     const PointRolloutArgs& a = c.f.p;
     const int O = c.f.state_dim;
     bool done;
@@ -608,6 +669,13 @@ PROMP_DEV void point_norm_collect_tail(const PointCollectArgs& c, const PointNor
     c.end_len[row] = end ? len : 0;
     len = end ? 0 : len;
     const long long nxt = row + c.n_envs;                         // (the table has a row behind the last step)
+    if constexpr (DEVICE_START) {
+        // drawn every step and selected, as the table reload is (the row behind the last step too): under the wrapper the draw
+        // beneath `if (end)`, which the plain kernels have, measured 2 % slower (profiles/point_start_timing.txt)
+        double fresh[4] = {0.0, 0.0, 0.0, 0.0};
+        point_start_state(bx, a.stream, (unsigned long long)nxt, O, fresh);
+        for (int k = 0; k < O; ++k) s[k] = end ? fresh[k] : s[k];
+    } else
     for (int k = 0; k < O; ++k) {
         const double fresh = a.start[nxt * O + k];
         s[k] = end ? fresh : s[k];
@@ -629,7 +697,8 @@ struct PointNormCollectArgs {
 };
 // grid = tasks, block = 64: k_point_collect under the normalize wrapper's running moments (a sibling: k_point_collect itself is
 // untouched, so the plain collection is the same machine code as before)
-__global__ void __launch_bounds__(64) k_point_norm_collect(PointNormCollectArgs g) {
+template <bool DEVICE_START>
+__global__ void __launch_bounds__(64) k_point_norm_collect(PointNormCollectArgs g, PointStartBox bx) {
     const PointCollectArgs& c = g.c;
     const PointNormArgs& n = g.n;
     const PointFamilyArgs& f = c.f;
@@ -647,6 +716,8 @@ __global__ void __launch_bounds__(64) k_point_norm_collect(PointNormCollectArgs 
     for (int b = threadIdx.x; b < a.B; b += 64) {
         const long long env = (long long)task * a.B + b;
         double s[4] = {0.0, 0.0, 0.0, 0.0};
+        if constexpr (DEVICE_START) point_start_state(bx, a.stream, (unsigned long long)env, O, s);
+        else
         for (int k = 0; k < O; ++k) s[k] = a.start[env * O + k];
         PointNormState w;
         point_norm_enter(n, w, s, O, env);
@@ -667,7 +738,7 @@ __global__ void __launch_bounds__(64) k_point_norm_collect(PointNormCollectArgs 
             for (int k = 0; k < O; ++k) a.obs[row * O + k] = o[k];
             a.mean[row * 2] = m[0];  a.mean[row * 2 + 1] = m[1];
             a.act[row * 2] = a0;  a.act[row * 2 + 1] = a1;
-            point_norm_collect_tail(c, n, w, s, tp, a0, a1, row, env, st, len);
+            point_norm_collect_tail<DEVICE_START>(c, n, bx, w, s, tp, a0, a1, row, env, st, len);
         }
     }
 }

@@ -9,8 +9,10 @@ resident and uploads nothing.
 MetaPointEnv and MetaPointEnvV2 end their episodes early (`done` at the origin): promp_collect_point_family runs every environment
 for as many vectorised steps as the reference's sampler could need, finds its stop step and lists the finished episodes on the
 device; the slab is ragged and envs_per_task is honoured (_obtain_terminating).
-The host keeps what it is good at: drawing tasks, start states and the exploration noise from NumPy's RNG, and
-materialising the path dicts the plugin API returns (one small download per sampling step)."""
+The host keeps what it is good at: drawing tasks and, unless told otherwise, start states and the exploration noise from NumPy's
+RNG, and materialising the path dicts the plugin API returns (one small download per sampling step).  device_noise=True draws the
+noise, device_starts=True every reset() on the device (Philox4x32-10, two counter domains under one seed per sampling step): a
+sampling step then uploads the task parameters and nothing else."""
 from collections import OrderedDict
 
 import numpy as np
@@ -95,6 +97,13 @@ def _point_env_options(env):
                       sparse_radius=float(bare.sparse_reward_radius))
 
 
+def _point_start_box(kind):
+    """(lo, hi) of the class's reset(): corner, walls uniform(-0.2, 0.2, 2); momentum and a velocity uniform(-0.1, 0.1, 2);
+    MetaPointEnv uniform(-2, 2, 2); MetaPointEnvV2 zeros(2)"""
+    hi = dict(corner=[0.2, 0.2], walls=[0.2, 0.2], momentum=[0.2, 0.2, 0.1, 0.1], origin=[2.0, 2.0], goal=[0.0, 0.0])[kind]
+    return [-h for h in hi], hi
+
+
 def _point_env_norm(env):
     """the options of the wrapper's running observation / reward normalisation (promp_point_norm_opts), or None when both are off"""
     from ..envs.normalized_env import NormalizedEnv
@@ -107,10 +116,14 @@ def _point_env_norm(env):
 class DevicePointEnvSampler(object):
     """device_noise=False: start states and exploration noise come from NumPy's RNG (reproducible from np.random.seed, and
     comparable step by step with the NumPy environment); True: the noise is drawn on the device (Philox4x32-10 keyed by a
-    seed taken from NumPy's RNG once per sampling step), nothing but goals and start states is uploaded."""
+    seed taken from NumPy's RNG once per sampling step), nothing but goals and start states is uploaded.
+    device_starts=True: every reset() is drawn on the device too, from the box of the class (promp_point_start_opts), and no start
+    table exists.  Whenever either mode is on, a sampling step draws ONE np.random.randint(0, 2 ** 31 - 1); it keys the noise and the
+    start states (their Philox counters differ in the high bit of word 2) and is kept as self.last_seed, so that a sampling step can
+    be logged and reproduced (Context.draw_point_starts restates its start table)."""
 
     def __init__(self, env, policy, rollouts_per_meta_task, meta_batch_size, max_path_length, envs_per_task=None,
-                 parallel=False, device_noise=False):
+                 parallel=False, device_noise=False, device_starts=False):
         assert hasattr(env, 'sample_tasks') and hasattr(env, 'set_task')
         self.env, self.policy = env, policy
         self._bare, self._env_opts = _point_env_options(env)
@@ -120,6 +133,9 @@ class DevicePointEnvSampler(object):
         assert policy.obs_dim == self.obs_dim and policy.action_dim == 2, \
             'the %s point mass has obs_dim %d and act_dim 2' % (self.kind, self.obs_dim)
         self.device_noise = device_noise
+        self.device_starts = device_starts
+        self.last_seed = None
+        self._start_box = _point_start_box(self.kind)
         self.batch_size = rollouts_per_meta_task
         self.meta_batch_size = meta_batch_size
         self.max_path_length = max_path_length
@@ -188,6 +204,8 @@ class DevicePointEnvSampler(object):
         if sess.task_thetas is not None:           # parameters set while no context existed yet
             ctx.set_task_thetas(sess.task_thetas)
             sess.task_thetas = None
+        if self.device_starts:
+            return self._obtain_fixed_device_starts(sess, ctx, log, log_prefix)
         start = np.random.uniform(-0.2, 0.2, size=(M, B, 2))         # reset() of all three classes
         if self.kind == 'momentum':                                  # MetaPointEnvMomentum.reset: and a velocity
             start = np.concatenate((start, np.random.uniform(-0.1, 0.1, size=(M, B, 2))), axis=2)
@@ -197,11 +215,28 @@ class DevicePointEnvSampler(object):
         else:
             rollout = lambda slot, *args, **kw: ctx.rollout_point_family(slot, self.kind, *args, **kw)
         if self.device_noise:
+            self.last_seed = int(np.random.randint(0, 2 ** 31 - 1))
             rollout(slot, self.goals, start, None, clip_infos=self.policy._pre_update_mode, path_length=T,
-                    seed=int(np.random.randint(0, 2 ** 31 - 1)), **self._env_opts)
+                    seed=self.last_seed, **self._env_opts)
         else:
             noise = np.random.normal(size=(M, B, T, 2)).astype(np.float32)
             rollout(slot, self.goals, start, noise, clip_infos=self.policy._pre_update_mode, **self._env_opts)
+        return self._rectangular_paths(sess, ctx, slot, log, log_prefix)
+
+    def _draw_seed(self):
+        """one draw per sampling step -> (the seed, dict(lo, hi, seed) for the start states)"""
+        self.last_seed = int(np.random.randint(0, 2 ** 31 - 1))
+        return self.last_seed, dict(lo=self._start_box[0], hi=self._start_box[1], seed=self.last_seed)
+
+    def _obtain_fixed_device_starts(self, sess, ctx, log, log_prefix):
+        """corner / walls / momentum, start states drawn on the device under row = environment.  Corner goes through the family's
+        entry point, which reproduces promp_rollout_point_env bit for bit."""
+        M, B, T = self.meta_batch_size, self.envs_per_task, self.max_path_length
+        seed, starts = self._draw_seed()
+        noise = None if self.device_noise else np.random.normal(size=(M, B, T, 2)).astype(np.float32)
+        slot = sess.next_slot()
+        ctx.rollout_point_family(slot, self.kind, self.goals, None, noise, clip_infos=self.policy._pre_update_mode, path_length=T,
+                                 seed=seed, starts=starts, envs_per_task=B, **self._env_opts)
         return self._rectangular_paths(sess, ctx, slot, log, log_prefix)
 
     def _rectangular_paths(self, sess, ctx, slot, log, log_prefix):
@@ -248,11 +283,21 @@ class DevicePointEnvSampler(object):
             ctx.set_task_thetas(sess.task_thetas)
             sess.task_thetas = None
         self._push_norm(ctx)
+        kw = dict(total_samples=n_envs * T, max_path_length=T, clip_infos=self.policy._pre_update_mode, norm=self._norm, **self._env_opts)
+        if self.device_starts:
+            seed, starts = self._draw_seed()
+            noise = None if self.device_noise else np.random.normal(size=(T, n_envs, 2)).astype(np.float32)
+            slot = sess.next_slot()
+            tables = ctx.collect_point_family(slot, self.kind, self.goals, None, noise, seed=seed, starts=starts, envs_per_task=B,
+                                              max_steps=T, **kw)
+            assert tables['n_steps'] == T and np.array_equal(tables['path_env'], np.arange(n_envs))
+            self._pull_norm(ctx)
+            return self._rectangular_paths(sess, ctx, slot, log, log_prefix)
         start = self._reset_states((T + 1, n_envs, 2))
         slot = sess.next_slot()
-        kw = dict(total_samples=n_envs * T, max_path_length=T, clip_infos=self.policy._pre_update_mode, norm=self._norm, **self._env_opts)
         if self.device_noise:
-            tables = ctx.collect_point_family(slot, self.kind, self.goals, start, None, seed=int(np.random.randint(0, 2 ** 31 - 1)), **kw)
+            self.last_seed = int(np.random.randint(0, 2 ** 31 - 1))
+            tables = ctx.collect_point_family(slot, self.kind, self.goals, start, None, seed=self.last_seed, **kw)
         else:
             noise = np.random.normal(size=(T, n_envs, 2)).astype(np.float32)
             tables = ctx.collect_point_family(slot, self.kind, self.goals, start, noise, **kw)
@@ -275,7 +320,9 @@ class DevicePointEnvSampler(object):
             ctx.set_task_thetas(sess.task_thetas)
             sess.task_thetas = None
         n_start = max_steps if self._norm is None else max_steps + 1       # normalised: and the reset() behind the last step
-        if self.kind == 'origin':                  # MetaPointEnv.reset
+        if self.device_starts:                     # no table: every reset() is drawn where an episode ends
+            start = None
+        elif self.kind == 'origin':                # MetaPointEnv.reset
             start = np.random.uniform(-2, 2, size=(n_start, n_envs, 2))
         else:                                      # MetaPointEnvV2.reset
             start = np.zeros((n_start, n_envs, 2))
@@ -285,8 +332,14 @@ class DevicePointEnvSampler(object):
             self._push_norm(ctx)
             kw['norm'] = self._norm
         try:
-            if self.device_noise:
-                tables = ctx.collect_point_family(slot, 'goal', self.goals, start, None, seed=int(np.random.randint(0, 2 ** 31 - 1)), **kw)
+            if self.device_starts:
+                seed, starts = self._draw_seed()
+                noise = None if self.device_noise else np.random.normal(size=(max_steps, n_envs, 2)).astype(np.float32)
+                tables = ctx.collect_point_family(slot, 'goal', self.goals, None, noise, seed=seed, starts=starts, envs_per_task=B,
+                                                  max_steps=max_steps, **kw)
+            elif self.device_noise:
+                self.last_seed = int(np.random.randint(0, 2 ** 31 - 1))
+                tables = ctx.collect_point_family(slot, 'goal', self.goals, start, None, seed=self.last_seed, **kw)
             else:
                 noise = np.random.normal(size=(max_steps, n_envs, 2)).astype(np.float32)
                 tables = ctx.collect_point_family(slot, 'goal', self.goals, start, noise, **kw)

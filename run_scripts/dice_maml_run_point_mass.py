@@ -36,6 +36,7 @@ DEFAULT = {
     'vpg': False,                  # True: VPG_DICEMAML (DiCE inner steps, vanilla policy gradient outside) with a return baseline
     'device_rollouts': True,       # False: MetaSampler on the host (the processor then uploads each batch once)
     'device_noise': False,
+    'device_starts': False,        # every reset() drawn on the device (Philox); no start table is built or uploaded
 }
 
 BASELINES = {'LinearFeatureBaseline': LinearFeatureBaseline, 'LinearTimeBaseline': LinearTimeBaseline}
@@ -54,7 +55,8 @@ def main(config):
                           meta_batch_size=config['meta_batch_size'], max_path_length=config['max_path_length'],
                           parallel=config['parallel'])
     if config.get('device_rollouts', True):
-        sampler = DevicePointEnvSampler(device_noise=bool(config.get('device_noise')), **sampler_kwargs)
+        sampler = DevicePointEnvSampler(device_noise=bool(config.get('device_noise')), device_starts=bool(config.get('device_starts')),
+                                        **sampler_kwargs)
     else:
         sampler = MetaSampler(**sampler_kwargs)
     extra = dict(return_baseline=LinearFeatureBaseline()) if config.get('vpg') else {}
@@ -85,6 +87,8 @@ if __name__ == '__main__':
     ap.add_argument('--normalize_reward', action='store_true', help='the normalize wrapper\'s running reward normalisation')
     ap.add_argument('--obs_alpha', type=float, default=None, help='step size of the running observation moments (default 0.001)')
     ap.add_argument('--reward_alpha', type=float, default=None, help='step size of the running reward moments (default 0.001)')
+    ap.add_argument('--device_starts', action='store_true',
+                    help='with device_rollouts: start states drawn on the device instead of NumPy\'s RNG (use with device_noise)')
     ap.add_argument('--quiet', action='store_true')
     args = ap.parse_args()
     cfg = dict(DEFAULT)
@@ -98,7 +102,7 @@ if __name__ == '__main__':
         cfg['n_itr'] = args.n_itr
     if args.vpg:
         cfg['vpg'] = True
-    for key in ('normalize_obs', 'normalize_reward'):
+    for key in ('normalize_obs', 'normalize_reward', 'device_starts'):
         if getattr(args, key):
             cfg[key] = True
     for key in ('obs_alpha', 'reward_alpha'):

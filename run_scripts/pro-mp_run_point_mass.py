@@ -34,6 +34,7 @@ DEFAULT = {
     'n_itr': 100, 'meta_batch_size': 4, 'num_inner_grad_steps': 1,
     'device_rollouts': False,      # True: the environment itself runs on the GPU (samplers/device_point_sampler.py)
     'device_noise': False,         # with device_rollouts: exploration noise drawn on the device (Philox) instead of NumPy's RNG
+    'device_starts': False,        # with device_rollouts: every reset() drawn on the device too; no start table is built or uploaded
 }
 
 
@@ -52,7 +53,8 @@ def main(config):
                           meta_batch_size=config['meta_batch_size'], max_path_length=config['max_path_length'],
                           parallel=config['parallel'])
     if config.get('device_rollouts'):
-        sampler = DevicePointEnvSampler(device_noise=bool(config.get('device_noise')), **sampler_kwargs)
+        sampler = DevicePointEnvSampler(device_noise=bool(config.get('device_noise')), device_starts=bool(config.get('device_starts')),
+                                        **sampler_kwargs)
     else:
         sampler = MetaSampler(**sampler_kwargs)
     sample_processor = MetaSampleProcessor(baseline=baseline, discount=config['discount'], gae_lambda=config['gae_lambda'],
@@ -90,6 +92,8 @@ if __name__ == '__main__':
     ap.add_argument('--normalize_reward', action='store_true', help='the normalize wrapper\'s running reward normalisation')
     ap.add_argument('--obs_alpha', type=float, default=None, help='step size of the running observation moments (default 0.001)')
     ap.add_argument('--reward_alpha', type=float, default=None, help='step size of the running reward moments (default 0.001)')
+    ap.add_argument('--device_starts', action='store_true',
+                    help='with device_rollouts: start states drawn on the device instead of NumPy\'s RNG (use with device_noise)')
     ap.add_argument('--quiet', action='store_true')
     args = ap.parse_args()
     cfg = dict(DEFAULT)
@@ -109,7 +113,7 @@ if __name__ == '__main__':
         cfg['outer_optimizer_args'] = dict(cfg.get('outer_optimizer_args') or {}, epsilon=args.adam_epsilon)
     if args.max_grad_norm is not None:
         cfg['max_grad_norm'] = args.max_grad_norm
-    for key in ('normalize_obs', 'normalize_reward'):
+    for key in ('normalize_obs', 'normalize_reward', 'device_starts'):
         if getattr(args, key):
             cfg[key] = True
     for key in ('obs_alpha', 'reward_alpha'):

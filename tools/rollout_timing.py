@@ -22,7 +22,15 @@
                                                          wrapper's running moments off (the plain kernels), on the observations, and
                                                          on observations and rewards: what staging the moments behind every step
                                                          ([199][2 O + 2][800] float64) and the commit launch cost.  A --lib from before
-                                                         the entry point runs the plain call only."""
+                                                         the entry point runs the plain call only.
+    python tools/rollout_timing.py --launch --collect [--normalize] --device-starts [--kinds corner goal]
+                                                         the same calls through promp_collect_point_family_dev: every reset() drawn on
+                                                         the device from the class's box (corner +-0.2, goal lo = hi = 0), no start
+                                                         table reserved or uploaded.  Not with a --lib from before the entry point.
+    python tools/rollout_timing.py --sampler-starts [--kinds goal origin corner]
+                                                         host time of one DevicePointEnvSampler.obtain_samples at M 40, B 20, T 100,
+                                                         (64,64) with device noise, start states from NumPy against device_starts=True:
+                                                         where the host's draw of the start table shows."""
 import argparse
 import sys
 import time
@@ -61,7 +69,8 @@ def bind(lib_path, kinds, need_family=False):
     from promp_amd import _lib
     if not lib_path:
         return _lib.Library()
-    newest = ['promp_collect_point_family_norm', 'promp_point_norm_set', 'promp_point_norm_get', 'promp_collect_point_family',
+    newest = ['promp_collect_point_family_dev', 'promp_rollout_point_family_dev', 'promp_draw_point_starts',
+              'promp_collect_point_family_norm', 'promp_point_norm_set', 'promp_point_norm_get', 'promp_collect_point_family',
               'promp_rollout_point_family']
     held = {}
     try:
@@ -91,7 +100,37 @@ def timed(run, ctx, repeats, launches, warm=20):
     return 1e6 * np.array(times)
 
 
-def collect_times(kinds, lib_path, repeats, launches, label, normalize=False):
+def sampler_start_times(kinds, repeats, launches):
+    from promp_amd.envs.normalized_env import normalize
+    from promp_amd.envs.point_env import make_point_env
+    from promp_amd.policies.meta_gaussian_mlp_policy import MetaGaussianMLPPolicy
+    from promp_amd.samplers.device_point_sampler import DevicePointEnvSampler
+    M, B, T, hidden = 40, 20, 100, (64, 64)
+    for kind in kinds:
+        for wrapper in (dict(), dict(normalize_obs=True, normalize_reward=True)):
+            for device_starts in (False, True):
+                np.random.seed(0)
+                env = normalize(make_point_env(kind), **wrapper)
+                policy = MetaGaussianMLPPolicy(name='p', obs_dim=int(np.prod(env.observation_space.shape)), action_dim=2,
+                                               meta_batch_size=M, hidden_sizes=hidden)
+                policy.switch_to_pre_update()
+                s = DevicePointEnvSampler(env=env, policy=policy, rollouts_per_meta_task=B, meta_batch_size=M, max_path_length=T,
+                                          envs_per_task=B, device_noise=True, device_starts=device_starts)
+                s.update_tasks()
+                s.obtain_samples()
+                times = []
+                for _ in range(repeats):
+                    t0 = time.perf_counter()
+                    for _ in range(launches):
+                        s.obtain_samples()
+                    times.append((time.perf_counter() - t0) / launches)
+                ms = 1e3 * np.array(times)
+                print('obtain_samples %-8s %-10s device_starts %-5s  median %9.3f ms  min %9.3f  max %9.3f  (%d windows of %d calls)' % (
+                    kind, 'normalised' if wrapper else 'plain', device_starts, np.median(ms), ms.min(), ms.max(), repeats, launches),
+                    flush=True)
+
+
+def collect_times(kinds, lib_path, repeats, launches, label, normalize=False, device_starts=False):
     from promp_amd import _lib, synthetic
     M, B, T, hidden = 40, 20, 100, (64, 64)
     S, N = 2 * T - 1, M * B
@@ -108,15 +147,18 @@ def collect_times(kinds, lib_path, repeats, launches, label, normalize=False):
             tasks, start, max_step = rng.randn(M, task_dim), rng.uniform(-0.2, 0.2, size=(S, N, O)), 0.2 if kind != 'momentum' else 0.1
         z = rng.randn(S, N, 2).astype(np.float32)
         out = {}
+        # device starts: the box the table above was drawn from; no table is handed over
+        half = 0.0 if kind == 'goal' else 0.2
+        dev = dict(starts=dict(lo=[-half] * O, hi=[half] * O, seed=12345), envs_per_task=B, max_steps=S) if device_starts else {}
         if normalize:
-            norm_times(ctx, lib, kind, tasks, start, z, max_step, S, N, T, O, repeats, launches, label)
+            norm_times(ctx, lib, kind, tasks, start, z, max_step, S, N, T, O, repeats, launches, label, dev)
             ctx.close()
             continue
         for noise in ('host', 'device'):
             def run():
-                out['t'] = ctx.collect_point_family(0, kind, tasks, start, z if noise == 'host' else None, total_samples=N * T,
-                                                    max_path_length=T, seed=12345, reward_type='dense', normalization_scale=10.0,
-                                                    max_step=max_step)
+                out['t'] = ctx.collect_point_family(0, kind, tasks, None if dev else start, z if noise == 'host' else None,
+                                                    total_samples=N * T, max_path_length=T, seed=12345, reward_type='dense',
+                                                    normalization_scale=10.0, max_step=max_step, **dev)
             us = timed(run, ctx, repeats, launches, warm=5)
             t = out['t']
             print('%scollect %-8s %-6s noise  median %9.2f us per call  min %9.2f  max %9.2f  = %7.2f us per vectorised step (%d steps); '
@@ -126,10 +168,11 @@ def collect_times(kinds, lib_path, repeats, launches, label, normalize=False):
         ctx.close()
 
 
-def norm_times(ctx, lib, kind, tasks, start, z, max_step, S, N, T, O, repeats, launches, label):
+def norm_times(ctx, lib, kind, tasks, start, z, max_step, S, N, T, O, repeats, launches, label, dev):
     """host noise; plain: promp_collect_point_family; off / obs / both: promp_collect_point_family_norm with a start table one row
     longer.  The moments start as a fresh wrapper's and move on from call to call (step sizes 0.001, the wrapper's default)."""
     modes = [('plain', None)]
+    longer = None
     if hasattr(lib.cdll, 'promp_collect_point_family_norm'):
         modes += [(name, dict(normalize_obs=n_obs, normalize_reward=n_rew, obs_alpha=0.001, reward_alpha=0.001))
                   for name, n_obs, n_rew in (('off', False, False), ('obs', True, False), ('both', True, True))]
@@ -139,8 +182,9 @@ def norm_times(ctx, lib, kind, tasks, start, z, max_step, S, N, T, O, repeats, l
     out = {}
     for name, norm in modes:
         def run():
-            out['t'] = ctx.collect_point_family(0, kind, tasks, start if norm is None else longer, z, total_samples=N * T, max_path_length=T,
-                                                seed=12345, reward_type='dense', normalization_scale=10.0, max_step=max_step, norm=norm)
+            table = None if dev else start if norm is None else longer
+            out['t'] = ctx.collect_point_family(0, kind, tasks, table, z, total_samples=N * T, max_path_length=T, seed=12345,
+                                                reward_type='dense', normalization_scale=10.0, max_step=max_step, norm=norm, **dev)
         us = timed(run, ctx, repeats, launches, warm=5)
         t = out['t']
         print('%scollect %-8s normalize %-5s  median %9.2f us per call  min %9.2f  max %9.2f  = %7.2f us per vectorised step (%d steps); '
@@ -182,15 +226,21 @@ if __name__ == '__main__':
     ap.add_argument('--collect', action='store_true')
     ap.add_argument('--wide', action='store_true')
     ap.add_argument('--normalize', action='store_true')
-    ap.add_argument('--kinds', nargs='+', default=None, choices=['corner', 'walls', 'momentum', 'goal'])
+    ap.add_argument('--device-starts', action='store_true')
+    ap.add_argument('--sampler-starts', action='store_true')
+    ap.add_argument('--kinds', nargs='+', default=None, choices=['corner', 'walls', 'momentum', 'goal', 'origin'])
     ap.add_argument('--lib', type=str, default='')
     ap.add_argument('--label', type=str, default='')
     ap.add_argument('--repeats', type=int, default=7)
     ap.add_argument('--launches', type=int, default=300)
     args = ap.parse_args()
     label = args.label and args.label + ' '
-    if args.launch and args.collect:
-        collect_times(args.kinds or ['corner', 'goal'], args.lib, args.repeats, args.launches, label, args.normalize)
+    if args.device_starts:
+        assert args.launch and args.collect, '--device-starts goes with --launch --collect [--normalize] [--lib PATH]'
+    if args.sampler_starts:
+        sampler_start_times(args.kinds or ['goal', 'origin', 'corner'], args.repeats, args.launches)
+    elif args.launch and args.collect:
+        collect_times(args.kinds or ['corner', 'goal'], args.lib, args.repeats, args.launches, label, args.normalize, args.device_starts)
     elif args.launch:
         launch_times(args.kinds or ['corner', 'walls', 'momentum'], args.lib, args.repeats, args.launches, label, args.wide)
     else:
