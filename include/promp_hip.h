@@ -477,6 +477,59 @@ int promp_collect_point_family_dev(promp_ctx* ctx, int step, int envs_per_task, 
                                    const promp_point_norm_opts* norm /* or NULL */, int32_t* n_paths, int32_t* n_steps,
                                    int32_t* task_path_offsets, int32_t* path_env, int32_t* path_start, int32_t* path_len);
 
+/* (c) ENVIRONMENTS THAT LIVE ON THE DEVICE: (a) and (a') for a simulator that runs on the same GPU (a vectorised environment written
+ *     with an array library on ROCm, a kernel of the caller's).  Observations, actions, rewards and `done` flags never visit the
+ *     host, and no call of the per-step loop synchronises.
+ *     ORDERING.  Every entry point below that reads or writes caller device memory takes `producer_stream`: the hipStream_t the
+ *     caller's simulator enqueues on, 0 = the null stream.  At entry the context's stream waits for an event recorded on the
+ *     producer stream; before returning, the producer stream waits for an event recorded on the context's stream.  So the call
+ *     sees everything the producer enqueued before it, and the caller may overwrite its buffers right after the call and read the
+ *     outputs in stream order, without synchronising.  Two events per context, timing disabled; no stream is created.
+ *     POINTERS.  promp_check_device_pointer returns 0 when the GPU can read through the pointer (device memory, page-locked host
+ *     memory), -1 with a message otherwise (NULL, pageable host memory); it launches nothing.  Every *_dev entry point applies it
+ *     to every caller pointer before it enqueues anything: a host pointer never reaches a kernel.
+ *   promp_policy_step_dev  promp_policy_step with d_obs [n_tasks][B][O] and d_actions [n_tasks][B][A] in device memory, after
+ *     promp_begin_rollout or promp_begin_collection: no copy, no synchronisation.  The same kernels file the same slab / staging
+ *     rows under the same Philox counter and stream word: for equal observations and seed, rows and actions are bit for bit those
+ *     of promp_policy_step.  Asynchronous.
+ *   promp_file_step_dev  files the outcome of vectorised step s, one thread per environment (environment = task * B + b).  The
+ *     context keeps a per-environment episode length, zeroed by s = 0:
+ *       len = ep_len[env] + 1;  end = (d_done && d_done[env]) || len == max_path_length
+ *       staged reward (s, env) = d_rewards[env];  end_len (s, env) = end ? len : 0;  ep_len[env] = end ? 0 : len
+ *       d_ended_out[env] = end
+ *     -- what k_point_collect files for its own environments.  The simulator must reset the environments flagged in d_ended_out
+ *     before the next policy step.  d_done and d_ended_out may each be NULL.  After promp_begin_rollout (fixed horizon) the reward
+ *     goes straight to slab row env * T + s, d_done is not read and `end` is s == T - 1.  Steps are filed in order 0, 1, 2, ...,
+ *     once each, each after its policy step; anything else is refused by name from host-side counters before any launch.
+ *     Asynchronous.
+ *   promp_collection_progress  the stop rule of (b'') over the steps filed so far: *stop_step = s*, the first step after which
+ *     total_samples steps lie in finished episodes, with *finished_rows their number at s*; -1 (and 0): not reached yet.
+ *     Synchronous.
+ *   promp_end_collection_dev  the tail of (b'') over the filed steps: stop step, path tables (count, offsets, write), the same
+ *     validations and refusals, then the finished episodes and their staged rewards go to the slab.  Out: as
+ *     promp_collect_point_family.  A refused call installs nothing and leaves the collection open; when total_samples has not been
+ *     reached, more steps can be filed and the call repeated.  Steps filed beyond s* are ignored.  Synchronous.
+ *   promp_upload_step_dev  promp_upload_step with obs, act, rew, old_mean and old_log_std in device memory (the two offset tables
+ *     stay on the host): device-to-device copies; the step is then in every respect what promp_upload_step leaves.
+ *   promp_dev_alloc / promp_dev_free / promp_dev_upload / promp_dev_download  hipMalloc, hipFree and synchronous copies on the
+ *     context's device and stream, for callers without a GPU array library.
+ *   Not here: running normalisation of an external environment, env_infos, float64 rewards, sharding one environment over ranks. */
+int promp_check_device_pointer(const void* p);
+void* promp_dev_alloc(promp_ctx* ctx, size_t bytes);
+void promp_dev_free(promp_ctx* ctx, void* p);
+int promp_dev_upload(promp_ctx* ctx, void* dst_device, const void* src_host, size_t bytes);
+int promp_dev_download(promp_ctx* ctx, void* dst_host, const void* src_device, size_t bytes);
+int promp_policy_step_dev(promp_ctx* ctx, int step, int t, const float* d_obs, uint64_t seed, int clip_infos, float* d_actions,
+                          void* producer_stream);
+int promp_file_step_dev(promp_ctx* ctx, int step, int s, const float* d_rewards, const uint8_t* d_done, int max_path_length,
+                        uint8_t* d_ended_out, void* producer_stream);
+int promp_collection_progress(promp_ctx* ctx, int step, int64_t total_samples, int32_t* stop_step, int64_t* finished_rows);
+int promp_end_collection_dev(promp_ctx* ctx, int step, int64_t total_samples, int32_t* n_paths, int32_t* n_steps,
+                             int32_t* task_path_offsets, int32_t* path_env, int32_t* path_start, int32_t* path_len);
+int promp_upload_step_dev(promp_ctx* ctx, int step, int n_paths, const int32_t* task_path_offsets, const int32_t* path_row_offsets,
+                          const float* obs, const float* act, const float* rew, const float* old_mean, const float* old_log_std,
+                          int log_std_per_row, void* producer_stream);
+
 /* Step slab back on the host (any pointer may be NULL): obs [rows][O], act [rows][A], rew [rows],
  * old_mean [rows][A], old_log_std [rows | n_tasks][A] as uploaded / produced by a device rollout. */
 int promp_download_step(promp_ctx* ctx, int step, float* obs, float* act, float* rew, float* old_mean, float* old_log_std);

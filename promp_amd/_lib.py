@@ -145,6 +145,16 @@ SIGNATURES = {
     'promp_begin_collection': (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     'promp_end_collection': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _F]),
     'promp_policy_step': (C.c_int, [_P, C.c_int, C.c_int, _F, C.c_uint64, C.c_int, _F]),
+    'promp_check_device_pointer': (C.c_int, [_P]),
+    'promp_dev_alloc': (C.c_void_p, [_P, C.c_size_t]),
+    'promp_dev_free': (None, [_P, _P]),
+    'promp_dev_upload': (C.c_int, [_P, _P, _P, C.c_size_t]),
+    'promp_dev_download': (C.c_int, [_P, _P, _P, C.c_size_t]),
+    'promp_policy_step_dev': (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_uint64, C.c_int, _P, _P]),
+    'promp_file_step_dev': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
+    'promp_collection_progress': (C.c_int, [_P, C.c_int, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    'promp_end_collection_dev': (C.c_int, [_P, C.c_int, C.c_int64, _I, _I, _I, _I, _I, _I]),
+    'promp_upload_step_dev': (C.c_int, [_P, C.c_int, C.c_int, _I, _I, _P, _P, _P, _P, _P, C.c_int, _P]),
     'promp_set_rewards': (C.c_int, [_P, C.c_int, _F]),
     'promp_download_step': (C.c_int, [_P, C.c_int, _F, _F, _F, _F, _F]),
     'promp_meta_grad': (C.c_int, [_P, C.c_float, _F, C.c_int, C.c_int, _F, _F]),
@@ -235,6 +245,111 @@ def pinned_empty(lib, shape, dtype=np.float32):
     raw = (C.c_char * nbytes).from_address(ptr)
     weakref.finalize(raw, lib.cdll.promp_host_free, C.c_void_p(ptr))     # every view keeps `raw` alive through .base
     return np.frombuffer(raw, dtype=dtype, count=count).reshape(shape)
+
+
+def _dev_release(ctx, ptr):
+    if ctx._h:                      # (a closed context's device memory goes with the process)
+        ctx.lib.cdll.promp_dev_free(ctx._h, C.c_void_p(ptr))
+
+
+class DeviceArray(object):
+    """A block of device memory of a context's GPU (promp_dev_alloc): pointer, shape, dtype; upload(ndarray) and download() are
+    synchronous copies on the context's stream.  For callers without a GPU array library, and the tests: what an environment
+    that lives on the GPU hands to Context.policy_step_dev / file_step_dev is any object device_pointer() understands."""
+
+    def __init__(self, ctx, shape, dtype=np.float32):
+        self.ctx = ctx
+        self.shape = tuple(int(x) for x in (shape if isinstance(shape, (tuple, list)) else (shape,)))
+        self.dtype = np.dtype(dtype)
+        self.size = int(np.prod(self.shape))
+        self.nbytes = self.size * self.dtype.itemsize
+        ptr = ctx.lib.cdll.promp_dev_alloc(ctx._h, C.c_size_t(self.nbytes))
+        if not ptr:
+            raise PrompError(ctx.lib.cdll.promp_last_error().decode())
+        self.ptr = int(ptr)
+        self._finalizer = weakref.finalize(self, _dev_release, ctx, self.ptr)
+
+    @property
+    def __cuda_array_interface__(self):     # (zero-copy views for GPU array libraries: torch.as_tensor(a, device='cuda'), cupy.asarray(a))
+        return dict(shape=self.shape, typestr=self.dtype.str, data=(self.ptr, False), version=2, strides=None)
+
+    def free(self):
+        self._finalizer()
+        self.ptr = 0
+
+    def upload(self, a):
+        a = np.ascontiguousarray(a, dtype=self.dtype)
+        if a.size != self.size:
+            raise PrompError('DeviceArray.upload: %d elements given, the array holds %d' % (a.size, self.size))
+        self.ctx._call('promp_dev_upload', C.c_void_p(self.ptr), a.ctypes.data_as(C.c_void_p), C.c_size_t(self.nbytes))
+        return self
+
+    def download(self):
+        out = np.empty(self.shape, self.dtype)
+        self.ctx._call('promp_dev_download', out.ctypes.data_as(C.c_void_p), C.c_void_p(self.ptr), C.c_size_t(self.nbytes))
+        return out
+
+
+_TORCH_DTYPES = {'float32': ('torch.float32',), 'uint8': ('torch.uint8', 'torch.bool')}
+
+
+def device_pointer(x, dtype, count, what='array'):
+    """The device address of `x` for an entry point that reads or writes `count` elements of `dtype` through it.  x: None (-> None), an
+    int (taken as it is: the caller's business), a DeviceArray, an object with data_ptr() (a torch tensor: must be contiguous, of
+    the dtype and on the GPU) or an object with __cuda_array_interface__ (CuPy, Numba: C-contiguous, of the dtype).  Anything
+    else -- a NumPy array above all -- is refused by name.  No GPU array library is imported here."""
+    if x is None:
+        return None
+    if isinstance(x, (int, np.integer)) and not isinstance(x, bool):
+        return int(x)
+    dt = np.dtype(dtype)
+    if isinstance(x, DeviceArray):
+        if x.dtype != dt:
+            raise PrompError('%s: DeviceArray of dtype %s, %s expected' % (what, x.dtype, dt))
+        if x.size != int(count):
+            raise PrompError('%s: DeviceArray of %d elements, %d expected' % (what, x.size, int(count)))
+        if not x.ptr:
+            raise PrompError('%s: the DeviceArray has been freed' % what)
+        return x.ptr
+    if hasattr(x, 'data_ptr'):
+        if str(x.dtype) not in _TORCH_DTYPES[dt.name]:
+            raise PrompError('%s: tensor of dtype %s, %s expected' % (what, x.dtype, ' or '.join(_TORCH_DTYPES[dt.name])))
+        if not x.is_contiguous():
+            raise PrompError('%s: the tensor is not contiguous' % what)
+        if not getattr(x, 'is_cuda', False):
+            raise PrompError('%s: the tensor lives on %s, not on the GPU' % (what, getattr(x, 'device', 'the host')))
+        if int(x.numel()) != int(count):
+            raise PrompError('%s: tensor of %d elements, %d expected' % (what, int(x.numel()), int(count)))
+        return int(x.data_ptr())
+    if hasattr(x, '__cuda_array_interface__'):
+        d = x.__cuda_array_interface__
+        if np.dtype(d['typestr']) != dt:
+            raise PrompError('%s: device array of dtype %s, %s expected' % (what, np.dtype(d['typestr']), dt))
+        shape = tuple(int(n) for n in d['shape'])
+        strides = d.get('strides')
+        if strides is not None:
+            want, acc = [], dt.itemsize
+            for n in reversed(shape):
+                want.append(acc)
+                acc *= n
+            if tuple(strides) != tuple(reversed(want)):
+                raise PrompError('%s: the device array is not C-contiguous' % what)
+        if int(np.prod(shape)) != int(count):
+            raise PrompError('%s: device array of %d elements, %d expected' % (what, int(np.prod(shape)), int(count)))
+        return int(d['data'][0])
+    raise PrompError('%s: %s is not device memory (an int address, a DeviceArray, an object with data_ptr() or with '
+                     '__cuda_array_interface__)' % (what, type(x).__name__))
+
+
+def stream_handle(stream):
+    """the hipStream_t of `stream` as an int: None / 0 the null stream, an int as it is, or an object with .cuda_stream (torch)"""
+    if stream is None:
+        return 0
+    if isinstance(stream, (int, np.integer)):
+        return int(stream)
+    if hasattr(stream, 'cuda_stream'):
+        return int(stream.cuda_stream)
+    raise PrompError('stream %r: None, an int handle or an object with .cuda_stream' % (stream,))
 
 
 class _HostPool(object):
@@ -1070,6 +1185,73 @@ class Context:
         r = _f32(rewards).reshape(-1)
         assert r.size == self.step_rows[step]
         self._call('promp_set_rewards', int(step), _ptr(r, C.c_float))
+
+    # ---- environments that live on the device (promp_*_dev) ----
+    def device_array(self, shape, dtype=np.float32):
+        return DeviceArray(self, shape, dtype)
+
+    def check_device_pointer(self, ptr):
+        """raises unless the GPU can read through the address (promp_check_device_pointer); launches nothing"""
+        self.lib.check(self.lib.cdll.promp_check_device_pointer(C.c_void_p(int(ptr)) if ptr else None))
+
+    def policy_step_dev(self, step, t, obs, actions, seed=0, clip_infos=True, stream=None):
+        """promp_policy_step_dev: obs [M, B, O] and actions [M, B, A] are float32 device arrays (device_pointer), stream the
+        simulator's.  Asynchronous: the actions are read in stream order."""
+        n = self.n_tasks * self._rollout_shape[0]
+        self._call('promp_policy_step_dev', int(step), int(t),
+                   device_pointer(obs, np.float32, n * self.dims.obs_dim, 'policy_step_dev: obs'), int(seed), int(bool(clip_infos)),
+                   device_pointer(actions, np.float32, n * self.dims.act_dim, 'policy_step_dev: actions'), stream_handle(stream))
+
+    def file_step_dev(self, step, s, rewards, done=None, max_path_length=0, ended_out=None, stream=None):
+        """promp_file_step_dev: rewards [n_envs] float32, done / ended_out [n_envs] uint8 or None, all device arrays"""
+        n = self.n_tasks * self._rollout_shape[0]
+        self._call('promp_file_step_dev', int(step), int(s), device_pointer(rewards, np.float32, n, 'file_step_dev: rewards'),
+                   device_pointer(done, np.uint8, n, 'file_step_dev: done'), int(max_path_length),
+                   device_pointer(ended_out, np.uint8, n, 'file_step_dev: ended_out'), stream_handle(stream))
+
+    def collection_progress(self, step, total_samples):
+        """-> (stop step or -1, rows in finished episodes at the stop step) over the steps filed so far; synchronous"""
+        stop, rows = C.c_int32(-1), C.c_int64(0)
+        self._call('promp_collection_progress', int(step), int(total_samples), C.byref(stop), C.byref(rows))
+        return int(stop.value), int(rows.value)
+
+    def end_collection_dev(self, step, total_samples):
+        """promp_end_collection_dev -> what collect_point_family returns: dict(n_steps, task_path_offsets, path_row_offsets, path_env,
+        path_start, path_len).  Raises, with the collection still open, while total_samples has not been reached."""
+        self._pre_write(step)
+        M, cap = self.n_tasks, int(self.dims.max_paths)
+        n_paths, n_steps = C.c_int32(0), C.c_int32(0)
+        tpo = np.zeros(M + 1, np.int32)
+        p_env, p_start, p_len = (np.zeros(cap, np.int32) for _ in range(3))
+        self._call('promp_end_collection_dev', int(step), int(total_samples), C.byref(n_paths), C.byref(n_steps), _ptr(tpo, C.c_int32),
+                   _ptr(p_env, C.c_int32), _ptr(p_start, C.c_int32), _ptr(p_len, C.c_int32))
+        n = int(n_paths.value)
+        p_env, p_start, p_len = p_env[:n].copy(), p_start[:n].copy(), p_len[:n].copy()
+        pro = np.concatenate([[0], np.cumsum(p_len)]).astype(np.int32)
+        self.step_rows[step], self.step_paths[step], self.step_ls_rows[step] = int(pro[-1]), n, M
+        self.step_tpo[step] = np.array(tpo, dtype=np.int64)
+        return dict(n_steps=int(n_steps.value), task_path_offsets=tpo, path_row_offsets=pro, path_env=p_env, path_start=p_start,
+                    path_len=p_len)
+
+    def upload_step_dev(self, step, task_path_offsets, path_row_offsets, obs, rew, act=None, old_mean=None, old_log_std=None,
+                        log_std_per_row=False, stream=None):
+        """promp_upload_step_dev: upload_step with obs [rows, O], rew [rows], act / old_mean [rows, A] and old_log_std
+        [rows | n_tasks, A] as float32 device arrays (float32 rewards only); the offset tables are host arrays"""
+        self._pre_write(step)
+        tpo = np.ascontiguousarray(task_path_offsets, dtype=np.int32)
+        pro = np.ascontiguousarray(path_row_offsets, dtype=np.int32)
+        R, O, A = int(pro[-1]), self.dims.obs_dim, self.dims.act_dim
+        ls_rows = R if log_std_per_row else self.n_tasks
+        self._call('promp_upload_step_dev', int(step), int(len(pro) - 1), _ptr(tpo, C.c_int32), _ptr(pro, C.c_int32),
+                   device_pointer(obs, np.float32, R * O, 'upload_step_dev: obs'),
+                   device_pointer(act, np.float32, R * A, 'upload_step_dev: act'),
+                   device_pointer(rew, np.float32, R, 'upload_step_dev: rew'),
+                   device_pointer(old_mean, np.float32, R * A, 'upload_step_dev: old_mean'),
+                   device_pointer(old_log_std, np.float32, ls_rows * A, 'upload_step_dev: old_log_std'),
+                   int(bool(log_std_per_row)), stream_handle(stream))
+        self.step_rows[step], self.step_paths[step] = R, int(len(pro) - 1)
+        self.step_tpo[step] = np.array(tpo, dtype=np.int64)
+        self.step_ls_rows[step] = ls_rows
 
     def download_step(self, step):
         """the slab of a sampling step back on the host: dict(obs, act, rew, old_mean, old_log_std)"""

@@ -258,6 +258,23 @@ PROMP_DEV float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }  // v_e
 PROMP_DEV f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
 #endif
 
+// Host side: can a kernel read through p?  Device memory, page-locked host memory and managed memory, as the runtime's allocation
+// table knows them; NULL, pageable host memory and anything the runtime has never seen cannot (promp_check_device_pointer).  Asks
+// the runtime and launches nothing.  The emulator's "device" is the host's heap: every non-NULL pointer passes there.
+inline bool promp_gpu_readable(const void* p) {
+    if (p == nullptr) return false;
+#ifdef PROMP_EMU
+    return true;
+#else
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();       // (runtimes that report an unknown pointer as an error: not a sticky one)
+        return false;
+    }
+    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeHost || at.type == hipMemoryTypeManaged;
+#endif
+}
+
 // Exact scales of the FP16 split's operands: 2^e as a float (e in [-126, 127]), and the exponent k that brings m = 2^e (1 + f) to
 // [2^t, 2^(t+1)): k = t - e.  (m = 0 / subnormal reads as e = -127, infinity / NaN as e = 128: callers test m and clamp k.)
 PROMP_DEV float pow2f(int e) { return __builtin_bit_cast(float, (unsigned)(e + 127) << 23); }

@@ -129,6 +129,9 @@ struct StepData {
     int n_work[2] = {0, 0};            // [0]: one workgroup per CU (wide passes, gram, fit), [1]: two per CU (k_normalize)
     int rollout_B = 0, rollout_T = 0;  // environments per task / horizon of a device-side rollout in progress (promp_begin_rollout)
     bool rollout_ragged = false;       // promp_begin_collection: rows go to the staging area, rollout_T = its capacity in vectorised steps
+    // promp_policy_step_dev / promp_file_step_dev since the last promp_begin_rollout / promp_begin_collection: policy steps
+    // 0 .. dev_policy_done - 1 have been taken, steps 0 .. dev_filed - 1 filed (host-side counters: every refusal precedes a launch)
+    int dev_policy_done = 0, dev_filed = 0;
     int n_chain_wg = 0;                // workgroups of the register-chained kernels k_pass / k_chain_hvp (segment table)
     bool has_policy = false, processed = false, has_adv = false;
     unsigned long long data_version = 0;   // bumped by every entry point that may change what the policy passes read from this step
@@ -372,6 +375,15 @@ struct promp_ctx {
     bool train_sizes = false;
     bool red_has_sizes = false;          // red's last Theta columns hold the step-size gradient's sums (promp_adam_step needs them)
     DevBuf<float> ginner, galpha, ss_grad, ss_m, ss_v;
+    // environments on the device (the promp_*_dev rollout entry points).  What has to survive between the calls of one collection
+    // has storage of its own -- rollout_buf is re-reserved by the other rollout calls --, reserved by the filing of step 0:
+    // the staged rewards [max_steps][n_envs]; one integer block: end_len [max_steps][n_envs], ep_len [n_envs], step sums [max_steps],
+    // task counts [tasks], task_path_offsets [tasks + 1], path_env / path_start / path_len [max_paths] each; k_collect_stop's record.
+    DevBuf<float> dev_rew_stage;
+    DevBuf<int> dev_tables;
+    DevBuf<long long> dev_stop;
+    // ordering against the caller's stream (producer_enter / producer_leave), created with the first such call, timing disabled
+    Event ev_producer, ev_consumer;
 };
 
 namespace {
@@ -1443,19 +1455,20 @@ static int set_step_layout(promp_ctx* c, StepData& S, hipStream_t st, bool async
 }
 
 static int copy_step_data(promp_ctx* c, StepData& S, hipStream_t st, const float* obs, const float* act, const float* rew,
-                          const float* old_mean, const float* old_ls, int ls_per_row) {
+                          const float* old_mean, const float* old_ls, int ls_per_row,
+                          hipMemcpyKind kind = hipMemcpyHostToDevice) {   // (promp_upload_step_dev: the sources are device memory)
     const int M = c->d.n_tasks;
     const size_t R = (size_t)S.n_rows;
     const size_t O = c->d.obs_dim, A = c->d.act_dim;
-    HIPCHECK(hipMemcpyAsync(S.obs, obs, sizeof(float) * R * O, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(S.obs, obs, sizeof(float) * R * O, kind, st));
     if (enqueue_obs_range(c, pass_slab(S), st)) return -2;
-    HIPCHECK(hipMemcpyAsync(S.rew, rew, sizeof(float) * R, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(S.rew, rew, sizeof(float) * R, kind, st));
     S.has_policy = act && old_mean && old_ls;
     if (S.has_policy) {
         S.ls_per_row = ls_per_row ? 1 : 0;
-        HIPCHECK(hipMemcpyAsync(S.act, act, sizeof(float) * R * A, hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(S.old_mean, old_mean, sizeof(float) * R * A, hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(S.old_ls, old_ls, sizeof(float) * (ls_per_row ? (size_t)R : (size_t)M) * A, hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(S.act, act, sizeof(float) * R * A, kind, st));
+        HIPCHECK(hipMemcpyAsync(S.old_mean, old_mean, sizeof(float) * R * A, kind, st));
+        HIPCHECK(hipMemcpyAsync(S.old_ls, old_ls, sizeof(float) * (ls_per_row ? (size_t)R : (size_t)M) * A, kind, st));
     }
     return 0;
 }
@@ -2251,6 +2264,7 @@ static int begin_fixed_rollout(StepScope& sc, int B, int T) {
     S.has_policy = true;
     S.ls_per_row = 0;
     S.rollout_B = B; S.rollout_T = T;
+    S.dev_policy_done = S.dev_filed = 0;
     return 0;
 }
 
@@ -2412,6 +2426,7 @@ int promp_begin_collection(promp_ctx* c, int step, int envs_per_task, int max_st
     const size_t need = (size_t)max_steps * c->d.n_tasks * envs_per_task * (c->d.obs_dim + 2 * c->d.act_dim);
     if (c->stage_rows.reserve(need, 1)) return -2;
     S.rollout_B = envs_per_task; S.rollout_T = max_steps; S.rollout_ragged = true;
+    S.dev_policy_done = S.dev_filed = 0;
     S.has_policy = false; S.processed = false; S.has_adv = false;
     return 0;
 }
@@ -2685,20 +2700,12 @@ int promp_point_norm_get(promp_ctx* c, int n_envs, int state_dim, double* moment
     return 0;
 }
 
-int promp_policy_step(promp_ctx* c, int step, int t, const float* obs, uint64_t seed, int clip_infos, float* actions_out) {
-    if (!c || !obs || !actions_out) return fail(-1, "NULL argument");
-    StepScope sc(c, step, /*writes=*/true, /*needs_data=*/false);
-    if (sc.rc) return sc.rc;
-    StepData& S = sc.S();
-    if (S.rollout_B < 1) return fail(-3, "promp_begin_rollout has not been called for step %d", step);
+// One vectorised policy step of a rollout in progress: d_obs [n_tasks][B][O] and d_act [n_tasks][B][A] are device memory, the rows go
+// to the slab (fixed horizon) or to the staging rows (ragged collection).  Shared by promp_policy_step and promp_policy_step_dev:
+// the same kernel, rows, Philox counter and stream word whoever owns the two arrays.
+static int launch_policy_step(promp_ctx* c, StepData& S, int step, int t, const float* d_obs, uint64_t seed, int clip_infos, float* d_act) {
     const int M = c->d.n_tasks, B = S.rollout_B, T = S.rollout_T, O = c->d.obs_dim, A = c->d.act_dim;
-    if (t < 0 || t >= T) return fail(-1, "time step %d outside the horizon %d", t, T);
-    const size_t n_obs = (size_t)M * B * O, n_act = (size_t)M * B * A;
-    if (c->rollout_buf.reserve(sizeof(float) * (n_obs + n_act), 2)) return -2;
-    float* d_obs = (float*)c->rollout_buf.p;
-    float* d_act = d_obs + n_obs;
     hipStream_t st = c->stream;
-    HIPCHECK(hipMemcpyAsync(d_obs, obs, sizeof(float) * n_obs, hipMemcpyHostToDevice, st));
     PolicyStepArgs a;
     if (tasks_materialize(c)) return -2;
     a.obs_in = d_obs; a.theta_tasks = c->theta_tasks;
@@ -2720,9 +2727,27 @@ int promp_policy_step(promp_ctx* c, int step, int t, const float* obs, uint64_t 
     } else
     PROMP_LAUNCH(k_policy_step, dim3((B + 63) / 64, M), 64, 0, st, a);
     HIPCHECK(hipGetLastError());
+    S.ps.obs_range_valid = false;
+    return 0;
+}
+
+int promp_policy_step(promp_ctx* c, int step, int t, const float* obs, uint64_t seed, int clip_infos, float* actions_out) {
+    if (!c || !obs || !actions_out) return fail(-1, "NULL argument");
+    StepScope sc(c, step, /*writes=*/true, /*needs_data=*/false);
+    if (sc.rc) return sc.rc;
+    StepData& S = sc.S();
+    if (S.rollout_B < 1) return fail(-3, "promp_begin_rollout has not been called for step %d", step);
+    const int M = c->d.n_tasks, B = S.rollout_B, T = S.rollout_T, O = c->d.obs_dim, A = c->d.act_dim;
+    if (t < 0 || t >= T) return fail(-1, "time step %d outside the horizon %d", t, T);
+    const size_t n_obs = (size_t)M * B * O, n_act = (size_t)M * B * A;
+    if (c->rollout_buf.reserve(sizeof(float) * (n_obs + n_act), 2)) return -2;
+    float* d_obs = (float*)c->rollout_buf.p;
+    float* d_act = d_obs + n_obs;
+    hipStream_t st = c->stream;
+    HIPCHECK(hipMemcpyAsync(d_obs, obs, sizeof(float) * n_obs, hipMemcpyHostToDevice, st));
+    if (launch_policy_step(c, S, step, t, d_obs, seed, clip_infos, d_act)) return -2;
     HIPCHECK(hipMemcpyAsync(actions_out, d_act, sizeof(float) * n_act, hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
-    S.ps.obs_range_valid = false;
     return 0;
 }
 
@@ -2752,6 +2777,269 @@ int promp_set_rewards_f64(promp_ctx* c, int step, const double* rew) {
     S.processed = false;
     S.has_rew64 = true;
     return 0;
+}
+
+// ---- environments that live on the device: the *_dev rollout entry points ----------------------------------------------------
+}  // extern "C"
+namespace {
+
+// a caller pointer a kernel or a device-side copy is about to read or write through
+int check_dev_ptr(const char* what, const void* p) {
+    if (!p) return fail(-1, "%s is NULL", what);
+    if (!promp_gpu_readable(p))
+        return fail(-1, "%s = %p is neither device nor page-locked host memory: the GPU cannot read it", what, p);
+    return 0;
+}
+
+// Ordering against the stream the caller's simulator enqueues on (0: the null stream).  enter: the context's stream waits for what
+// the producer has enqueued so far (its observations, rewards, flags are complete before a kernel here reads them); leave: the
+// producer waits for what the context has enqueued so far (it may overwrite its inputs and read the outputs in stream order).
+// Two events per context, timing disabled, created with the first call; no stream is created.
+int producer_enter(promp_ctx* c, void* producer_stream) {
+    if (!c->ev_producer) HIPCHECK(hipEventCreateWithFlags(&c->ev_producer.h, hipEventDisableTiming));
+    if (!c->ev_consumer) HIPCHECK(hipEventCreateWithFlags(&c->ev_consumer.h, hipEventDisableTiming));
+    HIPCHECK(hipEventRecord(c->ev_producer, (hipStream_t)producer_stream));
+    HIPCHECK(hipStreamWaitEvent(c->stream, c->ev_producer, 0));
+    return 0;
+}
+int producer_leave(promp_ctx* c, void* producer_stream) {
+    HIPCHECK(hipEventRecord(c->ev_consumer, c->stream));
+    HIPCHECK(hipStreamWaitEvent((hipStream_t)producer_stream, c->ev_consumer, 0));
+    return 0;
+}
+
+// the integer block of a device-side collection (promp_ctx::dev_tables), for a staging area of max_steps * n_envs rows
+struct DevCollectViews {
+    int *end_len, *ep_len, *step_sum, *count, *tpo, *env, *start, *len;
+    size_t n_int;
+};
+DevCollectViews dev_collect_views(const promp_ctx* c, int max_steps, long long n_envs) {
+    const size_t stage = (size_t)max_steps * (size_t)n_envs, M = (size_t)c->d.n_tasks, P = (size_t)c->d.max_paths;
+    DevCollectViews v;
+    v.end_len = c->dev_tables.p;
+    v.ep_len = v.end_len + stage;
+    v.step_sum = v.ep_len + n_envs;
+    v.count = v.step_sum + max_steps;
+    v.tpo = v.count + M;
+    v.env = v.tpo + (M + 1);
+    v.start = v.env + P;
+    v.len = v.start + P;
+    v.n_int = stage + (size_t)n_envs + (size_t)max_steps + M + (M + 1) + 3 * P;
+    return v;
+}
+
+// the checks promp_collection_progress and promp_end_collection_dev share; -> the open collection's step data
+int dev_collection_of(StepScope& sc, const char* who, long long total_samples) {
+    if (sc.rc) return sc.rc;
+    const StepData& S = sc.S();
+    if (!S.rollout_ragged || S.rollout_B < 1) return fail(-3, "%s: promp_begin_collection has not been called for step %d", who, sc.step);
+    if (total_samples < 1) return fail(-1, "%s: total_samples must be positive", who);
+    return 0;
+}
+
+// k_collect_stop over the steps filed so far -> stop[3] on the host (synchronises)
+int dev_collect_stop(promp_ctx* c, const StepData& S, long long total_samples, long long* stop) {
+    const long long n_envs = (long long)c->d.n_tasks * S.rollout_B;
+    const DevCollectViews v = dev_collect_views(c, S.rollout_T, n_envs);
+    CollectStopArgs cs;
+    cs.end_len = v.end_len; cs.step_sum = v.step_sum; cs.out = c->dev_stop; cs.max_steps = S.dev_filed; cs.n_envs = (int)n_envs;
+    cs.total_samples = total_samples;
+    PROMP_LAUNCH(k_collect_stop, dim3(1), 256, 0, c->stream, cs);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(stop, c->dev_stop.p, sizeof(long long) * 3, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+}  // namespace
+extern "C" {
+
+int promp_check_device_pointer(const void* p) { return check_dev_ptr("pointer", p) ? -1 : 0; }
+
+void* promp_dev_alloc(promp_ctx* c, size_t bytes) {
+    if (!c) {
+        fail(-1, "ctx is NULL");
+        return nullptr;
+    }
+    void* p = nullptr;
+    if (hipSetDevice(c->device) != hipSuccess || hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) {
+        fail(-2, "hipMalloc of %zu bytes failed", bytes);
+        return nullptr;
+    }
+    return p;
+}
+void promp_dev_free(promp_ctx* c, void* p) {
+    if (c && p) (void)hipFree(p);
+}
+int promp_dev_upload(promp_ctx* c, void* dst, const void* src, size_t bytes) {
+    NEED_CTX(c);
+    if (check_dev_ptr("promp_dev_upload: dst", dst)) return -1;
+    if (!src) return fail(-1, "promp_dev_upload: src is NULL");
+    HIPCHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+int promp_dev_download(promp_ctx* c, void* dst, const void* src, size_t bytes) {
+    NEED_CTX(c);
+    if (check_dev_ptr("promp_dev_download: src", src)) return -1;
+    if (!dst) return fail(-1, "promp_dev_download: dst is NULL");
+    HIPCHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int promp_policy_step_dev(promp_ctx* c, int step, int t, const float* d_obs, uint64_t seed, int clip_infos, float* d_actions,
+                          void* producer_stream) {
+    NEED_CTX(c);
+    if (check_dev_ptr("promp_policy_step_dev: d_obs", d_obs) || check_dev_ptr("promp_policy_step_dev: d_actions", d_actions)) return -1;
+    StepScope sc(c, step);
+    if (sc.rc) return sc.rc;
+    StepData& S = sc.S();
+    if (S.rollout_B < 1) return fail(-3, "promp_begin_rollout has not been called for step %d", step);
+    if (t < 0 || t >= S.rollout_T) return fail(-1, "time step %d outside the horizon %d", t, S.rollout_T);
+    if (sc.open(/*writes=*/true, /*needs_data=*/false)) return sc.rc;
+    if (producer_enter(c, producer_stream)) return -2;
+    if (launch_policy_step(c, S, step, t, d_obs, seed, clip_infos, d_actions)) return -2;
+    if (producer_leave(c, producer_stream)) return -2;
+    S.dev_policy_done = std::max(S.dev_policy_done, t + 1);
+    return 0;
+}
+
+int promp_file_step_dev(promp_ctx* c, int step, int s, const float* d_rewards, const uint8_t* d_done, int max_path_length,
+                        uint8_t* d_ended_out, void* producer_stream) {
+    NEED_CTX(c);
+    if (check_dev_ptr("promp_file_step_dev: d_rewards", d_rewards)) return -1;
+    if (d_done && check_dev_ptr("promp_file_step_dev: d_done", d_done)) return -1;
+    if (d_ended_out && check_dev_ptr("promp_file_step_dev: d_ended_out", d_ended_out)) return -1;
+    StepScope sc(c, step);
+    if (sc.rc) return sc.rc;
+    StepData& S = sc.S();
+    if (S.rollout_B < 1) return fail(-3, "promp_begin_rollout / promp_begin_collection has not been called for step %d", step);
+    const int M = c->d.n_tasks, B = S.rollout_B, T = S.rollout_T;
+    const long long n_envs = (long long)M * B;
+    if (s < 0 || s >= T) return fail(-1, "vectorised step %d outside [0, %d)", s, T);
+    if (s < S.dev_filed) return fail(-3, "step %d has already been filed: every step is filed once, the next one is %d", s, S.dev_filed);
+    if (s > S.dev_filed) return fail(-3, "step %d filed out of order: the next step to file is %d", s, S.dev_filed);
+    if (s >= S.dev_policy_done)
+        return fail(-3, "step %d filed before its policy step: promp_policy_step_dev has taken %d step(s)", s, S.dev_policy_done);
+    if (S.rollout_ragged && max_path_length < 1) return fail(-1, "max_path_length = %d must be positive", max_path_length);
+    if (n_envs * T > 0x7FFFFFFFll / 4) return fail(-1, "max_steps * environments = %lld staging rows are too many", n_envs * T);
+    if (sc.open(/*writes=*/true, /*needs_data=*/false)) return sc.rc;
+    FileStepArgs a;
+    a.rewards = d_rewards; a.done = d_done; a.ended_out = d_ended_out;
+    a.n_envs = (int)n_envs; a.s = s; a.max_path_length = max_path_length;
+    if (S.rollout_ragged) {
+        if (s == 0) {                  // a collection's storage is reserved by its first filing and stays put until the next one's
+            if (c->dev_rew_stage.reserve((size_t)T * n_envs, 1)) return -2;
+            if (c->dev_tables.reserve(dev_collect_views(c, T, n_envs).n_int, 1)) return -2;
+            if (c->dev_stop.reserve(4, 1)) return -2;
+        }
+        const DevCollectViews v = dev_collect_views(c, T, n_envs);
+        a.rew_out = c->dev_rew_stage.p + (size_t)s * n_envs; a.rew_env_stride = 1;
+        a.end_len = v.end_len + (size_t)s * n_envs; a.ep_len = v.ep_len; a.fixed_end = 0;
+    } else {                           // fixed horizon: slab row env * T + s, every episode ends with the last step
+        a.rew_out = S.rew.p + s; a.rew_env_stride = T;
+        a.end_len = nullptr; a.ep_len = nullptr; a.fixed_end = s == T - 1 ? 1 : 0;
+    }
+    if (producer_enter(c, producer_stream)) return -2;
+    PROMP_LAUNCH(k_file_step, dim3((unsigned)((n_envs + 255) / 256)), 256, 0, c->stream, a);
+    HIPCHECK(hipGetLastError());
+    if (producer_leave(c, producer_stream)) return -2;
+    S.dev_filed = s + 1;
+    if (!S.rollout_ragged) { S.processed = false; S.has_rew64 = false; }
+    return 0;
+}
+
+int promp_collection_progress(promp_ctx* c, int step, int64_t total_samples, int32_t* stop_step, int64_t* finished_rows) {
+    if (!c || !stop_step || !finished_rows) return fail(-1, "NULL argument");
+    StepScope sc(c, step);
+    if (const int rc = dev_collection_of(sc, "promp_collection_progress", total_samples)) return rc;
+    StepData& S = sc.S();
+    long long stop[3] = {-1, 0, 1};
+    if (S.dev_filed > 0) {
+        if (sc.open(/*writes=*/false, /*needs_data=*/false)) return sc.rc;
+        if (dev_collect_stop(c, S, total_samples, stop)) return -2;
+    }
+    *stop_step = (int32_t)stop[0];
+    *finished_rows = stop[1];
+    return 0;
+}
+
+int promp_end_collection_dev(promp_ctx* c, int step, int64_t total_samples, int32_t* n_paths_out, int32_t* n_steps_out,
+                             int32_t* task_path_offsets, int32_t* path_env, int32_t* path_start, int32_t* path_len) {
+    if (!c || !n_paths_out || !n_steps_out || !task_path_offsets || !path_env || !path_start || !path_len) return fail(-1, "NULL argument");
+    StepScope sc(c, step);
+    if (const int rc = dev_collection_of(sc, "promp_end_collection_dev", total_samples)) return rc;
+    StepData& S = sc.S();
+    const int M = c->d.n_tasks, B = S.rollout_B, filed = S.dev_filed, max_paths = c->d.max_paths;
+    const long long n_envs = (long long)M * B;
+    if (filed < 1) return fail(-3, "promp_end_collection_dev: no step has been filed for step %d (promp_file_step_dev)", step);
+    if (sc.open(/*writes=*/true, /*needs_data=*/false)) return sc.rc;
+    hipStream_t st = c->stream;
+    const DevCollectViews v = dev_collect_views(c, S.rollout_T, n_envs);
+    long long stop[3] = {-1, 0, 1};
+    if (dev_collect_stop(c, S, total_samples, stop)) return -2;
+    if (stop[2] != 0 || stop[0] < 0)   // (nothing installed, the collection stays open: more steps may be filed)
+        return fail(-1, "the %d vectorised steps filed do not reach total_samples = %lld", filed, (long long)total_samples);
+    if (stop[1] > c->d.max_rows) return fail(-1, "%lld collected rows exceed max_rows = %d", stop[1], c->d.max_rows);
+    CollectTablesArgs ct;
+    ct.end_len = v.end_len; ct.stop = c->dev_stop; ct.task_count = v.count; ct.task_path_offsets = v.tpo;
+    ct.path_env = v.env; ct.path_start = v.start; ct.path_len = v.len;
+    ct.B = B; ct.max_steps = filed; ct.n_envs = (int)n_envs; ct.n_tasks = M; ct.max_paths = max_paths; ct.write = 0;
+    PROMP_LAUNCH(k_collect_tables, dim3(M), 64, 0, st, ct);
+    PROMP_LAUNCH(k_collect_offsets, dim3(1), 64, 0, st, (const int*)v.count, v.tpo, M);
+    ct.write = 1;
+    PROMP_LAUNCH(k_collect_tables, dim3(M), 64, 0, st, ct);
+    HIPCHECK(hipGetLastError());
+    std::vector<int32_t> tpo((size_t)M + 1, 0);
+    HIPCHECK(hipMemcpyAsync(tpo.data(), v.tpo, sizeof(int32_t) * (M + 1), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    const int n_paths = tpo[M];
+    if (n_paths < 1 || n_paths > max_paths) return fail(-1, "%d paths outside [1, max_paths = %d]", n_paths, max_paths);
+    std::string empty;
+    for (int i = 0; i < M; ++i)
+        if (tpo[i + 1] == tpo[i]) empty += (empty.empty() ? "" : ", ") + std::to_string(i);
+    if (!empty.empty())
+        return fail(-1, "no finished episode for task(s) [%s] within total_samples = %lld (envs_per_task = %d)", empty.c_str(),
+                    (long long)total_samples, B);
+    // (the caller's tables are written only once the collection is accepted)
+    std::vector<int32_t> h_env((size_t)n_paths), h_start((size_t)n_paths), h_len((size_t)n_paths), pro((size_t)n_paths + 1, 0);
+    HIPCHECK(hipMemcpyAsync(h_env.data(), v.env, sizeof(int32_t) * n_paths, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(h_start.data(), v.start, sizeof(int32_t) * n_paths, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(h_len.data(), v.len, sizeof(int32_t) * n_paths, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    for (int p = 0; p < n_paths; ++p) {
+        if (h_len[p] < 1 || h_start[p] < 0 || h_start[p] + h_len[p] > filed || h_env[p] < 0 || h_env[p] >= n_envs)
+            return fail(-2, "path %d (environment %d, steps [%d, %d)) lies outside the collection", p, h_env[p], h_start[p], h_start[p] + h_len[p]);
+        pro[p + 1] = pro[p] + h_len[p];
+    }
+    if (pro[n_paths] != stop[1]) return fail(-2, "the path tables hold %d rows, the stop record %lld", pro[n_paths], stop[1]);
+    if (finish_collection(sc, n_paths, tpo.data(), pro.data(), nullptr, nullptr, v.env, v.start, nullptr, c->dev_rew_stage)) return -2;
+    S.dev_policy_done = S.dev_filed = 0;
+    for (int i = 0; i <= M; ++i) task_path_offsets[i] = tpo[i];
+    for (int p = 0; p < n_paths; ++p) { path_env[p] = h_env[p]; path_start[p] = h_start[p]; path_len[p] = h_len[p]; }
+    *n_paths_out = n_paths;
+    *n_steps_out = (int32_t)stop[0] + 1;
+    return 0;
+}
+
+int promp_upload_step_dev(promp_ctx* c, int step, int n_paths, const int32_t* tpo, const int32_t* pro, const float* obs,
+                          const float* act, const float* rew, const float* old_mean, const float* old_ls, int ls_per_row,
+                          void* producer_stream) {
+    NEED_CTX(c);
+    if (check_dev_ptr("promp_upload_step_dev: obs", obs) || check_dev_ptr("promp_upload_step_dev: rew", rew)) return -1;
+    if (act && old_mean && old_ls &&
+        (check_dev_ptr("promp_upload_step_dev: act", act) || check_dev_ptr("promp_upload_step_dev: old_mean", old_mean) ||
+         check_dev_ptr("promp_upload_step_dev: old_log_std", old_ls)))
+        return -1;
+    StepScope sc(c, step, /*writes=*/true, /*needs_data=*/false);
+    if (sc.rc) return sc.rc;
+    StepData& S = sc.S();
+    clear_selection(c, step);
+    if (set_step_layout(c, S, c->stream, false, n_paths, tpo, pro)) return -2;
+    if (producer_enter(c, producer_stream)) return -2;
+    if (copy_step_data(c, S, c->stream, obs, act, rew, old_mean, old_ls, ls_per_row, hipMemcpyDeviceToDevice)) return -2;
+    return producer_leave(c, producer_stream);
 }
 
 int promp_download_step(promp_ctx* c, int step, float* obs, float* act, float* rew, float* old_mean, float* old_log_std) {

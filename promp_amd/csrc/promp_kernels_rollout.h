@@ -848,3 +848,35 @@ __global__ void __launch_bounds__(64) k_collect_offsets(const int* task_count, i
     }
     task_path_offsets[n_tasks] = n;
 }
+
+// ---- collections whose environment lives on the device (promp_file_step_dev) -------------------------------------------------
+// The outcome of vectorised step s of every environment, filed where k_point_collect files its own: the reward under (s, env) of the
+// staged rewards, the length of an episode that ends at s under (s, env) of end_len (0: still running).  ep_len [n_envs] is the
+// length of every environment's episode in progress; the launch of s == 0 starts it from zero.
+//   len = ep_len[env] + 1;  end = (done && done[env]) || len == max_path_length
+// Fixed horizon (promp_begin_rollout): end_len == nullptr; the reward goes to slab row env * T + s (rew_env_stride = T), `done` is
+// not read and every environment reports fixed_end (s == T - 1).
+struct FileStepArgs {
+    const float* rewards;        // [n_envs]
+    const unsigned char* done;   // [n_envs] or nullptr
+    unsigned char* ended_out;    // [n_envs] or nullptr
+    float* rew_out;              // where environment 0's reward of this step goes; environment e: + e * rew_env_stride
+    long long rew_env_stride;
+    int* end_len;                // row s of end_len [max_steps][n_envs], or nullptr: fixed horizon
+    int* ep_len;                 // [n_envs] (ragged collections only)
+    int n_envs, s, max_path_length, fixed_end;
+};
+// grid = ceil(n_envs / 256), block = 256: one thread per environment, consecutive lanes = consecutive environments
+__global__ void __launch_bounds__(256) k_file_step(FileStepArgs a) {
+    const int env = blockIdx.x * 256 + threadIdx.x;
+    if (env >= a.n_envs) return;
+    a.rew_out[(long long)env * a.rew_env_stride] = a.rewards[env];
+    bool end = a.fixed_end != 0;
+    if (a.end_len != nullptr) {
+        const int len = (a.s == 0 ? 0 : a.ep_len[env]) + 1;
+        end = (a.done != nullptr && a.done[env] != 0) || len == a.max_path_length;
+        a.end_len[env] = end ? len : 0;
+        a.ep_len[env] = end ? 0 : len;
+    }
+    if (a.ended_out != nullptr) a.ended_out[env] = end ? 1 : 0;
+}
